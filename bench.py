@@ -339,6 +339,30 @@ def cpu_baseline(workload):
                         "schedule_efficiency": r["schedule_efficiency"], "sample": r["sample"]} for r in runs]}
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, rgba, count):
+    """--dump-outputs: the RenderLayer of the last timed step as a caller of Render() receives it -- rgba (H, W, 4) f32 and the
+    per-pixel sample count (written as f32: exact) -- as out_dir/rgba.npy and out_dir/count.npy.  A layer larger than DUMP_BYTES
+    (C5's 3840 x 2160) is written as a fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels: rgba (n, 4), count (n,) and the sampled
+    pixel indices (row-major, f64) as pixel_index.npy.  Returns what was written, for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = count.shape
+    arrays = {"rgba": rgba.astype(np.float32), "count": count.astype(np.float32)}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=DUMP_SAMPLE_PIXELS, replace=False))
+        arrays = {"rgba": arrays["rgba"].reshape(H * W, 4)[idx], "count": arrays["count"].reshape(H * W)[idx],
+                  "pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in arrays.items()},
+            "sampled": "pixel_index" in arrays, "bytes": sum(a.nbytes for a in arrays.values())}
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`
@@ -400,8 +424,12 @@ def main():
     ap.add_argument("--exchange", default="gather", choices=["gather", "reduce", "torch"],
                     help="N > 1: how the RenderLayer reaches rank 0: gather / reduce = RCCL inside libpbrhip "
                          "(pbrhip_comm_gather_layer / pbrhip_comm_reduce_layer), torch = torch.distributed.reduce")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the RenderLayer of the last timed step (rank 0) as DIR/<name>.npy")
     ap.add_argument("--spawn-selftest", action="store_true", help=argparse.SUPPRESS)   # CPU test of the launcher path (tests/test_dist_cpu.py)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.spawn_selftest and "WORLD_SIZE" in os.environ:
         # a rank started by spawn_ranks(): rendezvous over gloo on 127.0.0.1, one collective, rank 0 prints the line (no GPU involved)
         import torch
@@ -553,6 +581,7 @@ def main():
     elapsed, agg = timed(spp, args.steps, args.warmup, 0 if args.no_roofline else api.RENDER_TIMING_TRACE)
     diag = rank_diagnostics(dist, dev, clock["render"] / args.steps * 1e3, clock["exchange"] / args.steps * 1e3) if dist is not None else None
     check_layer(spp)
+    dumped = dump_outputs(args.dump_outputs, h_rgba.numpy(), h_count.numpy()) if (args.dump_outputs and rank == 0) else None
     h_elapsed, _ = timed(spp, args.steps, 1, 0, to_host=True)   # (one untimed step first: the pinned destination is touched, the copy engine is warm)
     host_layer = {"value": W * H * spp * args.steps / h_elapsed / 1e6, "unit": "Msamples/s", "ms_per_step": h_elapsed / args.steps * 1e3,
                   "note": "the same steps, each ending with the RenderLayer (rgba f32 + count u32: 20 bytes per pixel) copied to pinned host memory of rank 0 -- "
@@ -705,6 +734,8 @@ def main():
                                   "host_copy": "41.5 MB (1920 x 1080 x 20 B) over PCIe in 0.7-0.8 ms = its ~55 GB/s: the copy cannot start before the last pass is "
                                                "accumulated (the layer is a sum over all passes) -- it is the floor of host_layer.ms_per_step - ms_per_step"},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if diag is not None:   # N > 1: where each rank's time went (gathered after the timed region)
             out.update(diag)
         if other is not None:

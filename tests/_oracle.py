@@ -173,6 +173,26 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "ref_leaf_outputs.npz")
+_ref_outputs = None
+
+
+def ref_outputs(key, compute):
+    """What the reference's own leaf code returns for one test's seeded inputs, as a dict of arrays: compute(ref()) where
+    oracle/_ref/libref_leaf.so is built, else the same arrays read back from tests/golden/ref_leaf_outputs.npz (written by
+    tests/golden/make_ref_outputs.py with the very compute functions the tests pass here).  A key missing from the file is
+    an error, never a skip."""
+    global _ref_outputs
+    if have_ref():
+        return {k: np.asarray(v) for k, v in compute(ref()).items()}
+    if _ref_outputs is None:
+        _ref_outputs = dict(np.load(REF_OUTPUTS))
+    out = {k.split("/", 1)[1]: v for k, v in _ref_outputs.items() if k.split("/", 1)[0] == key}
+    if not out:
+        raise KeyError(f"{key}: not in {REF_OUTPUTS} (tests/golden/make_ref_outputs.py)")
+    return out
+
+
 def ref():
     global _ref
     if _ref is None:

@@ -42,3 +42,28 @@ def test_workloads_are_the_baseline_configurations():
     assert (w["c2"]["width"], w["c2"]["height"], w["c2"]["spp"]) == (1920, 1080, 64)       # BASELINE configs[1]: the metric's configuration
     assert (w["c3"]["spp"], w["c4"]["spp"]) == (256, 128) and (w["c5"]["width"], w["c5"]["height"], w["c5"]["spp"]) == (3840, 2160, 1024)
     assert bench.HBM_PEAK_GBS == 8000.0
+
+
+def test_dump_outputs_full_layer_and_seeded_sample(tmp_path):
+    """--dump-outputs: the whole RenderLayer when it fits the 64 MB budget, else the same seeded pixel sample on every run"""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    rgba, count = rng.random((108, 192, 4), dtype=np.float32), np.full((108, 192), 64, np.int32)
+    d = str(tmp_path / "full")
+    info = bench.dump_outputs(d, rgba, count)
+    assert not info["sampled"] and sorted(os.listdir(d)) == ["count.npy", "rgba.npy"]
+    a, c = np.load(os.path.join(d, "rgba.npy")), np.load(os.path.join(d, "count.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, rgba) and c.dtype == np.float32 and np.array_equal(c, count)
+    # the C5 frame (3840 x 2160) does not fit: a fixed sample, identical from run to run, within the budget
+    H, W = 2160, 3840
+    big, cnt = np.zeros((H, W, 4), np.float32), np.full((H, W), 1024, np.int32)
+    big[..., 0] = np.arange(H * W, dtype=np.float32).reshape(H, W)
+    infos = [bench.dump_outputs(str(tmp_path / f"s{k}"), big, cnt) for k in range(2)]
+    assert infos[0]["sampled"] and infos[0]["bytes"] <= bench.DUMP_BYTES
+    for name in ("rgba", "count", "pixel_index"):
+        x, y = (np.load(str(tmp_path / f"s{k}" / f"{name}.npy")) for k in range(2))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    idx = np.load(str(tmp_path / "s0" / "pixel_index.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "s0" / "rgba.npy"))[:, 0], big.reshape(-1, 4)[idx, 0])
+    total = sum(os.path.getsize(str(tmp_path / "s0" / f)) for f in os.listdir(str(tmp_path / "s0")))
+    assert total <= bench.DUMP_BYTES
