@@ -113,7 +113,7 @@ typedef struct {
                            light primitive, or the bounding box of every light), so nothing it could find changes the image (closest + tail_closest + pruned = the reference's count) */
   uint64_t passes_done; /* passes every pixel of this rank holds when the call returns (= num_sample unless cancelled) */
   uint64_t node_bytes;  /* footprint of one node of the tree k_trace walked: 64 (the Q tree: 4 children, quantised boxes; or the binary tree) */
-  uint64_t curve_bytes; /* bytes fetched per curve-piece test: 32 (Q tree: two 16-byte points of a chain) or 64 (binary tree: one slot) */
+  uint64_t curve_bytes; /* bytes fetched per curve-piece test: 32 (Q tree: the two 16-byte end points of a piece in a curve record) or 64 (binary tree: one slot) */
   uint64_t suspended_rays; /* PBRHIP_RENDER_STATS: closest-hit rays a k_trace launch suspended at its drain and the next launch resumed
                               (counted ONCE in closest_rays; their node / primitive counts are complete: nothing is traversed twice) */
   double ms_host_idle;  /* PBRHIP_RENDER_TIMING: sum over the path groups of the time their stream sat empty between two bursts of

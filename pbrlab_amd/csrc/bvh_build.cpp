@@ -282,7 +282,10 @@ void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const
 // lower bound; a child's bounds are rounded outwards on that grid and
 // then checked -- and moved out further if need be -- with the expression the traversal evaluates, fmaf(q, s, org) in single
 // precision; when the grid is too fine for that arithmetic (a step below the resolution of org) the step doubles.
-static bool quantise_node(const QChild* c, int n, QNode* nd) {
+struct QBox {
+  float lo[3], hi[3];
+};
+static bool quantise_node(const QBox* c, int n, QNode* nd) {
   memset(nd, 0, sizeof(*nd));
   uint32_t* qw[6] = {&nd->qlo_x, &nd->qlo_y, &nd->qlo_z, &nd->qhi_x, &nd->qhi_y, &nd->qhi_z};
   for (int a = 0; a < 3; a++) {
@@ -321,12 +324,10 @@ static bool quantise_node(const QChild* c, int n, QNode* nd) {
   return true;
 }
 
-uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uint32_t, const float*, const float*, QChild*)>& map_leaf,
-                     std::vector<QNode>* out) {
+uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out) {
   out->clear();
   if (N2.empty()) return 0;
-  // The binary tree as a tree of boxes whose leaves are the Q tree's leaf references (a leaf of the binary tree whose two
-  // curve pieces are not neighbours in a chain is an inner vertex with two leaves here).  Children follow their parent.
+  // The binary tree as a tree of boxes whose leaves are the Q tree's leaf references.  Children follow their parent.
   struct V {
     float lo[3], hi[3];
     int32_t l = -1, r = -1;  // children, or -1: leaf
@@ -334,7 +335,7 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
     uint32_t prims = 0;      // leaf: primitives behind the reference
   };
   std::vector<V> T;
-  T.reserve(N2.size() * 3);
+  T.reserve(N2.size() * 2 + 1);
   {
     struct Todo {
       uint32_t node2;
@@ -352,30 +353,12 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
       for (int k = 0; k < 2; k++) {
         const uint32_t ref = k ? b.c1 : b.c0;
         if (ref == kEmptyChild) continue;
-        float lo[3], hi[3];
-        for (int a = 0; a < 3; a++) lo[a] = b.lo[a][k], hi[a] = b.hi[a][k];
         const int32_t v = (int32_t)T.size();
         T.emplace_back();
-        for (int a = 0; a < 3; a++) T[v].lo[a] = lo[a], T[v].hi[a] = hi[a];
+        for (int a = 0; a < 3; a++) T[v].lo[a] = b.lo[a][k], T[v].hi[a] = b.hi[a][k];
         kids[nk++] = v;
-        if (!(ref & kLeafBit)) {
-          todo.push_back({ref, v});
-          continue;
-        }
-        QChild c[2];
-        const int m = map_leaf(ref, lo, hi, c);
-        if (m == 1) {
-          T[v].ref = c[0].ref, T[v].prims = ((c[0].ref & kCurveBit) && (c[0].ref & kCurvePairBit)) ? 2u : (c[0].ref & 3u) + 1u;  // (a curve record of two pieces: kCurvePairBit)
-          for (int a = 0; a < 3; a++) T[v].lo[a] = c[0].lo[a], T[v].hi[a] = c[0].hi[a];
-        } else {
-          for (int j = 0; j < 2; j++) {
-            const int32_t w = (int32_t)T.size();
-            T.emplace_back();
-            T[w].ref = c[j].ref, T[w].prims = (c[j].ref & 7u) + 1u;
-            for (int a = 0; a < 3; a++) T[w].lo[a] = c[j].lo[a], T[w].hi[a] = c[j].hi[a];
-            (j ? T[v].r : T[v].l) = w;
-          }
-        }
+        if (ref & kLeafBit) T[v].ref = map_leaf(ref), T[v].prims = (ref & 7u) + 1u;
+        else todo.push_back({ref, v});
       }
       // vertex t.v takes the node's children; a node with one child (a scene of one leaf) passes it through
       if (nk == 2) T[t.v].l = kids[0], T[t.v].r = kids[1];
@@ -468,7 +451,6 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
   std::deque<Item> work;
   out->emplace_back();
   work.push_back({0, 0u});
-  uint32_t levels = 0;
   while (!work.empty()) {
     Item it;
     if (out->size() < (size_t)kTopNodes) it = work.front(), work.pop_front();
@@ -482,12 +464,9 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
         if (choice[(size_t)it.v * 4 + m] >= 0) fr[n++] = choice[(size_t)it.v * 4 + m];
       // (a pass-through vertex hands on its only child; if that child is inner it gets a node of its own below)
     }
-    QChild c[4];
-    for (int i = 0; i < n; i++) {
-      const V& u = T[fr[i]];
-      c[i].ref = u.l < 0 ? u.ref : 0u;
-      for (int a = 0; a < 3; a++) c[i].lo[a] = u.lo[a], c[i].hi[a] = u.hi[a];
-    }
+    QBox c[4];
+    for (int i = 0; i < n; i++)
+      for (int a = 0; a < 3; a++) c[i].lo[a] = T[fr[i]].lo[a], c[i].hi[a] = T[fr[i]].hi[a];
     QNode nd;
     if (n == 0 || !quantise_node(c, n, &nd)) {
       out->clear();
@@ -510,7 +489,6 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
   // the stack a near-first traversal can need: on the way down every node leaves at most (children - 1) entries behind.
   // need(node) = max over its inner children of (children - 1 + need(child)), at least (children - 1); children have
   // larger indices than their parent, so one backward sweep does it
-  (void)levels;
   std::vector<uint32_t> need(out->size(), 0);
   for (size_t i = out->size(); i-- > 0;) {
     const QNode& nd = (*out)[i];
@@ -523,6 +501,135 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<int(uin
     need[i] = (nc ? nc - 1u : 0u) + deepest;
   }
   return need[0];
+}
+
+void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out) {
+  static_assert(kMaxLeaf <= 2, "a leaf of the binary tree becomes one TriPair / one curve record");
+  *out = QLayout();
+  std::vector<float4>&qtri = out->tri, &qpts = out->pts;
+  std::vector<uint32_t>& qhit = out->hit;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  // the complete hit code of slot k: k | routing bits
+  auto code = [&](uint32_t k) { return k | __builtin_bit_cast(uint32_t, slots[4 * (size_t)k + 2].w); };
+  // Triangle leaves.  Triangle-only scenes: one TriPair per leaf (dscene.h): its one or two triangles interleaved coordinate by
+  // coordinate, 80 bytes, both tested at once on packed fp32.  Scenes with curves (their kernels have no registers to spare
+  // and meet triangles rarely): 48 bytes per triangle -- three corners, the hit code in the third word's .w -- one after the other.
+  const bool tri_pairs = std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
+  auto tri_leaf = [&](uint32_t first, uint32_t count) -> uint32_t {
+    if (!tri_pairs) {
+      const uint32_t rec = (uint32_t)(qtri.size() / 3);
+      for (uint32_t i = 0; i < count; i++) {
+        for (int c = 0; c < 3; c++) qtri.push_back(slots[4 * (size_t)(first + i) + c]);
+        qtri.back().w = __builtin_bit_cast(float, code(first + i));
+      }
+      return rec;
+    }
+    const uint32_t rec = (uint32_t)(qtri.size() / kTriPairWords);
+    const float4* a = &slots[4 * (size_t)first];
+    const float4* b = count == 2 ? &slots[4 * (size_t)(first + 1)] : a;  // (one triangle: stored twice, the copy is no candidate)
+    const float ca = __builtin_bit_cast(float, code(first)), cb = __builtin_bit_cast(float, count == 2 ? code(first + 1) : kNone);
+    qtri.insert(qtri.end(), {make_float4(a[0].x, b[0].x, a[0].y, b[0].y), make_float4(a[0].z, b[0].z, a[1].x, b[1].x),
+                             make_float4(a[1].y, b[1].y, a[1].z, b[1].z), make_float4(a[2].x, b[2].x, a[2].y, b[2].y),
+                             make_float4(a[2].z, b[2].z, ca, cb)});
+    return rec;
+  };
+  // Curve leaves: a record (dscene.h) of the end points of the leaf's one or two pieces, at a point index P that is a multiple
+  // of 4.  Points 0..3 stay zero: the first record is at point 4.
+  qpts.assign(4, zero);
+  qhit.assign(4, kNone);
+  auto curve_leaf = [&](uint32_t first, uint32_t count) -> uint32_t {
+    while (qpts.size() % 4) qpts.push_back(zero);
+    const uint32_t P = (uint32_t)qpts.size();
+    uint32_t sub[2] = {0u, 0u};
+    for (uint32_t i = 0; i < count; i++) {
+      const float4* sl = &slots[4 * (size_t)(first + i)];  // (a piece's slot of the binary tree: its two end points, then its index in the cubic)
+      qpts.push_back(sl[0]), qpts.push_back(sl[1]);
+      sub[i] = __builtin_bit_cast(uint32_t, sl[2].x) & 3u;
+    }
+    qhit.resize(qpts.size(), kNone);
+    qhit[P] = code(first);
+    if (count == 2) qhit[P + 2] = code(first + 1);
+    (count == 2 ? out->leaves_pair : out->leaves_one)++;
+    return kLeafBit | kCurveBit | ((P | sub[0]) << 3) | (count == 2 ? (kCurvePairBit | sub[1]) : 0u);
+  };
+  auto map_leaf = [&](uint32_t ref) -> uint32_t {
+    const uint32_t first = (ref & 0x3FFFFFFFu) >> 3, count = (ref & 7u) + 1u;
+    if (ref & kCurveBit) return curve_leaf(first, count);
+    return kLeafBit | (tri_leaf(first, count) << 3) | (count - 1u);
+  };
+  // (a tree the traversal stack cannot hold, or with point indices beyond the reference's 27 bits, is dropped: no Q tree)
+  out->stack_need = build_qtree(bvh.nodes, map_leaf, &out->nodes);
+  if (out->stack_need > (uint32_t)kStackDepth || qpts.size() >= (1u << 27)) out->nodes.clear();
+  while (qtri.size() % 4) qtri.push_back(zero);    // (q_pt0 a multiple of 4: the low bits of a curve record's address are free)
+  for (int k = 0; k < 4; k++) qpts.push_back(zero);  // (the load site reads four words of a leaf)
+  qhit.resize(qpts.size(), kNone);
+}
+
+std::vector<SssEntry> build_sss_entries(const std::vector<QNode>& wide, const std::vector<float>& ilo, const std::vector<float>& ihi,
+                                        uint32_t max_foreign) {
+  const size_t ninst = ilo.size() / 3;
+  std::vector<SssEntry> entries(ninst, SssEntry{});
+  struct CutRef { uint32_t ref; float lo[3], hi[3]; };
+  for (size_t i = 0; i < ninst; i++) {
+    SssEntry& E = entries[i];
+    if (!(ilo[3 * i] <= ihi[3 * i])) continue;  // (no primitive)
+    float ext = 0.f;
+    for (int a = 0; a < 3; a++) ext = std::max(ext, ihi[3 * i + a] - ilo[3 * i + a]);
+    if (!(ext > 0.f) || !std::isfinite(ext)) continue;
+    const float m1 = 1e-4f * ext, m2 = 2e-3f * ext;  // the region rays may stay in / how far beyond it a primitive's box can matter
+    float rlo[3], rhi[3], wlo[3], whi[3];
+    for (int a = 0; a < 3; a++) rlo[a] = ilo[3 * i + a] - m1, rhi[a] = ihi[3 * i + a] + m1, wlo[a] = rlo[a] - m2, whi[a] = rhi[a] + m2;
+    std::vector<CutRef> cut{{0u, {-INFINITY, -INFINITY, -INFINITY}, {INFINITY, INFINITY, INFINITY}}};
+    for (bool changed = true; changed;) {
+      changed = false;
+      for (size_t c = 0; c < cut.size() && !changed; c++) {
+        if (cut[c].ref & kLeafBit) continue;
+        const QNode& nd = wide[cut[c].ref];
+        const float org[3] = {nd.org[0], nd.org[1], nd.org[2]}, st3[3] = {nd.sx, nd.sy, nd.sz};
+        const uint32_t ql[3] = {nd.qlo_x, nd.qlo_y, nd.qlo_z}, qh[3] = {nd.qhi_x, nd.qhi_y, nd.qhi_z};
+        std::vector<CutRef> kids;
+        int nchild = 0;
+        for (int k = 0; k < 4; k++) {
+          if (nd.c[k] == kEmptyChild) continue;
+          nchild++;
+          CutRef r;
+          r.ref = nd.c[k];
+          bool meets = true;
+          for (int a = 0; a < 3; a++) {  // the box the traversal rebuilds for this child (dtrace.h::box_test4q): fma(q, s, org)
+            r.lo[a] = fmaf((float)((ql[a] >> (8 * k)) & 255u), st3[a], org[a]);
+            r.hi[a] = fmaf((float)((qh[a] >> (8 * k)) & 255u), st3[a], org[a]);
+            meets = meets && r.lo[a] <= whi[a] && r.hi[a] >= wlo[a];
+          }
+          if (meets) kids.push_back(r);
+        }
+        // descend where that drops a child (or leads to an only child), while the cut stays small
+        if (((int)kids.size() < nchild || kids.size() == 1) && cut.size() - 1 + kids.size() <= 1u + max_foreign) {
+          cut.erase(cut.begin() + (ptrdiff_t)c);
+          cut.insert(cut.end(), kids.begin(), kids.end());
+          changed = true;
+        }
+      }
+    }
+    // the entry: the inner node of the cut that shares the most volume with the instance's bounds
+    int best = -1;
+    double best_v = -1.0;
+    for (size_t c = 0; c < cut.size(); c++) {
+      if (cut[c].ref & kLeafBit) continue;
+      double v = 1.0;
+      for (int a = 0; a < 3; a++) v *= std::max(0.0, (double)std::min(cut[c].hi[a], ihi[3 * i + a]) - (double)std::max(cut[c].lo[a], ilo[3 * i + a]));
+      if (v > best_v) best_v = v, best = (int)c;
+    }
+    if (best < 0 || cut[(size_t)best].ref == 0u) continue;  // (the root, or leaves only: start at the root)
+    E.entry = cut[(size_t)best].ref;
+    for (int a = 0; a < 3; a++) E.lo[a] = rlo[a], E.hi[a] = rhi[a];
+    for (size_t c = 0; c < cut.size(); c++) {
+      if ((int)c == best) continue;
+      auto& f = E.foreign[E.nforeign++];
+      f.ref = cut[c].ref;
+      for (int a = 0; a < 3; a++) f.lo[a] = cut[c].lo[a], f.hi[a] = cut[c].hi[a];
+    }
+  }
+  return entries;
 }
 
 }  // namespace pb

@@ -72,24 +72,15 @@ static_assert(sizeof(BvhNode) == 64, "node must be 64 B");
 // arithmetic on them, so the quantised test inherits its properties (monotone in the box, correct for axis-parallel rays).
 // Child references: an inner child = its item index; a triangle leaf = kLeafBit | first << 3 | (count - 1) with `first` the
 // index of the leaf's TriPair among the tree's own triangle records (DScene::q_tri0; 80 B each, below; scenes with curves: of
-// its first 48-byte triangle slot); a curve leaf = kLeafBit | kCurveBit | first << 3 |
-// (count - 1) with `first` a POINT index (DScene::q_pt0): the linear pieces of a strand are stored as a chain of points
-// (xyz + radius, 16 B), piece p = points p, p + 1, piece-in-cubic index = p & 3 (every cubic starts at a multiple of 4).
-// An unused child has reference kEmptyChild.
-// Round 6 (PB_CURVE_RECORDS): a curve leaf is a RECORD instead of a stretch of a chain: four consecutive 16-byte words a0 a1 b0 b1 -- the
-// end points of its one or two pieces, copied; 64-byte aligned: one item, like a node -- and both pieces are tested in ONE turn of the
-// traversal.  Why: nine in ten of the two-piece leaves the SAH builder makes over hair are two pieces of NEIGHBOURING STRANDS, side by
-// side, not neighbours in a chain; rounds 3-5 cut such a leaf into two leaves of one piece (two children of its node, two turns).
-// Its reference is  kLeafBit | kCurveBit | (P | i_a) << 3 | (two pieces ? kCurvePairBit | i_b : 0),  P = the record's first point index
-// (a multiple of 4), i_a / i_b = the pieces' indices in their cubics (what `p & 3` was for a chain piece); piece a is point P, piece b
-// point P + 2 (q_hitcode has their codes).  A build option (-DPB_CURVE_RECORDS=0: the chains of rounds 3-5, one piece per turn).
+// its first 48-byte triangle slot); a curve leaf is a RECORD (round 6): four consecutive 16-byte words a0 a1 b0 b1 -- the end
+// points (xyz + radius) of its one or two pieces, copied; 64-byte aligned: one item, like a node -- and both pieces are tested in
+// ONE turn of the traversal.  Its reference is
+//   kLeafBit | kCurveBit | (P | i_a) << 3 | (two pieces ? kCurvePairBit | i_b : 0)
+// with P = the record's first point index (DScene::q_pt0; a multiple of 4) and i_a / i_b = the pieces' indices in their cubics;
+// piece a is point P, piece b point P + 2 (q_hitcode has their codes).  Why records: nine in ten of the two-piece leaves the SAH
+// builder makes over hair are two pieces of NEIGHBOURING STRANDS, side by side; rounds 3-5 stored pieces as chains of points and
+// tested one piece per turn (DESIGN.md "curve records").  An unused child has reference kEmptyChild.
 constexpr uint32_t kCurvePairBit = 4u;
-#ifndef PB_CURVE_RECORDS
-#define PB_CURVE_RECORDS 1
-#endif
-#ifndef PB_CURVE_TWO
-#define PB_CURVE_TWO 1  // curve records: 1 = both pieces of a leaf in ONE traversal turn (88-91 registers: five blocks per CU), 0 = one piece per turn (six blocks per CU)
-#endif
 struct alignas(16) QNode {
   float org[3], sx;
   float sy, sz;

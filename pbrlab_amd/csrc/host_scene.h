@@ -76,20 +76,28 @@ void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const
 // binary node become the children of its Q node -- a frontier of at most four subtrees below it -- is chosen bottom-up by
 // dynamic programming over the surface-area cost WITH THE BOX A CHILD REALLY PRESENTS: its box rounded outwards on the node's
 // 8-bit grid (a thin primitive in a big node is a thick slab).
-// map_leaf turns a leaf reference of the binary tree into one or two children of the Q tree (its references use the Q
-// tree's own triangle slots and curve points; a curve leaf whose two pieces are not neighbours in a chain becomes two):
-// it fills ref / lo / hi and returns the count.  PRECONDITION on lo / hi (QChild): they are boxes as the binary tree stores
-// them, i.e. already widened with BvhNode::widen_lo / widen_hi -- for a curve leaf that map_leaf splits, the box of each piece
-// (end points +- the larger radius) widened the same way; quantise_node only rounds outwards from there, and the
-// traversal's exactness argument needs every stored box to contain the validation boxes below it.
+// map_leaf turns a leaf reference of the binary tree into the Q tree's; it is called in the collapse's visit order, which thus
+// decides where the leaves sit in memory.  The Q child takes the box the binary tree stores (already widened); quantise_node only
+// rounds outwards from there, as the traversal's exactness argument needs.
 // Returns the EXACT stack need of a near-first traversal of the Q tree: the maximum over root-to-leaf paths of the sum of
 // (children - 1) of the nodes on the path (a node pushes all hit children but the nearest).
-struct QChild {
-  uint32_t ref;
-  float lo[3], hi[3];
+uint32_t build_qtree(const std::vector<BvhNode>& nodes, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out);
+
+// The Q tree as the traversal kernels read it (DScene::wide: nodes, then `tri` from q_tri0, then `pts` from q_pt0; dscene.h::QNode).
+struct QLayout {
+  std::vector<QNode> nodes;   // empty: no Q tree (it would need more than kStackDepth stack entries, or 2^27 points or more)
+  std::vector<float4> tri, pts;  // triangle leaves padded to a multiple of 4 words; curve records, then four zero words
+  std::vector<uint32_t> hit;  // DScene::q_hitcode: per point, the hit code of the piece that starts there (else kNone)
+  uint32_t stack_need = 0;                 // what build_qtree reported
+  size_t leaves_one = 0, leaves_pair = 0;  // curve leaves of one / two pieces (counted over the collapse's visits)
 };
-uint32_t build_qtree(const std::vector<BvhNode>& nodes, const std::function<int(uint32_t, const float*, const float*, QChild*)>& map_leaf,
-                     std::vector<QNode>* out);
+// slots: the binary tree's slots as dscene.h lays them out (routing bits in slots[4k + 2].w); kinds: per primitive, 0 triangle / 1 curve.
+void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out);
+
+// Where the random walks' rays start (dscene.h::SssEntry), per instance: the cut of the Q tree around the instance's primitive
+// bounds ilo / ihi (3 floats per instance) with at most max_foreign foreign references.  entry 0: start at the root.
+std::vector<SssEntry> build_sss_entries(const std::vector<QNode>& wide, const std::vector<float>& ilo, const std::vector<float>& ihi,
+                                        uint32_t max_foreign);
 
 // The same tree format built on the GPU (bvh_gpu.hip: Morton-order linear BVH).  nodes_out: DEVICE array of
 // max(n - 1, 1) nodes; order_out: slot -> primitive index; depth_out: traversal stack depth needed.

@@ -405,43 +405,34 @@ static Material make_material(const HostMaterial& hm) {
 // End points of linear piece `sub` of a cubic Bezier (control points xyzr): B(sub/4) and B((sub+1)/4), evaluated with
 // the arithmetic of the intersection contract (Bernstein weights, products summed left to right, single precision,
 // no contraction) so that every back end tests the same segment.
-static void bezier_point(const float* cp, float u, float out[4]) {
-  const float s = 1.0f - u;
-  const float b0 = s * s * s, b1 = 3.0f * u * s * s, b2 = 3.0f * u * u * s, b3 = u * u * u;
-  for (int k = 0; k < 4; k++) out[k] = ((cp[k] * b0 + cp[4 + k] * b1) + cp[8 + k] * b2) + cp[12 + k] * b3;
-}
 static void curve_piece(const float* cp, uint32_t sub, float a[4], float b[4]) {
-  bezier_point(cp, (float)sub * 0.25f, a);
-  bezier_point(cp, (float)(sub + 1) * 0.25f, b);
+  for (uint32_t e = 0; e < 2; e++) {
+    const float u = (float)(sub + e) * 0.25f, s = 1.0f - u;
+    const float b0 = s * s * s, b1 = 3.0f * u * s * s, b2 = 3.0f * u * u * s, b3 = u * u * u;
+    for (int k = 0; k < 4; k++) (e ? b : a)[k] = ((cp[k] * b0 + cp[4 + k] * b1) + cp[8 + k] * b2) + cp[12 + k] * b3;
+  }
 }
 
-extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
-  return guarded([&]() -> int {
-  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
-  HIPCHK(hipSetDevice(s->device));
-  for (uint32_t i = 0; i < s->instances.size(); i++) register_lights(s, i);
-  commit_lights(s);
-
-  // flatten primitives in canonical (instance, geom, prim) order = gid
-  std::vector<PrimRef> prims;
+// Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.
+static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
   for (uint32_t i = 0; i < s->instances.size(); i++)
     for (uint32_t g = 0; g < s->instances[i].material_ids.size(); g++) {
       const HostMesh& m = *inst_mesh(s, i, g);
       if (s->instances[i].material_ids[g].size() != m.num_prims())
         return fail(PBRHIP_ESIZE, "material param error (instance %u geom %u)", i, g);
       for (uint32_t p = 0; p < m.num_prims(); p++)
-        for (uint32_t sub = 0; sub < (m.kind == 1 ? 4u : 1u); sub++) prims.push_back({i, g, p, (uint32_t)m.kind, sub});
+        for (uint32_t sub = 0; sub < (m.kind == 1 ? 4u : 1u); sub++) prims->push_back({i, g, p, (uint32_t)m.kind, sub});
     }
-  uint32_t np = (uint32_t)prims.size();
-  if (np >= (1u << 27)) return fail(PBRHIP_EUNSUPPORTED, "too many primitives (%u)", np);
-  std::vector<float> lo(3 * (size_t)np), hi(3 * (size_t)np);
-  std::vector<uint8_t> kinds(np);
+  return PBRHIP_OK;
+}
+
+// Scene bounds (rtcGetSceneBounds, raytracer_impl.cc:199-202; they place the camera): the union of the instances'
+// bounds.  An RTC_GEOMETRY_TYPE_INSTANCE (raytracer_impl.cc:61-81) reports the box of the transformed CORNERS of its local
+// scene's box -- larger than the box of the transformed geometry under rotation or shear; an instance whose matrix is
+// bit for bit the identity reports the local box.  Local box: triangles by their corners, curves by the hull of their
+// control points widened by the largest control radius.  (The tree is built over the transformed primitives.)
+static void scene_bounds(pbrhip_scene* s) {
   const float inf = std::numeric_limits<float>::infinity();
-  // Scene bounds (rtcGetSceneBounds, raytracer_impl.cc:199-202; they place the camera): the union of the instances'
-  // bounds.  An RTC_GEOMETRY_TYPE_INSTANCE (raytracer_impl.cc:61-81) reports the box of the transformed CORNERS of its local
-  // scene's box -- larger than the box of the transformed geometry under rotation or shear; an instance whose matrix is
-  // bit for bit the identity reports the local box.  Local box: triangles by their corners, curves by the hull of their
-  // control points widened by the largest control radius.  (The tree below is built over the transformed primitives.)
   float bmin[3] = {inf, inf, inf}, bmax[3] = {-inf, -inf, -inf};
   for (uint32_t i = 0; i < s->instances.size(); i++) {
     const HostInstance& inst = s->instances[i];
@@ -479,12 +470,22 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
       }
     }
   }
+  memcpy(s->bmin, bmin, sizeof(bmin));
+  memcpy(s->bmax, bmax, sizeof(bmax));
+}
+
+// The box (world space) and kind of every primitive: what the tree is built over.
+static void prim_boxes(const pbrhip_scene* s, const std::vector<PrimRef>& prims, std::vector<float>* lo, std::vector<float>* hi,
+                       std::vector<uint8_t>* kinds) {
+  const float inf = std::numeric_limits<float>::infinity();
+  const uint32_t np = (uint32_t)prims.size();
+  lo->assign(3 * (size_t)np, 0.f), hi->assign(3 * (size_t)np, 0.f), kinds->assign(np, 0);
   for (uint32_t g = 0; g < np; g++) {
     const PrimRef& pr = prims[g];
     const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
     const HostInstance& inst = s->instances[pr.instance_id];
     float l[3] = {inf, inf, inf}, h[3] = {-inf, -inf, -inf};
-    kinds[g] = (uint8_t)pr.kind;
+    (*kinds)[g] = (uint8_t)pr.kind;
     if (pr.kind == 0) {
       for (int c = 0; c < 3; c++) {
         V3 v = world_vertex(inst, m, pr.prim_id, c);
@@ -501,47 +502,20 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
       const float r = std::max(fabsf(a[3]), fabsf(b[3]));
       for (int k = 0; k < 3; k++) l[k] = std::min(a[k], b[k]) - r, h[k] = std::max(a[k], b[k]) + r;
     }
-    for (int k = 0; k < 3; k++) lo[3 * g + k] = l[k], hi[3 * g + k] = h[k];
+    for (int k = 0; k < 3; k++) (*lo)[3 * g + k] = l[k], (*hi)[3 * g + k] = h[k];
   }
-  memcpy(s->bmin, bmin, sizeof(bmin));
-  memcpy(s->bmax, bmax, sizeof(bmax));
+}
 
-  FlatBvh bvh;
-  bool gpu_built = false;
-  uint32_t num_nodes = 0;
-  int builder = s->bvh_builder;
-  if (const char* e = getenv("PBRHIP_BVH")) builder = (strcmp(e, "gpu") == 0) ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
-  if (builder == PBRHIP_BVH_GPU_LBVH && np > 0) {
-    HIPCHK(s->d_nodes.reserve(std::max<size_t>(np > 1 ? np - 1 : 1, 1) + np));  // nodes, then one 64-byte slot per primitive
-    HIPCHK(build_bvh_gpu(s->stream, lo, hi, kinds, s->d_nodes.p, &bvh.slot_gid, &bvh.depth));
-    if (bvh.depth > (uint32_t)kStackDepth) {
-      // a Morton-order tree over badly distributed primitives can be deeper than the traversal stack: use the SAH tree
-      fprintf(stderr, "pbrhip: GPU-built BVH is %u deep (stack %d): building on the host instead\n", bvh.depth, kStackDepth);
-      bvh = FlatBvh();
-    } else {
-      gpu_built = true;
-      num_nodes = np > 1 ? np - 1 : 1;
-    }
-  }
-  if (!gpu_built) {
-    build_bvh(lo, hi, kinds, &bvh);
-    num_nodes = (uint32_t)bvh.nodes.size();
-  }
-  s->bvh_built_on_gpu = gpu_built;
-  if (bvh.depth > (uint32_t)kStackDepth)
-    return fail(PBRHIP_EOVERFLOW, "BVH depth %u exceeds the traversal stack (%d)", bvh.depth, kStackDepth);
-  s->bvh_depth = bvh.depth;
-
-  // light records: one per (light, prim), concatenated
-  std::vector<LightHead> heads(s->lights.size());
-  std::vector<LightRec> lrecs;
-  std::vector<float> lprim_cdf;
+// Light records: one per (light, prim), concatenated; heads[l] is light l's stretch of them.
+static void light_records(const pbrhip_scene* s, std::vector<LightHead>* heads, std::vector<LightRec>* lrecs,
+                          std::vector<float>* lprim_cdf) {
+  heads->resize(s->lights.size());
   for (size_t l = 0; l < s->lights.size(); l++) {
     const HostLight& L = s->lights[l];
     const HostAreaLight& a = s->instances[L.instance_id].area_lights[L.geom_id];
     const HostMesh& m = *inst_mesh(s, L.instance_id, L.geom_id);
-    heads[l].first = (uint32_t)lrecs.size();
-    heads[l].count = m.nfaces;
+    (*heads)[l].first = (uint32_t)lrecs->size();
+    (*heads)[l].count = m.nfaces;
     for (uint32_t f = 0; f < m.nfaces; f++) {
       LightRec r;
       memset(&r, 0, sizeof(r));
@@ -557,29 +531,31 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
         V3 e = s->light_params[a.light_param_ids[f]];
         r.emission[0] = e.x, r.emission[1] = e.y, r.emission[2] = e.z;
       }
-      lrecs.push_back(r);
-      lprim_cdf.push_back(a.cdf[f]);
+      lrecs->push_back(r);
+      lprim_cdf->push_back(a.cdf[f]);
     }
   }
+}
 
-  // leaf-ordered slots (traversal geometry) + one 128-byte ShadeRec per slot (everything shading needs)
-  uint32_t ns = (uint32_t)bvh.slot_gid.size();
-  if (ns > kHitSlotMask) return fail(PBRHIP_EINVAL, "%u traversal primitives: at most %u are supported", ns, kHitSlotMask);
-  std::vector<float4> slots(4 * (size_t)ns);
-  std::vector<ShadeRec> shade(ns);
+// Leaf-ordered slots (traversal geometry, 64 B each) + one 128-byte ShadeRec per slot (everything shading needs).
+static int slots_and_shade(const pbrhip_scene* s, const std::vector<PrimRef>& prims, const std::vector<uint32_t>& slot_gid,
+                           const std::vector<LightHead>& heads, std::vector<float4>* slots, std::vector<ShadeRec>* shade) {
+  const uint32_t ns = (uint32_t)slot_gid.size();
+  slots->resize(4 * (size_t)ns);
+  shade->resize(ns);
   for (uint32_t k = 0; k < ns; k++) {
-    uint32_t g = bvh.slot_gid[k];
+    uint32_t g = slot_gid[k];
     const PrimRef& pr = prims[g];
     const HostInstance& in = s->instances[pr.instance_id];
     const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
     uint32_t mat = in.material_ids[pr.geom_id][pr.prim_id];
     if (mat != kNone && (mat >= s->materials.size() || mat >= 0x00FFFFFFu)) return fail(PBRHIP_EINVAL, "material id %u out of range", mat);
-    ShadeRec& sr = shade[k];
+    ShadeRec& sr = (*shade)[k];
     memset(&sr, 0, sizeof(sr));
     uint32_t flags = 0, lightrec = kNone;
     if (mat == kNone) flags |= kSlotMatNone;
     else if (s->materials[mat].kind == kMatHair) flags |= kSlotMatHair;
-    float4* sl = &slots[4 * (size_t)k];
+    float4* sl = &(*slots)[4 * (size_t)k];
     for (int c = 0; c < 4; c++) sl[c] = make_float4(0, 0, 0, 0);
     if (pr.kind == 0) {
       for (int c = 0; c < 3; c++) {
@@ -641,6 +617,75 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
     sl[2].w = __builtin_bit_cast(float, route);  // travels with the hit record (Hit::slot)
     sr.instance_id = pr.instance_id, sr.geom_id = pr.geom_id, sr.prim_id = pr.prim_id;
   }
+  return PBRHIP_OK;
+}
+
+// One box per light over all primitives of its mesh, packed two per node (an odd last one is stored twice).
+static std::vector<BvhNode> light_boxes(const std::vector<LightHead>& heads, const std::vector<LightRec>& lrecs) {
+  std::vector<BvhNode> boxes((heads.size() + 1) / 2);
+  for (size_t l = 0; l < heads.size(); l++) {
+    float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t f = heads[l].first; f < heads[l].first + heads[l].count; f++)
+      for (const float* p : {lrecs[f].p0, lrecs[f].p1, lrecs[f].p2})
+        for (int a = 0; a < 3; a++) lo3[a] = std::min(lo3[a], p[a]), hi3[a] = std::max(hi3[a], p[a]);
+    BvhNode& nd = boxes[l / 2];
+    if (l % 2 == 0) memset(&nd, 0, sizeof(nd)), nd.set_box(1, lo3, hi3);
+    nd.set_box(int(l % 2), lo3, hi3);
+  }
+  return boxes;
+}
+
+extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  HIPCHK(hipSetDevice(s->device));
+  for (uint32_t i = 0; i < s->instances.size(); i++) register_lights(s, i);
+  commit_lights(s);
+
+  std::vector<PrimRef> prims;
+  if (int rc = flatten_prims(s, &prims)) return rc;
+  uint32_t np = (uint32_t)prims.size();
+  if (np >= (1u << 27)) return fail(PBRHIP_EUNSUPPORTED, "too many primitives (%u)", np);
+  std::vector<float> lo, hi;
+  std::vector<uint8_t> kinds;
+  prim_boxes(s, prims, &lo, &hi, &kinds);
+  scene_bounds(s);
+
+  FlatBvh bvh;
+  bool gpu_built = false;
+  uint32_t num_nodes = 0;
+  int builder = s->bvh_builder;
+  if (const char* e = getenv("PBRHIP_BVH")) builder = (strcmp(e, "gpu") == 0) ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+  if (builder == PBRHIP_BVH_GPU_LBVH && np > 0) {
+    HIPCHK(s->d_nodes.reserve(std::max<size_t>(np > 1 ? np - 1 : 1, 1) + np));  // nodes, then one 64-byte slot per primitive
+    HIPCHK(build_bvh_gpu(s->stream, lo, hi, kinds, s->d_nodes.p, &bvh.slot_gid, &bvh.depth));
+    if (bvh.depth > (uint32_t)kStackDepth) {
+      // a Morton-order tree over badly distributed primitives can be deeper than the traversal stack: use the SAH tree
+      fprintf(stderr, "pbrhip: GPU-built BVH is %u deep (stack %d): building on the host instead\n", bvh.depth, kStackDepth);
+      bvh = FlatBvh();
+    } else {
+      gpu_built = true;
+      num_nodes = np > 1 ? np - 1 : 1;
+    }
+  }
+  if (!gpu_built) {
+    build_bvh(lo, hi, kinds, &bvh);
+    num_nodes = (uint32_t)bvh.nodes.size();
+  }
+  s->bvh_built_on_gpu = gpu_built;
+  if (bvh.depth > (uint32_t)kStackDepth)
+    return fail(PBRHIP_EOVERFLOW, "BVH depth %u exceeds the traversal stack (%d)", bvh.depth, kStackDepth);
+  s->bvh_depth = bvh.depth;
+
+  std::vector<LightHead> heads;
+  std::vector<LightRec> lrecs;
+  std::vector<float> lprim_cdf;
+  light_records(s, &heads, &lrecs, &lprim_cdf);
+  const uint32_t ns = (uint32_t)bvh.slot_gid.size();
+  if (ns > kHitSlotMask) return fail(PBRHIP_EINVAL, "%u traversal primitives: at most %u are supported", ns, kHitSlotMask);
+  std::vector<float4> slots;
+  std::vector<ShadeRec> shade;
+  if (int rc = slots_and_shade(s, prims, bvh.slot_gid, heads, &slots, &shade)) return rc;
   std::vector<Material> mats(s->materials.size());
   s->has_hair = s->has_sss = s->has_textured = false;
   for (size_t i = 0; i < mats.size(); i++) {
@@ -664,217 +709,39 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   }
   if (ns) HIPCHK(hipMemcpyAsync(s->d_nodes.p + num_nodes, slots.data(), (size_t)ns * 64, hipMemcpyHostToDevice, st));
   // The Q tree of the traversal kernels (host-built trees; PBRHIP_WIDE=0 at commit: none): the binary tree collapsed to four
-  // children per node with quantised boxes (64 B per node), followed by its own compact triangle slots and by the curve
-  // pieces stored as chains of points (16 B per piece instead of a 64-byte slot): dscene.h::QNode.
-  std::vector<QNode> wide;
-  std::vector<float4> qtri, qpts;
-  std::vector<uint32_t> qhit;
+  // children per node with quantised boxes (64 B per node), followed by its own compact triangle leaves and curve records
+  // (bvh_build.cpp::build_qlayout, dscene.h::QNode).
+  QLayout q;
   const char* wide_env = getenv("PBRHIP_WIDE");
-  static_assert(kMaxLeaf <= 2, "build_qtree expects at most two primitives per leaf of the binary tree");
   if (!gpu_built && num_nodes && !(wide_env && atoi(wide_env) == 0)) {
-    // points: the cubics in canonical order; a cubic whose first point equals the last point of its predecessor (same mesh,
-    // bit for bit: the segments of a strand) continues that chain, otherwise a new chain starts at the next multiple of 4
-    std::vector<uint32_t> piece_point(np, kNone);
-    {
-      uint32_t prev_inst = kNone, prev_geom = kNone;
-      for (uint32_t g = 0; g < np && !PB_CURVE_RECORDS; g++) {  // (curve records: no chains)
-        const PrimRef& pr = prims[g];
-        if (pr.kind != 1 || pr.sub != 0) continue;
-        float wcps[16], pt[5][4];
-        world_curve(s->instances[pr.instance_id], *inst_mesh(s, pr.instance_id, pr.geom_id), pr.prim_id, wcps);
-        for (int j = 0; j < 5; j++) bezier_point(wcps, (float)j * 0.25f, pt[j]);
-        const bool chained = !qpts.empty() && pr.instance_id == prev_inst && pr.geom_id == prev_geom &&
-                             memcmp(&qpts.back(), pt[0], 16) == 0;
-        if (!chained) {
-          while (qpts.size() % 4) qpts.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-          qpts.push_back(make_float4(pt[0][0], pt[0][1], pt[0][2], pt[0][3]));
-        }
-        const uint32_t start = (uint32_t)qpts.size() - 1u;  // index of this cubic's first point (a multiple of 4)
-        for (int j = 1; j < 5; j++) qpts.push_back(make_float4(pt[j][0], pt[j][1], pt[j][2], pt[j][3]));
-        for (uint32_t sub = 0; sub < 4; sub++) piece_point[g + sub] = start + sub;  // (the four pieces of a cubic are consecutive gids)
-        prev_inst = pr.instance_id, prev_geom = pr.geom_id;
-      }
-      for (int k = 0; k < 4; k++) qpts.push_back(make_float4(0.f, 0.f, 0.f, 0.f));  // (the last piece reads point p + 1)
-    }
-    // the complete hit code of every slot (slot | routing bits); curve pieces: per point
-    std::vector<uint32_t> slot_code(ns, kNone);
-    qhit.assign(qpts.size(), kNone);
-    for (uint32_t k = 0; k < ns; k++) {
-      const uint32_t g = bvh.slot_gid[k];
-      slot_code[k] = k | __builtin_bit_cast(uint32_t, slots[4 * (size_t)k + 2].w);
-      if (prims[g].kind != 0 && piece_point[g] != kNone) qhit[piece_point[g]] = slot_code[k];
-    }
-    // Triangle leaves.  Triangle-only scenes: one TriPair per leaf (dscene.h): its one or two triangles interleaved coordinate by
-    // coordinate, 80 bytes, both tested at once on packed fp32.  Scenes with curves (their kernels have no registers to spare
-    // and meet triangles rarely): 48 bytes per triangle -- three corners, the hit code in the third word's .w -- one after the other.
-    bool tri_pairs = true;
-    for (uint8_t kd : kinds) tri_pairs = tri_pairs && kd == 0;
-    // the five words of the TriPair of a triangle leaf (slots first .. first + count - 1 of the binary tree)
-    auto pair_words = [&](uint32_t first, uint32_t count, float4* o) {
-      const float4* a = &slots[4 * (size_t)first];
-      const float4* b = count == 2 ? &slots[4 * (size_t)(first + 1)] : a;  // (one triangle: stored twice, the copy is no candidate)
-      const float ca = __builtin_bit_cast(float, slot_code[first]), cb = __builtin_bit_cast(float, count == 2 ? slot_code[first + 1] : kNone);
-      o[0] = make_float4(a[0].x, b[0].x, a[0].y, b[0].y);
-      o[1] = make_float4(a[0].z, b[0].z, a[1].x, b[1].x);
-      o[2] = make_float4(a[1].y, b[1].y, a[1].z, b[1].z);
-      o[3] = make_float4(a[2].x, b[2].x, a[2].y, b[2].y);
-      o[4] = make_float4(a[2].z, b[2].z, ca, cb);
-    };
-    auto tri_pair = [&](uint32_t first, uint32_t count) -> uint32_t {
-      if (!tri_pairs) {
-        const uint32_t rec = (uint32_t)(qtri.size() / 3);
-        for (uint32_t i = 0; i < count; i++) {
-          for (int c = 0; c < 3; c++) qtri.push_back(slots[4 * (size_t)(first + i) + c]);
-          qtri.back().w = __builtin_bit_cast(float, slot_code[first + i]);
-        }
-        return rec;
-      }
-      const uint32_t rec = (uint32_t)(qtri.size() / kTriPairWords);
-      qtri.resize(qtri.size() + kTriPairWords);
-      pair_words(first, count, &qtri[(size_t)rec * kTriPairWords]);
-      return rec;
-    };
-    size_t leaves_one = 0, leaves_pair = 0, leaves_split = 0;  // curve leaves of one piece / of two pieces / binary leaves cut in two (PBRHIP_DEBUG)
-    const bool curve_records = PB_CURVE_RECORDS != 0;  // (a build option: the traversal kernels are compiled for one leaf format)
-    auto map_leaf = [&](uint32_t ref, const float* blo, const float* bhi, QChild* o) -> int {
-      const uint32_t first = (ref & 0x3FFFFFFFu) >> 3, count = (ref & 7u) + 1u;
-      if (!(ref & kCurveBit)) {
-        o[0].ref = kLeafBit | (tri_pair(first, count) << 3) | (count - 1u);
-        for (int a = 0; a < 3; a++) o[0].lo[a] = blo[a], o[0].hi[a] = bhi[a];
-        return 1;
-      }
-      if (curve_records) {
-        // a record (dscene.h): the end points of the leaf's one or two pieces, 64-byte aligned, tested in one turn
-        while (qpts.size() % 4) qpts.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-        const uint32_t P = (uint32_t)qpts.size();
-        uint32_t sub[2] = {0u, 0u};
-        for (uint32_t i = 0; i < count; i++) {
-          const float4* sl = &slots[4 * (size_t)(first + i)];  // (a piece's slot of the binary tree: its two end points, then its index in the cubic)
-          qpts.push_back(sl[0]), qpts.push_back(sl[1]);
-          sub[i] = __builtin_bit_cast(uint32_t, sl[2].x) & 3u;
-        }
-        qhit.resize(qpts.size(), kNone);
-        qhit[P] = slot_code[first];
-        if (count == 2) qhit[P + 2] = slot_code[first + 1];
-        o[0].ref = kLeafBit | kCurveBit | ((P | sub[0]) << 3) | (count == 2 ? (kCurvePairBit | sub[1]) : 0u);
-        for (int a = 0; a < 3; a++) o[0].lo[a] = blo[a], o[0].hi[a] = bhi[a];
-        (count == 2 ? leaves_pair : leaves_one)++;
-        return 1;
-      }
-      uint32_t p0 = piece_point[bvh.slot_gid[first]];
-      if (count == 2) {
-        uint32_t p1 = piece_point[bvh.slot_gid[first + 1]];
-        if ((p0 > p1 ? p0 - p1 : p1 - p0) != 1u) {  // not neighbours in a chain: two leaves, each with its own (widened) box
-          for (uint32_t i = 0; i < 2; i++) {
-            const uint32_t g = bvh.slot_gid[first + i];
-            o[i].ref = kLeafBit | kCurveBit | (piece_point[g] << 3);
-            for (int a = 0; a < 3; a++) o[i].lo[a] = BvhNode::widen_lo(lo[3 * (size_t)g + a]), o[i].hi[a] = BvhNode::widen_hi(hi[3 * (size_t)g + a]);
-          }
-          leaves_split++;
-          return 2;
-        }
-        p0 = std::min(p0, p1);
-      }
-      o[0].ref = kLeafBit | kCurveBit | (p0 << 3) | (count - 1u);
-      for (int a = 0; a < 3; a++) o[0].lo[a] = blo[a], o[0].hi[a] = bhi[a];
-      (count == 2 ? leaves_pair : leaves_one)++;
-      return 1;
-    };
-    if (build_qtree(bvh.nodes, map_leaf, &wide) > (uint32_t)kStackDepth || qpts.size() >= (1u << 27)) wide.clear();
-    while (qtri.size() % 4) qtri.push_back(make_float4(0.f, 0.f, 0.f, 0.f));  // (q_pt0 a multiple of 4: the low bits of a curve record's address are free)
-    for (int k = 0; k < 4; k++) qpts.push_back(make_float4(0.f, 0.f, 0.f, 0.f));  // (the load site reads four words of a leaf)
-    qhit.resize(qpts.size(), kNone);
-    if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces, %zu binary leaves cut in two\n", leaves_one, leaves_pair, leaves_split);
+    build_qlayout(bvh, slots, kinds, &q);
+    if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
   }
+  const std::vector<QNode>& wide = q.nodes;
   // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
   std::vector<SssEntry> sss_entries;
   if (!wide.empty() && env_u32("PBRHIP_SSS_ENTRY", 1u) != 0u) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
     const size_t ninst = s->instances.size();
-    // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
-    const uint32_t max_foreign = std::min(env_u32("PBRHIP_SSS_FOREIGN", 3u), kSssMaxForeign);
-    sss_entries.assign(ninst, SssEntry{});
     std::vector<float> ilo(3 * ninst, INFINITY), ihi(3 * ninst, -INFINITY);
     for (uint32_t g = 0; g < np; g++)
-      for (int a = 0; a < 3; a++) {
-        float& l = ilo[3 * (size_t)prims[g].instance_id + a];
-        float& h = ihi[3 * (size_t)prims[g].instance_id + a];
-        l = std::min(l, lo[3 * (size_t)g + a]), h = std::max(h, hi[3 * (size_t)g + a]);
-      }
-    struct CutRef {
-      uint32_t ref;
-      float lo[3], hi[3];
-    };
-    for (size_t i = 0; i < ninst; i++) {
-      SssEntry& E = sss_entries[i];
-      if (!(ilo[3 * i] <= ihi[3 * i])) continue;  // (no primitive)
-      float ext = 0.f;
-      for (int a = 0; a < 3; a++) ext = std::max(ext, ihi[3 * i + a] - ilo[3 * i + a]);
-      if (!(ext > 0.f) || !std::isfinite(ext)) continue;
-      const float m1 = 1e-4f * ext, m2 = 2e-3f * ext;  // the region rays may stay in / how far beyond it a primitive's box can matter
-      float rlo[3], rhi[3], wlo[3], whi[3];
-      for (int a = 0; a < 3; a++) rlo[a] = ilo[3 * i + a] - m1, rhi[a] = ihi[3 * i + a] + m1, wlo[a] = rlo[a] - m2, whi[a] = rhi[a] + m2;
-      std::vector<CutRef> cut{{0u, {-INFINITY, -INFINITY, -INFINITY}, {INFINITY, INFINITY, INFINITY}}};
-      for (bool changed = true; changed;) {
-        changed = false;
-        for (size_t c = 0; c < cut.size() && !changed; c++) {
-          if (cut[c].ref & kLeafBit) continue;
-          const QNode& nd = wide[cut[c].ref];
-          const float org[3] = {nd.org[0], nd.org[1], nd.org[2]}, st3[3] = {nd.sx, nd.sy, nd.sz};
-          const uint32_t ql[3] = {nd.qlo_x, nd.qlo_y, nd.qlo_z}, qh[3] = {nd.qhi_x, nd.qhi_y, nd.qhi_z};
-          std::vector<CutRef> kids;
-          int nchild = 0;
-          for (int k = 0; k < 4; k++) {
-            if (nd.c[k] == kEmptyChild) continue;
-            nchild++;
-            CutRef r;
-            r.ref = nd.c[k];
-            bool meets = true;
-            for (int a = 0; a < 3; a++) {  // the box the traversal rebuilds for this child (dtrace.h::box_test4q): fma(q, s, org)
-              r.lo[a] = fmaf((float)((ql[a] >> (8 * k)) & 255u), st3[a], org[a]);
-              r.hi[a] = fmaf((float)((qh[a] >> (8 * k)) & 255u), st3[a], org[a]);
-              meets = meets && r.lo[a] <= whi[a] && r.hi[a] >= wlo[a];
-            }
-            if (meets) kids.push_back(r);
-          }
-          // descend where that drops a child (or leads to an only child), while the cut stays small
-          if (((int)kids.size() < nchild || kids.size() == 1) && cut.size() - 1 + kids.size() <= 1u + max_foreign) {
-            cut.erase(cut.begin() + (ptrdiff_t)c);
-            cut.insert(cut.end(), kids.begin(), kids.end());
-            changed = true;
-          }
-        }
-      }
-      // the entry: the inner node of the cut that shares the most volume with the instance's bounds
-      int best = -1;
-      double best_v = -1.0;
-      for (size_t c = 0; c < cut.size(); c++) {
-        if (cut[c].ref & kLeafBit) continue;
-        double v = 1.0;
-        for (int a = 0; a < 3; a++) v *= std::max(0.0, (double)std::min(cut[c].hi[a], ihi[3 * i + a]) - (double)std::max(cut[c].lo[a], ilo[3 * i + a]));
-        if (v > best_v) best_v = v, best = (int)c;
-      }
-      if (best < 0 || cut[(size_t)best].ref == 0u) continue;  // (the root, or leaves only: start at the root)
-      E.entry = cut[(size_t)best].ref;
-      for (int a = 0; a < 3; a++) E.lo[a] = rlo[a], E.hi[a] = rhi[a];
-      for (size_t c = 0; c < cut.size(); c++) {
-        if ((int)c == best) continue;
-        auto& f = E.foreign[E.nforeign++];
-        f.ref = cut[c].ref;
-        for (int a = 0; a < 3; a++) f.lo[a] = cut[c].lo[a], f.hi[a] = cut[c].hi[a];
-      }
-      if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, E.entry, E.nforeign);
-    }
+      for (size_t a = 0, i = prims[g].instance_id; a < 3; a++)
+        ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * (size_t)g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * (size_t)g + a]);
+    // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
+    const uint32_t max_foreign = std::min(env_u32("PBRHIP_SSS_FOREIGN", 3u), kSssMaxForeign);
+    sss_entries = build_sss_entries(wide, ilo, ihi, max_foreign);
+    for (size_t i = 0; i < sss_entries.size() && getenv("PBRHIP_DEBUG"); i++)
+      if (sss_entries[i].entry) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, sss_entries[i].entry, sss_entries[i].nforeign);
   }
   if (sss_entries.empty()) s->d_sss_entries.release();
   else HIPCHK(s->d_sss_entries.upload(sss_entries, st));
   if (wide.empty()) s->d_wide.release(), s->d_qhit.release();
-  if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, qtri.size() / kTriPairWords, qpts.size());
+  if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q.tri.size() / kTriPairWords, q.pts.size());
   if (!wide.empty()) {
-    HIPCHK(s->d_wide.reserve(wide.size() * 4 + qtri.size() + qpts.size()));
+    HIPCHK(s->d_wide.reserve(wide.size() * 4 + q.tri.size() + q.pts.size()));
     HIPCHK(hipMemcpyAsync(s->d_wide.p, wide.data(), wide.size() * sizeof(QNode), hipMemcpyHostToDevice, st));
-    if (!qtri.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4, qtri.data(), qtri.size() * 16, hipMemcpyHostToDevice, st));
-    if (!qpts.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4 + qtri.size(), qpts.data(), qpts.size() * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(s->d_qhit.upload(qhit, st));
+    if (!q.tri.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4, q.tri.data(), q.tri.size() * 16, hipMemcpyHostToDevice, st));
+    if (!q.pts.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4 + q.tri.size(), q.pts.data(), q.pts.size() * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(s->d_qhit.upload(q.hit, st));
   }
   HIPCHK(s->d_shade.upload(shade, st));
   HIPCHK(s->d_materials.upload(mats, st));
@@ -882,18 +749,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   HIPCHK(s->d_heads.upload(heads, st));
   HIPCHK(s->d_lprim_cdf.upload(lprim_cdf, st));
   HIPCHK(s->d_lrecs.upload(lrecs, st));
-  // one box per light over all primitives of its mesh, packed two per node (an odd last one is stored twice)
-  std::vector<BvhNode> light_boxes((heads.size() + 1) / 2);
-  for (size_t l = 0; l < heads.size(); l++) {
-    float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t f = heads[l].first; f < heads[l].first + heads[l].count; f++)
-      for (const float* p : {lrecs[f].p0, lrecs[f].p1, lrecs[f].p2})
-        for (int a = 0; a < 3; a++) lo3[a] = std::min(lo3[a], p[a]), hi3[a] = std::max(hi3[a], p[a]);
-    BvhNode& nd = light_boxes[l / 2];
-    if (l % 2 == 0) memset(&nd, 0, sizeof(nd)), nd.set_box(1, lo3, hi3);
-    nd.set_box(int(l % 2), lo3, hi3);
-  }
-  HIPCHK(s->d_light_boxes.upload(light_boxes, st));
+  HIPCHK(s->d_light_boxes.upload(light_boxes(heads, lrecs), st));
   HIPCHK(s->d_tex_pixels.upload(s->tex_pixels, st));
   HIPCHK(s->d_tex_descs.upload(s->tex_descs, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -907,7 +763,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   d.num_curves = 0;
   for (uint8_t kd : kinds) d.num_curves += kd ? 1u : 0u;
   d.wide = wide.empty() ? nullptr : s->d_wide.p, d.wide_nodes = (uint32_t)wide.size();
-  d.q_tri0 = (uint32_t)wide.size() * 4u, d.q_pt0 = d.q_tri0 + (uint32_t)qtri.size(), d.q_hitcode = wide.empty() ? nullptr : s->d_qhit.p;
+  d.q_tri0 = (uint32_t)wide.size() * 4u, d.q_pt0 = d.q_tri0 + (uint32_t)q.tri.size(), d.q_hitcode = wide.empty() ? nullptr : s->d_qhit.p;
   d.top_nodes = gpu_built ? 0u : std::min<uint32_t>(num_nodes, (uint32_t)kTopNodes);
   d.wide_top_nodes = std::min<uint32_t>((uint32_t)wide.size(), (uint32_t)kTopNodes);
   // light sampling works on the meshes' local positions (light-manager.h:128-136 "TODO transform"), the raytracer on the

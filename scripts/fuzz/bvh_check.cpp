@@ -1,4 +1,5 @@
-// host BVH builder under ASan/UBSan: random / degenerate inputs, structural validation of the flattened tree
+// host BVH builders under ASan/UBSan: random / degenerate inputs, structural validation of the binary tree, of the Q tree's
+// device layout (build_qlayout) and of the random walks' entries (build_sss_entries)
 #include <math.h>
 #include <algorithm>
 #include <cstdio>
@@ -36,7 +37,7 @@ int main() {
     if (b.slot_gid.size() != n) return printf("FAIL: slot count\n"), 1;
     for (uint32_t g : b.slot_gid) { if (g >= n || seen[g]++) return printf("FAIL: slot permutation\n"), 1; }
     // walk: every leaf range valid, one kind, <= kMaxLeaf; child boxes (stored widened) contain their primitives
-    std::vector<uint32_t> stack{0};
+    std::vector<uint32_t> stack{0}, leaf_first(n, 0), leaf_cnt(n, 0);  // (the binary leaf of every slot: its first slot and count)
     size_t leaves_prims = 0;
     while (!stack.empty()) {
       uint32_t id = stack.back(); stack.pop_back();
@@ -53,49 +54,40 @@ int main() {
             uint32_t g = b.slot_gid[s];
             if ((kinds[g] != 0) != ((ch[c] & kCurveBit) != 0)) return printf("FAIL: leaf kind\n"), 1;
             if (!inside(bl, bh, &lo[3 * g], &hi[3 * g])) return printf("FAIL: leaf box\n"), 1;
+            leaf_first[s] = first, leaf_cnt[s] = cnt;
           }
           leaves_prims += cnt;
         } else stack.push_back(ch[c]);
       }
     }
     if (leaves_prims != n) return printf("FAIL: %zu prims in leaves, %u expected\n", leaves_prims, n), 1;
-    // the Q tree collapsed from it (dscene.h::QNode).  Curve leaves are mapped as the scene commit maps them: piece g of the
-    // input is point g here, so a two-piece leaf whose pieces are not neighbours becomes two leaves.  Checked: every
-    // primitive in exactly one leaf, every node reachable once, every quantised child box -- rebuilt with the device's expression
-    // fmaf(q, s, org) -- contains the binary tree's widened box of each of its primitives and is not looser than two steps, the
-    // reported stack need is the true maximum.
-    std::vector<uint32_t> tri_rank(n, 0);
-    { uint32_t r = 0; for (uint32_t s2 = 0; s2 < n; s2++) if (!kinds[b.slot_gid[s2]]) tri_rank[s2] = r++; }
-    auto map_leaf = [&](uint32_t ref, const float* blo, const float* bhi, QChild* o) -> int {
-      const uint32_t first = (ref & 0x3FFFFFFFu) >> 3, cnt = (ref & 7u) + 1u;
-      if (!(ref & kCurveBit)) {
-        o[0].ref = kLeafBit | (tri_rank[first] << 3) | (cnt - 1u);
-        for (int a = 0; a < 3; a++) o[0].lo[a] = blo[a], o[0].hi[a] = bhi[a];
-        return 1;
-      }
-      uint32_t p0 = b.slot_gid[first];
-      if (cnt == 2) {
-        const uint32_t p1 = b.slot_gid[first + 1];
-        if ((p0 > p1 ? p0 - p1 : p1 - p0) != 1u) {
-          for (uint32_t i = 0; i < 2; i++) {
-            const uint32_t g = b.slot_gid[first + i];
-            o[i].ref = kLeafBit | kCurveBit | (g << 3);
-            for (int a = 0; a < 3; a++) o[i].lo[a] = BvhNode::widen_lo(lo[3 * g + a]), o[i].hi[a] = BvhNode::widen_hi(hi[3 * g + a]);
-          }
-          return 2;
-        }
-        p0 = std::min(p0, p1);
-      }
-      o[0].ref = kLeafBit | kCurveBit | (p0 << 3) | (cnt - 1u);
-      for (int a = 0; a < 3; a++) o[0].lo[a] = blo[a], o[0].hi[a] = bhi[a];
-      return 1;
-    };
-    std::vector<QNode> w;
-    const uint32_t bound = build_qtree(b.nodes, map_leaf, &w);
+    // Slot words as the scene commit writes them (dscene.h): a triangle's corners inside its box, a curve piece's end points and
+    // its index in the cubic; every slot carries a recognisable routing code in slots[4k + 2].w.
+    std::vector<float4> slots(4 * (size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
+    auto code = [&](uint32_t k) { return k | ((b.slot_gid[k] * 0x9E3779B1u) & ~kHitSlotMask); };
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t g = b.slot_gid[k];
+      const float* l = &lo[3 * g]; const float* h = &hi[3 * g];
+      float4* sl = &slots[4 * (size_t)k];
+      sl[0] = make_float4(l[0], l[1], l[2], 0.f), sl[1] = make_float4(h[0], kinds[g] ? h[1] : l[1], h[2], 0.f);
+      sl[2] = kinds[g] ? make_float4(__builtin_bit_cast(float, g & 3u), 0.f, 0.f, 0.f) : make_float4(l[0], h[1], h[2], 0.f);
+      sl[2].w = __builtin_bit_cast(float, code(k) & ~kHitSlotMask);
+    }
+    // The Q tree collapsed from it and its leaves packed as the scene commit packs them (build_qlayout).  Checked: every primitive
+    // in exactly one leaf, every node reachable once, every quantised child box -- rebuilt with the device's expression
+    // fmaf(q, s, org) -- contains the binary tree's widened box of each of its primitives, the reported stack need is the true
+    // maximum; triangle leaves (TriPair / 48-byte) and curve records decode back to their binary leaf's slots and hit codes.
+    QLayout q;
+    build_qlayout(b, slots, kinds, &q);
+    const std::vector<QNode>& w = q.nodes;
     if (w.empty() || w.size() > b.nodes.size()) return printf("FAIL: wide node count\n"), 1;
+    if (q.tri.size() % 4) return printf("FAIL: q_pt0 = 4 x nodes + %zu triangle words is not a multiple of 4\n", q.tri.size()), 1;
+    if (q.pts.size() < 8 || q.pts.size() % 2 || q.hit.size() != q.pts.size()) return printf("FAIL: point / hit code array sizes\n"), 1;
+    if (std::any_of(&q.pts.back().x - 12, &q.pts.back().x + 4, [](float v) { return v != 0.f; })) return printf("FAIL: trailing point words\n"), 1;
+    const bool tri_pairs = std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
+    auto bits = [](float f) { return __builtin_bit_cast(uint32_t, f); };
     std::vector<int> visited(w.size(), 0), prim_seen(n, 0);
-    std::vector<uint32_t> tri_slot_of_rank;
-    for (uint32_t s2 = 0; s2 < n; s2++) if (!kinds[b.slot_gid[s2]]) tri_slot_of_rank.push_back(s2);
+    std::vector<uint32_t> parent(w.size(), kNone), prim_node(n, kNone), prim_leaf(n, kNone);
     struct It { uint32_t id, pending; };
     std::vector<It> st2{{0u, 0u}};
     uint32_t need = 0;
@@ -111,7 +103,8 @@ int main() {
       if (used == 0) return printf("FAIL: wide node without children\n"), 1;
       need = std::max(need, it.pending + (uint32_t)used - 1u);
       for (int c = 0; c < 4; c++) {
-        if (nd.c[c] == kEmptyChild) continue;
+        const uint32_t ref = nd.c[c];
+        if (ref == kEmptyChild) continue;
         float bl[3], bh[3];
         for (int a = 0; a < 3; a++) {
           if (!(sc[a] > 0.f) || !std::isfinite(sc[a])) return printf("FAIL: step\n"), 1;
@@ -122,28 +115,86 @@ int main() {
             if (!(bl[a] <= BvhNode::widen_lo(lo[3 * g + a]) && bh[a] >= BvhNode::widen_hi(hi[3 * g + a]))) return false;
           return true;
         };
-        if (nd.c[c] & kLeafBit) {
-          uint32_t first = (nd.c[c] & 0x3FFFFFFFu) >> 3, cnt = (nd.c[c] & 7u) + 1u;
-          for (uint32_t k = 0; k < cnt; k++) {
-            uint32_t g;
-            if (nd.c[c] & kCurveBit) g = first + k;
-            else {
-              if (first + k >= tri_slot_of_rank.size()) return printf("FAIL: triangle slot range\n"), 1;
-              g = b.slot_gid[tri_slot_of_rank[first + k]];
-            }
-            if (g >= n || prim_seen[g]++) return printf("FAIL: primitive in two wide leaves\n"), 1;
-            if ((kinds[g] != 0) != ((nd.c[c] & kCurveBit) != 0)) return printf("FAIL: wide leaf kind\n"), 1;
-            if (!check_prim(g)) return printf("FAIL: quantised box does not contain its primitive\n"), 1;
-          }
-          wide_prims += cnt;
-        } else {
-          st2.push_back({nd.c[c], it.pending + (uint32_t)used - 1u});
+        if (!(ref & kLeafBit)) {
+          if (ref < w.size()) parent[ref] = it.id;
+          st2.push_back({ref, it.pending + (uint32_t)used - 1u});
+          continue;
         }
+        // decode the leaf into the slots it holds
+        const uint32_t first = (ref & 0x3FFFFFFFu) >> 3;
+        uint32_t ks[2], cnt;
+        if (ref & kCurveBit) {  // a curve record: kLeafBit | kCurveBit | (P | i_a) << 3 | (pair ? kCurvePairBit | i_b : 0)
+          const uint32_t P = first & ~3u;
+          cnt = (ref & kCurvePairBit) ? 2u : 1u;
+          if (cnt == 1 && (ref & 3u)) return printf("FAIL: curve record of one piece with a second index\n"), 1;
+          if (P >= (1u << 27) || P + 2 * cnt > q.pts.size() - 4) return printf("FAIL: curve record position %u\n", P), 1;
+          for (uint32_t i = 0; i < cnt; i++) {
+            const uint32_t hc = q.hit[P + 2 * i], k = ks[i] = hc & kHitSlotMask;
+            if (k >= n || hc != code(k)) return printf("FAIL: hit code at point %u\n", P + 2 * i), 1;
+            if (memcmp(&q.pts[P + 2 * i], &slots[4 * (size_t)k], 32)) return printf("FAIL: record words\n"), 1;
+            if ((i ? ref : first) % 4 != (bits(slots[4 * (size_t)k + 2].x) & 3u)) return printf("FAIL: piece index in the reference\n"), 1;
+          }
+        } else {  // triangles: a TriPair (five words, the two interleaved coordinate by coordinate) or 48 bytes each (code in .w)
+          cnt = (ref & 7u) + 1u;
+          const size_t at0 = (size_t)first * (tri_pairs ? kTriPairWords : 3u);
+          if (at0 + (tri_pairs ? kTriPairWords : 3u * cnt) > q.tri.size()) return printf("FAIL: triangle leaf range\n"), 1;
+          const float* t = &q.tri[at0].x;
+          auto at = [&](uint32_t i, int c, int j) { return tri_pairs ? t[(3 * c + j) * 2 + i] : t[12 * i + 4 * c + j]; };
+          for (uint32_t i = 0; i < (tri_pairs ? 2u : cnt); i++) {
+            const uint32_t hc = bits(tri_pairs ? t[18 + i] : t[12 * i + 11]), k = ks[i] = hc & kHitSlotMask;
+            if (i == cnt) {  // a TriPair of one triangle stores it twice, the copy with code kNone
+              for (int c = 0; c < 9; c++) if (hc != kNone || at(1, c / 3, c % 3) != at(0, c / 3, c % 3)) return printf("FAIL: TriPair copy\n"), 1;
+              continue;
+            }
+            if (k >= n || hc != code(k)) return printf("FAIL: triangle code\n"), 1;
+            for (int c = 0; c < 9; c++)
+              if (at(i, c / 3, c % 3) != (&slots[4 * (size_t)k + c / 3].x)[c % 3]) return printf("FAIL: triangle corners\n"), 1;
+          }
+        }
+        // the leaf is exactly one binary leaf, in slot order
+        if (leaf_first[ks[0]] != ks[0] || leaf_cnt[ks[0]] != cnt || (cnt == 2 && ks[1] != ks[0] + 1u)) return printf("FAIL: Q leaf is not its binary leaf\n"), 1;
+        for (uint32_t i = 0; i < cnt; i++) {
+          const uint32_t g = b.slot_gid[ks[i]];
+          if (prim_seen[g]++) return printf("FAIL: primitive in two wide leaves\n"), 1;
+          if ((kinds[g] != 0) != ((ref & kCurveBit) != 0)) return printf("FAIL: wide leaf kind\n"), 1;
+          if (!check_prim(g)) return printf("FAIL: quantised box does not contain its primitive\n"), 1;
+          prim_node[g] = it.id, prim_leaf[g] = ref;
+        }
+        wide_prims += cnt;
       }
     }
     if (wide_prims != n) return printf("FAIL: %zu prims in wide leaves, %u expected\n", wide_prims, n), 1;
     for (int v : visited) if (v != 1) return printf("FAIL: unreachable wide node\n"), 1;
-    if (bound != need) return printf("FAIL: stack need %u reported, %u found\n", bound, need), 1;
+    if (q.stack_need != need) return printf("FAIL: stack need %u reported, %u found\n", q.stack_need, need), 1;
+    // Where random walks start (build_sss_entries), for instances made of the primitives of ninst slices along x, an instance
+    // with no primitive and one random box.  Checked: the entry is an inner node (or there is none), at most max_foreign foreign
+    // references, and every primitive whose box meets the widened region lies under the entry or under a foreign reference.
+    const uint32_t ninst = 1u + (uint32_t)it % 6u, max_foreign = (uint32_t)it % (kSssMaxForeign + 1u);
+    std::vector<float> ilo(3 * (ninst + 2), INFINITY), ihi(3 * (ninst + 2), -INFINITY);
+    for (uint32_t g = 0; g < n; g++) {
+      const uint32_t i = std::min(ninst - 1u, (uint32_t)std::max(0.f, (lo[3 * g] + 1.f) * 0.5f * (float)ninst));
+      for (int a = 0; a < 3; a++) ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * g + a]);
+    }
+    for (int a = 0; a < 3; a++) ilo[3 * (ninst + 1) + a] = -0.5f + 0.5f * U(rng), ihi[3 * (ninst + 1) + a] = 0.5f + 0.5f * U(rng);
+    const std::vector<SssEntry> E = build_sss_entries(w, ilo, ihi, max_foreign);
+    if (E.size() != ninst + 2) return printf("FAIL: SSS entry count\n"), 1;
+    for (size_t i = 0; i < E.size(); i++) {
+      if (E[i].entry == 0 && E[i].nforeign) return printf("FAIL: SSS foreign references without an entry\n"), 1;
+      if (E[i].entry == 0) continue;
+      if ((E[i].entry & kLeafBit) || E[i].entry >= w.size()) return printf("FAIL: SSS entry is not an inner node\n"), 1;
+      if (E[i].nforeign > max_foreign) return printf("FAIL: %u SSS foreign references, at most %u\n", E[i].nforeign, max_foreign), 1;
+      float m2 = 0.f;  // (how far beyond the region a primitive's box can matter: build_sss_entries)
+      for (int a = 0; a < 3; a++) m2 = std::max(m2, 2e-3f * (ihi[3 * i + a] - ilo[3 * i + a]));
+      for (uint32_t g = 0; g < n; g++) {
+        bool meets = true;
+        for (int a = 0; a < 3; a++) meets = meets && lo[3 * g + a] <= E[i].hi[a] + m2 && hi[3 * g + a] >= E[i].lo[a] - m2;
+        if (!meets) continue;
+        bool covered = false;  // (its leaf, then the nodes above it)
+        for (uint32_t v = prim_leaf[g], up = prim_node[g]; v != kNone && !covered; v = up, up = (up == 0 || up == kNone) ? kNone : parent[up])
+          for (uint32_t f = 0; f <= E[i].nforeign && !covered; f++) covered = v == (f ? E[i].foreign[f - 1].ref : E[i].entry);
+        if (!covered) return printf("FAIL: primitive %u meets instance %zu's region but is under no entry reference\n", g, i), 1;
+      }
+    }
     cases++;
   }
   printf("bvh builder: %zu cases ok\n", cases);

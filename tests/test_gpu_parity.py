@@ -171,7 +171,7 @@ def test_resumable_rays_are_exact(pa, pairs, name, turns, monkeypatch):
 def test_patch_order_does_not_matter(pa, pairs, monkeypatch):
     """Round 6: the 8 x 8 pixel patches of a pass are laid out in a scattered order (PBRHIP_PATCH_SHUFFLE: a batch of k_trace's ray queue is
     eight image regions instead of one).  A permutation of the work: the image is the oracle's either way, alone and sharded.  (The
-    curve leaves of the Q tree are 64-byte records of one or two arbitrary pieces since round 6 -- a build option, PB_CURVE_RECORDS --:
+    curve leaves of the Q tree are 64-byte records of one or two arbitrary pieces since round 6 (dscene.h):
     every hair / curve test of this file runs on them, and test_wide_and_binary_trees_agree compares them with the binary tree.)"""
     for name in ("hair", "ggx"):
         desc, sg, so = pairs[name]
@@ -539,7 +539,7 @@ def test_whole_frames_on_the_benchmark_scenes(pa, config, monkeypatch):
     ndiff, rel = image_check(a.rgba, rgba)
     assert ndiff == 0 and rel == 0.0, (ndiff, rel)
     assert a.rgba[..., :3].max() > 0
-    # host-built trees are walked through the Q tree (quantised 4-wide nodes, curve pieces as chains of points) by default:
+    # host-built trees are walked through the Q tree (quantised 4-wide nodes, curve leaves as 64-byte records) by default:
     # the binary tree must give the same frame
     monkeypatch.setenv("PBRHIP_WIDE", "0")
     b = pa.RenderLayer()
@@ -602,7 +602,7 @@ def test_gpu_built_bvh_gives_identical_results(pa, pairs, name):
 @pytest.mark.parametrize("name", ["lambert", "ggx", "sss", "textured", "hair"])
 def test_wide_and_binary_trees_agree(pa, pairs, name, monkeypatch):
     """Host-built trees are traversed through the Q tree (k_trace, k_sss_walk, k_tail, the trace hooks: quantised 4-wide nodes,
-    compact triangle slots, curve pieces as chains of points); PBRHIP_WIDE=0 selects the binary tree at every launch.  Hits
+    compact triangle slots, curve leaves as 64-byte records); PBRHIP_WIDE=0 selects the binary tree at every launch.  Hits
     and images must not depend on the choice (and both equal the oracle)."""
     from pbrlab_amd import scenes
     desc, sg, so = pairs[name]
