@@ -1,0 +1,572 @@
+"""Float64 expectations for single-bounce scenes: what a pixel of the renderer should converge to, derived from the
+reference's rules (SURVEY.md §8(a')) and not from the oracle's code.  Test infrastructure only.
+
+Scope: untransformed triangle meshes; one receiver (a planar principled surface: Lambert, or metallic GGX with only the
+specular closure on); emitters and occluders with a black material; area lights with constant shading normals per face.
+A camera ray that hits such a receiver gathers light along exactly one bounce:
+
+  E(x) = sum over the light faces of  int_{V(x)}  f(w) Le (cos_p cos_l / d^2) [w_nee(y) + w_bsdf(y)] dA(y)     (Lambert)
+
+with, from the rows of SURVEY §8(a'):
+  p_A(y)  = max(Le_f) / sum_faces(max(Le) area)                                   (Q10: face weight max(Le)*area)
+  q_nee   = p_A d^2 / (cos_l cos_p)                                                (Q3: both cosines)
+  q_bsdf  = the BSDF pdf the shader returns for w                                  (Lambert: cos_p / pi)
+  w_nee   = q_nee^2 / (q_nee^2 + q_bsdf^2)                                         (power heuristic)
+  w_bsdf  = q_bsdf^2 / (q_bsdf^2 + (p_A d^2 / |n_s.w|)^2), only for kFront hits   (Q2: the light's SHADING normal, and
+            (w.n_g < 0 and w.n_s < 0)                                                 kFront needs both normals)
+so w_nee + w_bsdf != 1 wherever cos_p is not 1 (Q3's inconsistency).
+
+Q15 (the GGX pdf, microfacet-ggx.h:233-238): MicrofacetGGXBsdfPdf returns pdf = G1o D / (4 cos_o cos_i), the density
+of its VNDF sampler G1o D / (4 cos_o) divided once more by cos_i.  For the GGX receiver the BSDF-sampled path then
+carries f cos_i / pdf = G1i cos_i and the MIS weights use the skewed pdf; the expectation of that path is
+int f Le cos_i^2 w_bsdf dw instead of int f Le cos_i w_bsdf dw.  NEE is unaffected except through w_nee.
+
+Why nothing else contributes at these geometries:
+  Q1 (Russian roulette with p = max(throughput), unclamped): at depth 0 the throughput is (1,1,1), p = 1 > every draw
+     in [0,1), so the camera path always survives; the only emission it can reach after that is added (render.cc:43-61)
+     before the roulette of depth 1, and every later vertex has throughput 0: emitters and occluders are black (their
+     closure weights are all 0, the shader's throughput is 0/0 -> 0), a planar receiver cannot be hit again by a ray
+     leaving it, and a miss ends the path.
+  Q9 (absolute 1e-3 offsets): the shadow ray spans [1e-3, d - 1e-3] and the next ray starts at 1e-3; every separation
+     in these scenes (receiver to emitter or occluder, occluder to emitter) is >= 5e-2, so neither interval cuts off
+     geometry that matters, and the planar emitter cannot occlude itself.
+  Camera rays that land on an emitter's front face are worth exactly Le (depth-0 weight 1, black shader adds 0);
+  rays that land on black geometry, on a back face of an emitter, or miss are worth exactly 0.
+
+Visibility: the shadow of a convex black occluder seen from x, projected onto the light's plane, is the convex hull of
+its projected vertices (valid when the occluder lies between x and that plane, which is asserted); the visible part of a
+light face, P \\ Q, is split into convex pieces by successive half-planes of Q and every piece is integrated with a
+collapsed Gauss-Legendre rule.  The hemisphere and kFront conditions are half-planes in y as well (n_s is constant per
+face), so every integrand is smooth on its piece."""
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+REFINE = 1.0        # quadrature: a triangle's longest edge <= REFINE x (its distance from x) ...
+MAX_SPLITS = 8      # ... reached by at most this many 4-way splits
+STEEP = 0.3       # pixel footprint: a 2 x 2 Gauss-Legendre rule; pixels whose 4 nodes spread by more than STEEP are left out
+CHUNK = 20000       # triangles per vectorised quadrature step
+
+
+# ------------------------------------------------------------------------------------------------- scene description
+@dataclass
+class Mesh:
+    name: str
+    verts: np.ndarray                    # (V,3)
+    faces: np.ndarray                    # (F,3)
+    material: dict                       # principled parameters (scenes.PRINCIPLED_DEFAULTS keys)
+    emission: Optional[np.ndarray] = None  # (F,3) per-face Le, or None: not an emitter
+    normals: Optional[np.ndarray] = None   # (V,3) per-vertex shading normals, or None (geometric)
+
+
+@dataclass
+class Scene:
+    meshes: List[Mesh]
+    receiver: int = 0                    # index of the receiving (non-black) mesh
+    occluders: List[int] = field(default_factory=list)   # convex black meshes that can shadow the lights
+
+
+def build(scene, S: Scene, make_principled):
+    """Replay S through the builder methods of pbrlab's Scene (both back ends: OracleScene / pbrlab_amd.Scene), one mesh +
+    local scene + identity instance per mesh, per-face light params where Le differs between faces."""
+    for m in S.meshes:
+        mid = scene.AddMaterialParam(make_principled(m.material))
+        v4 = np.concatenate([np.asarray(m.verts, np.float32), np.ones((len(m.verts), 1), np.float32)], 1)
+        f = np.asarray(m.faces, np.uint32)
+        if m.normals is not None:
+            n4 = np.concatenate([np.asarray(m.normals, np.float32), np.zeros((len(m.normals), 1), np.float32)], 1)
+            nid = f
+        else:
+            n4, nid = None, None
+        mesh = scene.AddTriangleMesh(v4, n4, None, f, nid, None, np.full(len(f), mid, np.uint32))
+        ls = scene.CreateLocalScene()
+        scene.AddMeshToLocalScene(ls, mesh)
+        inst = scene.CreateInstance(ls, None)
+        if m.emission is not None:
+            ids, seen = np.zeros(len(f), np.uint32), {}
+            for k, e in enumerate(np.asarray(m.emission, np.float32)):
+                key = tuple(float(c) for c in e)
+                if key not in seen:
+                    seen[key] = scene.AddLightParam(key)
+                ids[k] = seen[key]
+            scene.AttachLightParamIdsToInstance(inst, [ids])
+    scene.CommitScene()
+    return scene
+
+
+def material(**kw):
+    from pbrlab_amd import scenes
+    d = dict(scenes.PRINCIPLED_DEFAULTS, kind="principled", name="m")
+    d.update(kw)
+    return d
+
+
+BLACK = dict(base_color=(0.0, 0.0, 0.0), specular=0.0)
+
+
+def quad(c, a, b):
+    """quad centre c, half-edges a, b: two triangles with geometric normal along a x b"""
+    c, a, b = (np.asarray(x, np.float64) for x in (c, a, b))
+    return np.array([c - a - b, c + a - b, c + a + b, c - a + b]), np.array([[0, 1, 2], [0, 2, 3]])
+
+
+# ------------------------------------------------------------------------------------------------- float64 leaves
+def fresnel_dielectric_cos(c, eta):
+    """closure-util.h:10-29 in float64 (vectorised over c)"""
+    c = np.asarray(c, np.float64)
+    eta = np.where(c < 0, 1.0 / eta, eta)
+    c = np.abs(c)
+    g = eta * eta - 1 + c * c
+    gs = np.sqrt(np.maximum(g, 0.0))
+    A = (gs - c) / (gs + c)
+    B = (c * (gs + c) - 1) / (c * (gs - c) + 1)
+    return np.where(g > 0, 0.5 * A * A * (1 + B * B), 1.0)
+
+
+def ggx_eval(wi, wo, ax, ay):
+    """GTR2 GGX reflection, microfacet-ggx.h:164-245 read in float64: returns (f, pdf) with the reference's pdf
+    G1o D / (4 cos_o cos_i) (Q15).  wi, wo: (...,3) in the local frame (z = normal)."""
+    wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
+    ax, ay = np.asarray(ax, np.float64), np.asarray(ay, np.float64)
+    co, ci = wo[..., 2], wi[..., 2]
+    ok = (co > 0) & (ci > 0)
+    co_, ci_ = np.where(ok, co, 1.0), np.where(ok, ci, 1.0)
+    m = wi + wo
+    m = m / np.linalg.norm(m, axis=-1, keepdims=True)
+    mz = np.where(ok, m[..., 2], 1.0)
+    sx, sy = -m[..., 0] / (mz * ax), -m[..., 1] / (mz * ay)
+    sl = 1 + sx * sx + sy * sy
+    D = 1.0 / (sl * sl * np.pi * ax * ay * mz ** 4)          # = alpha^2 / (pi c^4 (alpha^2 + tan^2)^2) when ax == ay
+
+    def g1(w, c):
+        cp2 = w[..., 0] ** 2 + w[..., 1] ** 2
+        a2 = np.where(cp2 > 0, (w[..., 0] ** 2 * ax * ax + w[..., 1] ** 2 * ay * ay) / np.where(cp2 > 0, cp2, 1.0), ax * ay)
+        return 2 / (1 + np.sqrt(1 + a2 * (1 - c * c) / (c * c)))
+    G1o, G1i = g1(wo, co_), g1(wi, ci_)
+    common = D * 0.25 / co_ / ci_
+    return np.where(ok, G1o * G1i * common, 0.0), np.where(ok, G1o * common, 0.0)
+
+
+def _principled(mat):
+    """the closures cycles-principled-shader.cc:244-412 enables for the materials these scenes use"""
+    metallic, spec = float(mat["metallic"]), float(mat["specular"])
+    base = np.asarray(mat["base_color"], np.float64)
+    assert float(mat["subsurface"]) == 0 and float(mat["clearcoat"]) == 0 and float(mat["transmission"]) == 0
+    diffuse = (1 - metallic) * base if (1 - metallic) > 1e-3 and base.mean() > 1e-3 else None
+    specular = None
+    if spec > 1e-3 or metallic > 1e-3:
+        assert float(mat["anisotropic"]) == 0 and float(mat["specular_tint"]) == 0
+        ior = 2.0 / (1.0 - np.sqrt(0.08 * spec)) - 1.0
+        r2 = float(mat["roughness"]) ** 2
+        color = (1 - metallic) * 0.08 * spec + metallic * base
+        specular = dict(alpha=r2, ior=ior, color=color)
+    assert diffuse is None or specular is None, "one closure at a time: the selection weight would enter the pdf"
+    return diffuse, specular
+
+
+def specular_color(wi, wo, color, ior):
+    """cycles-principled-shader.cc:54-61: Fresnel tint with the half vector of (wi, wo)"""
+    h = wi + wo
+    h = h / np.linalg.norm(h, axis=-1, keepdims=True)
+    f0 = fresnel_dielectric_cos(1.0, ior)
+    fh = (fresnel_dielectric_cos(np.sum(h * wo, -1), ior) - f0) / (1.0 - f0)
+    return color * (1 - fh[..., None]) + fh[..., None]
+
+
+# ------------------------------------------------------------------------------------------------- ray casting (float64)
+def _tris(S: Scene):
+    out = []
+    for mi, m in enumerate(S.meshes):
+        v = np.asarray(m.verts, np.float64)
+        for fi, f in enumerate(np.asarray(m.faces)):
+            out.append((mi, fi, v[f[0]], v[f[1]], v[f[2]]))
+    return out
+
+
+def cast(S: Scene, org, dirs):
+    """closest hit of rays (org (3,), dirs (N,3)) over all triangles in float64: (mesh, face, t, front) per ray;
+    mesh = -1 for a miss.  front: the ray meets the face against its geometric normal."""
+    tris = _tris(S)
+    v0 = np.array([t[2] for t in tris]); e1 = np.array([t[3] for t in tris]) - v0; e2 = np.array([t[4] for t in tris]) - v0
+    d = dirs[:, None, :]
+    p = np.cross(d, e2[None])
+    det = np.sum(e1[None] * p, -1)
+    inv = 1.0 / np.where(det != 0, det, 1.0)
+    s = org[None, None, :] - v0[None]
+    u = np.sum(s * p, -1) * inv
+    q = np.cross(s, e1[None])
+    v = np.sum(d * q, -1) * inv
+    t = np.sum(e2[None] * q, -1) * inv
+    ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0)
+    t = np.where(ok, t, np.inf)
+    k = np.argmin(t, 1)
+    tk = t[np.arange(len(dirs)), k]
+    hit = np.isfinite(tk)
+    mesh = np.where(hit, np.array([tr[0] for tr in tris])[k], -1)
+    face = np.where(hit, np.array([tr[1] for tr in tris])[k], -1)
+    ng = np.cross(e1, e2)[k]
+    front = np.sum(dirs * ng, -1) < 0
+    return mesh, face, tk, front
+
+
+# ------------------------------------------------------------------------------------------------- camera (render.cc:132-171)
+class Camera:
+    """RenderingTile's pinhole camera in float64 from the scene's float32 AABB (pbr_oracle.c make_camera / camera_ray)"""
+
+    def __init__(self, bmin, bmax, width, height):
+        bmin, bmax = np.asarray(bmin, np.float64), np.asarray(bmax, np.float64)
+        if bmax[0] - bmin[0] > bmax[1] - bmin[1]:
+            hs = bmax[0] - bmin[0]
+            vs = hs * height / width
+        else:
+            vs = bmax[1] - bmin[1]
+            hs = vs * width / height
+        self.org = np.array([(bmax[0] + bmin[0]) * 0.5, (bmax[1] + bmin[1]) * 0.5, bmax[2] + hs * 0.5 * np.sqrt(3.0)])
+        self.xc, self.yc, self.zc = (bmax[0] + bmin[0]) * 0.5 - hs * 0.5, (bmax[1] + bmin[1]) * 0.5 + vs * 0.5, bmax[2]
+        self.dx, self.dy = hs / width, vs / height
+        self.width, self.height = width, height
+
+    def dirs(self, px, py, jx, jy):
+        """unit directions through image positions (px + jx, py + jy), jitter j in [0,1)"""
+        tgt = np.stack([self.xc + self.dx * (px + jx), self.yc - self.dy * (py + jy), np.full(np.shape(px + jx), self.zc)], -1)
+        d = tgt - self.org
+        return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+# ------------------------------------------------------------------------------------------------- polygon clipping (2D)
+def _clip(poly, a, b, c):
+    """Sutherland-Hodgman: keep the part of convex polygon poly (list of (u,w)) with a*u + b*w + c >= 0"""
+    out = []
+    n = len(poly)
+    for i in range(n):
+        p, q = poly[i], poly[(i + 1) % n]
+        fp, fq = a * p[0] + b * p[1] + c, a * q[0] + b * q[1] + c
+        if fp >= 0:
+            out.append(p)
+        if (fp >= 0) != (fq >= 0):
+            s = fp / (fp - fq)
+            out.append((p[0] + s * (q[0] - p[0]), p[1] + s * (q[1] - p[1])))
+    return out if len(out) >= 3 else []
+
+
+def _hull(pts):
+    """convex hull, counter-clockwise (monotone chain)"""
+    pts = sorted(set(pts))
+    if len(pts) < 3:
+        return pts
+
+    def cr(o, a, b):
+        return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+    lo, hi = [], []
+    for p in pts:
+        while len(lo) >= 2 and cr(lo[-2], lo[-1], p) <= 0:
+            lo.pop()
+        lo.append(p)
+    for p in reversed(pts):
+        while len(hi) >= 2 and cr(hi[-2], hi[-1], p) <= 0:
+            hi.pop()
+        hi.append(p)
+    return lo[:-1] + hi[:-1]
+
+
+def subtract(poly, hull):
+    """P \\ Q for convex P and convex CCW Q: piece k = P outside edge k of Q and inside edges 0..k-1 (disjoint, convex)"""
+    if len(hull) < 3:
+        return [poly]
+    pieces, rest = [], poly
+    for k in range(len(hull)):
+        p, q = hull[k], hull[(k + 1) % len(hull)]
+        # left of p->q (inside Q): (q-p) x (y-p) >= 0  ->  a u + b w + c >= 0
+        a, b = -(q[1] - p[1]), (q[0] - p[0])
+        c = -(a * p[0] + b * p[1])
+        out = _clip(rest, -a, -b, -c)
+        if out:
+            pieces.append(out)
+        rest = _clip(rest, a, b, c)
+        if not rest:
+            break
+    return pieces
+
+
+# ------------------------------------------------------------------------------------------------- the expectation
+def gauss_legendre01(n):
+    x, w = np.polynomial.legendre.leggauss(n)
+    return 0.5 * (x + 1), 0.5 * w
+
+
+class Expectation:
+    """E(x) for points x on the receiver seen along camera directions, per RGB channel."""
+
+    def __init__(self, S: Scene, order=5, physical_mis=False):
+        self.S, self.order, self.physical_mis = S, order, physical_mis
+        self.diffuse, self.specular = _principled(S.meshes[S.receiver].material)
+        rv = np.asarray(S.meshes[S.receiver].verts, np.float64)
+        rf = np.asarray(S.meshes[S.receiver].faces)
+        n = np.cross(rv[rf[:, 1]] - rv[rf[:, 0]], rv[rf[:, 2]] - rv[rf[:, 0]])
+        n /= np.linalg.norm(n, axis=1, keepdims=True)
+        assert np.allclose(n, n[0], atol=1e-12), "the receiver must be planar"
+        self.n_geo = n[0]
+        # the light table: every emitting face, p_A = max(Le) / sum(max(Le) area)  (Q10)
+        faces, total = [], 0.0
+        for m in S.meshes:
+            if m.emission is None:
+                continue
+            v = np.asarray(m.verts, np.float64)
+            for k, f in enumerate(np.asarray(m.faces)):
+                p0, p1, p2 = v[f[0]], v[f[1]], v[f[2]]
+                ng = np.cross(p1 - p0, p2 - p0)
+                area = 0.5 * np.linalg.norm(ng)
+                le = np.asarray(m.emission[k], np.float64)
+                if m.normals is not None:
+                    ns = np.asarray(m.normals, np.float64)[f]
+                    assert np.allclose(ns, ns[0], atol=1e-12), "shading normals must be constant per face (kFront is a half-plane)"
+                    ns = ns[0] / np.linalg.norm(ns[0])
+                else:
+                    ns = ng / np.linalg.norm(ng)
+                faces.append(dict(p=(p0, p1, p2), ng=ng / np.linalg.norm(ng), ns=ns, area=area, le=le))
+                total += le.max() * area
+        for fc in faces:
+            fc["pA"] = fc["le"].max() / total
+            # 2D frame of the face's plane
+            e1 = fc["p"][1] - fc["p"][0]
+            e1 = e1 / np.linalg.norm(e1)
+            fc["e"] = (fc["p"][0], e1, np.cross(fc["ng"], e1))
+            fc["uv"] = [self._to2(fc, p) for p in fc["p"]]
+        self.faces = faces
+        self.occ = [np.asarray(S.meshes[i].verts, np.float64) for i in S.occluders]
+
+    @staticmethod
+    def _to2(fc, p):
+        o, e1, e2 = fc["e"]
+        return (float(np.dot(p - o, e1)), float(np.dot(p - o, e2)))
+
+    def _pieces(self, x, n_r, fc):
+        """convex pieces (2D, in fc's frame) of the light face visible from x, each tagged with kFront(n_s)"""
+        o, e1, e2 = fc["e"]
+        if np.dot(x - o, fc["ng"]) <= 0:           # cos_l <= 0 over the whole face: NEE's hemisphere test, and never kFront
+            return []
+        poly = list(fc["uv"])
+        # receiver hemisphere (y - x).n_r > 0
+        poly = _clip(poly, float(np.dot(e1, n_r)), float(np.dot(e2, n_r)), float(np.dot(o - x, n_r)))
+        if not poly:
+            return []
+        pieces = [poly]
+        phx = float(np.dot(x - o, fc["ng"]))
+        for ov in self.occ:
+            phv = (ov - o) @ fc["ng"]
+            ratio = phv / phx
+            if np.all(ratio >= 1):                 # the occluder is not between x and the light's plane
+                continue
+            assert np.all((ratio > 0) & (ratio < 1)), "occluder straddles x or the light's plane: the hull rule does not hold"
+            t = phx / (phx - phv)
+            proj = x + t[:, None] * (ov - x)
+            hull = _hull([(float(np.dot(p - o, e1)), float(np.dot(p - o, e2))) for p in proj])
+            pieces = [q for p in pieces for q in subtract(p, hull)]
+        # kFront on the light needs w.n_s < 0 as well:  (y - x).n_s < 0
+        ns = fc["ns"]
+        a, b, c = float(np.dot(e1, ns)), float(np.dot(e2, ns)), float(np.dot(o - x, ns))
+        out = []
+        for p in pieces:
+            fr = _clip(p, -a, -b, -c)
+            bk = _clip(p, a, b, c)
+            if fr:
+                out.append((fr, True))
+            if bk:
+                out.append((bk, False))
+        return out
+
+    def __call__(self, x, wo, order=None):
+        """x: (N,3) points on the receiver, wo: (N,3) unit directions towards the camera.  Returns (N,3)."""
+        order = order or self.order
+        x, wo = np.asarray(x, np.float64), np.asarray(wo, np.float64)
+        N = len(x)
+        n_r = np.where((wo @ self.n_geo)[:, None] > 0, self.n_geo, -self.n_geo)   # ez: the side the camera sees (kBack flips)
+        gs, gw = gauss_legendre01(order)
+        S_, T_ = np.meshgrid(gs, gs, indexing="ij")
+        W_ = np.outer(gw, gw).ravel()
+        S_, T_ = S_.ravel(), T_.ravel()
+        out = np.zeros((N, 3))
+        for fi, fc in enumerate(self.faces):
+            o, e1, e2 = fc["e"]
+            owner, tri, front = [], [], []
+            for i in range(N):
+                for poly, fr in self._pieces(x[i], n_r[i], fc):
+                    for k in range(1, len(poly) - 1):
+                        owner.append(i)
+                        tri.append((poly[0], poly[k], poly[k + 1]))
+                        front.append(fr)
+            if not owner:
+                continue
+            owner = np.asarray(owner)
+            tri = np.asarray(tri)                                     # (M,3,2)
+            front = np.asarray(front)
+            # 1/d^2 peaks near the foot of x on the light's plane: split a triangle into 4 while its longest edge exceeds
+            # REFINE x its distance from x (estimated from the distance to the plane and the distance to the centroid less the edge),
+            # at most MAX_SPLITS times
+            h = np.abs((x - o) @ fc["ng"])
+            x2 = np.stack([(x - o) @ e1, (x - o) @ e2], -1)
+            for _ in range(MAX_SPLITS):
+                edge = np.max(np.linalg.norm(tri - np.roll(tri, 1, axis=1), axis=-1), -1)
+                r = np.linalg.norm(tri.mean(1) - x2[owner], axis=-1)
+                big = edge > REFINE * np.sqrt(h[owner] ** 2 + np.maximum(r - edge, 0.0) ** 2)
+                if not big.any():
+                    break
+                t4 = tri[big]
+                a, b, c = t4[:, 0], t4[:, 1], t4[:, 2]
+                ab, bc, ca = (a + b) / 2, (b + c) / 2, (c + a) / 2
+                sub = np.concatenate([np.stack(q, 1) for q in ((a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca))])
+                tri = np.concatenate([tri[~big], sub])
+                owner = np.concatenate([owner[~big], np.tile(owner[big], 4)])
+                front = np.concatenate([front[~big], np.tile(front[big], 4)])
+            for c0 in range(0, len(tri), CHUNK):
+                self._integrate(fc, tri[c0:c0 + CHUNK], owner[c0:c0 + CHUNK], front[c0:c0 + CHUNK], x, n_r, wo, S_, T_, W_, out)
+        return out
+
+    def _integrate(self, fc, tri, owner, front, x, n_r, wo, S_, T_, W_, out):
+        o, e1, e2 = fc["e"]
+        A, B, C = tri[:, 0], tri[:, 1], tri[:, 2]
+        area2 = np.abs((B[:, 0] - A[:, 0]) * (C[:, 1] - A[:, 1]) - (B[:, 1] - A[:, 1]) * (C[:, 0] - A[:, 0]))
+        # collapsed square -> triangle: y = A + s (B - A) + s t (C - B), dA = area2 * s ds dt
+        uv = A[:, None] + S_[None, :, None] * (B - A)[:, None] + (S_ * T_)[None, :, None] * (C - B)[:, None]
+        wq = area2[:, None] * S_[None] * W_[None]
+        y = o + uv[..., :1] * e1 + uv[..., 1:] * e2               # (M,Q,3)
+        xm, nrm, wom = x[owner][:, None], n_r[owner][:, None], wo[owner][:, None]
+        dv = y - xm
+        d2 = np.sum(dv * dv, -1)
+        w = dv / np.sqrt(d2)[..., None]
+        cos_p = np.sum(w * nrm, -1)
+        cos_l = -np.sum(w * fc["ng"], -1)
+        ns_dot = np.abs(np.sum(w * fc["ns"], -1))
+        pA = fc["pA"]
+        q_nee = pA * d2 / (cos_l * cos_p)
+        q_light = pA * d2 / ns_dot
+        if self.diffuse is not None:
+            f = (self.diffuse / np.pi)[None, None, :] * np.ones(cos_p.shape)[..., None]
+            q_bsdf = cos_p / np.pi
+            bsdf_cos = cos_p                               # f cos / pdf * pdf_true = f cos
+        else:
+            sp = self.specular
+            tloc = np.cross(nrm, np.array([0.0, 0.0, 1.0]) if abs(self.n_geo[2]) < 0.9 else np.array([1.0, 0.0, 0.0]))
+            tloc = tloc / np.linalg.norm(tloc, axis=-1, keepdims=True)
+            bloc = np.cross(nrm, tloc)
+            loc = lambda v: np.stack([np.sum(v * tloc, -1), np.sum(v * bloc, -1), np.sum(v * nrm, -1)], -1)  # noqa: E731
+            wi_l, wo_l = loc(w), loc(np.broadcast_to(wom, w.shape))
+            g, q_bsdf = ggx_eval(wi_l, wo_l, sp["alpha"], sp["alpha"])
+            f = specular_color(wi_l, wo_l, sp["color"], sp["ior"]) * g[..., None]
+            bsdf_cos = cos_p * cos_p                       # Q15: f cos / (pdf_true / cos) * pdf_true = f cos^2
+        if self.physical_mis:
+            w_nee = np.ones_like(q_nee)
+            w_bsdf = np.zeros_like(q_nee)
+        else:
+            w_nee = q_nee ** 2 / (q_nee ** 2 + q_bsdf ** 2)
+            w_bsdf = np.where(front[:, None], q_bsdf ** 2 / (q_bsdf ** 2 + q_light ** 2), 0.0)
+        g_nee = (cos_p * cos_l / d2 * w_nee)[..., None] * f
+        g_bsdf = (bsdf_cos * cos_l / d2 * w_bsdf)[..., None] * f
+        val = np.sum((g_nee + g_bsdf) * wq[..., None], 1) * fc["le"]
+        np.add.at(out, owner, val)
+
+
+# ------------------------------------------------------------------------------------------------- Student's t
+def _betacf(a, b, x):
+    """continued fraction of the regularised incomplete beta function (modified Lentz)"""
+    tiny = 1e-300
+    c, d = 1.0, 1.0 - (a + b) * x / (a + 1.0)
+    d = 1.0 / (d if abs(d) > tiny else tiny)
+    h = d
+    for m in range(1, 500):
+        for num in (m * (b - m) * x / ((a + 2 * m - 1) * (a + 2 * m)), -(a + m) * (a + b + m) * x / ((a + 2 * m) * (a + 2 * m + 1))):
+            d = 1.0 + num * d
+            d = 1.0 / (d if abs(d) > tiny else tiny)
+            c = 1.0 + num / c
+            c = c if abs(c) > tiny else tiny
+            h *= d * c
+        if abs(d * c - 1.0) < 1e-15:
+            break
+    return h
+
+
+def betainc(a, b, x):
+    """regularised incomplete beta I_x(a, b)"""
+    import math
+    if x <= 0.0 or x >= 1.0:
+        return float(x >= 1.0)
+    lf = math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x)
+    if x < (a + 1.0) / (a + b + 2.0):
+        return math.exp(lf) * _betacf(a, b, x) / a
+    return 1.0 - math.exp(lf) * _betacf(b, a, 1.0 - x) / b
+
+
+def student_t_two_sided(x, dof):
+    """P(|T| > x) for Student's t with dof degrees of freedom"""
+    return betainc(dof / 2.0, 0.5, dof / (dof + x * x))
+
+
+def student_t_bar(p_two_sided, dof):
+    """x with P(|T| > x) = p_two_sided (bisection; P is monotone in x)"""
+    lo, hi = 0.0, 1e3
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if student_t_two_sided(mid, dof) > p_two_sided:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+# ------------------------------------------------------------------------------------------------- per-pixel classes
+PIX_MIXED, PIX_RECEIVER, PIX_ZERO, PIX_LIGHT = 0, 1, 2, 3
+
+
+def classify_and_expect(S: Scene, cam: Camera, expectation: Expectation, sub=2, probe=6):
+    """Per pixel: its class (from a probe x probe grid over the slightly widened footprint, float64 rays), the exact value of
+    PIX_LIGHT / PIX_ZERO pixels and, for PIX_RECEIVER pixels, the mean of E over the footprint (the jitter is uniform over
+    the pixel) by a sub x sub Gauss-Legendre rule (exact for polynomials of degree 2 sub - 1 in each direction); receiver
+    pixels whose nodes spread by more than STEEP (next to an emitter) become PIX_MIXED.  tests/test_analytic_radiance.py
+    checks the rule against an 8 x 8 one.
+    Returns (cls (H,W), value (H,W,3), (receiver points, directions to the camera))."""
+    W, H = cam.width, cam.height
+    py, px = np.mgrid[0:H, 0:W]
+    js = np.linspace(-0.02, 1.02, probe)
+    jx, jy = np.meshgrid(js, js, indexing="ij")
+    d = cam.dirs(px[..., None].astype(np.float64), py[..., None].astype(np.float64), jx.ravel(), jy.ravel())
+    mesh, face, t, front = cast(S, cam.org, d.reshape(-1, 3))
+    mesh, face, front = mesh.reshape(H, W, -1), face.reshape(H, W, -1), front.reshape(H, W, -1)
+    emits = np.array([m.emission is not None for m in S.meshes] + [False])
+    cls = np.full((H, W), PIX_MIXED)
+    value = np.zeros((H, W, 3))
+    on_recv = np.all(mesh == S.receiver, -1)
+    zero = np.all((mesh < 0) | ~emits[mesh] & (mesh != S.receiver) | emits[mesh] & ~front, -1)
+    cls[zero] = PIX_ZERO
+    for mi, m in enumerate(S.meshes):
+        if m.emission is None:
+            continue
+        em = np.asarray(m.emission, np.float64)
+        for k in range(len(em)):
+            same = np.all(em == em[k], 1)
+            lit = np.all((mesh == mi) & front & same[np.where(mesh == mi, face, 0)], -1)
+            cls[lit] = PIX_LIGHT
+            value[lit] = em[k]
+    cls[on_recv] = PIX_RECEIVER
+    # E over the footprints of the receiver pixels
+    ys, xs = np.nonzero(on_recv)
+    e, ev, pts, wo = pixel_mean(S, cam, expectation, xs, ys, sub, nodes=True)
+    value[ys, xs] = e
+    # where E is steep on the scale of a pixel (right next to an emitter) the rule is not trusted: such pixels are left out
+    steep = (ev.max(1) - ev.min(1)).max(1) > STEEP * np.abs(e).max(1)
+    cls[ys[steep], xs[steep]] = PIX_MIXED
+    return cls, value, (pts, wo)
+
+
+def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False):
+    """mean of E over the footprints of receiver pixels (xs, ys) by a sub x sub Gauss-Legendre rule; with nodes=True also
+    the values at the nodes (P, sub^2, 3), the nodes' receiver points and their directions towards the camera"""
+    g, gw = gauss_legendre01(sub)
+    gx, gy = np.meshgrid(g, g, indexing="ij")
+    d = cam.dirs(np.asarray(xs, np.float64)[:, None], np.asarray(ys, np.float64)[:, None], gx.ravel(), gy.ravel()).reshape(-1, 3)
+    m, _, t, _ = cast(S, cam.org, d)
+    assert np.all(m == S.receiver)
+    pts = cam.org + t[:, None] * d
+    v = expectation(pts, -d).reshape(len(xs), sub * sub, 3)
+    e = np.einsum("pqc,q->pc", v, np.outer(gw, gw).ravel())
+    return (e, v, pts, -d) if nodes else e

@@ -1,0 +1,331 @@
+"""The intersection contract of DESIGN.md section 2 against float64 geometry, on both back ends' trace_closest hooks.
+
+Every other intersection test compares float32 implementations with each other (oracle tree, oracle brute force, GPU).  Here
+the closest hit of each ray is computed in float64 straight from the contract:
+  * triangles: Moller-Trumbore, u, v = the barycentrics of v1 and v2, Ng = (v1 - v0) x (v2 - v0) in the instance's LOCAL space;
+  * cubic Bezier curves: a ray-facing flat ribbon of 4 linear pieces between the Bezier points at u = i/4 (xyz and radius
+    both linear along a piece), projected into the frame of the ray (the branchless ONB of the unit direction); a piece is hit
+    where the ray passes within the interpolated radius r of it: s = the piece parameter of the closest point in that frame,
+    u = (i + s) / 4, v = signed distance / r in [-1, 1], t = the depth of that point; Ng = dP/du at u.
+and each back end is held to it wherever the float64 answer is unambiguous.
+
+Tolerances (named below):
+  MARGIN  1e-3  a float64 hit is unambiguous when its barycentrics (u, v, 1-u-v), or for a ribbon piece s, 1-s and 1-|v|,
+                are all >= MARGIN; a primitive is robustly missed when one of them is <= -MARGIN.  A float32 hit differs
+                from the float64 one by a few ulps of the operands (~1e-6 relative), three orders below it.
+  T_SEP   1e-4  the winner must be more than T_SEP (relative) nearer than every other candidate, hit or ambiguous, so the
+                float32 order of the two cannot flip.
+  T_TOL   1e-5  relative agreement of t, plus POS_TOL |o| / |d| (the rounding of the origin's coordinates).  MT's t = (e2.q)/det carries ~10 float32 roundings (~6e-7 each) amplified by the
+                ray's obliquity; rays closer than GRAZE to a primitive's plane are not held to it (nor to the winner).
+  T_TOL_AMB 1e-3  the t agreement asked of a reported hit whose float64 candidate is ambiguous (grazing, on an edge).
+  GRAZE   2e-2  |cos| between the ray and the triangle's plane normal below which a triangle candidate is ambiguous.
+  UV_TOL  1e-4  absolute agreement of u and v (the barycentrics and v = dist / r are ratios of float32 dot products).
+  NG_COS  1 - 1e-5  cosine between the reported normal_g and the float64 Ng (or dP/du).
+  POS_TOL 1e-6  float32 positions and ray-frame coordinates are good to ~8 ulps of their magnitude |p|: on a ribbon of
+                radius r that moves v by up to POS_TOL |p| / r, which is added to the |v| margin and to v's tolerance.
+  SLIVER  1e-4  triangles with area / longest-edge^2 below this are numerically degenerate (tests/_soups.py): float32
+                barycentrics of them mean little, so they are never required; a reported hit on one must lie in the
+                triangle's box (the contract's validation rule) instead of matching float64 u, v.
+"""
+import numpy as np
+import pytest
+
+import _oracle as O
+import _soups
+from golden.make_golden import golden_scenes
+from pbrlab_amd import scenes
+
+MARGIN = 1e-3
+T_SEP = 1e-4
+T_TOL = 1e-5
+T_TOL_AMB = 1e-3
+GRAZE = 2e-2
+UV_TOL = 1e-4
+NG_COS = 1.0 - 1e-5
+SLIVER = 1e-4
+POS_TOL = 1e-6
+NONE = 0xFFFFFFFF
+N_RANDOM, N_AIMED = 1500, 1500
+
+
+# ---------------------------------------------------------------------------------------------------------- scenes
+def ribbon_scene(seed=5):
+    """tapered curves (radius 0.06 at one end, 0.004 at the other: a piece's radius varies along it) over a floor"""
+    rng = np.random.RandomState(seed)
+    b = scenes._Builder()
+    b.add("floor", *scenes._quad((-1, -1, 1), (1, -1, 1), (1, -1, -1), (-1, -1, -1)), 0)
+    n = 60
+    cps = []
+    for _ in range(n):
+        p0 = rng.uniform(-0.8, 0.8, 3)
+        pts = np.array([p0 + rng.uniform(-0.25, 0.25, 3) * k for k in range(4)])
+        r = np.linspace(0.06, 0.004, 4) if rng.rand() < 0.5 else np.linspace(0.004, 0.06, 4)
+        cps.append(np.concatenate([pts, r[:, None]], 1))
+    cv = np.concatenate(cps).astype(np.float32)
+    curve = scenes.CurveShape("tapered", cv, (np.arange(n) * 4).astype(np.uint32))
+    return b.finish(scenes.demo_materials("lambert"), [curve])
+
+
+def transformed_scene():
+    """an icosphere instance rotated about three axes and translated, a quad scaled + rotated, and an untransformed floor"""
+    b = scenes._Builder()
+    v, f = scenes._icosphere(2)
+    b.add("ball", v * 0.5, f, 0)
+    b.add("card", *scenes._quad((-0.5, -0.5, 0), (0.5, -0.5, 0), (0.5, 0.5, 0), (-0.5, 0.5, 0)), 0)
+    b.add("floor", *scenes._quad((-1, -1, 1), (1, -1, 1), (1, -1, -1), (-1, -1, -1)), 0)
+    d = b.finish(scenes.demo_materials("lambert"))
+    d.shapes[0].transform = scenes.instance_matrix((20.0, 35.0, -10.0), translate=(0.3, -0.2, 0.1))
+    d.shapes[1].transform = scenes.instance_matrix((-30.0, 10.0, 50.0), scale=(1.5, 0.7, 1.0), translate=(-0.4, 0.5, -0.3))
+    return d
+
+
+def scene(name):
+    if name == "soup":
+        return _soups.triangle_soup(1, extra_slivers=60)[0]
+    if name == "ribbons":
+        return ribbon_scene()
+    if name == "transformed":
+        return transformed_scene()
+    return golden_scenes()[name]
+
+
+SCENES = ["lambert", "hair", "soup", "ribbons", "transformed"]
+
+
+# ---------------------------------------------------------------------------------------------------------- float64 geometry
+class Geometry:
+    """every primitive of a SceneDesc in float64, with the instance / prim ids build_scene gives it"""
+
+    def __init__(self, desc):
+        tri_w, tri_l, tri_id = [], [], []
+        V = desc.vertices[:, :3].astype(np.float64)
+        for inst, sh in enumerate(desc.shapes):
+            loc = V[sh.vertex_ids.astype(np.int64)]                       # (F,3,3)
+            wld = loc
+            if sh.transform is not None:
+                M = sh.transform.astype(np.float64)
+                wld = loc @ M[:3, :3] + M[3, :3]                          # v' = v M (row vectors)
+            tri_w.append(wld), tri_l.append(loc)
+            tri_id.append(np.stack([np.full(len(loc), inst), np.arange(len(loc))], 1))
+        self.tri = np.concatenate(tri_w)
+        loc = np.concatenate(tri_l)
+        self.tri_id = np.concatenate(tri_id)
+        self.tri_ng = np.cross(loc[:, 1] - loc[:, 0], loc[:, 2] - loc[:, 0])          # local space, unnormalised
+        wn = np.cross(self.tri[:, 1] - self.tri[:, 0], self.tri[:, 2] - self.tri[:, 0])
+        edge = np.max([np.linalg.norm(self.tri[:, (k + 1) % 3] - self.tri[:, k], axis=1) for k in range(3)], 0)
+        self.tri_wn = wn / np.maximum(np.linalg.norm(wn, axis=1, keepdims=True), 1e-300)
+        self.sliver = 0.5 * np.linalg.norm(wn, axis=1) < SLIVER * edge ** 2
+        cps, cid = [], []
+        for k, cs in enumerate(desc.curves):
+            assert cs.transform is None, "ribbons are ray-facing in world space: curves stay untransformed here"
+            cv = cs.vertices.astype(np.float64)
+            cps.append(np.stack([cv[cs.indices.astype(np.int64) + j] for j in range(4)], 1))    # (S,4,4)
+            cid.append(np.stack([np.full(len(cs.indices), len(desc.shapes) + k), np.arange(len(cs.indices))], 1))
+        self.cp = np.concatenate(cps) if cps else np.zeros((0, 4, 4))
+        self.cp_id = np.concatenate(cid) if cid else np.zeros((0, 2), np.int64)
+        uu = np.arange(5) / 4.0
+        B = np.stack([(1 - uu) ** 3, 3 * uu * (1 - uu) ** 2, 3 * uu ** 2 * (1 - uu), uu ** 3], 1)      # (5,4)
+        self.pts = np.einsum("kj,sjc->skc", B, self.cp)                    # (S,5,4): xyz + radius at u = i/4
+
+    @staticmethod
+    def tangent(cp, u):
+        s = 1 - u
+        c = np.stack([-3 * s * s, 3 * s * s - 6 * u * s, 6 * u * s - 3 * u * u, 3 * u * u], -1)
+        return np.einsum("...j,...jc->...c", c, cp[..., :3])
+
+    def candidates(self, o, d, tmin):
+        """per ray: arrays over all candidate sub-primitives (triangles; ribbon pieces) of
+        (t, margin, ambiguous-anyway, u, v, kind, index): margin >= 0 is a hit, |margin| < MARGIN is ambiguous"""
+        out = []
+        # triangles
+        v0, e1, e2 = self.tri[:, 0], self.tri[:, 1] - self.tri[:, 0], self.tri[:, 2] - self.tri[:, 0]
+        p = np.cross(d[:, None], e2[None])
+        det = np.sum(e1[None] * p, -1)
+        inv = 1.0 / np.where(det != 0, det, 1.0)
+        s = o[:, None] - v0[None]
+        u = np.sum(s * p, -1) * inv
+        q = np.cross(s, e1[None])
+        v = np.sum(d[:, None] * q, -1) * inv
+        t = np.sum(e2[None] * q, -1) * inv
+        dn = d / np.linalg.norm(d, axis=1, keepdims=True)
+        cosg = np.abs(dn @ self.tri_wn.T)
+        m = np.where(det != 0, np.minimum(np.minimum(u, v), 1 - u - v), -np.inf)
+        amb = cosg < GRAZE
+        kind = np.zeros_like(t, dtype=np.int64)
+        idx = np.broadcast_to(np.arange(len(self.tri)), t.shape)
+        out.append((t, m, amb, u, v, kind, idx, np.zeros_like(t)))
+        if len(self.cp):
+            sign = np.where(dn[:, 2] >= 0, 1.0, -1.0)
+            a = -1.0 / (sign + dn[:, 2])
+            b = dn[:, 0] * dn[:, 1] * a
+            bx = np.stack([1 + sign * dn[:, 0] ** 2 * a, sign * b, -sign * dn[:, 0]], 1)
+            by = np.stack([b, sign + dn[:, 1] ** 2 * a, -dn[:, 1]], 1)
+            rel = self.pts[None, :, :, :3] - o[:, None, None]              # (N,S,5,3)
+            px, py = np.einsum("nskc,nc->nsk", rel, bx), np.einsum("nskc,nc->nsk", rel, by)
+            pz = np.einsum("nskc,nc->nsk", rel, dn)
+            pr = self.pts[None, :, :, 3]
+            dl = np.linalg.norm(d, axis=1)[:, None, None]
+            ex, ey = px[..., 1:] - px[..., :-1], py[..., 1:] - py[..., :-1]
+            len2 = ex * ex + ey * ey
+            ss = -(px[..., :-1] * ex + py[..., :-1] * ey) / np.where(len2 > 0, len2, 1.0)
+            dist = (ey * px[..., :-1] - ex * py[..., :-1]) / np.sqrt(np.where(len2 > 0, len2, 1.0))
+            r = pr[..., :-1] + ss * (pr[..., 1:] - pr[..., :-1])
+            tc = (pz[..., :-1] + ss * (pz[..., 1:] - pz[..., :-1])) / dl
+            vv = dist / np.where(r > 0, r, 1.0)
+            # float32 positions carry ~POS_TOL x their magnitude: on a thin ribbon that is a visible share of r
+            slack = POS_TOL * (np.linalg.norm(o, axis=1)[:, None, None] + np.abs(pz[..., :-1])) / np.where(r > 0, r, 1.0)
+            mc = np.where((len2 > 0) & (r > 0), np.minimum(np.minimum(ss, 1 - ss), 1 - np.abs(vv) - slack), -np.inf)
+            n, S = tc.shape[:2]
+            uc = (np.arange(4)[None, None] + ss) / 4
+            out.append((tc.reshape(n, -1), mc.reshape(n, -1), np.zeros((n, S * 4), bool), uc.reshape(n, -1), vv.reshape(n, -1),
+                        np.ones((n, S * 4), np.int64), np.broadcast_to(np.repeat(np.arange(S), 4), (n, S * 4)),
+                        slack.reshape(n, -1)))
+        t, m, amb, u, v, kind, idx, vt = (np.concatenate([c[k] for c in out], 1) for k in range(8))
+        # ambiguous: within MARGIN of an edge, t within T_SEP of tmin, a sliver, or a grazing ray near the triangle
+        tm = tmin[:, None]
+        near = m > -MARGIN
+        at_tmin = near & (np.abs(t - tm) <= T_SEP * np.maximum(np.abs(t), np.abs(tm)))
+        valid = t > tm
+        amb = valid & ((near & (m < MARGIN)) | (kind == 0) & amb & (m > -0.1))
+        amb |= at_tmin
+        # a sliver may be reported wherever the ray crosses its (slightly widened) box -- the contract's validation rule --
+        # so it is ambiguous from the box's entry on, and never a required hit
+        sv = np.nonzero(self.sliver)[0]
+        if len(sv):
+            lo, hi = self.tri[sv].min(1), self.tri[sv].max(1)
+            pad = POS_TOL * (np.abs(self.tri[sv]).max((1, 2)) + 1.0)[:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = 1.0 / d
+                ta = ((lo - pad)[None] - o[:, None]) * inv[:, None]
+                tb = ((hi + pad)[None] - o[:, None]) * inv[:, None]
+                tn = np.nanmax(np.minimum(ta, tb), -1)
+                tf = np.nanmin(np.maximum(ta, tb), -1)
+            tn = np.maximum(tn, tmin[:, None])
+            crosses = tf >= tn
+            t[:, sv] = np.where(crosses, tn, t[:, sv])
+            amb[:, sv] = crosses
+            m[:, sv] = np.where(crosses, 0.0, -np.inf)
+            valid[:, sv] = crosses
+        m = np.where(valid, m, -np.inf)
+        return t, m, amb, u, v, kind, idx, vt
+
+    def ids(self, kind, idx):
+        return np.where(kind[..., None] == 0, self.tri_id[np.where(kind == 0, idx, 0)],
+                        self.cp_id[np.where(kind == 1, idx, 0)] if len(self.cp) else 0)
+
+
+def rays_for(geo, lo, hi, seed):
+    """random rays through the scene box, plus rays aimed at random points of random primitives (triangle interiors,
+    ribbon points within 1.5 radii of the centre line) from random origins"""
+    rng = np.random.RandomState(seed)
+    rays = scenes.random_rays((lo, hi), N_RANDOM, seed=seed)
+    lo64, hi64 = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    org = lo64 + (hi64 - lo64) * rng.rand(N_AIMED, 3)
+    tgt = np.zeros((N_AIMED, 3))
+    ntri = N_AIMED if not len(geo.cp) else N_AIMED // 3
+    k = rng.randint(len(geo.tri), size=ntri)
+    w = rng.dirichlet((1, 1, 1), size=ntri)
+    tgt[:ntri] = np.einsum("nk,nkc->nc", w, geo.tri[k])
+    if len(geo.cp):
+        nc = N_AIMED - ntri
+        k = rng.randint(len(geo.cp), size=nc)
+        uu = rng.rand(nc)
+        s = 1 - uu
+        B = np.stack([s ** 3, 3 * uu * s * s, 3 * uu * uu * s, uu ** 3], 1)
+        c = np.einsum("nj,njc->nc", B, geo.cp[k])
+        side = rng.normal(size=(nc, 3))
+        side /= np.linalg.norm(side, axis=1, keepdims=True)
+        tgt[ntri:] = c[:, :3] + side * c[:, 3:] * rng.uniform(0, 1.5, (nc, 1))
+    aimed = np.zeros(N_AIMED, rays.dtype)
+    aimed["org"], aimed["dir"] = org, (tgt - org) * rng.uniform(0.5, 2.0, (N_AIMED, 1))
+    aimed["tmin"], aimed["tmax"] = 1e-3, 1.844e18
+    return np.concatenate([rays, aimed])
+
+
+def check(desc, hits, rays, geo):
+    """the contract, ray by ray; returns counts of (required hits, required misses, reported hits checked)"""
+    o = rays["org"].astype(np.float64)
+    d = rays["dir"].astype(np.float64)
+    tmin = rays["tmin"].astype(np.float64)
+    n_hit = n_miss = n_rep = 0
+    for c0 in range(0, len(rays), 250):
+        sl = slice(c0, c0 + 250)
+        t, m, amb, u, v, kind, idx, vt = geo.candidates(o[sl], d[sl], tmin[sl])
+        h = hits[sl]
+        tpos = POS_TOL * np.linalg.norm(o[sl], axis=1) / np.linalg.norm(d[sl], axis=1)     # t's floor: the origin's rounding
+        cand = (m >= 0) | amb
+        for r in range(len(h)):
+            ci = np.nonzero(cand[r])[0]
+            rid = c0 + r
+            got = h[r]["instance_id"] != NONE
+            if len(ci) == 0:
+                n_miss += 1
+                assert not got, f"ray {rid}: float64 misses every primitive by >= {MARGIN}, the back end reports {h[r]}"
+            else:
+                w = ci[np.argmin(t[r, ci])]
+                others = ci[ci != w]
+                clear = (not amb[r, w] and m[r, w] >= MARGIN
+                         and np.all(t[r, others] > t[r, w] * (1 + T_SEP) + tpos[r]))
+                if clear:
+                    n_hit += 1
+                    assert got, f"ray {rid}: misses; float64 hits kind {kind[r, w]} #{idx[r, w]} at t={t[r, w]}"
+                    inst, prim = geo.ids(kind[r, w], idx[r, w])
+                    assert (h[r]["instance_id"], h[r]["prim_id"]) == (inst, prim), \
+                        f"ray {rid}: reports ({h[r]['instance_id']}, {h[r]['prim_id']}), float64 winner ({inst}, {prim})"
+                    assert abs(h[r]["t"] - t[r, w]) <= T_TOL * t[r, w] + tpos[r], (rid, h[r]["t"], t[r, w])
+                    assert abs(h[r]["u"] - u[r, w]) <= UV_TOL and abs(h[r]["v"] - v[r, w]) <= UV_TOL + vt[r, w], \
+                        (rid, (h[r]["u"], h[r]["v"]), (u[r, w], v[r, w]))
+                    if kind[r, w] == 0:
+                        ng = geo.tri_ng[idx[r, w]]
+                    else:
+                        ng = Geometry.tangent(geo.cp[idx[r, w]], u[r, w])
+                    cosn = np.dot(h[r]["normal_g"].astype(np.float64), ng) / np.linalg.norm(ng) / np.linalg.norm(h[r]["normal_g"])
+                    assert cosn >= NG_COS, (rid, h[r]["normal_g"], ng / np.linalg.norm(ng))
+            if got:
+                # every reported hit is a float64 hit of the reported primitive, within tolerance
+                n_rep += 1
+                inst, prim = int(h[r]["instance_id"]), int(h[r]["prim_id"])
+                is_curve = inst >= len(desc.shapes)
+                sel = np.nonzero((kind[r] == int(is_curve)) & np.all(geo.ids(kind[r], idx[r]) == (inst, prim), -1))[0]
+                assert len(sel), (rid, inst, prim)
+                if not is_curve and geo.sliver[sel[0]]:
+                    p = o[rid] + float(h[r]["t"]) * d[rid]
+                    tri = geo.tri[sel[0]]
+                    pad = 1e-5 * (np.abs(tri).max() + 1.0)
+                    assert np.all(p >= tri.min(0) - pad) and np.all(p <= tri.max(0) + pad), (rid, p, tri)
+                    continue
+                dt = np.abs(t[r, sel] - h[r]["t"])
+                ok = (m[r, sel] >= -UV_TOL) & (dt <= T_TOL * np.abs(t[r, sel]) + tpos[r])
+                ok |= amb[r, sel] & (dt <= T_TOL_AMB * np.abs(t[r, sel]))
+                assert ok.any(), (rid, h[r], t[r, sel], m[r, sel])
+    return n_hit, n_miss, n_rep
+
+
+def _run(name, tracer):
+    desc = scene(name)
+    so = O.oracle_scene_from_desc(desc)
+    geo = Geometry(desc)
+    lo, hi = so.FetchSceneAABB()
+    rays = rays_for(geo, lo, hi, seed=11)
+    hits = tracer(desc, so, rays)
+    n_hit, n_miss, n_rep = check(desc, hits, rays, geo)
+    print(f"{name}: {n_hit} required hits, {n_miss} required misses, {n_rep} reported hits checked of {len(rays)} rays")
+    assert n_hit >= 400 and n_miss >= 150, (n_hit, n_miss)   # the check has teeth on every scene
+
+
+def _oracle_tracer(desc, so, rays):
+    return so.trace_closest(rays)
+
+
+def _gpu_tracer(desc, so, rays):
+    import pbrlab_amd as pa
+    if pa.device_count() < 1:
+        pytest.fail("no HIP device: the GPU tests must run on an MI355X (there is no CPU fallback)")
+    pa.set_device(0)
+    return pa.scene_from_desc(desc).trace_closest(rays)
+
+
+@pytest.mark.parametrize("backend", ["oracle", pytest.param("gpu", marks=pytest.mark.gpu)])
+@pytest.mark.parametrize("name", SCENES)
+def test_trace_closest_matches_f64_contract(name, backend):
+    _run(name, _oracle_tracer if backend == "oracle" else _gpu_tracer)

@@ -186,6 +186,7 @@ def test_libm_tolerance_at_the_configurations_own_spp(pa, config):
         # largest differences: 7.0e-5; without 1 000: 1.3e-6).  Any two libm builds differ from each other in the same way.
         # that is the 1e-4 contract NOT MET against this host's libm, not a weaker bar to assert -- report it as such
         if not r < REL_L2_TOL:
+            assert r < 3e-3, r      # the xfail covers the measured band (1.1e-3) only, not any r >= 1e-4
             pytest.xfail(f"C5 at 1024 spp against a libm the device does not restate ({' '.join(platform.libc_ver())}): plain rel L2 {r:.2e} >= 1e-4 "
                          f"(NOT MET; without the {nflip} pixels holding a flipped sample: {r_rest:.1e})")
 
