@@ -203,6 +203,14 @@ int pbrhip_scene_aabb(const pbrhip_scene*, float bmin[3], float bmax[3]);
  * material's parameters in place on a committed scene */
 int pbrhip_scene_update_principled_material(pbrhip_scene*, uint32_t material_id, const pbrhip_principled_param*);
 int pbrhip_scene_update_hair_material(pbrhip_scene*, uint32_t material_id, const pbrhip_hair_param*);
+/* A lat-long environment light: rgb = width x height x 3 floats, row 0 = the top (+y up; a ray along -z sees the
+ * middle of the map), nearest-sampled, times `scale`.  world_to_env: a 3x3 rotation, row-major, applied to world directions before
+ * the lookup (NULL: identity).  A ray that leaves the scene collects it (with MIS), and NEE samples it by luminance x solid angle.
+ * rgb == NULL removes the environment; an all-black map is no environment.  Valid before or after pbrhip_scene_commit: takes
+ * effect at the next render.  A negative, NaN or infinite texel or scale, a zero size or a matrix that is no rotation:
+ * PBRHIP_EINVAL.  The map is copied. */
+int pbrhip_scene_set_environment(pbrhip_scene*, const float* rgb, uint32_t width, uint32_t height, float scale,
+                                 const float world_to_env[9]);
 /* BVH facts for reports: node count, leaf slots, depth, device bytes */
 int pbrhip_scene_info(const pbrhip_scene*, uint64_t* num_nodes, uint64_t* num_slots, uint32_t* depth,
                       uint64_t* device_bytes);

@@ -366,6 +366,11 @@ public:
   }
   // scene.cc:251-259 (the header there names the arguments (bmax, bmin); every caller passes (bmin, bmax))
   void FetchSceneAABB(float* bmin, float* bmax) const { Check(pbrhip_scene_aabb(h_, bmin, bmax)); }
+  // A lat-long environment light (pbrhip_scene_set_environment): rgb = width x height x 3 floats, row 0 = the top; world_to_env a
+  // row-major rotation or null.  rgb == nullptr removes it.  Takes effect at the next Render().
+  void SetEnvironment(const float* rgb, uint32_t width, uint32_t height, float scale = 1.0f, const float* world_to_env = nullptr) {
+    Check(pbrhip_scene_set_environment(h_, rgb, width, height, scale, world_to_env));
+  }
 
   // scene.h:81, scene.cc:206-208: the scene's material table; the GUI edits its elements between renders
   // (pc/glfw-window.cc:866-979 through EditQueue, pc/pc-common.cc:57-84).  An edit reaches the GPU at the next Render():

@@ -230,6 +230,18 @@ class Scene:
         _chk(self.L.pbrhip_scene_add_texture(self.h, _ptr(px), px.shape[1], px.shape[0], px.shape[2], C.byref(out)))
         return out.value
 
+    def SetEnvironment(self, rgb_hw3, scale=1.0, world_to_env=None):
+        """A lat-long environment light (DESIGN.md §10): rgb_hw3 (H, W, 3) float radiance, row 0 = the top, times `scale`;
+        world_to_env a 3x3 rotation (None: identity).  None removes it; an all-black map is none.  Takes effect at the next render."""
+        if rgb_hw3 is None:
+            _chk(self.L.pbrhip_scene_set_environment(self.h, None, 0, 0, C.c_float(1.0), None))
+            return
+        px = np.ascontiguousarray(rgb_hw3, np.float32)
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("environment map must be (H, W, 3)")
+        m = None if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(9)
+        _chk(self.L.pbrhip_scene_set_environment(self.h, _ptr(px), px.shape[1], px.shape[0], C.c_float(scale), _ptr(m)))
+
     def AddLightParam(self, emission):
         e = np.ascontiguousarray(emission, np.float32).reshape(3)
         out = C.c_uint32()

@@ -260,6 +260,13 @@ struct DScene {
   uint32_t lights_transformed;  // an emissive instance has a transform: lrecs / light_boxes are not what the raytracer sees
   const SssEntry* sss_entries;  // per instance (num_sss_entries), or null: where its random walks' rays start
   uint32_t num_sss_entries;
+  // the lat-long environment light (denv.h, env_tables.cpp), appended so that the fields above keep their offsets
+  const float4* env_texels;     // env_w x env_h: radiance x scale (rgb), pdf_env per steradian (w); null: no environment
+  const uint2* env_alias;       // per texel: (keep probability as float bits, alias texel)
+  uint32_t env_w, env_h;
+  float env_p;                  // probability that a NEE event samples the environment (1 without area lights, else 1/2)
+  float env_area_scale;         // 1 - env_p: applied to the area lights' pdf by the environment kernels
+  float env_m[9];               // world_to_env, row-major (a rotation)
 };
 
 // camera of RenderingTile (render.cc:132-158), derived on the host from the scene AABB

@@ -2,6 +2,7 @@
 // principled closure set, random-walk SSS coefficients, hair set-up.  file:line = pbrlab code.
 #pragma once
 
+#include "denv.h"
 #include "dtrace.h"
 
 namespace pb {
@@ -161,9 +162,49 @@ __device__ __forceinline__ bool nee_sample_from(const Tables& lt, uint32_t num_l
   n.pdf_sigma = fabsf(pdf * n.dist * n.dist / (wl_dot_nl * wl_dot_np));
   return (!hemisphere) || (wl_dot_nl > 0.0f && wl_dot_np > 0.0f);
 }
+// The environment's NEE: a texel in proportion to lum * solid angle (alias table: the texel from 64 raw random bits,
+// the coin from 32 more), then a direction uniform over the texel's solid angle (two draws).  emission = L |dot(w, N)| and
+// pdf_sigma = p_env pdf_env, both per steradian, so nee_contribution's weight is power_heuristic(p_env pdf_env, bsdf_pdf) and the estimate
+// f L |cos| / (p_env pdf_env); the shadow ray spans [kEps, kInf] (Q9).
+__device__ __forceinline__ bool env_nee(const DScene& sc, Rng& rng, V3 global_normal, bool hemisphere, Nee& n) {
+  // a texel uniformly from 64 random bits (the high word of bits x W H: each texel within W H / 2^64 relative of 1 / (W H)), then
+  // the alias coin from 32 more (kept when below the threshold: within 2^-32 of the table's keep probability)
+  const uint32_t hi = pcg32(rng);
+  const uint32_t lo = pcg32(rng);
+  const uint32_t i = (uint32_t)__umul64hi(((uint64_t)hi << 32) | lo, (uint64_t)sc.env_w * sc.env_h);
+  const uint32_t coin = pcg32(rng);
+  const float u = draw(rng);
+  const float v = draw(rng);
+  const uint2 a = sc.env_alias[i];  // (keep threshold, alias texel)
+  const uint32_t t = coin < a.x ? i : a.y;
+  const float4 L = sc.env_texels[t];
+  const uint32_t row = t / sc.env_w, col = t - row * sc.env_w;
+  n.dir = env_to_world(sc.env_m, env_texel_dir(col, row, sc.env_w, sc.env_h, u, v));
+  n.dist = kInf;
+  const float c = dot(n.dir, global_normal);
+  n.emission = V3(L.x, L.y, L.z) * V3(fabsf(c));
+  n.pdf_sigma = sc.env_p * L.w;
+  return (!hemisphere) || c > 0.0f;
+}
 // lds_lights: the light tables staged in LDS (LdsLightTables layout), or null
+// ENV (the environment kernels): one draw first picks the environment (probability env_p) or the area lights, whose pdf then carries 1 - env_p
+template <bool ENV = false>
 __device__ __forceinline__ bool nee_sample(const DScene& sc, Rng& rng, V3 pos, V3 global_normal, bool hemisphere, Nee& n,
                                            const float* lds_lights = nullptr) {
+  if (ENV) {
+    const float u_sel = draw(rng);
+    if (u_sel < sc.env_p) return env_nee(sc, rng, global_normal, hemisphere, n);
+    bool r;
+    if (lds_lights) {
+      const LdsLightTables lt = {(LdsFloats)lds_lights};
+      r = nee_sample_from(lt, sc.num_lights, rng, pos, global_normal, hemisphere, n);
+    } else {
+      const GlobalLightTables lt = {sc};
+      r = nee_sample_from(lt, sc.num_lights, rng, pos, global_normal, hemisphere, n);
+    }
+    n.pdf_sigma = n.pdf_sigma * sc.env_area_scale;
+    return r;
+  }
   if (lds_lights) {
     const LdsLightTables lt = {(LdsFloats)lds_lights};
     return nee_sample_from(lt, sc.num_lights, rng, pos, global_normal, hemisphere, n);

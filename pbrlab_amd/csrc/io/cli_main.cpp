@@ -1,13 +1,14 @@
 // pbrlab-hip-cli -- pbrlab-cli (pc/pbrlab-cli.cc:16-60) on the MI355X path tracer.
 //
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
-//                  [--gpus N] [--bvh host|gpu]
+//                  [--gpus N] [--bvh host|gpu] [--env FILE [--env-scale S]]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
 // GPU g % (GPUs present): one host thread per rank, the scene is ingested once and copied device-to-device, the shards
 // are gathered on the first GPU over xGMI inside the library (pbrhip_render_multi).  --bvh gpu builds the acceleration structure
-// on the GPU (faster commit, slightly slower traversal, same image).
+// on the GPU (faster commit, slightly slower traversal, same image).  --env FILE lights the scene with a lat-long environment map
+// (.hdr, .exr or any LDR format pbrio_image_load reads), times --env-scale (default 1).
 #include <atomic>
 #include <cerrno>
 #include <cstdio>
@@ -26,6 +27,8 @@ int main(int argc, char** argv) {
   size_t width = 512, height = 512, samples = 32;  // pbrlab-cli.cc:36-38
   int gpus = 1, bvh = PBRHIP_BVH_HOST_SAH;
   std::string out = "rgba.png";
+  const char* env = nullptr;
+  float env_scale = 1.0f;
   std::vector<const char*> files;
   files.push_back(argv[0]);
   for (int i = 1; i < argc; ++i) {
@@ -55,6 +58,16 @@ int main(int argc, char** argv) {
     else if (a == "--out") out = value("--out");
     else if (a == "--gpus") gpus = int(number("--gpus", 1024));
     else if (a == "--bvh") bvh = std::string(value("--bvh")) == "gpu" ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+    else if (a == "--env") env = value("--env");
+    else if (a == "--env-scale") {
+      const char* v = value("--env-scale");
+      char* end = nullptr;
+      env_scale = strtof(v, &end);
+      if (end == v || *end || !(env_scale >= 0.0f) || env_scale > 3.0e38f) {
+        std::cerr << "--env-scale needs a finite number >= 0, got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
+    }
     else files.push_back(argv[i]);
   }
   if (files.size() < 2) {
@@ -78,6 +91,28 @@ int main(int argc, char** argv) {
   if (pbrio_create_scene(int(files.size()), files.data(), scene.handle()) != PBRHIP_OK) {
     std::cerr << "scene: " << pbrio_last_error() << std::endl;
     return EXIT_FAILURE;
+  }
+  if (env) {  // the map as RGB (one channel: grey; two: grey + alpha, alpha dropped; four: alpha dropped)
+    float* px = nullptr;
+    size_t w = 0, h = 0, c = 0;
+    const std::string path(env);
+    const size_t cut = path.find_last_of('/');
+    const std::string edir = cut == std::string::npos ? "./" : path.substr(0, cut + 1);
+    const std::string ename = cut == std::string::npos ? path : path.substr(cut + 1);
+    if (pbrio_image_load(ename.c_str(), edir.c_str(), &px, &w, &h, &c) != PBRHIP_OK) {
+      std::cerr << "--env: " << pbrio_last_error() << std::endl;
+      return EXIT_FAILURE;
+    }
+    std::vector<float> rgb(w * h * 3);
+    for (size_t i = 0; i < w * h; ++i)
+      for (size_t k = 0; k < 3; ++k) rgb[3 * i + k] = px[c * i + (c >= 3 ? k : 0)];
+    pbrio_free(px);
+    try {
+      scene.SetEnvironment(rgb.data(), uint32_t(w), uint32_t(h), env_scale);
+    } catch (const std::exception& e) {
+      std::cerr << "--env: " << e.what() << std::endl;
+      return EXIT_FAILURE;
+    }
   }
   std::atomic_bool cancel_render_flag(false);
   std::atomic_size_t finish_pass(0);

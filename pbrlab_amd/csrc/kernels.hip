@@ -439,55 +439,62 @@ struct TileCompactor {
 // ShadeRec (kHitMore: corner normals / texcoords: the smooth meshes), then the hits on flat triangles -- so that a shading wave is
 // mostly one kind or the other: the same queue, the same lines touched per tile, fewer waves that run both sides of every branch
 // (north star: "per-closure material sorting", here by what the hit code already says; separate queues lose: profiles/README.md).
-__global__ __launch_bounds__(kBlock) void k_classify(PathState P, DScene sc) {
-  constexpr int kItemsPerThread = kClassifyItems, kTileItems = kItemsPerThread * kBlock;
-  __shared__ uint32_t wcount[4][kItemsPerThread][kWavesPerBlock];
-  __shared__ uint32_t base[4];
-  __shared__ uint32_t tile_principled[2];  // this tile's two runs: counted in LDS, reserved in the queue with ONE atomic
-  const uint32_t n = P.counts[kCntIn];
-  const uint32_t ntiles = (n + kTileItems - 1) / kTileItems;
-  uint32_t* const counters[4] = {&P.counts[kCntSss], &tile_principled[0], &P.counts[kCntHair], &tile_principled[1]};
-  uint32_t* const queues[4] = {P.q_sss, P.q_principled, P.q_hair, P.q_principled};
-  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    uint32_t p[kItemsPerThread], dest[kItemsPerThread];  // p: path slot | kQFirst (handed on to the shading queues)
-    bool doomed[kItemsPerThread];
-#pragma unroll
-    for (int j = 0; j < kItemsPerThread; j++) {
-      uint32_t i = tile * kTileItems + j * kBlock + threadIdx.x;
-      dest[j] = 0, p[j] = 0, doomed[j] = false;
-      if (i < n) {
-        const uint32_t e = P.first ? ((P.slot0 + i) | kQFirst) : P.q_in[i];  // (a group's first bounce: entry i is path slot0 + i)
-        p[j] = e & (kQPathMask | kQFirst | kQDoomed);  // (kQDoomed rides along: a held path hands it back, kernels.h::kRHold)
-        dest[j] = (!P.no_medium && (e & kQSssBit)) ? 1u : 0xFFu;  // (without media bit 31 is kQHold: the path is routed by its hit like any other)
-        doomed[j] = (e & kQDoomed) != 0u;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kItemsPerThread; j++)
-      if (dest[j] == 0xFFu) {
-        const uint32_t code = __float_as_uint(P.hit[p[j] & kQPathMask].w);
-        dest[j] = (code & kHitHair) ? 3u : ((PB_CLASSIFY_RUNS == 2 && (code & kHitMore)) ? 2u : 4u);
-        if (code == kNone || (!(code & kHitLight) && (doomed[j] || (code & kHitNoMaterial)))) dest[j] = 0u;
-        // a path whose ray was suspended (its ray goes on in the next launch) rides through the principled queue untouched: the shading
-        // kernel turns its entry into a "resume" result word and k_compact re-queues it -- no atomic, no queue of its own
-        if (code == kHitSuspended) dest[j] = 4u, p[j] |= kQResume;
-      }
-    if (threadIdx.x < 2) tile_principled[threadIdx.x] = 0u;
-    __syncthreads();
-    TileCompactor<4, kItemsPerThread> tc = {wcount, base, {}};
-    tc.run(dest, counters);  // (base[1] = base[3] = 0: the two runs were counted from 0)
-    if (threadIdx.x == 0) {
-      const uint32_t a = tile_principled[0], b = tile_principled[1];
-      const uint32_t g = (a + b) ? atomicAdd(&P.counts[kCntPrincipled], a + b) : 0u;
-      base[1] = g, base[3] = g + a;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kItemsPerThread; j++)
-      if (dest[j]) queues[dest[j] - 1][tc.slot(j, dest[j])] = p[j];
-    __syncthreads();
+// ENV (k_classify_env: scenes with an environment): a path whose ray missed goes to the principled queue's second run instead
+// of being dropped, doomed or not -- the principled shading adds the environment's radiance and ends it (or waits while it is held).
+// (The kernel body as a macro, spelled in each kernel: k_classify compiles to the instructions it did before the environment kernels
+// existed; a shared __device__ body moved its LDS addressing.)
+#define PB_CLASSIFY_KERNEL(ENV) \
+  constexpr int kItemsPerThread = kClassifyItems, kTileItems = kItemsPerThread * kBlock;                                                               \
+  __shared__ uint32_t wcount[4][kItemsPerThread][kWavesPerBlock];                                                                                      \
+  __shared__ uint32_t base[4];                                                                                                                         \
+  __shared__ uint32_t tile_principled[2]; /* this tile's two runs: counted in LDS, reserved in the queue with ONE atomic */                            \
+  const uint32_t n = P.counts[kCntIn];                                                                                                                 \
+  const uint32_t ntiles = (n + kTileItems - 1) / kTileItems;                                                                                           \
+  uint32_t* const counters[4] = {&P.counts[kCntSss], &tile_principled[0], &P.counts[kCntHair], &tile_principled[1]};                                   \
+  uint32_t* const queues[4] = {P.q_sss, P.q_principled, P.q_hair, P.q_principled};                                                                     \
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {                                                                                 \
+    uint32_t p[kItemsPerThread], dest[kItemsPerThread]; /* p: path slot | kQFirst (handed on to the shading queues) */                                 \
+    bool doomed[kItemsPerThread];                                                                                                                      \
+_Pragma("unroll")                                                                                                                                      \
+    for (int j = 0; j < kItemsPerThread; j++) {                                                                                                        \
+      uint32_t i = tile * kTileItems + j * kBlock + threadIdx.x;                                                                                       \
+      dest[j] = 0, p[j] = 0, doomed[j] = false;                                                                                                        \
+      if (i < n) {                                                                                                                                     \
+        const uint32_t e = P.first ? ((P.slot0 + i) | kQFirst) : P.q_in[i]; /* (a group's first bounce: entry i is path slot0 + i) */                  \
+        p[j] = e & (kQPathMask | kQFirst | kQDoomed); /* (kQDoomed rides along: a held path hands it back, kernels.h::kRHold) */                       \
+        dest[j] = (!P.no_medium && (e & kQSssBit)) ? 1u : 0xFFu; /* (without media bit 31 is kQHold: the path is routed by its hit like any other) */  \
+        doomed[j] = (e & kQDoomed) != 0u;                                                                                                              \
+      }                                                                                                                                                \
+    }                                                                                                                                                  \
+_Pragma("unroll")                                                                                                                                      \
+    for (int j = 0; j < kItemsPerThread; j++)                                                                                                          \
+      if (dest[j] == 0xFFu) {                                                                                                                          \
+        const uint32_t code = __float_as_uint(P.hit[p[j] & kQPathMask].w);                                                                             \
+        dest[j] = (code & kHitHair) ? 3u : ((PB_CLASSIFY_RUNS == 2 && (code & kHitMore)) ? 2u : 4u);                                                   \
+        if (code == kNone || (!(code & kHitLight) && (doomed[j] || (code & kHitNoMaterial)))) dest[j] = 0u;                                            \
+        if (ENV && code == kNone) dest[j] = 4u;                                                                                                        \
+        /* a path whose ray was suspended (its ray goes on in the next launch) rides through the principled queue untouched: the shading */            \
+        /* kernel turns its entry into a "resume" result word and k_compact re-queues it -- no atomic, no queue of its own */                          \
+        if (code == kHitSuspended) dest[j] = 4u, p[j] |= kQResume;                                                                                     \
+      }                                                                                                                                                \
+    if (threadIdx.x < 2) tile_principled[threadIdx.x] = 0u;                                                                                            \
+    __syncthreads();                                                                                                                                   \
+    TileCompactor<4, kItemsPerThread> tc = {wcount, base, {}};                                                                                         \
+    tc.run(dest, counters); /* (base[1] = base[3] = 0: the two runs were counted from 0) */                                                            \
+    if (threadIdx.x == 0) {                                                                                                                            \
+      const uint32_t a = tile_principled[0], b = tile_principled[1];                                                                                   \
+      const uint32_t g = (a + b) ? atomicAdd(&P.counts[kCntPrincipled], a + b) : 0u;                                                                   \
+      base[1] = g, base[3] = g + a;                                                                                                                    \
+    }                                                                                                                                                  \
+    __syncthreads();                                                                                                                                   \
+_Pragma("unroll")                                                                                                                                      \
+    for (int j = 0; j < kItemsPerThread; j++)                                                                                                          \
+      if (dest[j]) queues[dest[j] - 1][tc.slot(j, dest[j])] = p[j];                                                                                    \
+    __syncthreads();                                                                                                                                   \
   }
-}
+__global__ __launch_bounds__(kBlock) void k_classify(PathState P, DScene sc) { PB_CLASSIFY_KERNEL(false) }
+__global__ __launch_bounds__(kBlock) void k_classify_env(PathState P, DScene sc) { PB_CLASSIFY_KERNEL(true) }
+#undef PB_CLASSIFY_KERNEL
 
 // ------------------------------------------------------------------ k_compact
 // The shade kernels overwrite their queue entry with  path | kRShadow | kRAlive | kQSssBit | kQDoomed  instead of
@@ -556,7 +563,8 @@ enum : int { kHeadEnds = 0, kHeadGoes = 1, kHeadHeld = 2 };
 // HOLD: the kernel can meet held paths (scenes without media only: compiled out of the kernel of scenes with media, kShadeMedia, which sits at the
 // edge of its register class; the kShadeFull instances also serve scenes without media -- the statistics build of k_tail -- and keep the hold word
 // initialised: a hair shading of the same path reads it)
-template <bool HOLD = true>
+// ENV (the environment kernels): the area lights' pdf carries 1 - env_p, the probability that NEE samples them
+template <bool HOLD = true, bool ENV = false>
 __device__ __forceinline__ int path_head(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc, PathHead& c, bool first) {
   float4 h4 = P.hit[p];
   float4 o4 = make_float4(P.cam_org[0], P.cam_org[1], P.cam_org[2], 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -582,6 +590,7 @@ __device__ __forceinline__ int path_head(const PathState& P, const DScene& sc, u
   if (!held && c.s.face == kFront && c.s.lightrec != kNone) {  // render.cc:43-62, LightManager::ImplicitAreaLight
     const float4* lr = reinterpret_cast<const float4*>(sc.lrecs + c.s.lightrec);
     float pdf_area = lr[0].w;
+    if (ENV) pdf_area = pdf_area * sc.env_area_scale;
     V3 emission = ld3(lr[4]);
     float a2s = fabsf((c.h.t * c.h.t) / dot(c.s.n_s, c.dir));
     float w = (c.flags & kFlagNotFirst) ? power_heuristic(t4.w, pdf_area * a2s) : 1.0f;
@@ -602,6 +611,34 @@ template <bool HOLD = true>
 __device__ __forceinline__ void store_rng(const PathState& P, uint32_t p, uint64_t state) {
   if (HOLD) P.rng4[p] = make_uint4((uint32_t)state, (uint32_t)(state >> 32), 0u, 0u);
   else P.rng[p] = state;
+}
+
+// A path whose closest-hit ray missed, in a scene with an environment: L += thr L_env(w) weight, and the path ends (where
+// render.cc:34 breaks: before the roulette, no draw).  weight = 1 for a camera ray, else power_heuristic(bsdf_pdf, env_p pdf_env(w)) with
+// the pdf the path stored when it sampled the ray (P.thr.w).  Returns kRHold, touching nothing, while the path's shadow ray of the previous
+// bounce is suspended (path_head's rule: the shadow ray's contribution is added first).  A camera ray's direction is recomputed.
+__device__ __forceinline__ V3 env_radiance(const DScene& sc, V3 w, float& pdf) {
+  const float4 L = sc.env_texels[env_texel_index(env_from_world(sc.env_m, w), sc.env_w, sc.env_h)];
+  pdf = L.w;
+  return V3(L.x, L.y, L.z);
+}
+template <bool HOLD = true>
+__device__ __forceinline__ uint32_t env_miss_path(const PathState& P, const DScene& sc, uint32_t p, bool first) {
+  V3 dir;
+  float4 t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+  if (first) {
+    uint64_t state;
+    camera_sample(P, p - P.slot0, dir, state);
+  } else {
+    if (HOLD && P.no_medium != 0u && P.hold[p] != 0u) return kRHold;
+    dir = ld3(P.ray_d[p]), t4 = P.thr[p];
+  }
+  float pdf;
+  const V3 Le = env_radiance(sc, dir, pdf);
+  const float w = first ? 1.0f : power_heuristic(t4.w, sc.env_p * pdf);
+  const float4 L4 = P.L[p];
+  P.L[p] = mk4(ld3(L4) + w * Le * ld3(t4), L4.w);
+  return 0u;
 }
 
 // kQDoomed for a path that continues with throughput `thr` and generator state `state`: the head of its next shading
@@ -690,10 +727,17 @@ __device__ __forceinline__ bool stage_light_tables(const DScene& sc, float* lds)
 // lds_bsdf: the scene's closure sets staged in LDS by the caller (k_shade_principled when they fit), or null
 // MODE (what the scene's materials can do, so that code no hit can reach -- and the registers it holds -- is compiled out of the
 // wavefront kernel): kShadePlain: no medium, no texture; kShadeMedia: media (random-walk subsurface), no texture; kShadeFull.
-enum : int { kShadePlain = 0, kShadeMedia = 1, kShadeFull = 2 };
-template <int MODE = kShadeFull>
+// kShadeEnv (a bit on top of the three): the scene has an environment -- misses add its radiance, NEE samples it, the
+// doomed-path pretest is off.  Only the instances with the bit carry that code.
+enum : int { kShadePlain = 0, kShadeMedia = 1, kShadeFull = 2, kShadeEnv = 4 };
+constexpr int shade_base(int mode) { return mode & 3; }
+constexpr bool shade_env(int mode) { return (mode & kShadeEnv) != 0; }
+template <int MODE_ = kShadeFull>
 __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc, bool first,
                                                           const PrincipledBsdf* lds_bsdf = nullptr, const float* lds_lights = nullptr) {
+  constexpr int MODE = shade_base(MODE_);
+  constexpr bool ENV = shade_env(MODE_);
+  if (ENV && __float_as_uint(P.hit[p].w) == kNone) return env_miss_path<MODE != kShadeMedia>(P, sc, p, first);
   {
     const bool active = true;
     bool alive = false, shadow = false;
@@ -702,7 +746,7 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
     nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
     uint32_t sh_mode = kShNormal, qbit = 0u;
     PathHead c;
-    const int head = path_head<MODE != kShadeMedia>(P, sc, p, rng_inc, c, first);
+    const int head = path_head<MODE != kShadeMedia, ENV>(P, sc, p, rng_inc, c, first);
     if (active && head == kHeadGoes) {
       const Hit& h = c.h;
       const V3 dir = c.dir, thr = c.thr;
@@ -739,7 +783,7 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
         SampleWeight w = closure_sample_weight(wo, b);
         // DirectIllumination (shader-utils.h:166-212)
         V3 d1(0.f);
-        shadow = nee_sample(sc, rng, s.pos, fr.ez, true, nee, lds_lights);
+        shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ez, true, nee, lds_lights);
         if (shadow) {
           V3 f;
           float pdf;
@@ -832,7 +876,7 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
           V3 t2 = new_thr * thr;
           if (!is_black(t2)) {
             qbit = doomed_bit(t2, rng.state, rng_inc);
-            if (!(qbit && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
+            if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {  // (with an environment a doomed ray can still escape)
               alive = true;
               P.ray_o[p] = mk4(s.pos, 1e-3f);
               P.ray_d[p] = mk4(next_dir, kInf);
@@ -863,8 +907,17 @@ constexpr uint32_t kLdsMats = PB_LDS_MATS;  // closure sets staged in LDS by the
 #ifndef PB_SHADE_WAVES_MEDIA
 #define PB_SHADE_WAVES_MEDIA 4  // ... of scenes with media and no textures (C3, C5): 128-130 VGPRs by itself, pinned to the class it sits at the edge of
 #endif
-template <int MODE>
-__global__ __launch_bounds__(kBlock, MODE == kShadePlain ? PB_SHADE_WAVES : (MODE == kShadeMedia ? PB_SHADE_WAVES_MEDIA : PB_SHADE_WAVES_FULL)) void k_shade_principled(PathState P, DScene sc, uint64_t rng_inc) {
+#ifndef PB_SHADE_WAVES_MEDIA_ENV
+#define PB_SHADE_WAVES_MEDIA_ENV 3  // ... of scenes with media and an environment: at four waves the environment's NEE spilled 12 bytes
+#endif
+constexpr int shade_waves(int mode) {
+  return shade_base(mode) == kShadePlain ? PB_SHADE_WAVES
+                                         : (shade_base(mode) == kShadeMedia ? (shade_env(mode) ? PB_SHADE_WAVES_MEDIA_ENV : PB_SHADE_WAVES_MEDIA) : PB_SHADE_WAVES_FULL);
+}
+template <int MODE_>
+__global__ __launch_bounds__(kBlock, shade_waves(MODE_)) void k_shade_principled(PathState P, DScene sc, uint64_t rng_inc) {
+  constexpr int MODE = shade_base(MODE_);
+  constexpr bool ENV = shade_env(MODE_);
   __shared__ PrincipledBsdf lds_bsdf[kLdsMats ? kLdsMats : 1];
   __shared__ float lds_lights[kLdsMats ? kLdsLightWords : 1];
   const bool lights_staged = kLdsMats && stage_light_tables(sc, lds_lights);
@@ -894,6 +947,7 @@ __global__ __launch_bounds__(kBlock, MODE == kShadePlain ? PB_SHADE_WAVES : (MOD
       const uint32_t code = __float_as_uint(P.hit[p].w);
       const bool doomed = kAnyBounce && (e & kQDoomed);
       go = !(code == kNone || (!(code & kHitLight) && (doomed || (code & kHitNoMaterial))));  // (k_classify's drop rule)
+      if (ENV && code == kNone) go = true;  // (k_classify_env's: a miss collects the environment)
       if (code == kHitSuspended) {
         go = false, r = kRResume | kRResumeFirst;
         if (kAnyBounce && !P.first) r = kRResume | (e & kQDoomed) | ((e & kQFirst) ? kRResumeFirst : 0u);
@@ -901,13 +955,14 @@ __global__ __launch_bounds__(kBlock, MODE == kShadePlain ? PB_SHADE_WAVES : (MOD
     } else if (e & kQResume) {
       go = false, r = kRResume | (e & kQDoomed) | ((e & kQFirst) ? kRResumeFirst : 0u);
     }
-    if (go) r = shade_principled_path<MODE>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, staged ? lds_bsdf : nullptr, lights_staged ? lds_lights : nullptr);
+    if (go) r = shade_principled_path<MODE_>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, staged ? lds_bsdf : nullptr, lights_staged ? lds_lights : nullptr);
     if (r == kRHold && (e & kQDoomed) && (kAnyBounce ? !P.first : !direct)) r |= kRHoldDoomed;  // (a held path hands its queue entry's kQDoomed back)
     P.q_principled[i] = p | r;
   }
 }
 
 // ------------------------------------------------------------------ k_shade_hair (hair-shader.cc:153-229)
+template <bool ENV = false>
 __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc, bool first,
                                                     const float* lds_lights = nullptr) {
   {
@@ -918,7 +973,7 @@ __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DS
     Nee nee;
     nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
     PathHead c;
-    const int head = path_head(P, sc, p, rng_inc, c, first);
+    const int head = path_head<true, ENV>(P, sc, p, rng_inc, c, first);
     if (active && head == kHeadGoes) {
       const Hit& h = c.h;
       const V3 dir = c.dir, thr = c.thr;
@@ -936,7 +991,7 @@ __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DS
         HairSetup S;
         hair_prepare(wo, hb, S);
         V3 d1(0.f);
-        shadow = nee_sample(sc, rng, s.pos, fr.ex, false, nee, lds_lights);
+        shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ex, false, nee, lds_lights);
         if (shadow) {
           V3 wl = to_local(fr, nee.dir);
           float pdf;
@@ -959,7 +1014,7 @@ __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DS
         V3 t2 = new_thr * thr;
         if (!is_black(t2)) {
           qbit = doomed_bit(t2, rng.state, rng_inc);
-          if (!(qbit && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
+          if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
             alive = true;
             P.ray_o[p] = mk4(s.pos, 1e-3f);
             P.ray_d[p] = mk4(next_dir, kInf);
@@ -976,18 +1031,23 @@ __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DS
     return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
   }
 }
-__global__ __launch_bounds__(kBlock) void k_shade_hair(PathState P, DScene sc, uint64_t rng_inc) {
-  __shared__ float lds_lights[kLdsLightWords];
-  const bool lights_staged = stage_light_tables(sc, lds_lights);
-  if (lights_staged) __syncthreads();
-  const uint32_t n = P.counts[kCntHair];
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    const uint32_t e = P.q_hair[i], p = e & kQPathMask;
-    uint32_t r = shade_hair_path(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, lights_staged ? lds_lights : nullptr);
-    if (r == kRHold && (e & kQDoomed)) r |= kRHoldDoomed;  // (a held path hands its queue entry's kQDoomed back)
-    P.q_hair[i] = p | r;
+// (the kernel body as a macro, for k_shade_hair and k_shade_hair_env: spelled in the kernel itself, k_shade_hair compiles to the
+// instructions it did before the environment kernels existed; a shared __device__ body moved its LDS addressing)
+#define PB_SHADE_HAIR_KERNEL(ENV)                                                                                                     \
+  __shared__ float lds_lights[kLdsLightWords];                                                                                        \
+  const bool lights_staged = stage_light_tables(sc, lds_lights);                                                                     \
+  if (lights_staged) __syncthreads();                                                                                                 \
+  const uint32_t n = P.counts[kCntHair];                                                                                              \
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {                                              \
+    const uint32_t e = P.q_hair[i], p = e & kQPathMask;                                                                               \
+    uint32_t r = shade_hair_path<ENV>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, lights_staged ? lds_lights : nullptr); \
+    if (r == kRHold && (e & kQDoomed)) r |= kRHoldDoomed; /* (a held path hands its queue entry's kQDoomed back) */                 \
+    P.q_hair[i] = p | r;                                                                                                              \
   }
-}
+__global__ __launch_bounds__(kBlock) void k_shade_hair(PathState P, DScene sc, uint64_t rng_inc) { PB_SHADE_HAIR_KERNEL(false) }
+// scenes with an environment
+__global__ __launch_bounds__(kBlock) void k_shade_hair_env(PathState P, DScene sc, uint64_t rng_inc) { PB_SHADE_HAIR_KERNEL(true) }
+#undef PB_SHADE_HAIR_KERNEL
 
 // ------------------------------------------------------------------ k_sss_step
 // One iteration of RandomWalkSubsurface's loop after its TraceFirstHit1 (random-walk-sss.h:314-405),
@@ -1037,6 +1097,8 @@ __device__ __forceinline__ bool sss_scatter(WalkState& w, uint64_t rng_inc, V3* 
 }
 
 // hreg: the hit of the path's bounded ray when the caller holds it in registers, else it is read from P.hit.
+// ENV: the scene has an environment (the exit's NEE may sample it; no doomed-path pretest)
+template <bool ENV = false>
 __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc,
                                                   const Hit* hreg = nullptr, const float* lds_lights = nullptr) {
   {
@@ -1099,7 +1161,7 @@ __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DSce
           nb.diffuse_weight = wthr;
           SampleWeight w = closure_sample_weight(wo, nb);
           V3 d2(0.f);
-          shadow = nee_sample(sc, rng, s.pos, s.n_s, true, nee, lds_lights);  // :202-212 (Q5)
+          shadow = nee_sample<ENV>(sc, rng, s.pos, s.n_s, true, nee, lds_lights);  // :202-212 (Q5)
           if (shadow) {
             V3 f;
             float pdf;
@@ -1141,7 +1203,7 @@ __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DSce
           V3 t2 = new_thr * thr;
           if (!is_black(t2)) {
             qbit = doomed_bit(t2, rng.state, rng_inc);
-            if (!(qbit && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
+            if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
               alive = true;
               P.ray_o[p] = mk4(s.pos, 1e-3f);
               P.ray_d[p] = mk4(next_dir, kInf);
@@ -1164,16 +1226,20 @@ __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DSce
     return (shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit;
   }
 }
-__global__ __launch_bounds__(kBlock) void k_sss_step(PathState P, DScene sc, uint64_t rng_inc) {
-  __shared__ float lds_lights[kLdsLightWords];
-  const bool lights_staged = stage_light_tables(sc, lds_lights);
-  if (lights_staged) __syncthreads();
-  const uint32_t n = P.counts[kCntSss];
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    const uint32_t p = P.q_sss[i];
-    P.q_sss[i] = p | sss_step_path(P, sc, p, rng_inc, nullptr, lights_staged ? lds_lights : nullptr);
+// (a macro for the same reason as PB_SHADE_HAIR_KERNEL)
+#define PB_SSS_STEP_KERNEL(ENV)                                                                      \
+  __shared__ float lds_lights[kLdsLightWords];                                                       \
+  const bool lights_staged = stage_light_tables(sc, lds_lights);                                    \
+  if (lights_staged) __syncthreads();                                                                \
+  const uint32_t n = P.counts[kCntSss];                                                              \
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {             \
+    const uint32_t p = P.q_sss[i];                                                                   \
+    P.q_sss[i] = p | sss_step_path<ENV>(P, sc, p, rng_inc, nullptr, lights_staged ? lds_lights : nullptr); \
   }
-}
+__global__ __launch_bounds__(kBlock) void k_sss_step(PathState P, DScene sc, uint64_t rng_inc) { PB_SSS_STEP_KERNEL(false) }
+// scenes with an environment
+__global__ __launch_bounds__(kBlock) void k_sss_step_env(PathState P, DScene sc, uint64_t rng_inc) { PB_SSS_STEP_KERNEL(true) }
+#undef PB_SSS_STEP_KERNEL
 
 // ------------------------------------------------------------------ k_sss_walk
 // Fast-forward of the random walks (RandomWalkSubsurface's loop, random-walk-sss.h:287-405).  A walk alternates a bounded
@@ -1353,9 +1419,12 @@ __global__ __launch_bounds__(kBlock, STATS ? PB_WALK_WAVES : walk_blocks_per_cu(
 #define PB_TAIL_WAVES 3  // min waves per SIMD of k_tail (<= 168 VGPRs: three blocks per CU hold 196 k lanes, so every path of a 256 Ki tail starts at once;
                          // A/B on C2: 2 -> 59.1 ms per frame / 12.1 ms for an eighth, 3 -> 58.6 / 11.8)
 #endif
-// MODE: what the scene's materials can do (shade_principled_path): the branches no path can take are compiled out
-template <int MODE, bool STATS, bool CURVES, bool WIDE = false>
+// MODE: what the scene's materials can do (shade_principled_path): the branches no path can take are compiled out; kShadeEnv: the scene
+// has an environment (a miss collects it)
+template <int MODE_, bool STATS, bool CURVES, bool WIDE = false>
 __global__ __launch_bounds__(kBlock, PB_TAIL_WAVES) void k_tail(PathState P, DScene sc, uint64_t rng_inc) {
+  constexpr int MODE = shade_base(MODE_);
+  constexpr bool ENV = shade_env(MODE_);
   __shared__ uint32_t stk[kSimpleLdsStack * kBlock];
   uint32_t* const spill = P.spill + blockIdx.x * kBlock + threadIdx.x;  // stack entries beyond the LDS part (the group's spill area: this grid is smaller than k_trace's)
   const uint32_t spill_stride = gridDim.x * kBlock;
@@ -1398,12 +1467,14 @@ __global__ __launch_bounds__(kBlock, PB_TAIL_WAVES) void k_tail(PathState P, DSc
       uint32_t r = 0u;
       if (state & kHave) {
         if (MODE != kShadePlain && (state & kMedium)) {
-          r = sss_step_path(P, sc, p, rng_inc);
+          r = sss_step_path<ENV>(P, sc, p, rng_inc);
         } else {
           const uint32_t slot = __float_as_uint(P.hit[p].w);
-          if (slot != kNone)  // a miss ends the path (render.cc:34)
-            r = (slot & kHitHair) ? shade_hair_path(P, sc, p, rng_inc, (state & kFirst) != 0u)
-                                  : shade_principled_path<MODE>(P, sc, p, rng_inc, (state & kFirst) != 0u);
+          if (slot != kNone)  // a miss ends the path (render.cc:34) -- after collecting the environment, if there is one
+            r = (slot & kHitHair) ? shade_hair_path<ENV>(P, sc, p, rng_inc, (state & kFirst) != 0u)
+                                  : shade_principled_path<MODE_>(P, sc, p, rng_inc, (state & kFirst) != 0u);
+          else if (ENV)
+            r = env_miss_path<MODE != kShadeMedia>(P, sc, p, (state & kFirst) != 0u);
         }
         state &= ~kFirst;
       }
@@ -1868,23 +1939,34 @@ static inline uint32_t tiles_grid(uint32_t n_upper, int items_per_thread) {
   uint32_t g = (n_upper + tile - 1) / tile;
   return g < 1 ? 1 : (g < kShadeGridCap ? g : kShadeGridCap);
 }
+// a scene with an environment (DScene::env_texels) runs the environment instances of the routing and shading kernels
+static inline bool has_env(const DScene& sc) { return sc.env_texels != nullptr; }
 void launch_classify(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper) {
-  hipLaunchKernelGGL(k_classify, dim3(tiles_grid(n_upper, kClassifyItems)), dim3(kBlock), 0, s, P, sc);
+  if (has_env(sc)) hipLaunchKernelGGL(k_classify_env, dim3(tiles_grid(n_upper, kClassifyItems)), dim3(kBlock), 0, s, P, sc);
+  else hipLaunchKernelGGL(k_classify, dim3(tiles_grid(n_upper, kClassifyItems)), dim3(kBlock), 0, s, P, sc);
 }
 void launch_compact(hipStream_t s, const PathState& P, uint32_t n_upper) {
   hipLaunchKernelGGL(k_compact, dim3(tiles_grid(n_upper, kCompactItems)), dim3(kBlock), 0, s, P);
 }
 void launch_shade_principled(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool media, bool textured) {
   const dim3 g(grid_for(n_upper, kShadeGridCap));
+  if (has_env(sc)) {
+    if (textured) hipLaunchKernelGGL(k_shade_principled<kShadeFull | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    else if (media) hipLaunchKernelGGL(k_shade_principled<kShadeMedia | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    else hipLaunchKernelGGL(k_shade_principled<kShadePlain | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    return;
+  }
   if (textured) hipLaunchKernelGGL(k_shade_principled<kShadeFull>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
   else if (media) hipLaunchKernelGGL(k_shade_principled<kShadeMedia>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
   else hipLaunchKernelGGL(k_shade_principled<kShadePlain>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
 }
 void launch_shade_hair(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc) {
-  hipLaunchKernelGGL(k_shade_hair, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  if (has_env(sc)) hipLaunchKernelGGL(k_shade_hair_env, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  else hipLaunchKernelGGL(k_shade_hair, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
 }
 void launch_sss_step(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc) {
-  hipLaunchKernelGGL(k_sss_step, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  if (has_env(sc)) hipLaunchKernelGGL(k_sss_step_env, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  else hipLaunchKernelGGL(k_sss_step, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
 }
 void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats) {
   const bool curves = sc.num_curves != 0;
@@ -1913,6 +1995,13 @@ void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n
   dim3 g(blocks < 1u ? 1u : (blocks < PB_TAIL_BLOCKS ? blocks : PB_TAIL_BLOCKS));
   const bool curves = sc.num_curves != 0;
   const bool wide = use_wide(sc);
+  if (has_env(sc)) {
+    if (stats) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    else if (textured) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    else if (media) PB_LAUNCH_TRAV(k_tail, kShadeMedia | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    else PB_LAUNCH_TRAV(k_tail, kShadePlain | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+    return;
+  }
   if (stats) PB_LAUNCH_TRAV(k_tail, kShadeFull PB_COMMA true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
   else if (textured) PB_LAUNCH_TRAV(k_tail, kShadeFull PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
   else if (media) PB_LAUNCH_TRAV(k_tail, kShadeMedia PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);

@@ -292,6 +292,9 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
     dd.lprim_cdf = s->d_lprim_cdf.p, dd.lrecs = s->d_lrecs.p, dd.light_boxes = s->d_light_boxes.p;
     dd.sss_entries = src->dscene.sss_entries ? s->d_sss_entries.p : nullptr;
     dd.tex_pixels = s->d_tex_pixels.p, dd.textures = s->d_tex_descs.p;
+    dd.env_texels = nullptr, dd.env_alias = nullptr, dd.env_w = dd.env_h = 0;  // (the environment is rebuilt on this device)
+    if (!src->env_rgb.empty())
+      if (int r = set_environment(s, src->env_rgb.data(), src->env_w, src->env_h, src->env_scale, src->env_m)) return r;
     s->committed = true;
     *out = guard.release();
     return PBRHIP_OK;

@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "env_tables.h"
 #include "scene_impl.h"
 
 using namespace pb;
@@ -847,6 +848,62 @@ extern "C" int pbrhip_scene_update_hair_material(pbrhip_scene* s, uint32_t id, c
   });
 }
 
+// ------------------------------------------------------------------ environment light
+namespace pb {
+int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale, const float* world_to_env) {
+  float m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  EnvTables t;
+  if (rgb) {
+    if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "set_environment: zero size (%u x %u)", width, height);
+    if (world_to_env) {
+      for (int i = 0; i < 9; i++) {
+        if (!isfinite(world_to_env[i])) return fail(PBRHIP_EINVAL, "set_environment: world_to_env is not finite");
+        m[i] = world_to_env[i];
+      }
+      for (int i = 0; i < 3; i++)  // a rotation: M M^T = I
+        for (int j = 0; j < 3; j++) {
+          const double d = (double)m[3 * i] * m[3 * j] + (double)m[3 * i + 1] * m[3 * j + 1] + (double)m[3 * i + 2] * m[3 * j + 2];
+          if (fabs(d - (i == j ? 1.0 : 0.0)) > 1e-4) return fail(PBRHIP_EINVAL, "set_environment: world_to_env is not a rotation");
+        }
+    }
+    if (build_env_tables(rgb, width, height, scale, &t))
+      return fail(PBRHIP_EINVAL, "set_environment: a texel or the scale is negative, NaN or infinite, or the map is too large (%u x %u)", width, height);
+  }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (a render in flight still reads the old tables)
+  DScene& d = s->dscene;
+  // no environment until the new tables are on the device (a failed upload leaves none, not freed memory)
+  d.env_texels = nullptr, d.env_alias = nullptr, d.env_w = d.env_h = 0;
+  s->env_rgb.clear(), s->env_w = s->env_h = 0;
+  if (!t.present) {  // no map, or an all-black one: no environment -- the scene runs the kernels it ran without one
+    s->d_env_texels.release(), s->d_env_alias.release();
+    return PBRHIP_OK;
+  }
+  const size_t n = (size_t)width * height;
+  std::vector<float4> texels(n);
+  std::vector<uint2> alias(n);
+  for (size_t i = 0; i < n; i++) {
+    texels[i] = make_float4(t.texels[4 * i], t.texels[4 * i + 1], t.texels[4 * i + 2], t.texels[4 * i + 3]);
+    alias[i] = make_uint2(t.keep[i], t.alias[i]);
+  }
+  HIPCHK(s->d_env_texels.upload(texels, s->stream));
+  HIPCHK(s->d_env_alias.upload(alias, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  s->env_rgb.assign(rgb, rgb + 3 * n), s->env_w = width, s->env_h = height, s->env_scale = scale;
+  memcpy(s->env_m, m, sizeof(m));
+  d.env_texels = s->d_env_texels.p, d.env_alias = s->d_env_alias.p, d.env_w = width, d.env_h = height;
+  memcpy(d.env_m, m, sizeof(m));
+  return PBRHIP_OK;
+}
+}  // namespace pb
+extern "C" int pbrhip_scene_set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale,
+                                            const float world_to_env[9]) {
+  return guarded([&]() -> int {
+    if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+    return set_environment(s, rgb, width, height, scale, world_to_env);
+  });
+}
+
 // ------------------------------------------------------------------ tiles (render-tile.cc:29-41)
 extern "C" int pbrhip_create_tiles(uint32_t width, uint32_t height, uint32_t* out, uint32_t* num_tiles) {
   return guarded([&]() -> int {
@@ -1198,6 +1255,9 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
     HIPCHK(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long) * kStatNum, st));
     const Camera cam = make_camera(s, d->width, d->height);
     const uint64_t rng_inc = (d->seed_seq << 1u) | 1u;  // pcg32_srandom (rng.h:30-36)
+    // the environment's share of NEE events: the light count is known once the scene is committed
+    s->dscene.env_p = s->dscene.num_lights ? 0.5f : 1.0f;
+    s->dscene.env_area_scale = 1.0f - s->dscene.env_p;
     const DScene& sc = s->dscene;
 
     uint32_t tail_paths = d->tail_paths == 0xFFFFFFFFu ? 0u : (d->tail_paths ? d->tail_paths : 262144u);

@@ -103,6 +103,12 @@ struct pbrhip_scene {
   pb::DevBuf<pb::LightRec> d_lrecs;
   pb::DevBuf<pb::BvhNode> d_light_boxes;
   pb::DevBuf<pb::SssEntry> d_sss_entries;  // DScene::sss_entries
+  // the environment light as the caller set it (pbrhip_scene_set_environment; kept for pbrhip_scene_replicate) and its device tables
+  std::vector<float> env_rgb;
+  uint32_t env_w = 0, env_h = 0;
+  float env_scale = 1.0f, env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  pb::DevBuf<float4> d_env_texels;  // DScene::env_texels
+  pb::DevBuf<uint2> d_env_alias;    // DScene::env_alias
   pb::DScene dscene;
   // render working set (grown on demand, reused across calls)
   pb::DevBuf<float4> rec, srec, ssrec, L, hit, sss_A, sh_e;  // path state (kernels.h::PathState): rec = 4 words of 16 B per path, srec = 2
@@ -143,6 +149,8 @@ namespace pb {
 // pixel indices (y * w + x) of the blocks of rank `rank` in CreateTiles order (render-tile.cc:29-41 for block = 64)
 void shard_pixels(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block, std::vector<uint32_t>* out);
 int ensure_pixels(pbrhip_scene* s, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block);
+// pbrhip_scene_set_environment's body (rgb null: no environment); also what pbrhip_scene_replicate calls to carry it over
+int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale, const float* world_to_env);
 // the body of pbrhip_render_device (device pointers on the scene's device)
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
                 uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats);

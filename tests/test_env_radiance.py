@@ -1,0 +1,204 @@
+"""The environment light's radiance against float64 expectations (tests/_env_analytic.py).
+
+A Lambert floor with nothing above it, lit by a lat-long map only.  Same statistics as test_analytic_radiance.py: K seeded
+batches, per 8x8 cell and channel a Student-t bar with Bonferroni correction (a correct renderer fails with probability
+< 1e-6), plus the whole floor; 1.01 E must be rejected.  Background pixels whose footprint lies inside one texel are exact:
+count x L x scale.  The oracle has no environment, so these run on the GPU only."""
+import numpy as np
+import pytest
+
+import _analytic as A
+import _env_analytic as EA
+from test_analytic_radiance import CELL, MIN_CELL_PIXELS, P_FAIL, _pa
+
+W, H = 64, 48
+K, SPP = 48, 16
+SEED_SEQ = 1414213562
+
+
+def _render(pa, S, env, scale, m):
+    sg = A.build(pa.Scene(), S, pa.make_principled)
+    sg.SetEnvironment(env, scale, m)
+    rgba, count = [], []
+    for k in range(K):
+        layer = pa.RenderLayer()
+        pa.Render(sg, W, H, SPP, layer=layer, first_pass=k * SPP, seed_seq=SEED_SEQ)
+        rgba.append(np.array(layer.rgba, np.float32).reshape(H, W, 4))
+        count.append(np.array(layer.count, np.uint32).reshape(H, W))
+    cam = A.Camera(*sg.FetchSceneAABB(), W, H)
+    sg.close()
+    return np.stack(rgba), np.stack(count), cam
+
+
+def _receiver(S, cam, probe=6):
+    py, px = np.mgrid[0:H, 0:W]
+    js = np.linspace(-0.02, 1.02, probe)
+    jx, jy = np.meshgrid(js, js, indexing="ij")
+    d = cam.dirs(px[..., None].astype(np.float64), py[..., None].astype(np.float64), jx.ravel(), jy.ravel()).reshape(-1, 3)
+    mesh = A.cast(S, cam.org, d)[0].reshape(H, W, -1)
+    return np.all(mesh == S.receiver, -1)
+
+
+def _z(means, rec, E):
+    groups = []
+    for cy in range(0, H, CELL):
+        for cx in range(0, W, CELL):
+            g = np.zeros_like(rec)
+            g[cy:cy + CELL, cx:cx + CELL] = rec[cy:cy + CELL, cx:cx + CELL]
+            if g.sum() >= MIN_CELL_PIXELS:
+                groups.append(g)
+    groups.append(rec)
+    z = []
+    for g in groups:
+        bm = means[:, g].mean(1)
+        se = bm.std(0, ddof=1) / np.sqrt(K)
+        z.append((bm.mean(0) - E) / se)
+    z = np.array(z)
+    return z, A.student_t_bar(P_FAIL / z.size, K - 1)
+
+
+def _check(case, means, rec, E, also_reject=()):
+    z, bar = _z(means, rec, E)
+    rel = means.mean(0)[rec].mean(0) / E - 1
+    print(f"env {case}: {len(z) - 1} cells, max |z| {np.abs(z).max():.2f} (bar {bar:.2f}), whole-floor rel err "
+          f"{' '.join(f'{r:+.1e}' for r in rel)}")
+    assert np.abs(z).max() < bar, (case, z, bar)
+    for name, alt in (("1.01 E", 1.01 * E),) + tuple(also_reject):
+        za, _ = _z(means, rec, alt)
+        assert np.abs(za).max() >= bar, (case, f"{name} is not rejected", np.abs(za).max(), bar)
+
+
+@pytest.mark.gpu
+def test_env_furnace_constant_sky():
+    """A Lambert floor under a constant sky converges to rho L (the environment's two MIS weights sum to 1); the skewed NEE
+    weight of Q3 is rejected; the background is exactly count x L x scale"""
+    pa = _pa()
+    S = EA.floor_scene()
+    L = np.array([0.75, 1.25, 0.5])
+    scale = 2.0
+    env = np.tile(L.astype(np.float32), (4, 8, 1))
+    rgba, count, cam = _render(pa, S, env, scale, None)
+    assert (count == SPP).all() and (rgba[..., 3] == count).all()
+    rec = _receiver(S, cam)
+    assert rec.sum() > 1000
+    bg_r, _ = EA.background_texels(S, cam, np.eye(3), 8, 4)
+    bg = bg_r >= 0
+    assert bg.sum() > 100
+    assert (rgba[:, bg, :3] == (SPP * L * scale).astype(np.float32)).all(), "a background pixel is not count x L x scale"
+    means = rgba[..., :3] / count[..., None]
+    E = EA.constant_expectation(L * scale)
+    _check("furnace", means, rec, E, (("Q3-skewed NEE weight", EA.skewed_constant_expectation(L * scale)),))
+
+
+@pytest.mark.gpu
+def test_env_hdr_map_rotated_sun():
+    """A 32 x 16 sky with one bright sun texel, rotated so that env-up is the floor's normal: the horizon is a row boundary
+    and E = (rho / pi) sum_t L_t (phi1 - phi0)(sin^2 theta1 - sin^2 theta0) / 2; background pixels inside one texel are exact"""
+    pa = _pa()
+    S = EA.floor_scene()
+    rgb = EA.sky_map()
+    scale = 0.5
+    rgba, count, cam = _render(pa, S, rgb, scale, EA.Z_UP)
+    assert (count == SPP).all() and (rgba[..., 3] == count).all()
+    rec = _receiver(S, cam)
+    r, c = EA.background_texels(S, cam, EA.Z_UP, rgb.shape[1], rgb.shape[0])
+    bg = r >= 0
+    assert bg.sum() > 100
+    one = rgb[r[bg], c[bg]] * np.float32(scale)
+    want = np.zeros_like(one)
+    for _ in range(SPP):  # (the passes are added one by one, in float32)
+        want = want + one
+    assert (rgba[:, bg, :3] == want[None]).all(), "a background pixel inside one texel is not count x L x scale"
+    means = rgba[..., :3] / count[..., None]
+    E = EA.map_expectation(rgb, scale)
+    # the sun alone is most of E: a sampler that ignored it (uniform over the sky) would be far noisier than the bar allows
+    sun_only = EA.map_expectation(np.where(np.arange(16)[:, None, None] == 3, rgb * (np.arange(32)[None, :, None] == 21), 0), scale)
+    assert sun_only[0] > 0.5 * E[0]
+    _check("hdr_map", means, rec, E)
+
+
+def _per_pixel(S, cam, expectation, rec):
+    """E averaged over each receiver pixel's footprint (2 x 2 Gauss-Legendre, as test_analytic_radiance.py); pixels where E is steep on
+    the scale of a pixel are left out"""
+    ys, xs = np.nonzero(rec)
+    e, ev, _, _ = A.pixel_mean(S, cam, expectation, xs, ys, 2, nodes=True)
+    steep = (ev.max(1) - ev.min(1)).max(1) > A.STEEP * np.abs(e).max(1)
+    val = np.zeros((H, W, 3))
+    val[ys, xs] = e
+    keep = rec.copy()
+    keep[ys[steep], xs[steep]] = False
+    return val, keep
+
+
+def _zv(means, rec, val):
+    """_z with a per-pixel expectation: the cells' means of E"""
+    groups = []
+    for cy in range(0, H, CELL):
+        for cx in range(0, W, CELL):
+            g = np.zeros_like(rec)
+            g[cy:cy + CELL, cx:cx + CELL] = rec[cy:cy + CELL, cx:cx + CELL]
+            if g.sum() >= MIN_CELL_PIXELS:
+                groups.append(g)
+    groups.append(rec)
+    z = []
+    for g in groups:
+        bm = means[:, g].mean(1)
+        se = bm.std(0, ddof=1) / np.sqrt(K)
+        z.append((bm.mean(0) - val[g].mean(0)) / se)
+    z = np.array(z)
+    return z, A.student_t_bar(P_FAIL / z.size, K - 1)
+
+
+def _check_v(case, means, rec, val, also_reject=()):
+    z, bar = _zv(means, rec, val)
+    rel = means.mean(0)[rec].mean(0) / val[rec].mean(0) - 1
+    print(f"env {case}: {len(z) - 1} cells, max |z| {np.abs(z).max():.2f} (bar {bar:.2f}), whole-floor rel err "
+          f"{' '.join(f'{r:+.1e}' for r in rel)}")
+    assert np.abs(z).max() < bar, (case, z, bar)
+    for name, alt in (("1.01 E", 1.01 * val),) + tuple(also_reject):
+        za, _ = _zv(means, rec, alt)
+        assert np.abs(za).max() >= bar, (case, f"{name} is not rejected", np.abs(za).max(), bar)
+
+
+@pytest.mark.gpu
+def test_env_occluder_form_factor():
+    """A constant sky, the floor and a black plate above it: E(x) = rho L (1 - F(x)), F = the point-to-polygon form factor of the
+    plate (Lambert's formula).  Pins the environment's shadow rays: an occluded NEE sample adds nothing, an escaped BSDF ray does."""
+    pa = _pa()
+    S0 = EA.floor_scene()
+    pv, pf = A.quad((0.1, -0.05, 0.3), (0.25, 0.0, 0.0), (0.0, 0.18, 0.0))
+    S = A.Scene([S0.meshes[0], A.Mesh("plate", pv, pf, A.material(**A.BLACK)), S0.meshes[1]])
+    L = np.array([0.75, 1.25, 0.5])
+    env = np.tile(L.astype(np.float32), (4, 8, 1))
+    rgba, count, cam = _render(pa, S, env, 1.0, None)
+    assert (count == SPP).all() and (rgba[..., 3] == count).all()
+    rec = _receiver(S, cam)
+    val, keep = _per_pixel(S, cam, EA.SkyExpectation(L, [pv]), rec)
+    assert keep.sum() > 1000 and val[keep, 0].min() < 0.85 * val[keep, 0].max()  # (the plate hides up to a fifth of the sky)
+    means = rgba[..., :3] / count[..., None]
+    _check_v("occluder", means, keep, val)
+
+
+@pytest.mark.gpu
+def test_env_area_light_and_sky():
+    """test_analytic_radiance's tilted quad light plus a constant sky: NEE picks the sky with p_env = 1/2, so the light's pdf carries
+    1 - p_env on the NEE and on the emission-hit side.  E = _analytic.Expectation with every face's pA x 1/2 (Q3's skew kept for the
+    area part) + rho L_env (1 - F_light(x)).  The expectation without the 1/2 must be rejected."""
+    from test_analytic_radiance import _tilted_light
+    pa = _pa()
+    S0 = EA.floor_scene()
+    light = _tilted_light()
+    S = A.Scene([S0.meshes[0], light, S0.meshes[1]])
+    L = np.array([0.2, 0.25, 0.15])
+    env = np.tile(L.astype(np.float32), (4, 8, 1))
+    rgba, count, cam = _render(pa, S, env, 1.0, None)
+    assert (count == SPP).all() and (rgba[..., 3] == count).all()
+    rec = _receiver(S, cam)
+    half = A.Expectation(S)
+    for fc in half.faces:
+        fc["pA"] = fc["pA"] * 0.5
+    val, keep = _per_pixel(S, cam, EA.SkyExpectation(L, [light.verts], half), rec)
+    alt, _ = _per_pixel(S, cam, EA.SkyExpectation(L, [light.verts], A.Expectation(S)), rec)
+    assert keep.sum() > 800
+    means = rgba[..., :3] / count[..., None]
+    _check_v("area_light_and_sky", means, keep, val, (("pA without 1 - p_env", alt),))
