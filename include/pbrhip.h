@@ -211,6 +211,17 @@ int pbrhip_scene_update_hair_material(pbrhip_scene*, uint32_t material_id, const
  * PBRHIP_EINVAL.  The map is copied. */
 int pbrhip_scene_set_environment(pbrhip_scene*, const float* rgb, uint32_t width, uint32_t height, float scale,
                                  const float world_to_env[9]);
+/* A look-at camera in place of the reference's, which is fitted to the scene's box and looks down -z.  f = normalize(lookat
+ * - eye), r = normalize(f x up), u = r x f; pixel (x, y) (row 0 = the top) with jitter (jx, jy) -- the sample's first two draws -- sees
+ * along f + sx r + sy u, sx = (2 (x + jx) / W - 1) tan(vfov / 2) W / H, sy = (1 - 2 (y + jy) / H) tan(vfov / 2); vfov in degrees.
+ * lens_radius 0: a pinhole at eye.  lens_radius > 0: a thin lens -- two more draws u1, u2 pick the origin eye + rho (cos phi r + sin phi u),
+ * rho = lens_radius sqrt(u1), phi = 2 pi u2, and the ray passes through the pixel's point at distance focus_distance along f
+ * (0: |lookat - eye|), which is in focus.  eye == NULL restores the reference's camera.  Valid before or after pbrhip_scene_commit: takes
+ * effect at the next render (a PBRHIP_RENDER_NO_CLEAR render after a change mixes the two views).  A non-finite value, eye == lookat, up
+ * (nearly) parallel to lookat - eye, vfov outside (0, 180), a negative lens_radius or focus_distance: PBRHIP_EINVAL, and the camera
+ * stays as it was.  pbrhip_scene_replicate carries it over. */
+int pbrhip_scene_set_camera(pbrhip_scene*, const float eye[3], const float lookat[3], const float up[3], float vfov_degrees,
+                            float lens_radius, float focus_distance);
 /* BVH facts for reports: node count, leaf slots, depth, device bytes */
 int pbrhip_scene_info(const pbrhip_scene*, uint64_t* num_nodes, uint64_t* num_slots, uint32_t* depth,
                       uint64_t* device_bytes);
@@ -276,6 +287,10 @@ int pbrhip_comm_gather_layer(pbrhip_comm*, pbrhip_scene*, const pbrhip_render_de
  * array of rays: test hooks for hit-index parity */
 int pbrhip_trace_closest(pbrhip_scene*, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits);
 int pbrhip_trace_any(pbrhip_scene*, const pbrhip_ray* rays, size_t n, uint8_t* occluded);
+/* The camera ray the renderer traces for sample `pass` of pixel (x, y) of a width x height image (x_y_pass: n triples), evaluated on the
+ * device: the user camera when one is set, else the reference's (which needs a committed scene: its box).  For tests and picking
+ * (the ray of a pixel, for pbrhip_trace_closest). */
+int pbrhip_camera_rays(pbrhip_scene*, uint32_t width, uint32_t height, uint64_t seed_seq, const uint32_t* x_y_pass, size_t n, pbrhip_ray* rays);
 
 /* The device's leaf functions on arrays of inputs -- a test hook like the two above: what the kernels compute for the generator
  * (src/random/rng.h), the fast math of the hair BSDF (src/pbrlab_math.h:135-344), Fresnel and the MIS weight (closure-util.h,

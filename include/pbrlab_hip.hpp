@@ -371,6 +371,13 @@ public:
   void SetEnvironment(const float* rgb, uint32_t width, uint32_t height, float scale = 1.0f, const float* world_to_env = nullptr) {
     Check(pbrhip_scene_set_environment(h_, rgb, width, height, scale, world_to_env));
   }
+  // A look-at camera (pbrhip_scene_set_camera): vfov in degrees; lens_radius > 0 = a thin lens focused at focus_distance along the view
+  // direction (0: |lookat - eye|).  ResetCamera() restores the reference's camera.  Takes effect at the next Render().
+  void SetCamera(const float eye[3], const float lookat[3], const float up[3], float vfov_degrees = 30.0f, float lens_radius = 0.0f,
+                 float focus_distance = 0.0f) {
+    Check(pbrhip_scene_set_camera(h_, eye, lookat, up, vfov_degrees, lens_radius, focus_distance));
+  }
+  void ResetCamera() { Check(pbrhip_scene_set_camera(h_, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0.0f)); }
 
   // scene.h:81, scene.cc:206-208: the scene's material table; the GUI edits its elements between renders
   // (pc/glfw-window.cc:866-979 through EditQueue, pc/pc-common.cc:57-84).  An edit reaches the GPU at the next Render():

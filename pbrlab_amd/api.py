@@ -242,6 +242,28 @@ class Scene:
         m = None if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(9)
         _chk(self.L.pbrhip_scene_set_environment(self.h, _ptr(px), px.shape[1], px.shape[0], C.c_float(scale), _ptr(m)))
 
+    def SetCamera(self, eye, lookat=None, up=(0.0, 1.0, 0.0), fov=30.0, lens_radius=0.0, focus_distance=0.0):
+        """A look-at camera: eye, lookat, up 3-vectors, fov = vertical field of view in degrees; lens_radius > 0 makes it
+        a thin lens focused at focus_distance along the view direction (0: |lookat - eye|).  SetCamera(None) restores the reference's
+        camera.  Takes effect at the next render; invalid values raise and leave the camera as it was."""
+        if eye is None:
+            _chk(self.L.pbrhip_scene_set_camera(self.h, None, None, None, C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)))
+            return
+        if lookat is None:
+            raise ValueError("SetCamera needs lookat")
+        e, l, u = (np.ascontiguousarray(v, np.float32).reshape(3) for v in (eye, lookat, up))
+        _chk(self.L.pbrhip_scene_set_camera(self.h, _ptr(e), _ptr(l), _ptr(u), C.c_float(fov), C.c_float(lens_radius),
+                                            C.c_float(focus_distance)))
+
+    def CameraRays(self, width, height, x_y_pass, seed_seq=1234567890):
+        """pbrhip_camera_rays: the camera ray the renderer traces for each (x, y, pass) row of x_y_pass (n, 3) -> RAY_DT array.  The user
+        camera when one is set, else the reference's (a committed scene)."""
+        xyp = np.ascontiguousarray(x_y_pass, np.uint32).reshape(-1, 3)
+        rays = np.zeros(len(xyp), RAY_DT)
+        _chk(self.L.pbrhip_camera_rays(self.h, C.c_uint32(width), C.c_uint32(height), C.c_uint64(seed_seq), C.c_void_p(xyp.ctypes.data),
+                                       C.c_size_t(len(xyp)), C.c_void_p(rays.ctypes.data)))
+        return rays
+
     def AddLightParam(self, emission):
         e = np.ascontiguousarray(emission, np.float32).reshape(3)
         out = C.c_uint32()

@@ -275,4 +275,13 @@ struct Camera {
   float x_corner, y_corner, z_corner, dx, dy;
 };
 
+// a caller's look-at camera (pbrhip_scene_set_camera), derived on the host in double and rounded once:
+// f = normalize(lookat - eye), r = normalize(f x up), u = r x f; a pixel's point on the unit image plane is f + sx r + sy u with
+// sx = (2 (x + jx) / W - 1) ha, sy = (1 - 2 (y + jy) / H) h
+struct UserCamera {
+  float eye[3], f[3], r[3], u[3];
+  float h, ha;        // tan(vfov / 2), tan(vfov / 2) width / height
+  float lens, focus;  // lens radius (0: a pinhole, two draws per camera sample), focus distance (> 0)
+};
+
 }  // namespace pb

@@ -2,15 +2,19 @@
 //
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
 //                  [--gpus N] [--bvh host|gpu] [--env FILE [--env-scale S]]
+//                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
 // GPU g % (GPUs present): one host thread per rank, the scene is ingested once and copied device-to-device, the shards
 // are gathered on the first GPU over xGMI inside the library (pbrhip_render_multi).  --bvh gpu builds the acceleration structure
 // on the GPU (faster commit, slightly slower traversal, same image).  --env FILE lights the scene with a lat-long environment map
-// (.hdr, .exr or any LDR format pbrio_image_load reads), times --env-scale (default 1).
+// (.hdr, .exr or any LDR format pbrio_image_load reads), times --env-scale (default 1).  --eye / --lookat replace
+// the reference's camera with a look-at camera: --up (default 0,1,0), vertical --fov in degrees (default 30), a thin
+// lens of --lens-radius (default 0: a pinhole) focused at --focus along the view direction (default 0: |lookat - eye|).
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +33,8 @@ int main(int argc, char** argv) {
   std::string out = "rgba.png";
   const char* env = nullptr;
   float env_scale = 1.0f;
+  bool have_eye = false, have_lookat = false;
+  float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, 0}, up[3] = {0, 1, 0}, fov = 30.0f, lens_radius = 0.0f, focus = 0.0f;
   std::vector<const char*> files;
   files.push_back(argv[0]);
   for (int i = 1; i < argc; ++i) {
@@ -68,7 +74,41 @@ int main(int argc, char** argv) {
         exit(EXIT_FAILURE);
       }
     }
+    else if (a == "--eye" || a == "--lookat" || a == "--up") {  // X,Y,Z
+      const char* v = value(a.c_str());
+      float* dst = a == "--eye" ? eye : a == "--lookat" ? lookat : up;
+      const char* p = v;
+      bool ok = true;
+      for (int k = 0; k < 3 && ok; ++k) {
+        char* end = nullptr;
+        dst[k] = strtof(p, &end);
+        ok = end != p && std::isfinite(dst[k]) && (k < 2 ? *end == ',' : *end == '\0');
+        p = end + 1;
+      }
+      if (!ok) {
+        std::cerr << a << " needs three finite numbers X,Y,Z, got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
+      if (a == "--eye") have_eye = true;
+      if (a == "--lookat") have_lookat = true;
+    }
+    else if (a == "--fov" || a == "--lens-radius" || a == "--focus") {
+      const char* v = value(a.c_str());
+      char* end = nullptr;
+      const float x = strtof(v, &end);
+      if (end == v || *end || !std::isfinite(x)) {
+        std::cerr << a << " needs a finite number, got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
+      if (a == "--fov") fov = x;
+      else if (a == "--lens-radius") lens_radius = x;
+      else focus = x;
+    }
     else files.push_back(argv[i]);
+  }
+  if (have_eye != have_lookat) {
+    std::cerr << (have_eye ? "--eye needs --lookat" : "--lookat needs --eye") << std::endl;
+    return EXIT_FAILURE;
   }
   if (files.size() < 2) {
     std::cerr << "not specified obj filename" << std::endl;
@@ -111,6 +151,14 @@ int main(int argc, char** argv) {
       scene.SetEnvironment(rgb.data(), uint32_t(w), uint32_t(h), env_scale);
     } catch (const std::exception& e) {
       std::cerr << "--env: " << e.what() << std::endl;
+      return EXIT_FAILURE;
+    }
+  }
+  if (have_eye) {
+    try {
+      scene.SetCamera(eye, lookat, up, fov, lens_radius, focus);
+    } catch (const std::exception& e) {
+      std::cerr << "camera: " << e.what() << std::endl;
       return EXIT_FAILURE;
     }
   }

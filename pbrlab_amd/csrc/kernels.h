@@ -185,6 +185,12 @@ struct HookHit {  // == pbrhip_hit == TraceResult (raytracer.h:9-17)
 };
 
 void launch_generate(hipStream_t s, const PathState& P, uint32_t npaths);  // clears the radiance of the group's paths (PathState::slot0 ...)
+// a user camera: clears the radiance AND stores each path's first ray, throughput (1, 1, 1 | pdf +inf: MIS weight 1),
+// generator state (hold 0) and trace-queue entry -- the group then runs its first bounce as an ordinary one (PathState::first = 0)
+void launch_generate_camera(hipStream_t s, const PathState& P, const UserCamera& cam, uint32_t height, uint32_t npaths);
+// test / picking hook: the camera ray of (x, y, pass) triples -- the user camera when `user`, else the reference's camera `dc`
+void launch_camera_rays(hipStream_t s, const UserCamera& cam, const Camera& dc, bool user, uint32_t width, uint32_t height, uint64_t seed_seq,
+                        const uint32_t* x_y_pass, uint32_t n, float4* rays);
 void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats);
 bool trace_uses_wide(const DScene& sc);  // the traversal kernels walk the 4-wide tree of this scene (now: PBRHIP_WIDE is read per launch)
 void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured);

@@ -56,6 +56,70 @@ __global__ __launch_bounds__(kBlock) void k_generate(PathState P, uint32_t npath
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < npaths; j += gridDim.x * kBlock) P.L[P.slot0 + j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// ------------------------------------------------------------------ the user camera
+// The camera ray of pixel (x, y) from a generator seeded for its sample: jx, jy, then (thin lens only) u1, u2 for the lens point
+// rho (cos phi, sin phi), rho = lens sqrt(u1), phi = 2 pi u2.  Direction: through the pixel's point on the focal plane.
+__device__ __forceinline__ void user_camera_ray(const UserCamera& c, uint32_t x, uint32_t y, uint32_t width, uint32_t height, Rng& rng, V3& o,
+                                                V3& d) {
+  const float jx = draw(rng);
+  const float jy = draw(rng);
+  const float sx = (2.0f * ((float)x + jx) / (float)width - 1.0f) * c.ha;
+  const float sy = (1.0f - 2.0f * ((float)y + jy) / (float)height) * c.h;
+  const V3 f(c.f[0], c.f[1], c.f[2]), r(c.r[0], c.r[1], c.r[2]), u(c.u[0], c.u[1], c.u[2]);
+  const V3 p = f + sx * r + sy * u;
+  o = V3(c.eye[0], c.eye[1], c.eye[2]);
+  if (c.lens > 0.0f) {
+    const float u1 = draw(rng);
+    const float u2 = draw(rng);
+    const float rho = c.lens * sqrtf(u1), phi = 2.0f * kPi * u2;
+    const V3 lo = (rho * cosf(phi)) * r + (rho * sinf(phi)) * u;
+    o = o + lo;
+    d = normalize_raw(c.focus * p - lo);
+  } else {
+    d = normalize_raw(p);
+  }
+}
+// A user camera does not fit the implied first bounce (PathState::first: one origin for every path, nothing stored): its first rays are
+// materialised here, and the group's first bounce runs through the ordinary kernels, which load them.  pdf = +inf makes every MIS
+// weight of the first hit or miss power_heuristic(inf, finite) = 1, the depth-0 weight.  The default camera never comes here.
+__global__ __launch_bounds__(kBlock) void k_generate_camera(PathState P, UserCamera c, uint32_t height, uint32_t npaths) {
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < npaths; j += gridDim.x * kBlock) {
+    const uint32_t R = P.pass_run, q = j / R;  // (camera_sample's path order)
+    const uint32_t pass = P.first_pass + (q / P.npix) * R + j % R;
+    const uint32_t gpix = P.pix_index[q % P.npix];
+    Rng rng = rng_seed(((uint64_t)pass << 32) + (uint64_t)gpix, P.seed_seq);
+    V3 o, d;
+    user_camera_ray(c, gpix % P.width, gpix / P.width, P.width, height, rng, o, d);
+    const uint32_t p = P.slot0 + j;
+    P.L[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    P.ray_o[p] = mk4(o, 0.0f);
+    P.ray_d[p] = mk4(d, kInf);
+    P.thr[p] = make_float4(1.0f, 1.0f, 1.0f, __builtin_huge_valf());
+    P.rng4[p] = make_uint4((uint32_t)rng.state, (uint32_t)(rng.state >> 32), 0u, 0u);
+    P.q_in[j] = p;
+  }
+}
+// pbrhip_camera_rays: the ray of each (x, y, pass) as the renderer computes it (the reference's camera: camera_sample's arithmetic)
+__global__ __launch_bounds__(kBlock) void k_camera_rays(UserCamera c, Camera dc, uint32_t user, uint32_t width, uint32_t height, uint64_t seed_seq,
+                                                        const uint32_t* xyp, uint32_t n, float4* rays) {
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const uint32_t x = xyp[3 * i], y = xyp[3 * i + 1], pass = xyp[3 * i + 2];
+    Rng rng = rng_seed(((uint64_t)pass << 32) + (uint64_t)(y * width + x), seed_seq);
+    V3 o, d;
+    if (user) {
+      user_camera_ray(c, x, y, width, height, rng, o, d);
+    } else {
+      const float jx = draw(rng);
+      const float jy = draw(rng);
+      o = V3(dc.org[0], dc.org[1], dc.org[2]);
+      const V3 target(dc.x_corner + dc.dx * ((float)x + jx), dc.y_corner - dc.dy * ((float)y + jy), dc.z_corner);
+      d = normalize_raw(target - o);
+    }
+    rays[2 * i] = mk4(o, 0.0f);
+    rays[2 * i + 1] = mk4(d, kInf);
+  }
+}
+
 // ------------------------------------------------------------------ k_trace
 // ONE persistent phase-voting traversal launch per wavefront iteration (dtrace_pv.h): it serves the closest-hit
 // rays of this bounce (rtcIntersect1, raytracer_impl.cc:268-278; queue q_in) AND the shadow rays the previous
@@ -1879,6 +1943,13 @@ static inline uint32_t quad_grid(uint32_t n) {  // one ray per quad of lanes: 64
 
 void launch_generate(hipStream_t s, const PathState& P, uint32_t npaths) {
   hipLaunchKernelGGL(k_generate, dim3(grid_for(npaths, 8192)), dim3(kBlock), 0, s, P, npaths);
+}
+void launch_generate_camera(hipStream_t s, const PathState& P, const UserCamera& cam, uint32_t height, uint32_t npaths) {
+  hipLaunchKernelGGL(k_generate_camera, dim3(grid_for(npaths, 8192)), dim3(kBlock), 0, s, P, cam, height, npaths);
+}
+void launch_camera_rays(hipStream_t s, const UserCamera& cam, const Camera& dc, bool user, uint32_t width, uint32_t height, uint64_t seed_seq,
+                        const uint32_t* x_y_pass, uint32_t n, float4* rays) {
+  hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, cam, dc, user ? 1u : 0u, width, height, seed_seq, x_y_pass, n, rays);
 }
 void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats) {
   // Persistent kernel: at most the resident set.  A launch with fewer rays than that would fill gets fewer waves, so that

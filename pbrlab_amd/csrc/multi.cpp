@@ -295,6 +295,8 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
     dd.env_texels = nullptr, dd.env_alias = nullptr, dd.env_w = dd.env_h = 0;  // (the environment is rebuilt on this device)
     if (!src->env_rgb.empty())
       if (int r = set_environment(s, src->env_rgb.data(), src->env_w, src->env_h, src->env_scale, src->env_m)) return r;
+    if (src->cam_set)
+      if (int r = set_camera(s, src->cam_eye, src->cam_lookat, src->cam_up, src->cam_vfov, src->cam_lens, src->cam_focus)) return r;
     s->committed = true;
     *out = guard.release();
     return PBRHIP_OK;

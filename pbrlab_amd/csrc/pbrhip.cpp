@@ -904,6 +904,56 @@ extern "C" int pbrhip_scene_set_environment(pbrhip_scene* s, const float* rgb, u
   });
 }
 
+// ------------------------------------------------------------------ look-at camera
+namespace pb {
+int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const float* up, float vfov, float lens_radius, float focus_distance) {
+  if (!eye) {
+    s->cam_set = false;
+    return PBRHIP_OK;
+  }
+  if (!lookat || !up) return fail(PBRHIP_EINVAL, "set_camera: lookat or up is NULL");
+  for (int k = 0; k < 3; k++)
+    if (!isfinite(eye[k]) || !isfinite(lookat[k]) || !isfinite(up[k])) return fail(PBRHIP_EINVAL, "set_camera: eye, lookat or up is not finite");
+  if (!isfinite(vfov) || !isfinite(lens_radius) || !isfinite(focus_distance)) return fail(PBRHIP_EINVAL, "set_camera: a parameter is not finite");
+  if (!(vfov > 0.0f && vfov < 180.0f)) return fail(PBRHIP_EINVAL, "set_camera: vfov %g is not in (0, 180)", (double)vfov);
+  if (lens_radius < 0.0f) return fail(PBRHIP_EINVAL, "set_camera: lens_radius %g < 0", (double)lens_radius);
+  if (focus_distance < 0.0f) return fail(PBRHIP_EINVAL, "set_camera: focus_distance %g < 0", (double)focus_distance);
+  const double fx = (double)lookat[0] - eye[0], fy = (double)lookat[1] - eye[1], fz = (double)lookat[2] - eye[2];
+  const double fl = sqrt(fx * fx + fy * fy + fz * fz), ul = sqrt((double)up[0] * up[0] + (double)up[1] * up[1] + (double)up[2] * up[2]);
+  if (!(fl > 0.0)) return fail(PBRHIP_EINVAL, "set_camera: eye == lookat");
+  // sin of the angle between up and the view direction
+  const double cx = fy * up[2] - fz * up[1], cy = fz * up[0] - fx * up[2], cz = fx * up[1] - fy * up[0];
+  if (!(ul > 0.0) || sqrt(cx * cx + cy * cy + cz * cz) <= 1e-6 * fl * ul) return fail(PBRHIP_EINVAL, "set_camera: up is parallel to the view direction");
+  memcpy(s->cam_eye, eye, sizeof(s->cam_eye)), memcpy(s->cam_lookat, lookat, sizeof(s->cam_lookat)), memcpy(s->cam_up, up, sizeof(s->cam_up));
+  s->cam_vfov = vfov, s->cam_lens = lens_radius, s->cam_focus = focus_distance, s->cam_set = true;
+  return PBRHIP_OK;
+}
+}  // namespace pb
+extern "C" int pbrhip_scene_set_camera(pbrhip_scene* s, const float eye[3], const float lookat[3], const float up[3], float vfov_degrees,
+                                       float lens_radius, float focus_distance) {
+  return guarded([&]() -> int {
+    if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+    return set_camera(s, eye, lookat, up, vfov_degrees, lens_radius, focus_distance);
+  });
+}
+// the frame of the scene's user camera for a width x height image, in double, rounded once (dscene.h::UserCamera)
+static UserCamera make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
+  double f[3], r[3], u[3], up[3];
+  for (int k = 0; k < 3; k++) f[k] = (double)s->cam_lookat[k] - s->cam_eye[k], up[k] = s->cam_up[k];
+  const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+  for (int k = 0; k < 3; k++) f[k] /= fl;
+  r[0] = f[1] * up[2] - f[2] * up[1], r[1] = f[2] * up[0] - f[0] * up[2], r[2] = f[0] * up[1] - f[1] * up[0];
+  const double rl = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  for (int k = 0; k < 3; k++) r[k] /= rl;
+  u[0] = r[1] * f[2] - r[2] * f[1], u[1] = r[2] * f[0] - r[0] * f[2], u[2] = r[0] * f[1] - r[1] * f[0];
+  UserCamera c;
+  for (int k = 0; k < 3; k++) c.eye[k] = s->cam_eye[k], c.f[k] = (float)f[k], c.r[k] = (float)r[k], c.u[k] = (float)u[k];
+  const double h = tan((double)s->cam_vfov * M_PI / 360.0);
+  c.h = (float)h, c.ha = (float)(h * width / height);
+  c.lens = s->cam_lens, c.focus = s->cam_focus > 0.0f ? s->cam_focus : (float)fl;
+  return c;
+}
+
 // ------------------------------------------------------------------ tiles (render-tile.cc:29-41)
 extern "C" int pbrhip_create_tiles(uint32_t width, uint32_t height, uint32_t* out, uint32_t* num_tiles) {
   return guarded([&]() -> int {
@@ -1254,6 +1304,9 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
     }
     HIPCHK(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long) * kStatNum, st));
     const Camera cam = make_camera(s, d->width, d->height);
+    // a user camera: k_generate_camera stores each path's first ray and the first bounce is an ordinary one (PathState::first = 0)
+    const bool user_cam = s->cam_set;
+    const UserCamera ucam = user_cam ? make_user_camera(s, d->width, d->height) : UserCamera{};
     const uint64_t rng_inc = (d->seed_seq << 1u) | 1u;  // pcg32_srandom (rng.h:30-36)
     // the environment's share of NEE events: the light count is known once the scene is committed
     s->dscene.env_p = s->dscene.num_lights ? 0.5f : 1.0f;
@@ -1336,7 +1389,7 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
       auto enqueue_iteration = [&](Group& gr, uint32_t n_upper, bool to_tail) -> int {
         hipStream_t gst = lane_stream(gr.lane);
         const uint32_t n = std::max(n_upper, 1u);
-        gr.P.first = gr.iters++ == 0 ? 1u : 0u;
+        gr.P.first = gr.iters++ == 0 && !user_cam ? 1u : 0u;
         // the launch's suspend records: written by this k_trace, read by the next (alternating halves of the lane's area)
         uint32_t* const susp_lane = s->susp.p + (size_t)gr.lane * 2u * kSuspRecords * kSuspWords;
         gr.P.susp_out = susp_lane + (size_t)(gr.iters & 1u) * kSuspRecords * kSuspWords;
@@ -1425,7 +1478,8 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
         hc[kCntIn] = gr.n0;
         HIPCHK(hipMemcpyAsync(gr.P.counts, hc, sizeof(uint32_t) * kCntNum, hipMemcpyHostToDevice, gst));
         HIPCHK(gr.tm.begin(&S.ms_generate));
-        launch_generate(gst, gr.P, gr.n0);
+        if (user_cam) launch_generate_camera(gst, gr.P, ucam, d->height, gr.n0);
+        else launch_generate(gst, gr.P, gr.n0);
         HIPCHK(gr.tm.end());
         return feed(gr);
       };
@@ -1649,6 +1703,29 @@ extern "C" int pbrhip_leaf_eval(uint32_t op, const float* in, size_t n, uint32_t
   });
 }
 
+extern "C" int pbrhip_camera_rays(pbrhip_scene* s, uint32_t width, uint32_t height, uint64_t seed_seq, const uint32_t* x_y_pass, size_t n,
+                                  pbrhip_ray* rays) {
+  return guarded([&]() -> int {
+  if (!s || (!x_y_pass && n) || (!rays && n)) return fail(PBRHIP_EINVAL, "camera_rays: NULL argument");
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "camera_rays: zero image size");
+  if (!s->cam_set && !s->committed) return fail(PBRHIP_ESTATE, "camera_rays: the reference camera needs a committed scene");
+  if (n == 0) return PBRHIP_OK;
+  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
+  for (size_t i = 0; i < n; i++)
+    if (x_y_pass[3 * i] >= width || x_y_pass[3 * i + 1] >= height) return fail(PBRHIP_EINVAL, "camera_rays: pixel %zu is outside the image", i);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(s->hook_rays.reserve(2 * n));
+  HIPCHK(s->hook_xyp.reserve(3 * n));
+  HIPCHK(hipMemcpyAsync(s->hook_xyp.p, x_y_pass, 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+  const UserCamera uc = s->cam_set ? make_user_camera(s, width, height) : UserCamera{};
+  const Camera dc = s->cam_set ? Camera{} : make_camera(s, width, height);
+  launch_camera_rays(s->stream, uc, dc, s->cam_set, width, height, seed_seq, s->hook_xyp.p, (uint32_t)n, s->hook_rays.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(rays, s->hook_rays.p, n * sizeof(pbrhip_ray), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return PBRHIP_OK;
+  });
+}
 extern "C" int pbrhip_trace_closest(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits) {
   return guarded([&]() -> int {
   if (!s || (!rays && n) || (!hits && n)) return fail(PBRHIP_EINVAL, "trace_closest: NULL argument");

@@ -109,6 +109,11 @@ struct pbrhip_scene {
   float env_scale = 1.0f, env_m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   pb::DevBuf<float4> d_env_texels;  // DScene::env_texels
   pb::DevBuf<uint2> d_env_alias;    // DScene::env_alias
+  // the look-at camera as the caller set it (pbrhip_scene_set_camera; kept for pbrhip_scene_replicate): none = the reference's
+  bool cam_set = false;
+  float cam_eye[3] = {0, 0, 0}, cam_lookat[3] = {0, 0, -1}, cam_up[3] = {0, 1, 0};
+  float cam_vfov = 30.0f, cam_lens = 0.0f, cam_focus = 0.0f;
+  pb::DevBuf<uint32_t> hook_xyp;  // pbrhip_camera_rays' (x, y, pass) triples
   pb::DScene dscene;
   // render working set (grown on demand, reused across calls)
   pb::DevBuf<float4> rec, srec, ssrec, L, hit, sss_A, sh_e;  // path state (kernels.h::PathState): rec = 4 words of 16 B per path, srec = 2
@@ -151,6 +156,8 @@ void shard_pixels(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_
 int ensure_pixels(pbrhip_scene* s, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block);
 // pbrhip_scene_set_environment's body (rgb null: no environment); also what pbrhip_scene_replicate calls to carry it over
 int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale, const float* world_to_env);
+// pbrhip_scene_set_camera's body (eye null: the reference's camera); also what pbrhip_scene_replicate calls to carry it over
+int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const float* up, float vfov, float lens_radius, float focus_distance);
 // the body of pbrhip_render_device (device pointers on the scene's device)
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
                 uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats);
