@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dscene.h"
+#include "knobs.h"
 
 namespace pb {
 
@@ -191,15 +192,16 @@ void launch_generate_camera(hipStream_t s, const PathState& P, const UserCamera&
 // test / picking hook: the camera ray of (x, y, pass) triples -- the user camera when `user`, else the reference's camera `dc`
 void launch_camera_rays(hipStream_t s, const UserCamera& cam, const Camera& dc, bool user, uint32_t width, uint32_t height, uint64_t seed_seq,
                         const uint32_t* x_y_pass, uint32_t n, float4* rays);
-void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats);
-bool trace_uses_wide(const DScene& sc);  // the traversal kernels walk the 4-wide tree of this scene (now: PBRHIP_WIDE is read per launch)
-void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured);
+void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats, const Knobs& k);
+bool trace_uses_wide(const DScene& sc, const Knobs& k);  // the traversal kernels walk the 4-wide tree of this scene (PBRHIP_WIDE)
+void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured,
+                 const Knobs& k);
 void launch_classify(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper);
 void launch_compact(hipStream_t s, const PathState& P, uint32_t n_upper);
 void launch_shade_principled(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool media, bool textured);
 void launch_shade_hair(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc);
 void launch_sss_step(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc);
-void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats);
+void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, const Knobs& k);
 void launch_accumulate(hipStream_t s, const PathState& P, const uint32_t* pix_index, uint32_t npix, uint32_t npass,
                        float* rgba, uint32_t* count);
 void launch_advance(hipStream_t s, const PathState& P, uint32_t* ring_slot, uint32_t stamp);  // (also resets P.heads)  // ring_slot: 4 words of device-visible host memory (or null)
@@ -209,8 +211,8 @@ void launch_leaf_eval(hipStream_t s, uint32_t op, const float* in, uint32_t n, u
 void launch_layer_pack(hipStream_t s, const uint32_t* pix, uint32_t npix, const float* rgba, const uint32_t* count, float* shard);
 void launch_layer_unpack_add(hipStream_t s, const uint32_t* pix, uint32_t npix, const float* shard, float* rgba, uint32_t* count);
 void launch_hook_closest(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* out, uint32_t* counts,
-                         uint32_t* spill, bool simple);
+                         uint32_t* spill, const Knobs& k);
 void launch_hook_any(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, uint8_t* out, uint32_t* counts,
-                     uint32_t* spill, bool simple);
+                     uint32_t* spill, const Knobs& k);
 
 }  // namespace pb

@@ -2,7 +2,7 @@
 //
 // One path = one (pixel, pass) sample.  Path state lives in HBM, in records indexed by the path slot
 // (kernels.h::PathState); stages exchange *queues of slot ids*, compacted tile-wise (2048 entries, one atomic per
-// tile and queue).  One iteration of the host loop (pbrhip.cpp::render_impl) =
+// tile and queue).  One iteration of the host loop (pbrhip.cpp::ChunkRun) =
 //
 //   k_trace           rtcIntersect1 (raytracer_impl.cc:268-278) for the live paths' rays AND rtcOccluded1 + the tail of
 //                     DirectIllumination (shader-utils.h:192-208) for the shadow rays of the previous bounce
@@ -1900,11 +1900,8 @@ __global__ void k_advance(uint32_t* counts, uint32_t* heads, uint32_t* ring, uin
 }
 
 // ------------------------------------------------------------------ launchers
-// the Q tree serves the scenes whose tree was built on the host (PBRHIP_WIDE=0: never; read per launch)
-static inline bool use_wide(const DScene& sc) {
-  const char* e = getenv("PBRHIP_WIDE");
-  return sc.wide != nullptr && !(e && atoi(e) == 0);
-}
+// the Q tree serves the scenes whose tree was built on the host (PBRHIP_WIDE=0: never)
+static inline bool use_wide(const DScene& sc, const Knobs& k) { return sc.wide != nullptr && k.wide; }
 // launches KERNEL<..., CURVES, WIDE> for this scene: (curves, binary), (no curves, binary), (curves, Q), (no curves, Q)
 #define PB_LAUNCH_TRAV(KERNEL, PRE, curves, wide, ...)                                          \
   do {                                                                                          \
@@ -1913,24 +1910,13 @@ static inline bool use_wide(const DScene& sc) {
     else if (curves) hipLaunchKernelGGL((KERNEL<PRE, true, false>), __VA_ARGS__);               \
     else hipLaunchKernelGGL((KERNEL<PRE, false, false>), __VA_ARGS__);                          \
   } while (0)
-bool trace_uses_wide(const DScene& sc) { return use_wide(sc); }
+bool trace_uses_wide(const DScene& sc, const Knobs& k) { return use_wide(sc, k); }
 #ifndef PB_TRACE_SMALL1_RAYS
 #define PB_TRACE_SMALL1_RAYS 16000000u  // launches of at most this many rays (upper bound): PB_TRACE_SMALL1_BLOCKS blocks per CU
 #define PB_TRACE_SMALL1_BLOCKS 4u
 #define PB_TRACE_SMALL2_RAYS 4000000u   // ... and of at most this many: PB_TRACE_SMALL2_BLOCKS
 #define PB_TRACE_SMALL2_BLOCKS 3u
 #endif
-#ifndef PB_QUAD_RAYS
-#define PB_QUAD_RAYS 0u  // k_trace launches of at most this many rays run on k_trace_quad (PBRHIP_QUAD_RAYS overrides)
-#endif
-static inline uint32_t quad_rays() {
-  const char* e = getenv("PBRHIP_QUAD_RAYS");
-  return e ? (uint32_t)strtoul(e, nullptr, 10) : PB_QUAD_RAYS;
-}
-static inline bool use_quad() {
-  const char* e = getenv("PBRHIP_QUAD");
-  return e && e[0] == '1';
-}
 static inline uint32_t grid_for(uint32_t n, uint32_t cap) {
   uint32_t g = (n + kBlock - 1) / kBlock;
   if (g < 1) g = 1;
@@ -1951,26 +1937,18 @@ void launch_camera_rays(hipStream_t s, const UserCamera& cam, const Camera& dc, 
                         const uint32_t* x_y_pass, uint32_t n, float4* rays) {
   hipLaunchKernelGGL(k_camera_rays, dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, cam, dc, user ? 1u : 0u, width, height, seed_seq, x_y_pass, n, rays);
 }
-void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats) {
+void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, bool stats, const Knobs& k) {
   // Persistent kernel: at most the resident set.  A launch with fewer rays than that would fill gets fewer waves, so that
   // every wave still has a queue to refill its lanes from (kRaysPerWave rays each): a wave that starts with one ray per
   // lane and nothing to refill from runs until its longest ray ends with most lanes idle, and with seven such waves per
   // SIMD the launch is bound by the instructions those mostly empty waves issue.
-  const char* e = getenv("PBRHIP_RAYS_PER_WAVE");  // (tuning knob; read per launch)
-  const uint32_t rays_per_wave = e ? (uint32_t)strtoul(e, nullptr, 10) : 4u;
-  uint32_t blocks = (n_upper + 4u * rays_per_wave - 1u) / (4u * rays_per_wave);
+  uint32_t blocks = (n_upper + 4u * k.rays_per_wave - 1u) / (4u * k.rays_per_wave);
   const bool curves = sc.num_curves != 0;
-  const bool wide = use_wide(sc);
+  const bool wide = use_wide(sc, k);
   uint32_t cap = 256u * trace_blocks_per_cu(curves, wide);
-  if (const char* b = getenv("PBRHIP_TRACE_BLOCKS")) {  // (tuning knob, read per launch: resident blocks per CU, at most the kernel's)
-    const uint32_t k = (uint32_t)strtoul(b, nullptr, 10);
-    if (k >= 1u && 256u * k < cap) cap = 256u * k;
-  }
-  if (const char* b = getenv("PBRHIP_TRACE_BLOCKS_SMALL")) {  // "k,n": k blocks per CU for launches of at most n rays ("0,0": none)
-    char* end = nullptr;
-    const uint32_t k = (uint32_t)strtoul(b, &end, 10);
-    const uint32_t lim = (end && *end == ',') ? (uint32_t)strtoul(end + 1, nullptr, 10) : 0u;
-    if (k >= 1u && n_upper <= lim && 256u * k < cap) cap = 256u * k;
+  if (k.trace_blocks >= 1u && 256u * k.trace_blocks < cap) cap = 256u * k.trace_blocks;
+  if (!k.small_caps) {
+    if (k.small_blocks >= 1u && n_upper <= k.small_rays && 256u * k.small_blocks < cap) cap = 256u * k.small_blocks;
   } else if (wide && !curves) {
     // Fewer resident blocks for the launches that do not fill the chip for long (round 4, after the shading kernels got faster;
     // scripts/sched_ab.py, rank 0's share of the C2 frame): their drain -- every wave waiting for its longest ray -- runs at
@@ -1994,7 +1972,7 @@ void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t 
 #undef PB_LAUNCH_FIRST
     return;
   }
-  if (wide && !curves && n_upper <= quad_rays()) {
+  if (wide && !curves && n_upper <= k.quad_rays) {
     // a small launch: one ray per quad of lanes
     const dim3 gq(quad_grid(n_upper));
     if (stats) hipLaunchKernelGGL((k_trace_quad<true>), gq, dim3(kBlock), 0, s, P, sc);
@@ -2039,10 +2017,9 @@ void launch_sss_step(hipStream_t s, const PathState& P, const DScene& sc, uint32
   if (has_env(sc)) hipLaunchKernelGGL(k_sss_step_env, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
   else hipLaunchKernelGGL(k_sss_step, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
 }
-void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats) {
+void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, const Knobs& k) {
   const bool curves = sc.num_curves != 0;
-  const char* ww = getenv("PBRHIP_WIDE_WALK");
-  const bool wide = use_wide(sc) && !(ww && atoi(ww) == 0);
+  const bool wide = use_wide(sc, k) && k.wide_walk;
   // persistent: the resident blocks (<= kTraceGridCap: the walk shares k_trace's spill area)
   const uint32_t cap = 256u * (stats ? (uint32_t)PB_WALK_WAVES : walk_blocks_per_cu(curves, wide));
   const uint32_t blocks = (n_upper + 15u) / 16u;
@@ -2061,11 +2038,12 @@ static_assert((size_t)(kStackDepth - kSimpleLdsStack) * PB_TAIL_BLOCKS * 256 <= 
 static_assert(trace_blocks_per_cu(false, true) * 256u <= kTraceGridCap && trace_blocks_per_cu(true, true) * 256u <= kTraceGridCap,
               "the Q tree's k_trace grids fit the spill area sized by kTraceGridCap");
 #define PB_COMMA ,
-void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured) {
+void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured,
+                 const Knobs& k) {
   uint32_t blocks = (n_upper + 3u) / 4u;  // one path per wave while that fits, at most 2 blocks per CU
   dim3 g(blocks < 1u ? 1u : (blocks < PB_TAIL_BLOCKS ? blocks : PB_TAIL_BLOCKS));
   const bool curves = sc.num_curves != 0;
-  const bool wide = use_wide(sc);
+  const bool wide = use_wide(sc, k);
   if (has_env(sc)) {
     if (stats) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
     else if (textured) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
@@ -2092,16 +2070,16 @@ void launch_layer_unpack_add(hipStream_t s, const uint32_t* pix, uint32_t npix, 
 void launch_advance(hipStream_t s, const PathState& P, uint32_t* ring_slot, uint32_t stamp) { hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, s, P.counts, P.heads, ring_slot, stamp); }
 // counts: kCntNum zeroed words (queue head + overflow flag); spill: traversal-stack spill area
 void launch_hook_closest(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* out, uint32_t* counts,
-                         uint32_t* spill, bool simple) {
+                         uint32_t* spill, const Knobs& k) {
   // the variant of the traversal the render of this scene runs; the binary tree's hooks always carry the curve code
-  const bool wide = use_wide(sc), curves = !wide || sc.num_curves != 0;
-  if (simple) {
+  const bool wide = use_wide(sc, k), curves = !wide || sc.num_curves != 0;
+  if (k.simple_traversal) {
     if (wide && curves) hipLaunchKernelGGL((k_hook_closest<true, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     else if (wide) hipLaunchKernelGGL((k_hook_closest<false, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     else hipLaunchKernelGGL((k_hook_closest<true, false>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     return;
   }
-  if (wide && !curves && use_quad()) {
+  if (wide && !curves && k.quad) {
     hipLaunchKernelGGL((k_hook_quad<false>), dim3(quad_grid(n)), dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts + kCntOverflow, spill);
     return;
   }
@@ -2111,15 +2089,15 @@ void launch_hook_closest(hipStream_t s, const DScene& sc, const float4* rays, ui
   else hipLaunchKernelGGL((k_hook_pv<false, true, false>), g, dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts, spill);
 }
 void launch_hook_any(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, uint8_t* out, uint32_t* counts,
-                     uint32_t* spill, bool simple) {
-  const bool wide = use_wide(sc), curves = !wide || sc.num_curves != 0;
-  if (simple) {
+                     uint32_t* spill, const Knobs& k) {
+  const bool wide = use_wide(sc, k), curves = !wide || sc.num_curves != 0;
+  if (k.simple_traversal) {
     if (wide && curves) hipLaunchKernelGGL((k_hook_any<true, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     else if (wide) hipLaunchKernelGGL((k_hook_any<false, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     else hipLaunchKernelGGL((k_hook_any<true, false>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
     return;
   }
-  if (wide && !curves && use_quad()) {
+  if (wide && !curves && k.quad) {
     hipLaunchKernelGGL((k_hook_quad<true>), dim3(quad_grid(n)), dim3(kBlock), 0, s, sc, rays, n, (HookHit*)nullptr, out, counts + kCntOverflow, spill);
     return;
   }

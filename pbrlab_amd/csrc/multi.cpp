@@ -203,7 +203,7 @@ extern "C" int pbrhip_comm_gather_layer(pbrhip_comm* c, pbrhip_scene* s, const p
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     if (c->rank != root) {
-      if (int rc = ensure_pixels(s, d->width, d->height, d->tile_rank, world, d->shard_block)) return rc;
+      if (int rc = ensure_pixels(s, read_knobs(), d->width, d->height, d->tile_rank, world, d->shard_block)) return rc;
       const uint32_t npix = s->pk_npix;
       HIPCHK(s->xchg_send.reserve(shard_words(npix)));
       if (npix == 0) return PBRHIP_OK;  // (the root posts no receive for a rank without pixels either)

@@ -66,9 +66,49 @@ extern "C" int pbrhip_set_device(int device) {
   return PBRHIP_OK;
 }
 
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* e = getenv(name);
-  return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt;
+// ------------------------------------------------------------------ knobs (knobs.h)
+Knobs pb::read_knobs() {
+  auto env = [](const char* name) -> const char* { return getenv(name); };
+  auto u32 = [&](const char* name, uint32_t dflt) { const char* e = env(name); return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt; };
+  auto not_zero = [&](const char* name) { const char* e = env(name); return !(e && atoi(e) == 0); };  // (atoi: a non-number is 0 too)
+  Knobs k;
+  if (const char* e = env("PBRHIP_BVH")) k.bvh = strcmp(e, "gpu") == 0 ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+  k.wide = not_zero("PBRHIP_WIDE");
+  k.sss_entry = u32("PBRHIP_SSS_ENTRY", 1u) != 0u;
+  k.sss_foreign = u32("PBRHIP_SSS_FOREIGN", 3u);
+  k.debug = env("PBRHIP_DEBUG") != nullptr;
+  k.pixel_tile = u32("PBRHIP_PIXEL_TILE", 8u);
+  k.patch_shuffle = u32("PBRHIP_PATCH_SHUFFLE", 1u) != 0u;
+  if (const char* e = env("PBRHIP_PASS_RUN")) k.pass_run = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));
+  k.groups = env("PBRHIP_GROUPS");
+  if (const char* e = env("PBRHIP_TAIL_PATHS")) k.tail_paths = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char* e = env("PBRHIP_STREAMS")) k.streams = (uint32_t)atoi(e);
+  k.window = std::max(1u, u32("PBRHIP_WINDOW", k.groups ? 1u : (uint32_t)kMaxGroups));
+  k.bulk_div = u32("PBRHIP_BULK_DIV", 0u);
+  k.pipe_depth = std::min(std::max(1u, u32("PBRHIP_PIPE_DEPTH", 2u)), kRingSlots - 1u);
+  k.pipe_depth_small = std::min(std::max(1u, u32("PBRHIP_PIPE_DEPTH_SMALL", 8u)), kRingSlots - 1u);
+  if (const char* e = env("PBRHIP_PIPE_STOP")) k.pipe_stop = atof(e);
+  k.trace_sched = env("PBRHIP_TRACE_SCHED") != nullptr;
+  k.wave_log = env("PBRHIP_WAVE_LOG");
+  k.pv_stats = env("PBRHIP_PV_STATS") != nullptr;
+  k.susp_turns = u32("PBRHIP_SUSP_TURNS", 24u);
+  k.shadow_first = u32("PBRHIP_SHADOW_FIRST", 1u);
+  k.first_direct = u32("PBRHIP_FIRST_DIRECT", 1u) != 0u;
+  k.direct = u32("PBRHIP_DIRECT", 1u) != 0u;
+  k.sss_walk = u32("PBRHIP_SSS_WALK", 1u) != 0u;
+  k.wide_walk = not_zero("PBRHIP_WIDE_WALK");
+  k.rays_per_wave = u32("PBRHIP_RAYS_PER_WAVE", 4u);
+  k.trace_blocks = u32("PBRHIP_TRACE_BLOCKS", 0u);
+  if (const char* e = env("PBRHIP_TRACE_BLOCKS_SMALL")) {  // (present at all: the built-in caps are off, even for "0,0")
+    char* end = nullptr;
+    k.small_caps = false;
+    k.small_blocks = (uint32_t)strtoul(e, &end, 10);
+    k.small_rays = (end && *end == ',') ? (uint32_t)strtoul(end + 1, nullptr, 10) : 0u;
+  }
+  k.quad_rays = u32("PBRHIP_QUAD_RAYS", PB_QUAD_RAYS);
+  if (const char* e = env("PBRHIP_QUAD")) k.quad = e[0] == '1';
+  k.simple_traversal = env("PBRHIP_SIMPLE_TRAVERSAL") != nullptr;
+  return k;
 }
 
 // ------------------------------------------------------------------ scene construction
@@ -639,6 +679,7 @@ static std::vector<BvhNode> light_boxes(const std::vector<LightHead>& heads, con
 extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   return guarded([&]() -> int {
   if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  const Knobs k = read_knobs();
   HIPCHK(hipSetDevice(s->device));
   for (uint32_t i = 0; i < s->instances.size(); i++) register_lights(s, i);
   commit_lights(s);
@@ -655,8 +696,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   FlatBvh bvh;
   bool gpu_built = false;
   uint32_t num_nodes = 0;
-  int builder = s->bvh_builder;
-  if (const char* e = getenv("PBRHIP_BVH")) builder = (strcmp(e, "gpu") == 0) ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+  const int builder = k.bvh >= 0 ? k.bvh : s->bvh_builder;
   if (builder == PBRHIP_BVH_GPU_LBVH && np > 0) {
     HIPCHK(s->d_nodes.reserve(std::max<size_t>(np > 1 ? np - 1 : 1, 1) + np));  // nodes, then one 64-byte slot per primitive
     HIPCHK(build_bvh_gpu(s->stream, lo, hi, kinds, s->d_nodes.p, &bvh.slot_gid, &bvh.depth));
@@ -713,30 +753,29 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   // children per node with quantised boxes (64 B per node), followed by its own compact triangle leaves and curve records
   // (bvh_build.cpp::build_qlayout, dscene.h::QNode).
   QLayout q;
-  const char* wide_env = getenv("PBRHIP_WIDE");
-  if (!gpu_built && num_nodes && !(wide_env && atoi(wide_env) == 0)) {
+  if (!gpu_built && num_nodes && k.wide) {
     build_qlayout(bvh, slots, kinds, &q);
-    if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
+    if (k.debug) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
   }
   const std::vector<QNode>& wide = q.nodes;
   // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
   std::vector<SssEntry> sss_entries;
-  if (!wide.empty() && env_u32("PBRHIP_SSS_ENTRY", 1u) != 0u) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
+  if (!wide.empty() && k.sss_entry) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
     const size_t ninst = s->instances.size();
     std::vector<float> ilo(3 * ninst, INFINITY), ihi(3 * ninst, -INFINITY);
     for (uint32_t g = 0; g < np; g++)
       for (size_t a = 0, i = prims[g].instance_id; a < 3; a++)
         ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * (size_t)g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * (size_t)g + a]);
     // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
-    const uint32_t max_foreign = std::min(env_u32("PBRHIP_SSS_FOREIGN", 3u), kSssMaxForeign);
+    const uint32_t max_foreign = std::min(k.sss_foreign, kSssMaxForeign);
     sss_entries = build_sss_entries(wide, ilo, ihi, max_foreign);
-    for (size_t i = 0; i < sss_entries.size() && getenv("PBRHIP_DEBUG"); i++)
+    for (size_t i = 0; i < sss_entries.size() && k.debug; i++)
       if (sss_entries[i].entry) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, sss_entries[i].entry, sss_entries[i].nforeign);
   }
   if (sss_entries.empty()) s->d_sss_entries.release();
   else HIPCHK(s->d_sss_entries.upload(sss_entries, st));
   if (wide.empty()) s->d_wide.release(), s->d_qhit.release();
-  if (getenv("PBRHIP_DEBUG")) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q.tri.size() / kTriPairWords, q.pts.size());
+  if (k.debug) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q.tri.size() / kTriPairWords, q.pts.size());
   if (!wide.empty()) {
     HIPCHK(s->d_wide.reserve(wide.size() * 4 + q.tri.size() + q.pts.size()));
     HIPCHK(hipMemcpyAsync(s->d_wide.p, wide.data(), wide.size() * sizeof(QNode), hipMemcpyHostToDevice, st));
@@ -1084,11 +1123,10 @@ void pb::shard_pixels(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uin
     }
 }
 
-int pb::ensure_pixels(pbrhip_scene* s, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block) {
+int pb::ensure_pixels(pbrhip_scene* s, const Knobs& k, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block) {
   if (block == 0) block = 64;
-  uint32_t pt = 8u;
-  if (const char* e = getenv("PBRHIP_PIXEL_TILE")) pt = (uint32_t)strtoul(e, nullptr, 10);
-  const bool shuffle = env_u32("PBRHIP_PATCH_SHUFFLE", 1u) != 0u;
+  uint32_t pt = k.pixel_tile;
+  const bool shuffle = k.patch_shuffle;
   pt |= shuffle ? 0x80000000u : 0u;  // (part of the cache key below)
   if (s->pk_w == w && s->pk_h == h && s->pk_rank == rank && s->pk_world == world && s->pk_block == block && s->pk_tile == pt && s->pix_index.p) return PBRHIP_OK;
   std::vector<uint32_t> pix;
@@ -1171,9 +1209,8 @@ static int ensure_paths(pbrhip_scene* s, size_t n) {
 
 // PathState::pass_run of a group of `npass` passes: 1 for scenes of surfaces; scenes with curves: the largest power of two <= 64 that
 // divides npass.  PBRHIP_PASS_RUN=R forces a run length (when it divides npass; 1 = off): A/B and tests.
-static uint32_t pass_run_for(uint32_t npass, bool curves) {
-  uint32_t want = curves ? 64u : 1u;
-  if (const char* e = getenv("PBRHIP_PASS_RUN")) want = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));
+static uint32_t pass_run_for(const Knobs& k, uint32_t npass, bool curves) {
+  const uint32_t want = k.pass_run ? k.pass_run : (curves ? 64u : 1u);
   uint32_t r = 1u;
   while (r * 2u <= want && npass % (r * 2u) == 0u) r *= 2u;
   return r;
@@ -1181,13 +1218,13 @@ static uint32_t pass_run_for(uint32_t npass, bool curves) {
 
 // How the passes of a chunk are split into path groups (each group = its own queues, counters and HIP stream; path
 // slots stay global and passes are accumulated in ascending order, so the image does not depend on the split: GPU test).
-// The scheduler in render_impl starts groups in order while fewer than `window` of them are in their bulk phase (default:
+// The scheduler (ChunkRun) starts groups in order while fewer than `window` of them are in their bulk phase (default:
 // all at once).  PBRHIP_GROUPS="56,8" (passes per group, started one after the other: PBRHIP_WINDOW defaults to 1 then)
 // and pbrhip_render_desc.num_streams = n (n equal groups at once) override the default plan; the pipelined plans that
 // were tried (geometric sizes, big-then-small pairs) all lost to it, see profiles/README.md.
-static std::vector<uint32_t> plan_groups(uint32_t np, uint32_t npix, uint32_t want_groups) {
+static std::vector<uint32_t> plan_groups(const Knobs& k, uint32_t np, uint32_t npix, uint32_t want_groups) {
   std::vector<uint32_t> g;
-  if (const char* e = getenv("PBRHIP_GROUPS")) {  // explicit passes per group, e.g. "32,16,8,4,2,1,1" (the rest joins the last)
+  if (const char* e = k.groups) {  // explicit passes per group, e.g. "32,16,8,4,2,1,1" (the rest joins the last)
     uint32_t left = np;
     for (const char* p = e; *p && left;) {
       uint32_t v = (uint32_t)strtoul(p, (char**)&p, 10);
@@ -1219,19 +1256,411 @@ static std::vector<uint32_t> plan_groups(uint32_t np, uint32_t npix, uint32_t wa
   return g;
 }
 
-int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
-                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats) {
-  auto t_begin = std::chrono::steady_clock::now();
+static int check_render_desc(const pbrhip_scene* s, const pbrhip_render_desc* d) {
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
   if (d->width == 0 || d->height == 0) return fail(PBRHIP_EINVAL, "empty image");
   if ((uint64_t)d->width * d->height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "image too large");
-  uint32_t world = d->tile_world ? d->tile_world : 1;
+  const uint32_t world = d->tile_world ? d->tile_world : 1;
   if (d->tile_rank >= world) return fail(PBRHIP_EINVAL, "tile_rank %u >= tile_world %u", d->tile_rank, world);
   if (d->shard_block > 4096) return fail(PBRHIP_EINVAL, "shard_block %u is not a sensible block edge", d->shard_block);
-  auto cancelled = [&]() { return cancel && __atomic_load_n(cancel, __ATOMIC_RELAXED) != 0; };
-  auto publish = [&](size_t passes) {
-    if (finish_pass) __atomic_store_n(finish_pass, passes, __ATOMIC_RELEASE);
-  };
+  return PBRHIP_OK;
+}
+
+// Passes per chunk.  Default: as many paths in flight as 60 % of the free HBM holds (288 GB: a whole 1080p x 64 spp frame,
+// 132.7 M paths x 244 B, is one chunk) -- fewer, larger launches and one tail instead of many
+static int chunk_passes_for(const pbrhip_scene* s, const pbrhip_render_desc* d, const Knobs& k, uint32_t npix, uint32_t* out) {
+  uint64_t max_paths = d->max_paths_in_flight;
+  if (!max_paths) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    // what this scene already holds for path state counts as available
+    size_t have = (s->rec.n + s->srec.n + s->ssrec.n + s->L.n + s->hit.n + s->sh_e.n + s->sss_A.n) * 16;
+    for (auto& b : s->q) have += b.n * 4;
+    max_paths = std::min<uint64_t>(kMaxPathsInFlight,
+                                   std::max<uint64_t>(1ull << 20, (uint64_t)((free_b + have) * 0.6) / kBytesPerPath));
+  }
+  if (max_paths > kMaxPathsInFlight) max_paths = kMaxPathsInFlight;
+  if (k.debug) {
+    size_t fb = 0, tb = 0;
+    (void)hipMemGetInfo(&fb, &tb);
+    fprintf(stderr, "pbrhip: free %.1f GB total %.1f GB max_paths %llu npix %u\n", fb / 1e9, tb / 1e9, (unsigned long long)max_paths, npix);
+  }
+  if (npix > kMaxPathsInFlight) return fail(PBRHIP_EUNSUPPORTED, "more than 2^28 pixels per rank");
+  uint32_t chunk_passes = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(d->num_sample, max_paths / npix));
+  if ((uint64_t)chunk_passes * npix >= (1ull << 32)) chunk_passes = (uint32_t)(((1ull << 32) - 1) / npix);
+  // A working set that is nearly large enough is used as it is: growing it means freeing and re-allocating every path-state
+  // array (65 GB at the largest chunk: 1.3 s), and the chunk size does not change the image.  (An eighth of the C5 frame asks
+  // for 258 passes = 267.5 M paths where the whole frame had allocated 265.4 M.)
+  if (s->hit.n < (size_t)chunk_passes * npix && s->hit.n / npix >= 1 && (double)(s->hit.n / npix) >= 0.75 * chunk_passes)
+    chunk_passes = (uint32_t)(s->hit.n / npix);
+  *out = chunk_passes;
+  return PBRHIP_OK;
+}
+
+// The path state every group of a render starts from: the scene's working set (ensure_paths), before a group takes its slice
+static PathState base_path_state(const pbrhip_scene* s, bool want_stats) {
+  PathState P;
+  P.pass_run = 1u;
+  P.ray_o.base = s->rec.p, P.ray_d.base = s->rec.p + 1, P.thr.base = s->rec.p + 2, P.L = s->L.p, P.hit = s->hit.p;
+  P.rng.base = reinterpret_cast<uint64_t*>(s->rec.p + 3);
+  P.hold.base = reinterpret_cast<uint32_t*>(s->rec.p + 3) + 2;
+  P.rng4.base = reinterpret_cast<uint4*>(s->rec.p + 3);
+  P.sss_sigt.base = s->ssrec.p, P.sss_sigs.base = s->ssrec.p + 1, P.sss_thr.base = s->ssrec.p + 2;
+  P.sss_ez.base = s->ssrec.p + 3, P.sss_A = s->sss_A.p;
+  P.q_in = s->q[0].p, P.q_out = s->q[1].p, P.q_principled = s->q[2].p, P.q_hair = s->q[3].p, P.q_sss = s->q[4].p, P.q_shadow = s->q[5].p, P.q_shadow_in = s->q[6].p;
+  P.sh_d.base = s->srec.p, P.sh_c.base = s->srec.p + 1, P.sh_e = s->sh_e.p;
+  P.counts = s->counts.p, P.stats = want_stats ? s->stats.p : nullptr, P.spill = s->spill.p;
+  P.first = 0u, P.direct = 0u, P.cam_org[0] = P.cam_org[1] = P.cam_org[2] = 0.f;
+  P.heads = nullptr;
+  P.susp_turns = 0u, P.susp_out = nullptr, P.susp_in = nullptr, P.shadow_first = 0u;
+  P.no_medium = s->has_sss ? 0u : 1u;
+  P.wave_log = nullptr, P.wave_log_launch = 0;
+  return P;
+}
+
+namespace {
+struct Group {
+  PathState P;
+  uint32_t n0, first_pass, npass, slot0;  // paths at the start, pass range, first path slot
+  uint32_t n = 0, iters = 0;
+  int lane = -1;  // stream / counter / spill slot while active
+  bool started = false, finished = false;
+  uint32_t enq = 0, seen = 0;     // iterations enqueued / heard of (ring stamps)
+  uint32_t stamps[kRingSlots];    // stamp of enqueued iteration i at [i % kRingSlots]
+  bool tail_enqueued = false;
+  Timer tm;
+};
+
+// The chunks of one render, one after the other.  A chunk's passes are split into path groups (plan_groups), and a group runs
+// on a lane (stream + counters + spill area + suspend area) while it is active.  Resumable rays and the pipelined host loop
+// (round 6; kernels.h::PathState::susp_turns, scene_impl.h::h_ring): every enqueued iteration ends with k_advance, which tells
+// the host (ring) what is left; iterations are enqueued ahead of what the host has heard of, their launches sized by the last
+// count it saw (live paths only ever decrease: an upper bound).
+struct ChunkRun {
+  pbrhip_scene* s;
+  const pbrhip_render_desc* d;
+  const Knobs& k;
+  const PathState& P;  // base_path_state
+  pbrhip_render_stats& S;
+  const volatile unsigned char* cancel;
+  size_t* finish_pass;
+  float* d_rgba;
+  uint32_t* d_count;
+  std::chrono::steady_clock::time_point t_begin;
+  const DScene& sc = s->dscene;
+  const uint32_t npix = s->pk_npix;
+  const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;
+  const bool trace_timing_only = (d->flags & PBRHIP_RENDER_TIMING) == 0 && (d->flags & PBRHIP_RENDER_TIMING_TRACE) != 0;
+  const bool want_timing = (d->flags & (PBRHIP_RENDER_TIMING | PBRHIP_RENDER_TIMING_TRACE)) != 0;
+  const Camera cam = make_camera(s, d->width, d->height);
+  // a user camera: k_generate_camera stores each path's first ray and the first bounce is an ordinary one (PathState::first = 0)
+  const bool user_cam = s->cam_set;
+  const UserCamera ucam = user_cam ? make_user_camera(s, d->width, d->height) : UserCamera{};
+  const uint64_t rng_inc = (d->seed_seq << 1u) | 1u;  // pcg32_srandom (rng.h:30-36)
+  const uint32_t tail_paths = k.tail_paths.value_or(d->tail_paths == 0xFFFFFFFFu ? 0u : (d->tail_paths ? d->tail_paths : 262144u));
+  const uint32_t want_groups = k.streams.value_or(d->num_streams);
+  uint32_t lanes = 1;  // reserve_lanes
+  uint32_t wave_log_launches = 0;
+  bool stop = false;  // cancelled: what is in flight is dropped, no further chunk starts
+  // the chunk in flight
+  std::vector<Group> G;
+  bool lane_busy[kMaxGroups];
+  uint32_t next_start, acc_prefix, active, acc_passes, idle_polls;
+  bool cancelled() const { return cancel && __atomic_load_n(cancel, __ATOMIC_RELAXED) != 0; }
+  hipStream_t lane_stream(int lane) const { return lane == 0 ? s->stream : s->group_streams[lane - 1]; }
+  static size_t ring_slot(int lane, uint32_t i) { return (size_t)(lane * kRingSlots + i % kRingSlots) * 4u; }
+  bool reported(const Group& gr, uint32_t i) const {  // has the k_advance of gr's enqueued iteration i written its stamp?
+    const volatile uint32_t* slot = s->h_ring + ring_slot(gr.lane, i);
+    return __atomic_load_n(&slot[3], __ATOMIC_ACQUIRE) == gr.stamps[i % kRingSlots];
+  }
+  // lanes for the groups this call can have in flight: the first chunk is the largest, so its plan has the most groups
+  int reserve_lanes(uint32_t chunk_passes) {
+    const size_t ng = plan_groups(k, std::min(chunk_passes, d->num_sample), npix, want_groups).size();
+    lanes = std::max(1u, std::min<uint32_t>((uint32_t)kMaxGroups, (uint32_t)ng));
+    if (int rc = ensure_groups(s, lanes)) return rc;
+    HIPCHK(s->heads.reserve((size_t)kMaxGroups * kTraceHeads * kHeadStride));
+    HIPCHK(s->susp.reserve((size_t)lanes * 2u * kSuspRecords * kSuspWords));  // (2 x 113 MB per lane)
+    return PBRHIP_OK;
+  }
+  // Passes done .. done + np: groups start in order while fewer than k.window of them are in their bulk phase; a group whose
+  // oldest enqueued iteration has reported gets more work enqueued behind what is still running; a finished group frees its
+  // lane; passes are accumulated (ascending, on the main stream) as soon as every earlier group of the chunk is complete, and
+  // *finish_pass follows.  *cancel is read on every turn.  *passes: the passes accumulated.
+  int run(uint32_t done, uint32_t np, uint32_t* passes) {
+    HIPCHK(hipStreamSynchronize(s->stream));  // clears / the previous chunk's accumulates are done before groups start
+    const std::vector<uint32_t> plan = plan_groups(k, np, npix, want_groups);
+    G.assign(plan.size(), Group());
+    for (uint32_t g = 0, p0 = 0; g < plan.size(); p0 += plan[g], g++) init_group(G[g], done, p0, plan[g]);
+    std::fill(lane_busy, lane_busy + kMaxGroups, false);
+    next_start = acc_prefix = active = acc_passes = idle_polls = 0;
+    for (;;) {
+      if (!stop && cancelled()) stop = true;
+      if (int rc = start_groups()) return rc;
+      if (active == 0) break;
+      bool progressed = false;
+      for (Group& gr : G)
+        if (int rc = poll(gr, &progressed)) return rc;
+      if (int rc = accumulate_prefix(done)) return rc;
+      if (progressed) {
+        idle_polls = 0;
+        continue;
+      }
+      std::this_thread::yield();
+      if ((++idle_polls & 1023u) == 0u)
+        if (int rc = check_idle_streams()) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *passes = acc_passes;
+    return PBRHIP_OK;
+  }
+  void init_group(Group& gr, uint32_t done, uint32_t p0, uint32_t npass) {
+    gr.P = P, gr.n0 = npass * npix, gr.first_pass = d->first_pass + done + p0, gr.npass = npass, gr.slot0 = p0 * npix;
+    const size_t off = gr.slot0;
+    gr.P.q_in += off, gr.P.q_out += off, gr.P.q_principled += off, gr.P.q_hair += off, gr.P.q_sss += off, gr.P.q_shadow += off, gr.P.q_shadow_in += off;
+    for (int a = 0; a < 3; a++) gr.P.cam_org[a] = cam.org[a];
+    gr.P.cam = cam, gr.P.pix_index = s->path_pix.p, gr.P.npix = npix, gr.P.width = d->width, gr.P.first_pass = gr.first_pass;
+    gr.P.slot0 = gr.slot0, gr.P.seed_seq = d->seed_seq;
+    gr.P.pass_run = pass_run_for(k, gr.npass, sc.num_curves != 0);
+    gr.P.shadow_first = k.shadow_first, gr.P.susp_turns = 0u;
+    gr.tm = Timer{s, want_timing, nullptr};
+    gr.tm.only = trace_timing_only ? &S.ms_trace_closest : nullptr;
+    gr.tm.idle_acc = &S.ms_host_idle;
+  }
+  // start groups while the window allows: a group is in its bulk phase until it has handed its remaining paths to k_tail (or,
+  // with PBRHIP_BULK_DIV = k, until fewer than 1/k of its paths are alive)
+  int start_groups() {
+    while (!stop && next_start < G.size()) {
+      uint32_t bulk = 0;
+      for (const Group& gr : G)
+        if (gr.started && !gr.finished && gr.n > std::max<uint64_t>(tail_paths, k.bulk_div ? gr.n0 / k.bulk_div : 0u)) bulk++;
+      const int lane = (int)(std::find(lane_busy, lane_busy + lanes, false) - lane_busy);
+      if (bulk >= k.window || lane == (int)lanes) break;
+      if (int rc = start(G[next_start], lane)) return rc;
+      next_start++, active++;
+    }
+    return PBRHIP_OK;
+  }
+  int start(Group& gr, int lane) {
+    gr.lane = lane, gr.started = true, gr.n = gr.n0, lane_busy[lane] = true;
+    hipStream_t gst = lane_stream(lane);
+    gr.tm.stream = gst;
+    gr.P.counts = s->counts.p + lane * kCntNum;
+    gr.P.spill = s->spill.p + (size_t)lane * kSpillWords;
+    gr.P.heads = s->heads.p + (size_t)lane * kTraceHeads * kHeadStride;
+    HIPCHK(hipMemsetAsync(gr.P.heads, 0, sizeof(uint32_t) * kTraceHeads * kHeadStride, gst));
+    uint32_t* hc = s->h_counts + lane * kCntNum;
+    memset(hc, 0, sizeof(uint32_t) * kCntNum);
+    hc[kCntIn] = gr.n0;
+    HIPCHK(hipMemcpyAsync(gr.P.counts, hc, sizeof(uint32_t) * kCntNum, hipMemcpyHostToDevice, gst));
+    HIPCHK(gr.tm.begin(&S.ms_generate));
+    if (user_cam) launch_generate_camera(gst, gr.P, ucam, d->height, gr.n0);
+    else launch_generate(gst, gr.P, gr.n0);
+    HIPCHK(gr.tm.end());
+    return feed(gr);
+  }
+  // keeps group gr's stream fed: k.pipe_depth iterations ahead of the counts the host has seen (gr.n = the last count heard: an
+  // upper bound for every later iteration).  Close to the hand-over to k_tail (live paths <= k.pipe_stop x tail_paths) nothing is
+  // enqueued ahead: the hand-over is decided on exact counts (an iteration enqueued ahead would run as a full wavefront iteration
+  // on what k_tail finishes faster).
+  int feed(Group& gr) {
+    if (gr.tail_enqueued) return PBRHIP_OK;
+    const uint32_t depth = gr.n < (1u << 18) ? k.pipe_depth_small : k.pipe_depth;
+    while (gr.enq - gr.seen < depth) {
+      const bool exact = gr.enq == gr.seen;  // the host knows this iteration's input counts
+      if (gr.n <= tail_paths) {
+        if (int rc = enqueue_iteration(gr, gr.n, true)) return rc;
+        break;
+      }
+      if (!exact && tail_paths && (double)gr.n <= k.pipe_stop * (double)tail_paths) break;
+      if (int rc = enqueue_iteration(gr, gr.n, false)) return rc;
+    }
+    return PBRHIP_OK;
+  }
+  // one iteration of group gr, its launches sized for at most n_upper live paths (and as many pending shadow rays)
+  int enqueue_iteration(Group& gr, uint32_t n_upper, bool to_tail) {
+    hipStream_t gst = lane_stream(gr.lane);
+    const uint32_t n = std::max(n_upper, 1u);
+    gr.P.first = gr.iters++ == 0 && !user_cam ? 1u : 0u;
+    // the launch's suspend records: written by this k_trace, read by the next (alternating halves of the lane's area)
+    uint32_t* const susp_lane = s->susp.p + (size_t)gr.lane * 2u * kSuspRecords * kSuspWords;
+    gr.P.susp_out = susp_lane + (size_t)(gr.iters & 1u) * kSuspRecords * kSuspWords;
+    gr.P.susp_in = susp_lane + (size_t)((gr.iters & 1u) ^ 1u) * kSuspRecords * kSuspWords;
+    gr.P.susp_turns = to_tail ? 0u : k.susp_turns;  // (k_tail takes every path to its end: the rays in front of it all finish)
+    gr.tm.iteration_begins();
+    HIPCHK(gr.tm.begin(&S.ms_trace_closest));
+    gr.P.wave_log_launch = wave_log_launches++;
+    launch_trace(gst, gr.P, sc, 2 * n, want_stats, k);  // this bounce's closest rays + last bounce's shadow rays
+    HIPCHK(gr.tm.end());
+    S.n_trace_closest++, S.iterations++;
+    if (to_tail) {
+      // few live paths: after this bounce's trace (and the pending shadow rays) every path is finished in one launch
+      HIPCHK(gr.tm.begin(&S.ms_tail));
+      launch_tail(gst, gr.P, sc, n, rng_inc, want_stats, s->has_sss, s->has_textured, k);
+      HIPCHK(gr.tm.end());
+      S.n_tail++;
+      gr.tm.iteration_ends();
+      advance(gr, gst);  // nothing was queued: both "in" counts become 0
+      gr.tail_enqueued = true;
+      return PBRHIP_OK;
+    }
+    // a first bounce in a scene without hair needs no routing -- every hit takes the principled shader --: the shading kernel
+    // walks the group's paths itself (PathState::direct); so does every bounce of a scene of principled surfaces only (no hair,
+    // no media: C2 frame -3 %)
+    // (media do not matter to a first bounce: no path is inside one before its first shading)
+    const bool direct = !s->has_hair && ((gr.P.first && k.first_direct) || (!s->has_sss && k.direct));
+    gr.P.direct = direct ? 1u : 0u;
+    if (!direct) {
+      HIPCHK(gr.tm.begin(&S.ms_surface));
+      launch_classify(gst, gr.P, sc, n);
+      HIPCHK(gr.tm.end());
+      S.n_surface++;
+    }
+    HIPCHK(gr.tm.begin(&S.ms_shade_principled));
+    launch_shade_principled(gst, gr.P, sc, n, rng_inc, s->has_sss, s->has_textured);
+    HIPCHK(gr.tm.end());
+    if (s->has_hair) {
+      HIPCHK(gr.tm.begin(&S.ms_shade_hair));
+      launch_shade_hair(gst, gr.P, sc, n, rng_inc);
+      HIPCHK(gr.tm.end());
+      S.n_shade_hair++;
+    }
+    if (s->has_sss) {
+      HIPCHK(gr.tm.begin(&S.ms_sss_step));
+      if (k.sss_walk) launch_sss_walk(gst, gr.P, sc, n, rng_inc, want_stats, k);  // every walk forward to its last event ...
+      launch_sss_step(gst, gr.P, sc, n, rng_inc);                                  // ... which the step kernel handles
+      HIPCHK(gr.tm.end());
+      S.n_sss_step++;
+    }
+    HIPCHK(gr.tm.begin(&S.ms_compact));
+    launch_compact(gst, gr.P, n);
+    HIPCHK(gr.tm.end());
+    S.n_shade_principled++;
+    gr.tm.iteration_ends();
+    advance(gr, gst);
+    std::swap(gr.P.q_in, gr.P.q_out);
+    std::swap(gr.P.q_shadow, gr.P.q_shadow_in);
+    return PBRHIP_OK;
+  }
+  void advance(Group& gr, hipStream_t gst) {
+    const uint32_t stamp = ++s->ring_stamp ? s->ring_stamp : ++s->ring_stamp;  // (never 0: the rings start zeroed)
+    gr.stamps[gr.enq % kRingSlots] = stamp;
+    launch_advance(gst, gr.P, s->d_ring + ring_slot(gr.lane, gr.enq), stamp);
+    gr.enq++;
+  }
+  // what group gr's ring says: the iterations that have reported, then whether the group is complete -- or abandoned: a
+  // cancelled render drops what is in flight --, else more work for it
+  int poll(Group& gr, bool* progressed) {
+    if (!gr.started || gr.finished) return PBRHIP_OK;
+    while (gr.seen < gr.enq && reported(gr, gr.seen)) {
+      const volatile uint32_t* slot = s->h_ring + ring_slot(gr.lane, gr.seen);
+      *progressed = true;
+      if (slot[2]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
+      gr.n = std::max(slot[0], slot[1]);  // pending shadow rays need one more trace
+      gr.seen++;
+      if (k.trace_sched)
+        fprintf(stderr, "sched %8.3f ms  group %d (passes %u)  iter %u of %u enqueued  live %u\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(),
+                (int)(&gr - G.data()), gr.npass, gr.seen, gr.enq, gr.n);
+    }
+    if (gr.seen == gr.enq && (gr.n == 0 || stop)) {
+      HIPCHK(hipStreamSynchronize(lane_stream(gr.lane)));  // (its last k_advance has written the stamp: the stream is about to be idle)
+      HIPCHK(gr.tm.collect());
+      gr.finished = gr.n == 0;
+      if (!gr.finished) gr.started = false;
+      lane_busy[gr.lane] = false, active--;
+      *progressed = true;
+      return PBRHIP_OK;
+    }
+    if (gr.n != 0 && !stop) return feed(gr);
+    return PBRHIP_OK;
+  }
+  // accumulate the complete prefix of the chunk's groups
+  int accumulate_prefix(uint32_t done) {
+    hipStream_t st = s->stream;
+    while (acc_prefix < G.size() && G[acc_prefix].finished) {
+      const Group& gr = G[acc_prefix];
+      PathState PA = P;
+      PA.L = P.L + gr.slot0, PA.pass_run = gr.P.pass_run;
+      Timer tm{s, want_timing, st};
+      tm.only = trace_timing_only ? &S.ms_trace_closest : nullptr;
+      HIPCHK(tm.begin(&S.ms_accumulate));
+      launch_accumulate(st, PA, s->path_pix.p, npix, gr.npass, d_rgba, d_count);
+      HIPCHK(tm.end());
+      HIPCHK(hipGetLastError());
+      if (want_timing && !trace_timing_only) {  // (trace-only timing has nothing to collect here and must not stall the host)
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(tm.collect());
+      }
+      acc_passes += gr.npass, acc_prefix++;
+      S.samples += (uint64_t)gr.npass * npix;
+      if (finish_pass) __atomic_store_n(finish_pass, (size_t)done + acc_passes, __ATOMIC_RELEASE);  // render.cc:224-231
+    }
+    return PBRHIP_OK;
+  }
+  // (now and then: a stream that failed, or went idle without its last stamp, must not leave the loop spinning)
+  int check_idle_streams() {
+    for (Group& gr : G) {
+      if (!gr.started || gr.finished || gr.seen == gr.enq) continue;
+      const hipError_t q = hipStreamQuery(lane_stream(gr.lane));
+      if (q == hipErrorNotReady) continue;
+      HIPCHK(q);
+      if (!reported(gr, gr.enq - 1u)) return fail(PBRHIP_EHIP, "render: a path group's stream went idle without reporting its last iteration");
+    }
+    return PBRHIP_OK;
+  }
+};
+}  // namespace
+
+// PBRHIP_WAVE_LOG: the log of the render's k_trace waves, as the kernels wrote it (scripts/wave_log.py reads it)
+static int write_wave_log(const DevBuf<unsigned long long>& log, const char* path) {
+  std::vector<unsigned long long> h((size_t)kWaveLogLaunches * kWaveLogWaves * 4);
+  HIPCHK(hipMemcpy(h.data(), log.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(path, "wb")) {
+    fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+    fclose(f);
+  }
+  return PBRHIP_OK;
+}
+
+static double ratio(unsigned long long a, unsigned long long b) { return a / (double)std::max<unsigned long long>(1, b); }
+
+// the device's statistics counters (PBRHIP_RENDER_STATS) into S; PBRHIP_PV_STATS prints the traversal's on stderr
+static int read_render_stats(const pbrhip_scene* s, const Knobs& k, pbrhip_render_stats* S) {
+  unsigned long long hs[kStatNum];
+  HIPCHK(hipMemcpy(hs, s->stats.p, sizeof(hs), hipMemcpyDeviceToHost));
+  S->closest_rays = hs[kStatClosestRays] - hs[kStatSuspended] - hs[kStatHeld], S->closest_nodes = hs[kStatClosestNodes];  // (a suspended ray is counted by the launch that suspends it and by the one that resumes it)
+  S->suspended_rays = hs[kStatSuspended] + hs[kStatSuspendedShadow];
+  S->closest_tris = hs[kStatClosestTris], S->closest_curves = hs[kStatClosestCurves];
+  S->shadow_rays = hs[kStatShadowRays] - hs[kStatSuspendedShadow], S->shadow_nodes = hs[kStatShadowNodes];
+  S->tail_closest_rays = hs[kStatTailClosestRays], S->tail_shadow_rays = hs[kStatTailShadowRays];
+  S->pruned_rays = hs[kStatPrunedRays];
+  S->shadow_tris = hs[kStatShadowTris], S->shadow_curves = hs[kStatShadowCurves];
+  if (!k.pv_stats) return PBRHIP_OK;
+  fprintf(stderr, "pv closest: it node %llu tri %llu curve %llu refill %llu | lanes/iter node %.1f tri %.1f curve %.1f\n",
+          hs[kStatPvItNode], hs[kStatPvItTri], hs[kStatPvItCurve], hs[kStatPvItRefill],
+          ratio(hs[kStatPvLnNode], hs[kStatPvItNode]), ratio(hs[kStatPvLnTri], hs[kStatPvItTri]), ratio(hs[kStatPvLnCurve], hs[kStatPvItCurve]));
+  const unsigned long long cyc = hs[kStatCycNode] + hs[kStatCycTri] + hs[kStatCycCurve] + hs[kStatCycRefill];
+  fprintf(stderr, "pv cycles per wave turn (shader clock, lane 0 of every wave, from one turn's start to the next's): node %.0f  triangle %.0f  curve %.0f  refill %.0f | share of the waves' time: %.3f %.3f %.3f %.3f\n",
+          ratio(hs[kStatCycNode], hs[kStatPvItNode]), ratio(hs[kStatCycTri], hs[kStatPvItTri]),
+          ratio(hs[kStatCycCurve], hs[kStatPvItCurve]), ratio(hs[kStatCycRefill], hs[kStatPvItRefill]),
+          ratio(hs[kStatCycNode], cyc), ratio(hs[kStatCycTri], cyc), ratio(hs[kStatCycCurve], cyc), ratio(hs[kStatCycRefill], cyc));
+  fprintf(stderr, "pv steps per closest-hit ray (<=16, 32, 64, 128, 256, 512, 1024, more):");
+  for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", hs[kStatStepHist0 + i]);
+  fprintf(stderr, " | max %llu | most loop turns of one wave (whole render) %llu\n", hs[kStatMaxSteps], hs[kStatMaxWaveIters]);
+  fprintf(stderr, "pv steps per shadow ray:");
+  for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", hs[kStatAnyHist0 + i]);
+  fprintf(stderr, " | max %llu\n", hs[kStatAnyMaxSteps]);
+  fprintf(stderr, "walk: nodes %llu prims %llu | wave turns: traversal %llu, step / refill %llu | cycles per traversal turn %.0f, per step / refill turn %.0f (share %.3f)\n", hs[kStatWalkNodes], hs[kStatWalkTris],
+          hs[kStatWalkTurns], hs[kStatWalkSteps], ratio(hs[kStatWalkCycTrav], hs[kStatWalkTurns]), ratio(hs[kStatWalkCycStep], hs[kStatWalkSteps]),
+          ratio(hs[kStatWalkCycStep], hs[kStatWalkCycStep] + hs[kStatWalkCycTrav]));
+  return PBRHIP_OK;
+}
+
+int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
+                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (int rc = check_render_desc(s, d)) return rc;
+  const Knobs k = read_knobs();
   HIPCHK(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const size_t npx_img = (size_t)d->width * d->height;
@@ -1239,394 +1668,49 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
     HIPCHK(hipMemsetAsync(d_rgba, 0, npx_img * 4 * sizeof(float), st));
     HIPCHK(hipMemsetAsync(d_count, 0, npx_img * sizeof(uint32_t), st));
   }
-  publish(0);
+  if (finish_pass) __atomic_store_n(finish_pass, (size_t)0, __ATOMIC_RELEASE);
   pbrhip_render_stats S;
   memset(&S, 0, sizeof(S));
-  if (int rc = ensure_pixels(s, d->width, d->height, d->tile_rank, world, d->shard_block)) return rc;
+  if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
   const uint32_t npix = s->pk_npix;
   const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;
-  const bool trace_timing_only = (d->flags & PBRHIP_RENDER_TIMING) == 0 && (d->flags & PBRHIP_RENDER_TIMING_TRACE) != 0;
-  const bool want_timing = (d->flags & (PBRHIP_RENDER_TIMING | PBRHIP_RENDER_TIMING_TRACE)) != 0;
   uint32_t done = 0;  // passes accumulated into the layer
   if (npix > 0 && d->num_sample > 0) {
-    // default: as many paths in flight as 60 % of the free HBM holds (288 GB: a whole 1080p x 64 spp frame,
-    // 132.7 M paths x 244 B, is one chunk) -- fewer, larger launches and one tail instead of many
-    uint64_t max_paths = d->max_paths_in_flight;
-    if (!max_paths) {
-      size_t free_b = 0, total_b = 0;
-      HIPCHK(hipMemGetInfo(&free_b, &total_b));
-      // what this scene already holds for path state counts as available
-      size_t have = (s->rec.n + s->srec.n + s->ssrec.n + s->L.n + s->hit.n + s->sh_e.n + s->sss_A.n) * 16;
-      for (auto& b : s->q) have += b.n * 4;
-      max_paths = std::min<uint64_t>(kMaxPathsInFlight,
-                                     std::max<uint64_t>(1ull << 20, (uint64_t)((free_b + have) * 0.6) / kBytesPerPath));
-    }
-    if (max_paths > kMaxPathsInFlight) max_paths = kMaxPathsInFlight;
-    if (getenv("PBRHIP_DEBUG")) {
-      size_t fb = 0, tb = 0;
-      (void)hipMemGetInfo(&fb, &tb);
-      fprintf(stderr, "pbrhip: free %.1f GB total %.1f GB max_paths %llu npix %u\n", fb / 1e9, tb / 1e9, (unsigned long long)max_paths, npix);
-    }
-    if (npix > kMaxPathsInFlight) return fail(PBRHIP_EUNSUPPORTED, "more than 2^28 pixels per rank");
-    uint32_t chunk_passes = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(d->num_sample, max_paths / npix));
-    if ((uint64_t)chunk_passes * npix >= (1ull << 32)) chunk_passes = (uint32_t)(((1ull << 32) - 1) / npix);
-    // A working set that is nearly large enough is used as it is: growing it means freeing and re-allocating every path-state
-    // array (65 GB at the largest chunk: 1.3 s), and the chunk size does not change the image.  (An eighth of the C5 frame asks
-    // for 258 passes = 267.5 M paths where the whole frame had allocated 265.4 M.)
-    if (s->hit.n < (size_t)chunk_passes * npix && s->hit.n / npix >= 1 && (double)(s->hit.n / npix) >= 0.75 * chunk_passes)
-      chunk_passes = (uint32_t)(s->hit.n / npix);
+    uint32_t chunk_passes = 0;
+    if (int rc = chunk_passes_for(s, d, k, npix, &chunk_passes)) return rc;
     if (int rc = ensure_paths(s, (size_t)chunk_passes * npix)) return rc;
-    PathState P;
-    P.pass_run = 1u;
-    P.ray_o.base = s->rec.p, P.ray_d.base = s->rec.p + 1, P.thr.base = s->rec.p + 2, P.L = s->L.p, P.hit = s->hit.p;
-    P.rng.base = reinterpret_cast<uint64_t*>(s->rec.p + 3);
-    P.hold.base = reinterpret_cast<uint32_t*>(s->rec.p + 3) + 2;
-    P.rng4.base = reinterpret_cast<uint4*>(s->rec.p + 3);
-    P.sss_sigt.base = s->ssrec.p, P.sss_sigs.base = s->ssrec.p + 1, P.sss_thr.base = s->ssrec.p + 2;
-    P.sss_ez.base = s->ssrec.p + 3, P.sss_A = s->sss_A.p;
-    P.q_in = s->q[0].p, P.q_out = s->q[1].p, P.q_principled = s->q[2].p, P.q_hair = s->q[3].p, P.q_sss = s->q[4].p, P.q_shadow = s->q[5].p, P.q_shadow_in = s->q[6].p;
-    P.sh_d.base = s->srec.p, P.sh_c.base = s->srec.p + 1, P.sh_e = s->sh_e.p;
-    P.counts = s->counts.p, P.stats = want_stats ? s->stats.p : nullptr, P.spill = s->spill.p;
-    P.first = 0u, P.direct = 0u, P.cam_org[0] = P.cam_org[1] = P.cam_org[2] = 0.f;
-    P.heads = nullptr;
-    P.susp_turns = 0u, P.susp_out = nullptr, P.susp_in = nullptr, P.shadow_first = 0u;
-    P.no_medium = s->has_sss ? 0u : 1u;
-    P.wave_log = nullptr, P.wave_log_launch = 0;
-    // debugging aid: PBRHIP_WAVE_LOG=<file> with PBRHIP_RENDER_STATS dumps start / end / turns of every wave of every
-    // k_trace launch (scripts/wave_log.py reads it)
-    DevBuf<unsigned long long> wave_log;
-    const char* wave_log_path = getenv("PBRHIP_WAVE_LOG");
-    uint32_t wave_log_launches = 0;
-    if (wave_log_path) {
+    PathState P = base_path_state(s, want_stats);
+    DevBuf<unsigned long long> wave_log;  // (PBRHIP_WAVE_LOG)
+    if (k.wave_log) {
       HIPCHK(wave_log.reserve((size_t)kWaveLogLaunches * kWaveLogWaves * 4));
       HIPCHK(hipMemsetAsync(wave_log.p, 0, sizeof(unsigned long long) * kWaveLogLaunches * kWaveLogWaves * 4, st));
       P.wave_log = wave_log.p;
     }
     HIPCHK(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long) * kStatNum, st));
-    const Camera cam = make_camera(s, d->width, d->height);
-    // a user camera: k_generate_camera stores each path's first ray and the first bounce is an ordinary one (PathState::first = 0)
-    const bool user_cam = s->cam_set;
-    const UserCamera ucam = user_cam ? make_user_camera(s, d->width, d->height) : UserCamera{};
-    const uint64_t rng_inc = (d->seed_seq << 1u) | 1u;  // pcg32_srandom (rng.h:30-36)
     // the environment's share of NEE events: the light count is known once the scene is committed
     s->dscene.env_p = s->dscene.num_lights ? 0.5f : 1.0f;
     s->dscene.env_area_scale = 1.0f - s->dscene.env_p;
-    const DScene& sc = s->dscene;
-
-    uint32_t tail_paths = d->tail_paths == 0xFFFFFFFFu ? 0u : (d->tail_paths ? d->tail_paths : 262144u);
-    if (const char* e = getenv("PBRHIP_TAIL_PATHS")) tail_paths = (uint32_t)strtoul(e, nullptr, 10);  // 0 = never
-    uint32_t want_groups = d->num_streams;
-    if (const char* e = getenv("PBRHIP_STREAMS")) want_groups = (uint32_t)atoi(e);
-    // at most `window` groups in their bulk phase at a time; a group is in its bulk phase until it has handed its
-    // remaining paths to k_tail (or, with PBRHIP_BULK_DIV = k, until fewer than 1/k of its paths are alive)
-    const uint32_t window = std::max(1u, env_u32("PBRHIP_WINDOW", getenv("PBRHIP_GROUPS") ? 1u : (uint32_t)kMaxGroups));
-    const uint32_t bulk_div = env_u32("PBRHIP_BULK_DIV", 0u);
-    const bool trace_sched = getenv("PBRHIP_TRACE_SCHED") != nullptr;
-    const bool sss_walk = env_u32("PBRHIP_SSS_WALK", 1u) != 0u;  // 0: one wavefront iteration per step of a random walk (A/B)
-    // lanes (stream + counters + 117 MB of traversal spill area each) for the groups this call can have in flight: the first
-    // chunk is the largest, so its plan has the most groups
-    const uint32_t max_lanes = std::min<uint32_t>((uint32_t)kMaxGroups, (uint32_t)plan_groups(std::min(chunk_passes, d->num_sample), npix, want_groups).size());
-    if (int rc = ensure_groups(s, std::max(1u, max_lanes))) return rc;
-    // Resumable rays and the pipelined host loop (round 6; kernels.h::PathState::susp_turns, scene_impl.h::h_ring).
-    // susp_turns: loop turns a k_trace wave keeps draining after the queue ran dry before it suspends its closest-hit rays (0: never);
-    // pipe_depth: iterations of a group enqueued ahead of what the host has heard of (1: the old round trip per iteration).  An
-    // iteration enqueued ahead sizes its launches by the last count the host saw (live paths only ever decrease: an upper bound).
-    const uint32_t susp_turns = env_u32("PBRHIP_SUSP_TURNS", 24u);
-    const bool direct_all = env_u32("PBRHIP_DIRECT", 1u) != 0u;  // scenes of principled surfaces only (no hair, no media): no k_classify on any bounce (C2 frame -3 %)
-    const uint32_t pipe_depth = std::min(std::max(1u, env_u32("PBRHIP_PIPE_DEPTH", 2u)), kRingSlots - 1u);
-    const uint32_t pipe_depth_small = std::min(std::max(1u, env_u32("PBRHIP_PIPE_DEPTH_SMALL", 8u)), kRingSlots - 1u);  // below 256 Ki live paths (renders without k_tail)
-    // close to the hand-over to k_tail (live paths <= pipe_stop x tail_paths) nothing is enqueued ahead: the hand-over is decided on
-    // exact counts (an iteration enqueued ahead would run as a full wavefront iteration on what k_tail finishes faster)
-    const double pipe_stop = getenv("PBRHIP_PIPE_STOP") ? atof(getenv("PBRHIP_PIPE_STOP")) : 2.0;
-    const uint32_t shadow_first = env_u32("PBRHIP_SHADOW_FIRST", 1u);
-    HIPCHK(s->heads.reserve((size_t)kMaxGroups * kTraceHeads * kHeadStride));
-    HIPCHK(s->susp.reserve((size_t)std::max(1u, max_lanes) * 2u * kSuspRecords * kSuspWords));  // (264 MB per group in flight)
-    struct Group {
-      PathState P;
-      uint32_t n0, first_pass, npass, slot0;  // paths at the start, pass range, first path slot
-      uint32_t n = 0, iters = 0;
-      int lane = -1;  // stream / counter / spill slot while active
-      bool started = false, finished = false;
-      uint32_t enq = 0, seen = 0;     // iterations enqueued / heard of (ring stamps)
-      uint32_t stamps[kRingSlots];    // stamp of enqueued iteration i at [i % kRingSlots]
-      bool tail_enqueued = false;
-      Timer tm;
-    };
-
-    bool stop = false;
-    for (; done < d->num_sample && !stop;) {
-      if (cancelled()) break;  // render.cc:217
-      const uint32_t np = std::min(chunk_passes, d->num_sample - done);
-      HIPCHK(hipStreamSynchronize(st));  // clears / the previous chunk's accumulates are done before groups start
-      const std::vector<uint32_t> plan = plan_groups(np, npix, want_groups);
-      const uint32_t ng = (uint32_t)plan.size();
-      std::vector<Group> G(ng);
-      for (uint32_t g = 0, p0 = 0; g < ng; p0 += plan[g], g++) {
-        Group& gr = G[g];
-        gr.P = P, gr.n0 = plan[g] * npix, gr.first_pass = d->first_pass + done + p0, gr.npass = plan[g], gr.slot0 = p0 * npix;
-        const size_t off = gr.slot0;
-        gr.P.q_in += off, gr.P.q_out += off, gr.P.q_principled += off, gr.P.q_hair += off, gr.P.q_sss += off, gr.P.q_shadow += off, gr.P.q_shadow_in += off;
-        for (int k = 0; k < 3; k++) gr.P.cam_org[k] = cam.org[k];
-        gr.P.cam = cam, gr.P.pix_index = s->path_pix.p, gr.P.npix = npix, gr.P.width = d->width, gr.P.first_pass = gr.first_pass;
-        gr.P.slot0 = gr.slot0, gr.P.seed_seq = d->seed_seq;
-        gr.P.pass_run = pass_run_for(gr.npass, sc.num_curves != 0);
-        gr.P.shadow_first = shadow_first, gr.P.susp_turns = 0u;
-        gr.tm = Timer{s, want_timing, nullptr};
-        gr.tm.only = trace_timing_only ? &S.ms_trace_closest : nullptr;
-        gr.tm.idle_acc = &S.ms_host_idle;
-      }
-      bool lane_busy[kMaxGroups] = {};
-      auto lane_stream = [&](int lane) { return lane == 0 ? st : s->group_streams[lane - 1]; };
-      auto ring_slot = [&](int lane, uint32_t i) { return (size_t)(lane * kRingSlots + i % kRingSlots) * 4u; };
-      // every enqueued iteration ends with k_advance, which tells the host (ring) what is left
-      auto advance = [&](Group& gr, hipStream_t gst) {
-        const uint32_t stamp = ++s->ring_stamp ? s->ring_stamp : ++s->ring_stamp;  // (never 0: the rings start zeroed)
-        gr.stamps[gr.enq % kRingSlots] = stamp;
-        launch_advance(gst, gr.P, s->d_ring + ring_slot(gr.lane, gr.enq), stamp);
-        gr.enq++;
-      };
-      // one iteration of group gr, its launches sized for at most n_upper live paths (and as many pending shadow rays)
-      auto enqueue_iteration = [&](Group& gr, uint32_t n_upper, bool to_tail) -> int {
-        hipStream_t gst = lane_stream(gr.lane);
-        const uint32_t n = std::max(n_upper, 1u);
-        gr.P.first = gr.iters++ == 0 && !user_cam ? 1u : 0u;
-        // the launch's suspend records: written by this k_trace, read by the next (alternating halves of the lane's area)
-        uint32_t* const susp_lane = s->susp.p + (size_t)gr.lane * 2u * kSuspRecords * kSuspWords;
-        gr.P.susp_out = susp_lane + (size_t)(gr.iters & 1u) * kSuspRecords * kSuspWords;
-        gr.P.susp_in = susp_lane + (size_t)((gr.iters & 1u) ^ 1u) * kSuspRecords * kSuspWords;
-        gr.P.susp_turns = to_tail ? 0u : susp_turns;  // (k_tail takes every path to its end: the rays in front of it all finish)
-        gr.tm.iteration_begins();
-        HIPCHK(gr.tm.begin(&S.ms_trace_closest));
-        gr.P.wave_log_launch = wave_log_launches++;
-        launch_trace(gst, gr.P, sc, 2 * n, want_stats);  // this bounce's closest rays + last bounce's shadow rays
-        HIPCHK(gr.tm.end());
-        S.n_trace_closest++, S.iterations++;
-        if (to_tail) {
-          // few live paths: after this bounce's trace (and the pending shadow rays) every path is finished in one launch
-          HIPCHK(gr.tm.begin(&S.ms_tail));
-          launch_tail(gst, gr.P, sc, n, rng_inc, want_stats, s->has_sss, s->has_textured);
-          HIPCHK(gr.tm.end());
-          S.n_tail++;
-          gr.tm.iteration_ends();
-          advance(gr, gst);  // nothing was queued: both "in" counts become 0
-          gr.tail_enqueued = true;
-          return PBRHIP_OK;
-        }
-        // a first bounce in a scene without hair needs no routing -- every hit takes the principled shader --: the shading kernel
-        // walks the group's paths itself (PathState::direct)
-        // (media do not matter here: no path is inside one before its first shading)
-        const bool direct = !s->has_hair && ((gr.P.first && env_u32("PBRHIP_FIRST_DIRECT", 1u) != 0u) || (!s->has_sss && direct_all));
-        gr.P.direct = direct ? 1u : 0u;
-        if (!direct) {
-          HIPCHK(gr.tm.begin(&S.ms_surface));
-          launch_classify(gst, gr.P, sc, n);
-          HIPCHK(gr.tm.end());
-          S.n_surface++;
-        }
-        HIPCHK(gr.tm.begin(&S.ms_shade_principled));
-        launch_shade_principled(gst, gr.P, sc, n, rng_inc, s->has_sss, s->has_textured);
-        HIPCHK(gr.tm.end());
-        if (s->has_hair) {
-          HIPCHK(gr.tm.begin(&S.ms_shade_hair));
-          launch_shade_hair(gst, gr.P, sc, n, rng_inc);
-          HIPCHK(gr.tm.end());
-          S.n_shade_hair++;
-        }
-        if (s->has_sss) {
-          HIPCHK(gr.tm.begin(&S.ms_sss_step));
-          if (sss_walk) launch_sss_walk(gst, gr.P, sc, n, rng_inc, want_stats);  // every walk forward to its last event ...
-          launch_sss_step(gst, gr.P, sc, n, rng_inc);                            // ... which the step kernel handles
-          HIPCHK(gr.tm.end());
-          S.n_sss_step++;
-        }
-        HIPCHK(gr.tm.begin(&S.ms_compact));
-        launch_compact(gst, gr.P, n);
-        HIPCHK(gr.tm.end());
-        S.n_shade_principled++;
-        gr.tm.iteration_ends();
-        advance(gr, gst);
-        std::swap(gr.P.q_in, gr.P.q_out);
-        std::swap(gr.P.q_shadow, gr.P.q_shadow_in);
-        return PBRHIP_OK;
-      };
-      // keeps group gr's stream fed: iterations are enqueued ahead of the counts the host has seen (gr.n = the last count heard:
-      // an upper bound for every later iteration)
-      auto feed = [&](Group& gr) -> int {
-        if (gr.tail_enqueued) return PBRHIP_OK;
-        const uint32_t depth = gr.n < (1u << 18) ? pipe_depth_small : pipe_depth;
-        while (gr.enq - gr.seen < depth) {
-          const bool exact = gr.enq == gr.seen;  // the host knows this iteration's input counts
-          if (gr.n <= tail_paths) {
-            if (int rc = enqueue_iteration(gr, gr.n, true)) return rc;
-            break;
-          }
-          if (!exact && tail_paths && (double)gr.n <= pipe_stop * (double)tail_paths) break;
-          if (int rc = enqueue_iteration(gr, gr.n, false)) return rc;
-        }
-        return PBRHIP_OK;
-      };
-      auto start = [&](Group& gr, int lane) -> int {
-        gr.lane = lane, gr.started = true, gr.n = gr.n0, lane_busy[lane] = true;
-        hipStream_t gst = lane_stream(lane);
-        gr.tm.stream = gst;
-        gr.P.counts = s->counts.p + lane * kCntNum;
-        gr.P.spill = s->spill.p + (size_t)lane * kSpillWords;
-        gr.P.heads = s->heads.p + (size_t)lane * kTraceHeads * kHeadStride;
-        HIPCHK(hipMemsetAsync(gr.P.heads, 0, sizeof(uint32_t) * kTraceHeads * kHeadStride, gst));
-        uint32_t* hc = s->h_counts + lane * kCntNum;
-        memset(hc, 0, sizeof(uint32_t) * kCntNum);
-        hc[kCntIn] = gr.n0;
-        HIPCHK(hipMemcpyAsync(gr.P.counts, hc, sizeof(uint32_t) * kCntNum, hipMemcpyHostToDevice, gst));
-        HIPCHK(gr.tm.begin(&S.ms_generate));
-        if (user_cam) launch_generate_camera(gst, gr.P, ucam, d->height, gr.n0);
-        else launch_generate(gst, gr.P, gr.n0);
-        HIPCHK(gr.tm.end());
-        return feed(gr);
-      };
-      // Scheduler: poll the active groups' rings; a group whose oldest enqueued iteration has reported gets more work enqueued
-      // behind what is still running; a finished group frees its lane; passes are accumulated (ascending, on the main stream) as
-      // soon as every earlier group of the chunk is complete, and *finish_pass follows.  *cancel is read on every turn.
-      uint32_t next_start = 0, acc_prefix = 0, active = 0, acc_passes = 0, idle_polls = 0;
-      for (;;) {
-        if (!stop && cancelled()) stop = true;
-        // start groups while the window allows
-        while (!stop && next_start < ng) {
-          uint32_t bulk = 0;
-          for (const Group& gr : G)
-            if (gr.started && !gr.finished && gr.n > std::max<uint64_t>(tail_paths, bulk_div ? gr.n0 / bulk_div : 0u)) bulk++;
-          int lane = -1;
-          for (int l = 0; l < (int)std::max(1u, max_lanes); l++)
-            if (!lane_busy[l]) {
-              lane = l;
-              break;
-            }
-          if (bulk >= window || lane < 0) break;
-          if (int rc = start(G[next_start], lane)) return rc;
-          next_start++, active++;
-        }
-        if (active == 0) break;
-        bool progressed = false;
-        for (Group& gr : G) {
-          if (!gr.started || gr.finished) continue;
-          // the oldest iteration the host has not heard of: has its k_advance written the stamp?
-          while (gr.seen < gr.enq) {
-            const volatile uint32_t* slot = s->h_ring + ring_slot(gr.lane, gr.seen);
-            if (__atomic_load_n(&slot[3], __ATOMIC_ACQUIRE) != gr.stamps[gr.seen % kRingSlots]) break;
-            progressed = true;
-            if (slot[2]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-            gr.n = std::max(slot[0], slot[1]);  // pending shadow rays need one more trace
-            gr.seen++;
-            if (trace_sched)
-              fprintf(stderr, "sched %8.3f ms  group %d (passes %u)  iter %u of %u enqueued  live %u\n",
-                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(),
-                      (int)(&gr - G.data()), gr.npass, gr.seen, gr.enq, gr.n);
-          }
-          if (gr.seen == gr.enq && (gr.n == 0 || stop)) {  // complete -- or abandoned: a cancelled render drops what is in flight
-            HIPCHK(hipStreamSynchronize(lane_stream(gr.lane)));  // (its last k_advance has written the stamp: the stream is about to be idle)
-            HIPCHK(gr.tm.collect());
-            gr.finished = gr.n == 0;
-            if (!gr.finished) gr.started = false;
-            lane_busy[gr.lane] = false, active--;
-            progressed = true;
-            continue;
-          }
-          if (gr.n != 0 && !stop)
-            if (int rc = feed(gr)) return rc;
-        }
-        // accumulate the complete prefix of the chunk's groups
-        while (acc_prefix < ng && G[acc_prefix].finished) {
-          const Group& gr = G[acc_prefix];
-          PathState PA = P;
-          PA.L = P.L + gr.slot0, PA.pass_run = gr.P.pass_run;
-          Timer tm{s, want_timing, st};
-          tm.only = trace_timing_only ? &S.ms_trace_closest : nullptr;
-          HIPCHK(tm.begin(&S.ms_accumulate));
-          launch_accumulate(st, PA, s->path_pix.p, npix, gr.npass, d_rgba, d_count);
-          HIPCHK(tm.end());
-          HIPCHK(hipGetLastError());
-          if (want_timing && !trace_timing_only) {  // (trace-only timing has nothing to collect here and must not stall the host)
-            HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(tm.collect());
-          }
-          acc_passes += gr.npass, acc_prefix++;
-          S.samples += (uint64_t)gr.npass * npix;
-          publish((size_t)done + acc_passes);  // render.cc:224-231
-        }
-        if (!progressed) {
-          std::this_thread::yield();
-          // (now and then: a stream that failed, or went idle without its last stamp, must not leave this loop spinning)
-          if ((++idle_polls & 1023u) == 0u)
-            for (Group& gr : G) {
-              if (!gr.started || gr.finished || gr.seen == gr.enq) continue;
-              const hipError_t q = hipStreamQuery(lane_stream(gr.lane));
-              if (q == hipErrorNotReady) continue;
-              HIPCHK(q);
-              const volatile uint32_t* slot = s->h_ring + ring_slot(gr.lane, gr.enq - 1u);
-              if (__atomic_load_n(&slot[3], __ATOMIC_ACQUIRE) != gr.stamps[(gr.enq - 1u) % kRingSlots])
-                return fail(PBRHIP_EHIP, "render: a path group's stream went idle without reporting its last iteration");
-            }
-        } else {
-          idle_polls = 0;
-        }
-      }
-      HIPCHK(hipStreamSynchronize(st));
-      done += acc_passes;
+    ChunkRun run{s, d, k, P, S, cancel, finish_pass, d_rgba, d_count, t_begin};
+    if (int rc = run.reserve_lanes(chunk_passes)) return rc;
+    while (done < d->num_sample && !run.stop && !run.cancelled()) {  // render.cc:217
+      uint32_t passes = 0;
+      if (int rc = run.run(done, std::min(chunk_passes, d->num_sample - done), &passes)) return rc;
+      done += passes;
       S.chunks++;
     }
     HIPCHK(hipStreamSynchronize(st));
-    if (wave_log_path) {
-      std::vector<unsigned long long> h((size_t)kWaveLogLaunches * kWaveLogWaves * 4);
-      HIPCHK(hipMemcpy(h.data(), wave_log.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(wave_log_path, "wb")) {
-        fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-        fclose(f);
-      }
-    }
-    if (want_stats) {
-      unsigned long long hs[kStatNum];
-      HIPCHK(hipMemcpy(hs, s->stats.p, sizeof(hs), hipMemcpyDeviceToHost));
-      S.closest_rays = hs[kStatClosestRays] - hs[kStatSuspended] - hs[kStatHeld], S.closest_nodes = hs[kStatClosestNodes];  // (a suspended ray is counted by the launch that suspends it and by the one that resumes it)
-      S.suspended_rays = hs[kStatSuspended] + hs[kStatSuspendedShadow];
-      S.closest_tris = hs[kStatClosestTris], S.closest_curves = hs[kStatClosestCurves];
-      S.shadow_rays = hs[kStatShadowRays] - hs[kStatSuspendedShadow], S.shadow_nodes = hs[kStatShadowNodes];
-      S.tail_closest_rays = hs[kStatTailClosestRays], S.tail_shadow_rays = hs[kStatTailShadowRays];
-      S.pruned_rays = hs[kStatPrunedRays];
-      S.shadow_tris = hs[kStatShadowTris], S.shadow_curves = hs[kStatShadowCurves];
-      if (getenv("PBRHIP_PV_STATS"))
-        fprintf(stderr, "pv closest: it node %llu tri %llu curve %llu refill %llu | lanes/iter node %.1f tri %.1f curve %.1f\n",
-                hs[kStatPvItNode], hs[kStatPvItTri], hs[kStatPvItCurve], hs[kStatPvItRefill],
-                hs[kStatPvLnNode] / (double)std::max<unsigned long long>(1, hs[kStatPvItNode]),
-                hs[kStatPvLnTri] / (double)std::max<unsigned long long>(1, hs[kStatPvItTri]),
-                hs[kStatPvLnCurve] / (double)std::max<unsigned long long>(1, hs[kStatPvItCurve]));
-      if (getenv("PBRHIP_PV_STATS"))
-        fprintf(stderr, "pv cycles per wave turn (shader clock, lane 0 of every wave, from one turn's start to the next's): node %.0f  triangle %.0f  curve %.0f  refill %.0f | share of the waves' time: %.3f %.3f %.3f %.3f\n",
-                hs[kStatCycNode] / (double)std::max<unsigned long long>(1, hs[kStatPvItNode]), hs[kStatCycTri] / (double)std::max<unsigned long long>(1, hs[kStatPvItTri]),
-                hs[kStatCycCurve] / (double)std::max<unsigned long long>(1, hs[kStatPvItCurve]), hs[kStatCycRefill] / (double)std::max<unsigned long long>(1, hs[kStatPvItRefill]),
-                hs[kStatCycNode] / (double)std::max<unsigned long long>(1, hs[kStatCycNode] + hs[kStatCycTri] + hs[kStatCycCurve] + hs[kStatCycRefill]),
-                hs[kStatCycTri] / (double)std::max<unsigned long long>(1, hs[kStatCycNode] + hs[kStatCycTri] + hs[kStatCycCurve] + hs[kStatCycRefill]),
-                hs[kStatCycCurve] / (double)std::max<unsigned long long>(1, hs[kStatCycNode] + hs[kStatCycTri] + hs[kStatCycCurve] + hs[kStatCycRefill]),
-                hs[kStatCycRefill] / (double)std::max<unsigned long long>(1, hs[kStatCycNode] + hs[kStatCycTri] + hs[kStatCycCurve] + hs[kStatCycRefill]));
-      if (getenv("PBRHIP_PV_STATS")) {
-        fprintf(stderr, "pv steps per closest-hit ray (<=16, 32, 64, 128, 256, 512, 1024, more):");
-        for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", hs[kStatStepHist0 + i]);
-        fprintf(stderr, " | max %llu | most loop turns of one wave (whole render) %llu\n", hs[kStatMaxSteps], hs[kStatMaxWaveIters]);
-        fprintf(stderr, "pv steps per shadow ray:");
-        for (int i = 0; i < 8; i++) fprintf(stderr, " %llu", hs[kStatAnyHist0 + i]);
-        fprintf(stderr, " | max %llu\n", hs[kStatAnyMaxSteps]);
-        fprintf(stderr, "walk: nodes %llu prims %llu | wave turns: traversal %llu, step / refill %llu | cycles per traversal turn %.0f, per step / refill turn %.0f (share %.3f)\n", hs[kStatWalkNodes], hs[kStatWalkTris],
-                hs[kStatWalkTurns], hs[kStatWalkSteps], hs[kStatWalkCycTrav] / (double)std::max<unsigned long long>(1, hs[kStatWalkTurns]),
-                hs[kStatWalkCycStep] / (double)std::max<unsigned long long>(1, hs[kStatWalkSteps]),
-                hs[kStatWalkCycStep] / (double)std::max<unsigned long long>(1, hs[kStatWalkCycStep] + hs[kStatWalkCycTrav]));
-      }
-    }
+    if (k.wave_log)
+      if (int rc = write_wave_log(wave_log, k.wave_log)) return rc;
+    if (want_stats)
+      if (int rc = read_render_stats(s, k, &S)) return rc;
   } else {
     HIPCHK(hipStreamSynchronize(st));
     done = d->num_sample;
-    publish(done);
+    if (finish_pass) __atomic_store_n(finish_pass, (size_t)done, __ATOMIC_RELEASE);
   }
   S.passes_done = done;
-  S.node_bytes = trace_uses_wide(s->dscene) ? sizeof(QNode) : sizeof(BvhNode);
-  S.curve_bytes = trace_uses_wide(s->dscene) ? 32 : 64;
+  S.node_bytes = trace_uses_wide(s->dscene, k) ? sizeof(QNode) : sizeof(BvhNode);
+  S.curve_bytes = trace_uses_wide(s->dscene, k) ? 32 : 64;
   S.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   if (stats) *stats = S;
   return PBRHIP_OK;
@@ -1726,49 +1810,35 @@ extern "C" int pbrhip_camera_rays(pbrhip_scene* s, uint32_t width, uint32_t heig
   return PBRHIP_OK;
   });
 }
-extern "C" int pbrhip_trace_closest(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits) {
-  return guarded([&]() -> int {
-  if (!s || (!rays && n) || (!hits && n)) return fail(PBRHIP_EINVAL, "trace_closest: NULL argument");
+// the body of pbrhip_trace_closest (any = false: `out` receives n pbrhip_hit) and pbrhip_trace_any (any: n occlusion bytes)
+static int trace_hook(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, void* out, bool any) {
+  const char* name = any ? "trace_any" : "trace_closest";
+  if (!s || (!rays && n) || (!out && n)) return fail(PBRHIP_EINVAL, "%s: NULL argument", name);
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
   if (n == 0) return PBRHIP_OK;
   if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
+  const Knobs k = read_knobs();
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(s->hook_rays.reserve(2 * n));
-  HIPCHK(s->hook_hits.reserve(n));
+  if (any) HIPCHK(s->hook_occ.reserve(n));
+  else HIPCHK(s->hook_hits.reserve(n));
   HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
   HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
   HIPCHK(hipMemcpyAsync(s->hook_rays.p, rays, n * sizeof(pbrhip_ray), hipMemcpyHostToDevice, s->stream));
   HIPCHK(s->spill.reserve(kSpillWords));
-  launch_hook_closest(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_hits.p, s->counts.p, s->spill.p,
-                      getenv("PBRHIP_SIMPLE_TRAVERSAL") != nullptr);
+  if (any) launch_hook_any(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_occ.p, s->counts.p, s->spill.p, k);
+  else launch_hook_closest(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_hits.p, s->counts.p, s->spill.p, k);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(hits, s->hook_hits.p, n * sizeof(pbrhip_hit), hipMemcpyDeviceToHost, s->stream));
+  if (any) HIPCHK(hipMemcpyAsync(out, s->hook_occ.p, n, hipMemcpyDeviceToHost, s->stream));
+  else HIPCHK(hipMemcpyAsync(out, s->hook_hits.p, n * sizeof(pbrhip_hit), hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
   return PBRHIP_OK;
-  });
+}
+extern "C" int pbrhip_trace_closest(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits) {
+  return guarded([&]() -> int { return trace_hook(s, rays, n, hits, false); });
 }
 extern "C" int pbrhip_trace_any(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, uint8_t* occluded) {
-  return guarded([&]() -> int {
-  if (!s || (!rays && n) || (!occluded && n)) return fail(PBRHIP_EINVAL, "trace_any: NULL argument");
-  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-  if (n == 0) return PBRHIP_OK;
-  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(s->hook_rays.reserve(2 * n));
-  HIPCHK(s->hook_occ.reserve(n));
-  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
-  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
-  HIPCHK(hipMemcpyAsync(s->hook_rays.p, rays, n * sizeof(pbrhip_ray), hipMemcpyHostToDevice, s->stream));
-  HIPCHK(s->spill.reserve(kSpillWords));
-  launch_hook_any(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_occ.p, s->counts.p, s->spill.p,
-                  getenv("PBRHIP_SIMPLE_TRAVERSAL") != nullptr);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(occluded, s->hook_occ.p, n, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-  return PBRHIP_OK;
-  });
+  return guarded([&]() -> int { return trace_hook(s, rays, n, occluded, true); });
 }

@@ -128,7 +128,7 @@ struct pbrhip_scene {
   // Round 6: what the host learns about an iteration it enqueued -- written by the iteration's last kernel (k_advance) straight into
   // pinned host memory: kRingSlots slots of 4 words per group lane: live paths, pending shadow rays, overflow flag, stamp (a number
   // that is unique per scene and launch, written last).  The host polls the stamp: no copy, no stream query, and the NEXT iteration
-  // is already enqueued behind this one (pbrhip.cpp::render_impl).
+  // is already enqueued behind this one (pbrhip.cpp::ChunkRun).
   uint32_t* h_ring = nullptr;              // pinned, kMaxGroups x kRingSlots x 4
   uint32_t* d_ring = nullptr;              // the same memory as the device addresses it
   uint32_t ring_stamp = 0;                 // last stamp handed out
@@ -153,7 +153,7 @@ struct pbrhip_scene {
 namespace pb {
 // pixel indices (y * w + x) of the blocks of rank `rank` in CreateTiles order (render-tile.cc:29-41 for block = 64)
 void shard_pixels(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block, std::vector<uint32_t>* out);
-int ensure_pixels(pbrhip_scene* s, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block);
+int ensure_pixels(pbrhip_scene* s, const Knobs& k, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block);
 // pbrhip_scene_set_environment's body (rgb null: no environment); also what pbrhip_scene_replicate calls to carry it over
 int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale, const float* world_to_env);
 // pbrhip_scene_set_camera's body (eye null: the reference's camera); also what pbrhip_scene_replicate calls to carry it over

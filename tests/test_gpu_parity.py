@@ -420,20 +420,17 @@ def test_group_schedules_are_exact(pa, pairs, name, monkeypatch):
     desc, sg, so = pairs[name]
     ref = pa.RenderLayer()
     pa.Render(sg, 96, 80, 11, layer=ref, num_streams=1)
-    for plan, window, minp in (("6,3,1,1", "2", None), ("1,1,1,1,1,1,1,1,1,1,1", "3", None), ("5,6", "1", None),
-                               ("8", "2", None), (None, "2", "4096"), (None, "1", "1")):
+    for plan, window in (("6,3,1,1", "2"), ("1,1,1,1,1,1,1,1,1,1,1", "3"), ("5,6", "1"), ("8", "2"), (None, "2"), (None, "1")):
         if plan is None:
             monkeypatch.delenv("PBRHIP_GROUPS", raising=False)
         else:
             monkeypatch.setenv("PBRHIP_GROUPS", plan)
         monkeypatch.setenv("PBRHIP_WINDOW", window)
-        if minp is not None:
-            monkeypatch.setenv("PBRHIP_GROUP_MIN_PATHS", minp)
         for tail in (0, 0xFFFFFFFF, 500):
             lay = pa.RenderLayer()
             fin = C.c_size_t(0)
             pa.Render(sg, 96, 80, 11, layer=lay, tail_paths=tail, finish_pass=fin)
-            assert fin.value == 11 and lay.rgba.tobytes() == ref.rgba.tobytes(), (plan, window, minp, tail)
+            assert fin.value == 11 and lay.rgba.tobytes() == ref.rgba.tobytes(), (plan, window, tail)
 
 
 @pytest.mark.parametrize("name", ["sss", "hair"])
