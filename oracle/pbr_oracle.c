@@ -131,6 +131,11 @@ struct orc_scene {
   uint32_t nnodes, bvh_depth;
   float bmin[3], bmax[3];
   int committed;
+  /* the lat-long environment light; env_texels == NULL: none */
+  float* env_texels; /* 4 per texel: rgb x scale, pdf_env (per steradian) */
+  uint32_t *env_keep, *env_alias;
+  uint32_t env_w, env_h;
+  float env_m[9]; /* world_to_env, row-major */
 };
 
 static void* xrealloc(void* p, size_t n) {
@@ -179,7 +184,41 @@ void orc_scene_destroy(orc_scene* s) {
   free(s->textures);
   free(s->meshes), free(s->locals), free(s->instances), free(s->materials), free(s->light_params);
   free(s->lights), free(s->light_cdf), free(s->prims), free(s->prim_geo), free(s->order), free(s->nodes);
+  free(s->env_texels), free(s->env_keep), free(s->env_alias);
   free(s);
+}
+
+/* env_tables.cpp's build_env_tables, through orc_env.cc */
+int orc_env_tables(const float* rgb, uint32_t w, uint32_t h, float scale, float** texels, uint32_t** keep, uint32_t** alias);
+
+/* pbrhip.cpp::set_environment's checks, in the same order */
+int orc_scene_set_environment(orc_scene* s, const float* rgb, uint32_t w, uint32_t h, float scale, const float world_to_env[9]) {
+  float m[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  float* texels = NULL;
+  uint32_t *keep = NULL, *alias = NULL;
+  int present = 0;
+  if (rgb) {
+    if (w == 0 || h == 0) return -1;
+    if (world_to_env) {
+      for (int i = 0; i < 9; i++) {
+        if (!isfinite(world_to_env[i])) return -1;
+        m[i] = world_to_env[i];
+      }
+      for (int i = 0; i < 3; i++) /* a rotation: M M^T = I */
+        for (int j = 0; j < 3; j++) {
+          const double d = (double)m[3 * i] * m[3 * j] + (double)m[3 * i + 1] * m[3 * j + 1] + (double)m[3 * i + 2] * m[3 * j + 2];
+          if (fabs(d - (i == j ? 1.0 : 0.0)) > 1e-4) return -1;
+        }
+    }
+    present = orc_env_tables(rgb, w, h, scale, &texels, &keep, &alias);
+    if (present < 0) return -1;
+  }
+  free(s->env_texels), free(s->env_keep), free(s->env_alias);
+  s->env_texels = NULL, s->env_keep = s->env_alias = NULL, s->env_w = s->env_h = 0;
+  if (!present) return 0; /* no map, or an all-black one: no environment */
+  s->env_texels = texels, s->env_keep = keep, s->env_alias = alias, s->env_w = w, s->env_h = h;
+  memcpy(s->env_m, m, sizeof(m));
+  return 0;
 }
 
 int orc_add_triangle_mesh(orc_scene* s, const float* vertices_xyzw, uint32_t num_vertices,
@@ -1375,11 +1414,104 @@ static int shadow_ray(orc_ctx* c, f3 pos, f3 dir, float dist) {
   return trace_any_hit(c, &r);
 }
 
-/* shader-utils.h:166-212 */
+/* ---------------------------------------------------- the lat-long environment light (pbrlab_amd/csrc/denv.h)
+ * This project's own light, not the reference's: the device's operations in the device's order, cos / sin through orc_cosf / orc_sinf
+ * (the device's f_cos / f_sin in ORC_MATH_GLIBCF), so that a frame is the GPU's bit for bit. */
+/* denv.h::env_atan2: Cephes' atanf on the octant, in plain float operations */
+static float env_atan2(float y, float x) {
+  const float ax = fabsf(x), ay = fabsf(y);
+  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+  float a = mx > 0.0f ? mn / mx : 0.0f, base = 0.0f;
+  if (a > 0.4142135623730950f) a = (a - 1.0f) / (a + 1.0f), base = 0.7853981633974483f;
+  const float z = a * a;
+  float p = fmaf(8.05374449538e-2f, z, -1.38776856032e-1f);
+  p = fmaf(p, z, 1.99777106478e-1f);
+  p = fmaf(p, z, -3.33329491539e-1f);
+  float r = base + fmaf(p * z, a, a);
+  if (ay > ax) r = 1.5707963267948966f - r;
+  if (x < 0.0f) r = ORC_PI - r;
+  return y < 0.0f ? -r : r;
+}
+/* denv.h::env_texel_index: theta = acos(y), phi = atan2(x, -z) + pi; row 0 is the top */
+static uint32_t env_texel_index(f3 d, uint32_t w, uint32_t h) {
+  const float y = fminf(fmaxf(d.y, -1.0f), 1.0f);
+  const float theta = env_atan2(sqrtf((1.0f - y) * (1.0f + y)), y);
+  const float phi = env_atan2(d.x, -d.z) + ORC_PI;
+  const float fc = fminf(fmaxf(floorf(phi / (2.0f * ORC_PI) * (float)w), 0.0f), (float)(w - 1u));
+  const float fr = fminf(fmaxf(floorf(theta / ORC_PI * (float)h), 0.0f), (float)(h - 1u));
+  return (uint32_t)fr * w + (uint32_t)fc;
+}
+/* denv.h::env_texel_dir: uniform in phi and cos(theta) over texel (col, row) */
+static f3 env_texel_dir(uint32_t col, uint32_t row, uint32_t w, uint32_t h, float u, float v) {
+  const float phi = 2.0f * ORC_PI * (((float)col + u) / (float)w) - ORC_PI;
+  const float c0 = orc_cosf(ORC_PI * ((float)row / (float)h)), c1 = orc_cosf(ORC_PI * ((float)(row + 1u) / (float)h));
+  const float ct = c0 + v * (c1 - c0);
+  const float st = sqrtf(fmaxf(0.0f, 1.0f - ct * ct));
+  return f3_make(st * orc_sinf(phi), ct, -(st * orc_cosf(phi)));
+}
+static f3 env_from_world(const float* m, f3 a) {
+  return f3_make(m[0] * a.x + m[1] * a.y + m[2] * a.z, m[3] * a.x + m[4] * a.y + m[5] * a.z, m[6] * a.x + m[7] * a.y + m[8] * a.z);
+}
+static f3 env_to_world(const float* m, f3 d) { /* the transpose: m is a rotation */
+  return f3_make(m[0] * d.x + m[3] * d.y + m[6] * d.z, m[1] * d.x + m[4] * d.y + m[7] * d.z, m[2] * d.x + m[5] * d.y + m[8] * d.z);
+}
+/* the share of NEE events that sample the environment: 1 without area lights, 1/2 with */
+static float env_p(const orc_scene* s) { return s->nlights ? 0.5f : 1.0f; }
+/* L(w) x scale and pdf_env(w) of a world direction (a miss) */
+static f3 env_radiance(const orc_scene* s, f3 w, float* pdf) {
+  const float* L = s->env_texels + 4 * (size_t)env_texel_index(env_from_world(s->env_m, w), s->env_w, s->env_h);
+  *pdf = L[3];
+  return f3_make(L[0], L[1], L[2]);
+}
+/* dshade.h::env_nee's sample: the texel from 64 raw bits (the high word of bits x W H), the alias coin from 32 more, then a
+ * direction uniform over the texel's solid angle (two draws) */
+static f3 env_sample(const orc_scene* s, orc_rng* rng, f3* L, float* pdf) {
+  const uint32_t hi = orc_pcg32_next(rng);
+  const uint32_t lo = orc_pcg32_next(rng);
+  const uint32_t i = (uint32_t)(((unsigned __int128)((((uint64_t)hi) << 32) | lo) * (uint64_t)((uint64_t)s->env_w * s->env_h)) >> 64);
+  const uint32_t coin = orc_pcg32_next(rng);
+  rng->draws += 3;
+  const float u = orc_rng_draw(rng);
+  const float v = orc_rng_draw(rng);
+  const uint32_t t = coin < s->env_keep[i] ? i : s->env_alias[i];
+  const float* T = s->env_texels + 4 * (size_t)t;
+  const uint32_t row = t / s->env_w, col = t - row * s->env_w;
+  *L = f3_make(T[0], T[1], T[2]);
+  *pdf = T[3];
+  return env_to_world(s->env_m, env_texel_dir(col, row, s->env_w, s->env_h, u, v));
+}
+
+/* shader-utils.h:166-212.  With an environment one draw first picks it (probability p_env) or the area lights, whose
+ * pdf then carries 1 - p_env; the environment's estimate is f L |cos| / (p_env pdf_env) times power_heuristic(p_env pdf_env, bsdf_pdf),
+ * with the call site's normal and hemisphere rule and a shadow ray over [kEps, kInf]. */
 static f3 direct_illumination(orc_ctx* c, f3 omega_out, const orc_surface* si, const orc_mat3* Rgl, f3 global_normal,
                               orc_rng* rng, const orc_eval* ev, int hemisphere) {
-  orc_light_sample ls = sample_all_light(c->scene, rng);
+  const orc_scene* s = c->scene;
   f3 contribute = f3_set1(0.f);
+  float area_scale = 1.0f;
+  if (s->env_texels) {
+    const float p_env = env_p(s);
+    const float u_sel = orc_rng_draw(rng);
+    if (u_sel < p_env) {
+      f3 L;
+      float pdf_env;
+      const f3 dir = env_sample(s, rng, &L, &pdf_env);
+      const float cs = f3_dot(dir, global_normal);
+      const f3 emission = f3_mul(L, f3_set1(fabsf(cs)));
+      const float pdf_sigma = p_env * pdf_env;
+      if (((!hemisphere) || cs > 0.0f) && !shadow_ray(c, si->global_position, dir, ORC_INF)) {
+        f3 omega_l = mult_v(dir, Rgl);
+        f3 bsdf_f = f3_set1(0.0f);
+        float ret_pdf = 0.f;
+        eval_dispatch(ev, omega_l, omega_out, &bsdf_f, &ret_pdf);
+        float weight = orc_power_heuristic(pdf_sigma, ret_pdf);
+        contribute = f3_divs(f3_scale(f3_mul(bsdf_f, emission), weight), pdf_sigma);
+      }
+      return contribute;
+    }
+    area_scale = 1.0f - p_env;
+  }
+  orc_light_sample ls = sample_all_light(s, rng);
   if (ls.valid) {
     f3 pos = si->global_position;
     f3 dir_to_light = f3_normalize(f3_sub(ls.position, si->global_position));
@@ -1387,6 +1519,7 @@ static f3 direct_illumination(orc_ctx* c, f3 omega_out, const orc_surface* si, c
     float wl_dot_nl = -f3_dot(dir_to_light, ls.normal);
     float wl_dot_np = f3_dot(dir_to_light, global_normal);
     float pdf_sigma = fabsf(ls.pdf * dist * dist / (wl_dot_nl * wl_dot_np));
+    if (s->env_texels) pdf_sigma = pdf_sigma * area_scale;
     if (((!hemisphere) || (wl_dot_nl > 0.0f && wl_dot_np > 0.0f)) && !shadow_ray(c, pos, dir_to_light, dist)) {
       f3 omega_l = mult_v(dir_to_light, Rgl);
       f3 bsdf_f = f3_set1(0.0f);
@@ -1818,12 +1951,23 @@ static f3 get_radiance(orc_ctx* c, const orc_rayf* input_ray, orc_rng* rng) {
   for (uint32_t depth = 0;; depth++) {
     if (orc_is_black(throughput)) break;
     orc_hit tr = trace_first_hit(c, &ray);
-    if (tr.instance_id == ORC_NONE) break;
+    if (tr.instance_id == ORC_NONE) {
+      /* a miss adds thr L(w) w and the path ends where render.cc:34 breaks (before the roulette, no draw);
+       * w = 1 for a camera ray, else power_heuristic(bsdf_pdf, p_env pdf_env(w)) */
+      if (c->scene->env_texels) {
+        float pdf_env;
+        const f3 Le = env_radiance(c->scene, ray.dir, &pdf_env);
+        const float weight = (depth == 0) ? 1.0f : orc_power_heuristic(bsdf_sampling_pdf, env_p(c->scene) * pdf_env);
+        contribution = f3_add(contribution, f3_mul(f3_scale(Le, weight), throughput));
+      }
+      break;
+    }
     orc_surface si = trace_result_to_surface(c->scene, &ray, &tr);
     if (si.face_direction == ORC_FRONT) {
       f3 emission = f3_set1(0.f);
       float pdf_area = 0.f;
       if (implicit_area_light(c->scene, tr.instance_id, tr.geom_id, tr.prim_id, &emission, &pdf_area)) {
+        if (c->scene->env_texels) pdf_area = pdf_area * (1.0f - env_p(c->scene)); /* §10: NEE picks the area lights with 1 - p_env */
         float a2s = fabsf((tr.t * tr.t) / f3_dot(si.normal_s, ray.dir));
         float weight = (depth == 0) ? 1.0f : orc_power_heuristic(bsdf_sampling_pdf, pdf_area * a2s);
         contribution = f3_add(contribution, f3_mul(f3_scale(emission, weight), throughput));

@@ -92,6 +92,11 @@ int orc_create_instance(orc_scene*, uint32_t local_scene_id, const float transfo
 int orc_attach_light_ids(orc_scene*, uint32_t instance_id, uint32_t geom_id, const uint32_t* ids, uint32_t n);
 int orc_attach_material_ids(orc_scene*, uint32_t instance_id, uint32_t geom_id, const uint32_t* ids, uint32_t n);
 int orc_commit(orc_scene*);
+/* pbrhip_scene_set_environment (this project's own light: the reference leaves a miss black): a lat-long map of
+ * w x h RGB texels (row 0 = the top) times `scale`, world_to_env a row-major rotation (NULL = identity).  rgb == NULL or an all-black
+ * map removes it: the scene then renders exactly as without.  Valid before or after orc_commit.  Returns 0, or -1 (the environment
+ * is left as it was) for a zero size, a texel or scale that is negative / NaN / infinite, or a matrix that is not a rotation. */
+int orc_scene_set_environment(orc_scene*, const float* rgb, uint32_t w, uint32_t h, float scale, const float world_to_env[9]);
 void orc_scene_aabb(const orc_scene*, float bmin[3], float bmax[3]);
 uint32_t orc_bvh_depth(const orc_scene*);
 

@@ -1,7 +1,9 @@
-"""Float64 expectations for the environment light on a Lambert floor with nothing above it.
+"""Float64 expectations for the environment light.
 
-The floor (z = 0, normal +z) sees the whole upper hemisphere of the map, so the reflected radiance is the same at every
-floor point: E = (rho / pi) * integral of L(w) cos(w, n) over the hemisphere."""
+A Lambert floor with nothing above it (z = 0, normal +z) sees the whole upper hemisphere of the map, so the reflected radiance
+is the same at every floor point: E = (rho / pi) * integral of L(w) cos(w, n) over the hemisphere.  A white Lambert box open
+to a constant sky is a furnace: every pixel converges to L, however often its paths bounce.  A metallic GGX floor under a
+constant sky keeps the reference's skewed GGX pdf (Q15) on the BSDF side: GGXSkyExpectation."""
 import numpy as np
 
 import _analytic as A
@@ -107,3 +109,94 @@ class SkyExpectation:
         F = sum(polygon_form_factor(x, (0.0, 0.0, 1.0), b) for b in self.blockers)
         e = RHO[None] * self.L[None] * (1.0 - F)[:, None]
         return e if self.area is None else e + self.area(x, wo)
+
+
+WHITE = dict(base_color=(1.0, 1.0, 1.0), specular=0.0)
+
+
+def deep_box_scene(depth=3.0):
+    """a white Lambert box (albedo 1), 1 wide and `depth` deep, open towards +z (the reference camera looks into it); every face
+    faces inwards.  The image is wider than the box: the columns beyond its rim see only the sky."""
+    d = 0.5 * depth
+    parts = [A.quad((0, 0, -depth), (0.5, 0, 0), (0, 0.5, 0)),                  # floor, +z
+             A.quad((-0.5, 0, -d), (0, 0.5, 0), (0, 0, d)),                      # x = -1/2, +x
+             A.quad((0.5, 0, -d), (0, 0, d), (0, 0.5, 0)),                       # x = +1/2, -x
+             A.quad((0, -0.5, -d), (0, 0, d), (0.5, 0, 0)),                      # y = -1/2, +y
+             A.quad((0, 0.5, -d), (0.5, 0, 0), (0, 0, d))]                       # y = +1/2, -y
+    v = np.concatenate([p[0] for p in parts])
+    f = np.concatenate([p[1] + 4 * k for k, p in enumerate(parts)])
+    return A.Scene([A.Mesh("box", v, f, A.material(**WHITE))])
+
+
+def sky_pixels(S, cam):
+    """pixels that no triangle's image can reach: outside the box, widened by a pixel, of every triangle's vertices projected through
+    the camera onto its image plane (probe rays alone can slip past a sliver thinner than their spacing)"""
+    W, H = cam.width, cam.height
+    free = np.ones((H, W), bool)
+    for m in S.meshes:
+        v = np.asarray(m.verts, np.float64)
+        assert (v[:, 2] < cam.org[2]).all()
+        p = cam.org + (v - cam.org) * ((cam.zc - cam.org[2]) / (v[:, 2] - cam.org[2]))[:, None]
+        px, py = (p[:, 0] - cam.xc) / cam.dx, (cam.yc - p[:, 1]) / cam.dy
+        for f in np.asarray(m.faces):
+            x0, x1 = int(np.floor(px[f].min())) - 1, int(np.ceil(px[f].max())) + 1
+            y0, y1 = int(np.floor(py[f].min())) - 1, int(np.ceil(py[f].max())) + 1
+            free[max(y0, 0):max(y1, 0), max(x0, 0):max(x1, 0)] = False
+    return free
+
+
+GGX_METAL = dict(base_color=(0.9, 0.6, 0.3), metallic=1.0, roughness=0.7, specular=0.5, anisotropic=0.0)
+
+
+def ggx_floor_scene():
+    """floor_scene with the receiver of test_analytic_radiance's ggx_metallic case"""
+    S = floor_scene()
+    return A.Scene([A.Mesh("floor", S.meshes[0].verts, S.meshes[0].faces, A.material(**GGX_METAL)), S.meshes[1]])
+
+
+class GGXSkyExpectation:
+    """E(wo) for the metallic GGX floor (its only closure is the specular one) under a constant sky L, no area light (p_env = 1,
+    pdf_env = 1 / 4 pi).  With q = the reference's pdf G1o D / (4 cos_o cos_i) (Q15) and p = 1 / 4 pi:
+        NEE:  E f L cos_i / p x p^2 / (p^2 + q^2)   over the env sample  ->  int f L cos_i w_env dw
+        BSDF: the VNDF draws wi with density q cos_i and the path carries f cos_i / q, weighted q^2 / (q^2 + p^2) at the miss
+                                                                         ->  int f L cos_i^2 w_bsdf dw
+    q15=False: what a GGX whose pdf were its sampling density would converge to, int f L cos_i dw (the weights sum to 1).
+    The floor is isotropic, so E depends on cos_o alone: a Gauss-Legendre (cos_i) x trapezoid (phi, periodic) rule over the
+    hemisphere on a grid of cos_o, interpolated."""
+
+    def __init__(self, S, L, q15=True, n_mu=96, n_phi=192, n_grid=400):
+        _, self.sp = A._principled(S.meshes[S.receiver].material)
+        self.L, self.q15 = np.asarray(L, np.float64), q15
+        self.n_mu, self.n_phi, self.n_grid = n_mu, n_phi, n_grid
+        self.grid = None
+
+    def at(self, co, n_mu=None, n_phi=None):
+        """E for view cosines co (N,), (N, 3)"""
+        n_mu, n_phi = n_mu or self.n_mu, n_phi or self.n_phi
+        mu, wmu = A.gauss_legendre01(n_mu)
+        phi = (np.arange(n_phi) + 0.5) * 2.0 * np.pi / n_phi
+        M, P = np.meshgrid(mu, phi, indexing="ij")
+        st = np.sqrt(1.0 - M * M)
+        wi = np.stack([st * np.cos(P), st * np.sin(P), M], -1).reshape(-1, 3)
+        wq = (wmu[:, None] * np.full(n_phi, 2.0 * np.pi / n_phi)[None]).ravel()
+        co = np.asarray(co, np.float64)
+        wo = np.stack([np.sqrt(1.0 - co * co), np.zeros_like(co), co], -1)
+        a = self.sp["alpha"]
+        g, q = A.ggx_eval(wi[None], wo[:, None], a, a)                        # (N, Q)
+        f = A.specular_color(wi[None], np.broadcast_to(wo[:, None], (len(co), len(wi), 3)), self.sp["color"], self.sp["ior"]) * g[..., None]
+        ci = wi[None, :, 2]
+        if self.q15:
+            p = 1.0 / (4.0 * np.pi)
+            w_env, w_bsdf = p * p / (p * p + q * q), q * q / (q * q + p * p)
+            k = ci * w_env + ci * ci * w_bsdf
+        else:
+            k = np.broadcast_to(ci, q.shape)
+        return np.einsum("nqc,nq,q->nc", f, k, wq) * self.L
+
+    def __call__(self, x, wo, order=None):
+        co = np.abs(np.asarray(wo, np.float64)[:, 2])                         # the floor's normal is +z
+        if self.grid is None:
+            self.grid = np.linspace(0.5, 1.0, self.n_grid)
+            self.table = np.concatenate([self.at(self.grid[i:i + 20]) for i in range(0, self.n_grid, 20)])
+        assert co.min() >= self.grid[0]
+        return np.stack([np.interp(co, self.grid, self.table[:, c]) for c in range(3)], -1)

@@ -126,6 +126,7 @@ def lib():
         L.orc_attach_light_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
         L.orc_attach_material_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
         L.orc_commit.argtypes = [C.c_void_p]
+        L.orc_scene_set_environment.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_uint32, C.c_float, fp]
         L.orc_scene_aabb.argtypes = [C.c_void_p, fp, fp]
         L.orc_bvh_depth.argtypes = [C.c_void_p]
         L.orc_bvh_depth.restype = C.c_uint32
@@ -308,6 +309,19 @@ class OracleScene:
 
     def CommitScene(self):
         self.L.orc_commit(self.h)
+
+    def SetEnvironment(self, rgb_hw3, scale=1.0, world_to_env=None):
+        """pbrlab_amd.Scene.SetEnvironment (DESIGN.md §10) on the oracle: rgb_hw3 (H, W, 3), row 0 = the top, times `scale`;
+        world_to_env a 3x3 rotation (None: identity).  None, or an all-black map, removes it."""
+        if rgb_hw3 is None:
+            self.L.orc_scene_set_environment(self.h, None, 0, 0, 1.0, None)
+            return
+        px = np.ascontiguousarray(rgb_hw3, np.float32)
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("environment map must be (H, W, 3)")
+        m = None if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(9)
+        if self.L.orc_scene_set_environment(self.h, _ptr(px), px.shape[1], px.shape[0], float(scale), _ptr(m)) != 0:
+            raise ValueError("orc_scene_set_environment: invalid map, scale or rotation")
 
     def FetchSceneAABB(self):
         lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
