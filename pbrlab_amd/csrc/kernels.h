@@ -210,9 +210,8 @@ void launch_leaf_eval(hipStream_t s, uint32_t op, const float* in, uint32_t n, u
 // RenderLayer shard of a pixel list: shard = npix x rgba (16 B) followed by npix x count (4 B); 16-byte aligned
 void launch_layer_pack(hipStream_t s, const uint32_t* pix, uint32_t npix, const float* rgba, const uint32_t* count, float* shard);
 void launch_layer_unpack_add(hipStream_t s, const uint32_t* pix, uint32_t npix, const float* shard, float* rgba, uint32_t* count);
-void launch_hook_closest(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* out, uint32_t* counts,
-                         uint32_t* spill, const Knobs& k);
-void launch_hook_any(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, uint8_t* out, uint32_t* counts,
-                     uint32_t* spill, const Knobs& k);
+// test hooks (pbrhip_trace_closest / pbrhip_trace_any): occ != null: any-hit, n occlusion bytes; else n HookHit in hits.  The other one is null.
+void launch_hook(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* hits, uint8_t* occ, uint32_t* counts, uint32_t* spill,
+                 const Knobs& k);
 
 }  // namespace pb

@@ -6,16 +6,19 @@
 //
 //   k_trace           rtcIntersect1 (raytracer_impl.cc:268-278) for the live paths' rays AND rtcOccluded1 + the tail of
 //                     DirectIllumination (shader-utils.h:192-208) for the shadow rays of the previous bounce
-//   k_classify        routes each traced path to its closure queue (in-medium / principled / hair), drops misses
+//   k_classify<ENV>   routes each traced path to its closure queue (in-medium / principled / hair), drops misses
 //   k_shade_principled GetRadiance head (render.cc:31-68: implicit light + MIS, Russian roulette) +
 //                     CyclesPrincipledShader (cycles-principled-shader.cc:414-484) incl. SSS entry
-//   k_shade_hair      HairShader             (hair-shader.cc:153-229)
-//   k_sss_step        RandomWalkSubsurface loop body + exit (random-walk-sss.h:287-405)
+//   k_shade_hair<ENV> HairShader             (hair-shader.cc:153-229)
+//   k_sss_step<ENV>   RandomWalkSubsurface loop body + exit (random-walk-sss.h:287-405)
 //   k_compact         result words of the shade kernels -> next ray queue + shadow-ray queue
 //   k_advance         queue flip
 //
+// (ENV: the instance of scenes with an environment light; k_shade_principled and k_tail carry it as a bit of their MODE.)
 // k_tail runs the same per-path functions in a loop once few paths are left; k_generate (render.cc:160-171) and
 // k_accumulate (render.cc:175-183) bracket a chunk of passes.
+#include <type_traits>
+
 #include "dshade.h"
 #include "kernels.h"
 #include "dtrace_pv.h"
@@ -250,6 +253,8 @@ struct TraceSinkT {
     o = ld3(o4), d = ld3(d4), tmin = o4.w, tmax = d4.w;
     return true;
   }
+  // (load_entry + load_ray's twin on purpose: written as load_ray(idx, load_entry(idx), ..) every k_trace that is not FIRST changes -- the
+  // production <false, false, true, false> 1937 -> 1964 instructions; the same is to be expected of done vs done_issue + done_finish)
   __device__ __forceinline__ bool load(uint32_t idx, uint32_t& tag, V3& o, V3& d, float& tmin, float& tmax) const {
     if (FIRST) {
       camera_ray(idx, tag, o, d, tmin, tmax);
@@ -503,62 +508,61 @@ struct TileCompactor {
 // ShadeRec (kHitMore: corner normals / texcoords: the smooth meshes), then the hits on flat triangles -- so that a shading wave is
 // mostly one kind or the other: the same queue, the same lines touched per tile, fewer waves that run both sides of every branch
 // (north star: "per-closure material sorting", here by what the hit code already says; separate queues lose: profiles/README.md).
-// ENV (k_classify_env: scenes with an environment): a path whose ray missed goes to the principled queue's second run instead
+// ENV (k_classify<true>: scenes with an environment): a path whose ray missed goes to the principled queue's second run instead
 // of being dropped, doomed or not -- the principled shading adds the environment's radiance and ends it (or waits while it is held).
-// (The kernel body as a macro, spelled in each kernel: k_classify compiles to the instructions it did before the environment kernels
-// existed; a shared __device__ body moved its LDS addressing.)
-#define PB_CLASSIFY_KERNEL(ENV) \
-  constexpr int kItemsPerThread = kClassifyItems, kTileItems = kItemsPerThread * kBlock;                                                               \
-  __shared__ uint32_t wcount[4][kItemsPerThread][kWavesPerBlock];                                                                                      \
-  __shared__ uint32_t base[4];                                                                                                                         \
-  __shared__ uint32_t tile_principled[2]; /* this tile's two runs: counted in LDS, reserved in the queue with ONE atomic */                            \
-  const uint32_t n = P.counts[kCntIn];                                                                                                                 \
-  const uint32_t ntiles = (n + kTileItems - 1) / kTileItems;                                                                                           \
-  uint32_t* const counters[4] = {&P.counts[kCntSss], &tile_principled[0], &P.counts[kCntHair], &tile_principled[1]};                                   \
-  uint32_t* const queues[4] = {P.q_sss, P.q_principled, P.q_hair, P.q_principled};                                                                     \
-  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {                                                                                 \
-    uint32_t p[kItemsPerThread], dest[kItemsPerThread]; /* p: path slot | kQFirst (handed on to the shading queues) */                                 \
-    bool doomed[kItemsPerThread];                                                                                                                      \
-_Pragma("unroll")                                                                                                                                      \
-    for (int j = 0; j < kItemsPerThread; j++) {                                                                                                        \
-      uint32_t i = tile * kTileItems + j * kBlock + threadIdx.x;                                                                                       \
-      dest[j] = 0, p[j] = 0, doomed[j] = false;                                                                                                        \
-      if (i < n) {                                                                                                                                     \
-        const uint32_t e = P.first ? ((P.slot0 + i) | kQFirst) : P.q_in[i]; /* (a group's first bounce: entry i is path slot0 + i) */                  \
-        p[j] = e & (kQPathMask | kQFirst | kQDoomed); /* (kQDoomed rides along: a held path hands it back, kernels.h::kRHold) */                       \
-        dest[j] = (!P.no_medium && (e & kQSssBit)) ? 1u : 0xFFu; /* (without media bit 31 is kQHold: the path is routed by its hit like any other) */  \
-        doomed[j] = (e & kQDoomed) != 0u;                                                                                                              \
-      }                                                                                                                                                \
-    }                                                                                                                                                  \
-_Pragma("unroll")                                                                                                                                      \
-    for (int j = 0; j < kItemsPerThread; j++)                                                                                                          \
-      if (dest[j] == 0xFFu) {                                                                                                                          \
-        const uint32_t code = __float_as_uint(P.hit[p[j] & kQPathMask].w);                                                                             \
-        dest[j] = (code & kHitHair) ? 3u : ((PB_CLASSIFY_RUNS == 2 && (code & kHitMore)) ? 2u : 4u);                                                   \
-        if (code == kNone || (!(code & kHitLight) && (doomed[j] || (code & kHitNoMaterial)))) dest[j] = 0u;                                            \
-        if (ENV && code == kNone) dest[j] = 4u;                                                                                                        \
-        /* a path whose ray was suspended (its ray goes on in the next launch) rides through the principled queue untouched: the shading */            \
-        /* kernel turns its entry into a "resume" result word and k_compact re-queues it -- no atomic, no queue of its own */                          \
-        if (code == kHitSuspended) dest[j] = 4u, p[j] |= kQResume;                                                                                     \
-      }                                                                                                                                                \
-    if (threadIdx.x < 2) tile_principled[threadIdx.x] = 0u;                                                                                            \
-    __syncthreads();                                                                                                                                   \
-    TileCompactor<4, kItemsPerThread> tc = {wcount, base, {}};                                                                                         \
-    tc.run(dest, counters); /* (base[1] = base[3] = 0: the two runs were counted from 0) */                                                            \
-    if (threadIdx.x == 0) {                                                                                                                            \
-      const uint32_t a = tile_principled[0], b = tile_principled[1];                                                                                   \
-      const uint32_t g = (a + b) ? atomicAdd(&P.counts[kCntPrincipled], a + b) : 0u;                                                                   \
-      base[1] = g, base[3] = g + a;                                                                                                                    \
-    }                                                                                                                                                  \
-    __syncthreads();                                                                                                                                   \
-_Pragma("unroll")                                                                                                                                      \
-    for (int j = 0; j < kItemsPerThread; j++)                                                                                                          \
-      if (dest[j]) queues[dest[j] - 1][tc.slot(j, dest[j])] = p[j];                                                                                    \
-    __syncthreads();                                                                                                                                   \
+// (The body is spelled in the kernel template, not in a __device__ function that two kernels share: a shared __device__ body moved
+// k_classify's LDS addressing.)
+template <bool ENV>
+__global__ __launch_bounds__(kBlock) void k_classify(PathState P, DScene sc) {
+  constexpr int kItemsPerThread = kClassifyItems, kTileItems = kItemsPerThread * kBlock;
+  __shared__ uint32_t wcount[4][kItemsPerThread][kWavesPerBlock];
+  __shared__ uint32_t base[4];
+  __shared__ uint32_t tile_principled[2];  // this tile's two runs: counted in LDS, reserved in the queue with ONE atomic
+  const uint32_t n = P.counts[kCntIn];
+  const uint32_t ntiles = (n + kTileItems - 1) / kTileItems;
+  uint32_t* const counters[4] = {&P.counts[kCntSss], &tile_principled[0], &P.counts[kCntHair], &tile_principled[1]};
+  uint32_t* const queues[4] = {P.q_sss, P.q_principled, P.q_hair, P.q_principled};
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    uint32_t p[kItemsPerThread], dest[kItemsPerThread];  // p: path slot | kQFirst (handed on to the shading queues)
+    bool doomed[kItemsPerThread];
+#pragma unroll
+    for (int j = 0; j < kItemsPerThread; j++) {
+      uint32_t i = tile * kTileItems + j * kBlock + threadIdx.x;
+      dest[j] = 0, p[j] = 0, doomed[j] = false;
+      if (i < n) {
+        const uint32_t e = P.first ? ((P.slot0 + i) | kQFirst) : P.q_in[i];  // (a group's first bounce: entry i is path slot0 + i)
+        p[j] = e & (kQPathMask | kQFirst | kQDoomed);  // (kQDoomed rides along: a held path hands it back, kernels.h::kRHold)
+        dest[j] = (!P.no_medium && (e & kQSssBit)) ? 1u : 0xFFu;  // (without media bit 31 is kQHold: the path is routed by its hit like any other)
+        doomed[j] = (e & kQDoomed) != 0u;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kItemsPerThread; j++)
+      if (dest[j] == 0xFFu) {
+        const uint32_t code = __float_as_uint(P.hit[p[j] & kQPathMask].w);
+        dest[j] = (code & kHitHair) ? 3u : ((PB_CLASSIFY_RUNS == 2 && (code & kHitMore)) ? 2u : 4u);
+        if (code == kNone || (!(code & kHitLight) && (doomed[j] || (code & kHitNoMaterial)))) dest[j] = 0u;
+        if (ENV && code == kNone) dest[j] = 4u;
+        // a path whose ray was suspended (its ray goes on in the next launch) rides through the principled queue untouched: the shading
+        // kernel turns its entry into a "resume" result word and k_compact re-queues it -- no atomic, no queue of its own
+        if (code == kHitSuspended) dest[j] = 4u, p[j] |= kQResume;
+      }
+    if (threadIdx.x < 2) tile_principled[threadIdx.x] = 0u;
+    __syncthreads();
+    TileCompactor<4, kItemsPerThread> tc = {wcount, base, {}};
+    tc.run(dest, counters);  // (base[1] = base[3] = 0: the two runs were counted from 0)
+    if (threadIdx.x == 0) {
+      const uint32_t a = tile_principled[0], b = tile_principled[1];
+      const uint32_t g = (a + b) ? atomicAdd(&P.counts[kCntPrincipled], a + b) : 0u;
+      base[1] = g, base[3] = g + a;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kItemsPerThread; j++)
+      if (dest[j]) queues[dest[j] - 1][tc.slot(j, dest[j])] = p[j];
+    __syncthreads();
   }
-__global__ __launch_bounds__(kBlock) void k_classify(PathState P, DScene sc) { PB_CLASSIFY_KERNEL(false) }
-__global__ __launch_bounds__(kBlock) void k_classify_env(PathState P, DScene sc) { PB_CLASSIFY_KERNEL(true) }
-#undef PB_CLASSIFY_KERNEL
+}
 
 // ------------------------------------------------------------------ k_compact
 // The shade kernels overwrite their queue entry with  path | kRShadow | kRAlive | kQSssBit | kQDoomed  instead of
@@ -802,161 +806,160 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
   constexpr int MODE = shade_base(MODE_);
   constexpr bool ENV = shade_env(MODE_);
   if (ENV && __float_as_uint(P.hit[p].w) == kNone) return env_miss_path<MODE != kShadeMedia>(P, sc, p, first);
-  {
-    const bool active = true;
-    bool alive = false, shadow = false;
-    V3 sh_pos(0.f), c_vis(0.f);
-    Nee nee;
-    nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
-    uint32_t sh_mode = kShNormal, qbit = 0u;
-    PathHead c;
-    const int head = path_head<MODE != kShadeMedia, ENV>(P, sc, p, rng_inc, c, first);
-    if (active && head == kHeadGoes) {
-      const Hit& h = c.h;
-      const V3 dir = c.dir, thr = c.thr;
-      const Surface& s = c.s;
-      Rng& rng = c.rng;
-      V3 new_thr(0.f), next_dir = -dir;
-      float new_pdf = 0.f;
-      if (s.face != kAmbiguous) {  // :418-424
-        V3 wo_g = -dir;
-        Frame fr;
-        fr.ez = (s.face == kFront) ? s.n_s : -s.n_s;
-        branchless_onb(fr.ez, fr.ex, fr.ey);
-        V3 wo = to_local(fr, wo_g);
-        PrincipledBsdf b;
-        if (lds_bsdf) {  // (LDS reads: off the vector-memory path the kernel is bound by)
-          constexpr uint32_t kWords = sizeof(PrincipledBsdf) / 4;
-          const auto* lw = (const __attribute__((address_space(3))) uint32_t*)reinterpret_cast<const uint32_t*>(lds_bsdf) + s.material * kWords;
-          uint32_t w[kWords];
+  bool alive = false, shadow = false;
+  V3 sh_pos(0.f), c_vis(0.f);
+  Nee nee;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  uint32_t sh_mode = kShNormal, qbit = 0u;
+  PathHead c;
+  const int head = path_head<MODE != kShadeMedia, ENV>(P, sc, p, rng_inc, c, first);
+  if (head == kHeadGoes) {
+    const Hit& h = c.h;
+    const V3 dir = c.dir, thr = c.thr;
+    const Surface& s = c.s;
+    Rng& rng = c.rng;
+    V3 new_thr(0.f), next_dir = -dir;
+    float new_pdf = 0.f;
+    if (s.face != kAmbiguous) {  // :418-424
+      V3 wo_g = -dir;
+      Frame fr;
+      fr.ez = (s.face == kFront) ? s.n_s : -s.n_s;
+      branchless_onb(fr.ez, fr.ex, fr.ey);
+      V3 wo = to_local(fr, wo_g);
+      PrincipledBsdf b;
+      if (lds_bsdf) {  // (LDS reads: off the vector-memory path the kernel is bound by)
+        constexpr uint32_t kWords = sizeof(PrincipledBsdf) / 4;
+        const auto* lw = (const __attribute__((address_space(3))) uint32_t*)reinterpret_cast<const uint32_t*>(lds_bsdf) + s.material * kWords;
+        uint32_t w[kWords];
 #pragma unroll
-          for (uint32_t k = 0; k < kWords; k++) w[k] = lw[k];
-          __builtin_memcpy(&b, w, sizeof(b));
-        } else {
-          b = sc.materials[s.material].bsdf;
-        }
-        const bool per_hit = MODE == kShadeFull && sc.materials[s.material].textured != 0u;
-        if (per_hit) {  // ParamToBsdf per hit (cycles-principled-shader.cc:281-301)
-          const PrincipledParam mp = sc.materials[s.material].param;
-          V3 bc(mp.base_color[0], mp.base_color[1], mp.base_color[2]);
-          V3 ssc(mp.subsurface_color[0], mp.subsurface_color[1], mp.subsurface_color[2]);
-          if (mp.base_color_tex_id != kNone) bc = texture_fetch3(sc, mp.base_color_tex_id, s.tu, s.tv);
-          if (mp.subsurface_color_tex_id != kNone) ssc = texture_fetch3(sc, mp.subsurface_color_tex_id, s.tu, s.tv);
-          b = param_to_bsdf(mp, bc, ssc);
-        }
-        SampleWeight w = closure_sample_weight(wo, b);
-        // DirectIllumination (shader-utils.h:166-212)
-        V3 d1(0.f);
-        shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ez, true, nee, lds_lights);
-        if (shadow) {
-          V3 f;
+        for (uint32_t k = 0; k < kWords; k++) w[k] = lw[k];
+        __builtin_memcpy(&b, w, sizeof(b));
+      } else {
+        b = sc.materials[s.material].bsdf;
+      }
+      const bool per_hit = MODE == kShadeFull && sc.materials[s.material].textured != 0u;
+      if (per_hit) {  // ParamToBsdf per hit (cycles-principled-shader.cc:281-301)
+        const PrincipledParam mp = sc.materials[s.material].param;
+        V3 bc(mp.base_color[0], mp.base_color[1], mp.base_color[2]);
+        V3 ssc(mp.subsurface_color[0], mp.subsurface_color[1], mp.subsurface_color[2]);
+        if (mp.base_color_tex_id != kNone) bc = texture_fetch3(sc, mp.base_color_tex_id, s.tu, s.tv);
+        if (mp.subsurface_color_tex_id != kNone) ssc = texture_fetch3(sc, mp.subsurface_color_tex_id, s.tu, s.tv);
+        b = param_to_bsdf(mp, bc, ssc);
+      }
+      SampleWeight w = closure_sample_weight(wo, b);
+      // DirectIllumination (shader-utils.h:166-212)
+      V3 d1(0.f);
+      shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ez, true, nee, lds_lights);
+      if (shadow) {
+        V3 f;
+        float pdf;
+        eval_bsdf(to_local(fr, nee.dir), wo, b, w, f, pdf);
+        d1 = nee_contribution(nee, f, pdf);
+        sh_pos = s.pos;
+      }
+      // SampleBsdf (:169-242)
+      float select = draw(rng);
+      int pick = pick_closure(select, w);
+      V3 wi(0.f);
+      bool sampled = true;
+      if (pick == 0) {
+        float u0 = draw(rng);
+        float u1 = draw(rng);
+        float pdf;
+        lambert_sample(u0, u1, wi, pdf);
+      } else if (pick == 2) {
+        float u0 = draw(rng);
+        float u1 = draw(rng);
+        ggx_sample(wo, b.alpha_x, b.alpha_y, u0, u1, wi);
+      } else if (pick == 3) {
+        float u0 = draw(rng);
+        float u1 = draw(rng);
+        ggx_sample(wo, b.clearcoat_alpha_x, b.clearcoat_alpha_y, u0, u1, wi);
+      } else if (MODE == kShadePlain) {
+        sampled = false;  // unreachable: no material has a subsurface weight
+      } else {
+        // RandomWalkSubsurface entry (random-walk-sss.h:236-287)
+        sampled = false;
+        bool ok = (s.face == kFront);
+        if (ok) {
+          float u0 = draw(rng);
+          float u1 = draw(rng);
+          V3 tmp;
           float pdf;
-          eval_bsdf(to_local(fr, nee.dir), wo, b, w, f, pdf);
-          d1 = nee_contribution(nee, f, pdf);
-          sh_pos = s.pos;
-        }
-        // SampleBsdf (:169-242)
-        float select = draw(rng);
-        int pick = pick_closure(select, w);
-        V3 wi(0.f);
-        bool sampled = true;
-        if (pick == 0) {
-          float u0 = draw(rng);
-          float u1 = draw(rng);
-          float pdf;
-          lambert_sample(u0, u1, wi, pdf);
-        } else if (pick == 2) {
-          float u0 = draw(rng);
-          float u1 = draw(rng);
-          ggx_sample(wo, b.alpha_x, b.alpha_y, u0, u1, wi);
-        } else if (pick == 3) {
-          float u0 = draw(rng);
-          float u1 = draw(rng);
-          ggx_sample(wo, b.clearcoat_alpha_x, b.clearcoat_alpha_y, u0, u1, wi);
-        } else if (MODE == kShadePlain) {
-          sampled = false;  // unreachable: no material has a subsurface weight
-        } else {
-          // RandomWalkSubsurface entry (random-walk-sss.h:236-287)
-          sampled = false;
-          bool ok = (s.face == kFront);
+          lambert_sample(u0, u1, tmp, pdf);
+          tmp = -tmp;
+          V3 gdir = to_global(fr, tmp);
+          ok = !(dot(-s.n_g, gdir) <= 0.0f);
           if (ok) {
-            float u0 = draw(rng);
-            float u1 = draw(rng);
-            V3 tmp;
-            float pdf;
-            lambert_sample(u0, u1, tmp, pdf);
-            tmp = -tmp;
-            V3 gdir = to_global(fr, tmp);
-            ok = !(dot(-s.n_g, gdir) <= 0.0f);
-            if (ok) {
-              // the medium's coefficients and the walk's first throughput (random-walk-sss.h:111-122, 243-258) depend on the
-              // closure set alone: for a material without textures they were computed at commit with these very functions
-              // (host and device share the f64r exp), otherwise they follow from this hit's closure set
-              V3 sigt, sigs, wthr;
-              if (per_hit) {
-                medium_coefficients(b, sigt, sigs, wthr);
-              } else {
-                const float4* mc = reinterpret_cast<const float4*>(&sc.materials[s.material].sss_sigt);
-                const float4 m0 = mc[0], m1 = mc[1], m2 = mc[2];
-                sigt = V3(m0.x, m0.y, m0.z), sigs = V3(m0.w, m1.x, m1.y), wthr = V3(m1.z, m1.w, m2.x);
-              }
-              float e0 = draw(rng);
-              float e1 = draw(rng);
-              V3 chpdf;
-              float t_scatter = sample_scatter_distance(wthr, sigs, sigt, e0, e1, chpdf);
-              P.ray_o[p] = mk4(s.pos, 1e-3f);
-              P.ray_d[p] = mk4(gdir, t_scatter);
-              P.sss_sigt[p] = mk4(sigt, 0.f);
-              P.sss_sigs[p] = mk4(sigs, __uint_as_float(sc.shade[h.slot & kHitSlotMask].instance_id));  // .w = entry instance id
-              P.sss_thr[p] = mk4(wthr, __uint_as_float(0u));  // .w = step index (kept with the data every step rewrites)
-              P.sss_ez[p] = mk4(fr.ez, 0.f);
-              P.sss_A[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-              P.thr[p] = mk4(thr, 0.f);  // Russian-roulette-scaled path throughput, used again at the exit
-              P.rng[p] = rng.state;
-              alive = true;
-              qbit = kQSssBit;
-              sh_mode = kShSssEntry;
-              c_vis = d1;  // raw: resolved into A when the shadow ray is traced (TraceSink::done)
-            }
-          }
-          // failed entry: omega_in = f = pdf = 0 -> 0*0/0 = NaN -> throughput 0 (:217-220, :474-483)
-        }
-        if (sampled) {
-          V3 f;
-          float pdf;
-          eval_bsdf(wi, wo, b, w, f, pdf);
-          next_dir = to_global(fr, wi);
-          float cos_i = fabsf(wi.z);
-          new_thr = f * cos_i / pdf;
-          new_pdf = pdf;
-          if (!is_finite(new_thr) || !isfinite(new_pdf)) {
-            new_thr = V3(0.f);
-            new_pdf = 0.f;
-          }
-        }
-        if (sh_mode == kShNormal) c_vis = thr * ((V3(0.f) + d1) + V3(0.f));  // render.cc:79
-        if (!alive) {
-          // render.cc:80-86
-          V3 t2 = new_thr * thr;
-          if (!is_black(t2)) {
-            qbit = doomed_bit(t2, rng.state, rng_inc);
-            if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {  // (with an environment a doomed ray can still escape)
-              alive = true;
-              P.ray_o[p] = mk4(s.pos, 1e-3f);
-              P.ray_d[p] = mk4(next_dir, kInf);
-              P.thr[p] = mk4(t2, new_pdf);
-              store_rng<MODE != kShadeMedia>(P, p, rng.state);
+            // the medium's coefficients and the walk's first throughput (random-walk-sss.h:111-122, 243-258) depend on the
+            // closure set alone: for a material without textures they were computed at commit with these very functions
+            // (host and device share the f64r exp), otherwise they follow from this hit's closure set
+            V3 sigt, sigs, wthr;
+            if (per_hit) {
+              medium_coefficients(b, sigt, sigs, wthr);
             } else {
-              qbit = 0u;
-              count_pruned(P);
+              const float4* mc = reinterpret_cast<const float4*>(&sc.materials[s.material].sss_sigt);
+              const float4 m0 = mc[0], m1 = mc[1], m2 = mc[2];
+              sigt = V3(m0.x, m0.y, m0.z), sigs = V3(m0.w, m1.x, m1.y), wthr = V3(m1.z, m1.w, m2.x);
             }
+            float e0 = draw(rng);
+            float e1 = draw(rng);
+            V3 chpdf;
+            float t_scatter = sample_scatter_distance(wthr, sigs, sigt, e0, e1, chpdf);
+            P.ray_o[p] = mk4(s.pos, 1e-3f);
+            P.ray_d[p] = mk4(gdir, t_scatter);
+            P.sss_sigt[p] = mk4(sigt, 0.f);
+            P.sss_sigs[p] = mk4(sigs, __uint_as_float(sc.shade[h.slot & kHitSlotMask].instance_id));  // .w = entry instance id
+            P.sss_thr[p] = mk4(wthr, __uint_as_float(0u));  // .w = step index (kept with the data every step rewrites)
+            P.sss_ez[p] = mk4(fr.ez, 0.f);
+            P.sss_A[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+            P.thr[p] = mk4(thr, 0.f);  // Russian-roulette-scaled path throughput, used again at the exit
+            P.rng[p] = rng.state;
+            alive = true;
+            qbit = kQSssBit;
+            sh_mode = kShSssEntry;
+            c_vis = d1;  // raw: resolved into A when the shadow ray is traced (TraceSink::done)
+          }
+        }
+        // failed entry: omega_in = f = pdf = 0 -> 0*0/0 = NaN -> throughput 0 (:217-220, :474-483)
+      }
+      if (sampled) {
+        V3 f;
+        float pdf;
+        eval_bsdf(wi, wo, b, w, f, pdf);
+        next_dir = to_global(fr, wi);
+        float cos_i = fabsf(wi.z);
+        new_thr = f * cos_i / pdf;
+        new_pdf = pdf;
+        if (!is_finite(new_thr) || !isfinite(new_pdf)) {
+          new_thr = V3(0.f);
+          new_pdf = 0.f;
+        }
+      }
+      if (sh_mode == kShNormal) c_vis = thr * ((V3(0.f) + d1) + V3(0.f));  // render.cc:79
+      if (!alive) {
+        // render.cc:80-86
+        V3 t2 = new_thr * thr;
+        if (!is_black(t2)) {
+          qbit = doomed_bit(t2, rng.state, rng_inc);
+          // (this "doomed / misses_all_lights / store the next ray" tail is spelled in shade_hair_path and sss_step_path too, on purpose: one
+          // shared function for the three kept every register count and changed the instructions of all 42 kernels that shade)
+          if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {  // (with an environment a doomed ray can still escape)
+            alive = true;
+            P.ray_o[p] = mk4(s.pos, 1e-3f);
+            P.ray_d[p] = mk4(next_dir, kInf);
+            P.thr[p] = mk4(t2, new_pdf);
+            store_rng<MODE != kShadeMedia>(P, p, rng.state);
+          } else {
+            qbit = 0u;
+            count_pruned(P);
           }
         }
       }
     }
-    if (shadow) put_shadow(P, sh_pos, nee, c_vis, V3(0.f), p, sh_mode, alive);
-    return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
   }
+  if (shadow) put_shadow(P, sh_pos, nee, c_vis, V3(0.f), p, sh_mode, alive);
+  return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
 }
 #ifndef PB_SHADE_WAVES
 #define PB_SHADE_WAVES 4  // min waves per SIMD of the plain kernel: <= 128 VGPRs (round 5: 117-119 by itself since kernels.hip is compiled without the SLP vectoriser; five waves spill: 10.5 -> 12.7 ms on C2.  Rounds 2-4, 133-168 VGPRs: 3)
@@ -1011,7 +1014,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(MODE_)) void k_shade_principled
       const uint32_t code = __float_as_uint(P.hit[p].w);
       const bool doomed = kAnyBounce && (e & kQDoomed);
       go = !(code == kNone || (!(code & kHitLight) && (doomed || (code & kHitNoMaterial))));  // (k_classify's drop rule)
-      if (ENV && code == kNone) go = true;  // (k_classify_env's: a miss collects the environment)
+      if (ENV && code == kNone) go = true;  // (k_classify<true>'s: a miss collects the environment)
       if (code == kHitSuspended) {
         go = false, r = kRResume | kRResumeFirst;
         if (kAnyBounce && !P.first) r = kRResume | (e & kQDoomed) | ((e & kQFirst) ? kRResumeFirst : 0u);
@@ -1029,89 +1032,84 @@ __global__ __launch_bounds__(kBlock, shade_waves(MODE_)) void k_shade_principled
 template <bool ENV = false>
 __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc, bool first,
                                                     const float* lds_lights = nullptr) {
-  {
-    const bool active = true;
-    bool alive = false, shadow = false;
-    uint32_t qbit = 0u;
-    V3 sh_pos(0.f), c_vis(0.f);
-    Nee nee;
-    nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
-    PathHead c;
-    const int head = path_head<true, ENV>(P, sc, p, rng_inc, c, first);
-    if (active && head == kHeadGoes) {
-      const Hit& h = c.h;
-      const V3 dir = c.dir, thr = c.thr;
-      const Surface& s = c.s;
-      Rng& rng = c.rng;
-      if (s.face != kAmbiguous) {
-        V3 wo_g = -dir;
-        Frame fr;
-        fr.ex = s.n_s;  // curve tangent
-        fr.ey = vnormalize(cross(cross(wo_g, fr.ex), fr.ex));
-        fr.ez = cross(fr.ex, fr.ey);
-        V3 wo = to_local(fr, wo_g);
-        HairBsdf hb = sc.materials[s.material].hair;
-        hb.h = h.v;  // :183 (Q12)
-        HairSetup S;
-        hair_prepare(wo, hb, S);
-        V3 d1(0.f);
-        shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ex, false, nee, lds_lights);
-        if (shadow) {
-          V3 wl = to_local(fr, nee.dir);
-          float pdf;
-          V3 fcos = hair_eval(S, wl, hb, pdf);
-          d1 = nee_contribution(nee, fcos / fabsf(wl.x), pdf);
-          sh_pos = s.pos;
-        }
-        float us[4];
-        us[0] = draw(rng), us[1] = draw(rng), us[2] = draw(rng), us[3] = draw(rng);
-        V3 wi(0.f);
-        float pdf = 0.f;
-        V3 fcos = hair_sample(S, hb, us, wi, pdf);
-        V3 next_dir = to_global(fr, wi);
-        V3 new_thr = fcos / pdf;
-        if (!is_finite(new_thr) || !isfinite(pdf)) {
-          new_thr = V3(0.f);
-          pdf = 0.f;
-        }
-        c_vis = thr * ((V3(0.f) + d1) + V3(0.f));
-        V3 t2 = new_thr * thr;
-        if (!is_black(t2)) {
-          qbit = doomed_bit(t2, rng.state, rng_inc);
-          if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
-            alive = true;
-            P.ray_o[p] = mk4(s.pos, 1e-3f);
-            P.ray_d[p] = mk4(next_dir, kInf);
-            P.thr[p] = mk4(t2, pdf);
-            store_rng(P, p, rng.state);
-          } else {
-            qbit = 0u;
-            count_pruned(P);
-          }
+  bool alive = false, shadow = false;
+  uint32_t qbit = 0u;
+  V3 sh_pos(0.f), c_vis(0.f);
+  Nee nee;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  PathHead c;
+  const int head = path_head<true, ENV>(P, sc, p, rng_inc, c, first);
+  if (head == kHeadGoes) {
+    const Hit& h = c.h;
+    const V3 dir = c.dir, thr = c.thr;
+    const Surface& s = c.s;
+    Rng& rng = c.rng;
+    if (s.face != kAmbiguous) {
+      V3 wo_g = -dir;
+      Frame fr;
+      fr.ex = s.n_s;  // curve tangent
+      fr.ey = vnormalize(cross(cross(wo_g, fr.ex), fr.ex));
+      fr.ez = cross(fr.ex, fr.ey);
+      V3 wo = to_local(fr, wo_g);
+      HairBsdf hb = sc.materials[s.material].hair;
+      hb.h = h.v;  // :183 (Q12)
+      HairSetup S;
+      hair_prepare(wo, hb, S);
+      V3 d1(0.f);
+      shadow = nee_sample<ENV>(sc, rng, s.pos, fr.ex, false, nee, lds_lights);
+      if (shadow) {
+        V3 wl = to_local(fr, nee.dir);
+        float pdf;
+        V3 fcos = hair_eval(S, wl, hb, pdf);
+        d1 = nee_contribution(nee, fcos / fabsf(wl.x), pdf);
+        sh_pos = s.pos;
+      }
+      float us[4];
+      us[0] = draw(rng), us[1] = draw(rng), us[2] = draw(rng), us[3] = draw(rng);
+      V3 wi(0.f);
+      float pdf = 0.f;
+      V3 fcos = hair_sample(S, hb, us, wi, pdf);
+      V3 next_dir = to_global(fr, wi);
+      V3 new_thr = fcos / pdf;
+      if (!is_finite(new_thr) || !isfinite(pdf)) {
+        new_thr = V3(0.f);
+        pdf = 0.f;
+      }
+      c_vis = thr * ((V3(0.f) + d1) + V3(0.f));
+      V3 t2 = new_thr * thr;
+      if (!is_black(t2)) {
+        qbit = doomed_bit(t2, rng.state, rng_inc);
+        if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
+          alive = true;
+          P.ray_o[p] = mk4(s.pos, 1e-3f);
+          P.ray_d[p] = mk4(next_dir, kInf);
+          P.thr[p] = mk4(t2, pdf);
+          store_rng(P, p, rng.state);
+        } else {
+          qbit = 0u;
+          count_pruned(P);
         }
       }
     }
-    if (shadow) put_shadow(P, sh_pos, nee, c_vis, V3(0.f), p, kShNormal, alive);
-    return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
+  }
+  if (shadow) put_shadow(P, sh_pos, nee, c_vis, V3(0.f), p, kShNormal, alive);
+  return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
+}
+// ENV: scenes with an environment.  (The body is spelled in the kernel template for k_classify's reason: a shared
+// __device__ body moved the LDS addressing.)
+template <bool ENV>
+__global__ __launch_bounds__(kBlock) void k_shade_hair(PathState P, DScene sc, uint64_t rng_inc) {
+  __shared__ float lds_lights[kLdsLightWords];
+  const bool lights_staged = stage_light_tables(sc, lds_lights);
+  if (lights_staged) __syncthreads();
+  const uint32_t n = P.counts[kCntHair];
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const uint32_t e = P.q_hair[i], p = e & kQPathMask;
+    uint32_t r = shade_hair_path<ENV>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, lights_staged ? lds_lights : nullptr);
+    if (r == kRHold && (e & kQDoomed)) r |= kRHoldDoomed;  // (a held path hands its queue entry's kQDoomed back)
+    P.q_hair[i] = p | r;
   }
 }
-// (the kernel body as a macro, for k_shade_hair and k_shade_hair_env: spelled in the kernel itself, k_shade_hair compiles to the
-// instructions it did before the environment kernels existed; a shared __device__ body moved its LDS addressing)
-#define PB_SHADE_HAIR_KERNEL(ENV)                                                                                                     \
-  __shared__ float lds_lights[kLdsLightWords];                                                                                        \
-  const bool lights_staged = stage_light_tables(sc, lds_lights);                                                                     \
-  if (lights_staged) __syncthreads();                                                                                                 \
-  const uint32_t n = P.counts[kCntHair];                                                                                              \
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {                                              \
-    const uint32_t e = P.q_hair[i], p = e & kQPathMask;                                                                               \
-    uint32_t r = shade_hair_path<ENV>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, lights_staged ? lds_lights : nullptr); \
-    if (r == kRHold && (e & kQDoomed)) r |= kRHoldDoomed; /* (a held path hands its queue entry's kQDoomed back) */                 \
-    P.q_hair[i] = p | r;                                                                                                              \
-  }
-__global__ __launch_bounds__(kBlock) void k_shade_hair(PathState P, DScene sc, uint64_t rng_inc) { PB_SHADE_HAIR_KERNEL(false) }
-// scenes with an environment
-__global__ __launch_bounds__(kBlock) void k_shade_hair_env(PathState P, DScene sc, uint64_t rng_inc) { PB_SHADE_HAIR_KERNEL(true) }
-#undef PB_SHADE_HAIR_KERNEL
 
 // ------------------------------------------------------------------ k_sss_step
 // One iteration of RandomWalkSubsurface's loop after its TraceFirstHit1 (random-walk-sss.h:314-405),
@@ -1165,145 +1163,138 @@ __device__ __forceinline__ bool sss_scatter(WalkState& w, uint64_t rng_inc, V3* 
 template <bool ENV = false>
 __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc,
                                                   const Hit* hreg = nullptr, const float* lds_lights = nullptr) {
-  {
-    const bool active = true;
-    bool alive = false, shadow = false;
-    uint32_t qbit = 0u;
-    V3 sh_pos(0.f), c_vis(0.f), c_occ(0.f);
-    Nee nee;
-    nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
-    if (active) {
-      float4 o4 = P.ray_o[p], d4 = P.ray_d[p];
-      float4 st4 = P.sss_sigt[p], ss4 = P.sss_sigs[p], wt4 = P.sss_thr[p];
-      Hit h;
-      if (hreg) {
-        h = *hreg;
+  bool alive = false, shadow = false;
+  uint32_t qbit = 0u;
+  V3 sh_pos(0.f), c_vis(0.f), c_occ(0.f);
+  Nee nee;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  float4 o4 = P.ray_o[p], d4 = P.ray_d[p];
+  float4 st4 = P.sss_sigt[p], ss4 = P.sss_sigs[p], wt4 = P.sss_thr[p];
+  Hit h;
+  if (hreg) {
+    h = *hreg;
+  } else {
+    const float4 h4 = P.hit[p];
+    h.t = h4.x, h.u = h4.y, h.v = h4.z, h.slot = __float_as_uint(h4.w);
+  }
+  V3 org = ld3(o4), dir = ld3(d4), sigt = ld3(st4), sigs = ld3(ss4), wthr = ld3(wt4);
+  uint32_t bounce = __float_as_uint(wt4.w), entry_inst = __float_as_uint(ss4.w);
+  Rng rng = {P.rng[p], rng_inc};
+  bool hit = (h.slot != kNone);
+  bool fail = false, exited = false;
+  if (hit) {
+    V3 chpdf = scatter_channel_pdf(wthr, sigs, sigt);  // what sample_scatter_distance computed when it drew this step's distance
+    V3 trans = attenuate_transmission(sigt, h.t);
+    float pdf = dot(chpdf, trans);
+    wthr = wthr * trans / pdf;
+    exited = true;
+  } else {
+    WalkState w = {org, dir, sigt, sigs, wthr, d4.w /* = t_scatter */, bounce, rng.state};
+    if (!sss_scatter(w, rng_inc)) {
+      fail = true;
+    } else {
+      P.ray_o[p] = mk4(w.org, 0.f);
+      P.ray_d[p] = mk4(w.dir, w.t_scatter);
+      P.sss_thr[p] = mk4(w.wthr, __uint_as_float(w.bounce));
+      P.rng[p] = w.rng_state;
+      alive = true;
+      qbit = kQSssBit;
+    }
+  }
+  V3 thr = ld3(P.thr[p]);
+  V3 A = ld3(P.sss_A[p]);
+  if (alive) {
+    // (the walk goes on: nothing else to do)
+  } else if (exited) {
+    uint32_t exit_inst;
+    Surface s = make_surface(sc, org, dir, h, &exit_inst);  // :369
+    if (exit_inst != entry_inst) fail = true;               // :372 (Q6)
+    if (s.face != kBack) fail = true;                      // :376
+    if (!fail) {
+      Frame fx;  // exit frame :382-394
+      fx.ez = s.n_s;
+      branchless_onb(fx.ez, fx.ex, fx.ey);
+      V3 wo = to_local(fx, dir);
+      PrincipledBsdf nb = default_bsdf();  // cycles-principled-shader.cc:198-200
+      nb.enable_diffuse = 1;
+      nb.diffuse_weight = wthr;
+      SampleWeight w = closure_sample_weight(wo, nb);
+      V3 d2(0.f);
+      shadow = nee_sample<ENV>(sc, rng, s.pos, s.n_s, true, nee, lds_lights);  // :202-212 (Q5)
+      if (shadow) {
+        V3 f;
+        float pdf;
+        eval_bsdf(to_local(fx, nee.dir), wo, nb, w, f, pdf);
+        d2 = nee_contribution(nee, f, pdf);
+        sh_pos = s.pos;
+      }
+      float select = draw(rng);
+      int pick = pick_closure(select, w);
+      V3 wi(0.f);
+      float u0 = draw(rng);
+      float u1 = draw(rng);
+      if (pick == 0) {
+        float pdf;
+        lambert_sample(u0, u1, wi, pdf);
       } else {
-        const float4 h4 = P.hit[p];
-        h.t = h4.x, h.u = h4.y, h.v = h4.z, h.slot = __float_as_uint(h4.w);
+        // diffuse weight 0 (NaN -> 0) falls through to the clearcoat branch with alpha (1,1) (Q7)
+        ggx_sample(wo, nb.clearcoat_alpha_x, nb.clearcoat_alpha_y, u0, u1, wi);
       }
-      V3 org = ld3(o4), dir = ld3(d4), sigt = ld3(st4), sigs = ld3(ss4), wthr = ld3(wt4);
-      uint32_t bounce = __float_as_uint(wt4.w), entry_inst = __float_as_uint(ss4.w);
-      Rng rng = {P.rng[p], rng_inc};
-      bool hit = (h.slot != kNone);
-      bool fail = false, exited = false;
-      if (hit) {
-        V3 chpdf = scatter_channel_pdf(wthr, sigs, sigt);  // what sample_scatter_distance computed when it drew this step's distance
-        V3 trans = attenuate_transmission(sigt, h.t);
-        float pdf = dot(chpdf, trans);
-        wthr = wthr * trans / pdf;
-        exited = true;
-      } else {
-        WalkState w = {org, dir, sigt, sigs, wthr, d4.w /* = t_scatter */, bounce, rng.state};
-        if (!sss_scatter(w, rng_inc)) {
-          fail = true;
-        } else {
-          P.ray_o[p] = mk4(w.org, 0.f);
-          P.ray_d[p] = mk4(w.dir, w.t_scatter);
-          P.sss_thr[p] = mk4(w.wthr, __uint_as_float(w.bounce));
-          P.rng[p] = w.rng_state;
-          alive = true;
-          qbit = kQSssBit;
-        }
+      V3 f;
+      float pdf;
+      eval_bsdf(wi, wo, nb, w, f, pdf);
+      // local -> global with the ENTRY frame (cycles-principled-shader.cc:467-469)
+      Frame fe;
+      fe.ez = ld3(P.sss_ez[p]);
+      branchless_onb(fe.ez, fe.ex, fe.ey);
+      V3 next_dir = to_global(fe, wi);
+      V3 new_thr = f * fabsf(wi.z) / pdf;
+      if (!is_finite(new_thr) || !isfinite(pdf)) {
+        new_thr = V3(0.f);
+        pdf = 0.f;
       }
-      V3 thr = ld3(P.thr[p]);
-      V3 A = ld3(P.sss_A[p]);
-      if (alive) {
-        // (the walk goes on: nothing else to do)
-      } else if (exited) {
-        uint32_t exit_inst;
-        Surface s = make_surface(sc, org, dir, h, &exit_inst);  // :369
-        if (exit_inst != entry_inst) fail = true;               // :372 (Q6)
-        if (s.face != kBack) fail = true;                      // :376
-        if (!fail) {
-          Frame fx;  // exit frame :382-394
-          fx.ez = s.n_s;
-          branchless_onb(fx.ez, fx.ex, fx.ey);
-          V3 wo = to_local(fx, dir);
-          PrincipledBsdf nb = default_bsdf();  // cycles-principled-shader.cc:198-200
-          nb.enable_diffuse = 1;
-          nb.diffuse_weight = wthr;
-          SampleWeight w = closure_sample_weight(wo, nb);
-          V3 d2(0.f);
-          shadow = nee_sample<ENV>(sc, rng, s.pos, s.n_s, true, nee, lds_lights);  // :202-212 (Q5)
-          if (shadow) {
-            V3 f;
-            float pdf;
-            eval_bsdf(to_local(fx, nee.dir), wo, nb, w, f, pdf);
-            d2 = nee_contribution(nee, f, pdf);
-            sh_pos = s.pos;
-          }
-          float select = draw(rng);
-          int pick = pick_closure(select, w);
-          V3 wi(0.f);
-          float u0 = draw(rng);
-          float u1 = draw(rng);
-          if (pick == 0) {
-            float pdf;
-            lambert_sample(u0, u1, wi, pdf);
-          } else {
-            // diffuse weight 0 (NaN -> 0) falls through to the clearcoat branch with alpha (1,1) (Q7)
-            ggx_sample(wo, nb.clearcoat_alpha_x, nb.clearcoat_alpha_y, u0, u1, wi);
-          }
-          V3 f;
-          float pdf;
-          eval_bsdf(wi, wo, nb, w, f, pdf);
-          // local -> global with the ENTRY frame (cycles-principled-shader.cc:467-469)
-          Frame fe;
-          fe.ez = ld3(P.sss_ez[p]);
-          branchless_onb(fe.ez, fe.ex, fe.ey);
-          V3 next_dir = to_global(fe, wi);
-          V3 new_thr = f * fabsf(wi.z) / pdf;
-          if (!is_finite(new_thr) || !isfinite(pdf)) {
-            new_thr = V3(0.f);
-            pdf = 0.f;
-          }
-          c_vis = thr * (A + d2);
-          c_occ = thr * (A + V3(0.f));
-          if (!shadow) {
-            float4 L4 = P.L[p];
-            P.L[p] = mk4(ld3(L4) + c_occ, L4.w);
-          }
-          V3 t2 = new_thr * thr;
-          if (!is_black(t2)) {
-            qbit = doomed_bit(t2, rng.state, rng_inc);
-            if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
-              alive = true;
-              P.ray_o[p] = mk4(s.pos, 1e-3f);
-              P.ray_d[p] = mk4(next_dir, kInf);
-              P.thr[p] = mk4(t2, pdf);
-              P.rng[p] = rng.state;
-            } else {
-              qbit = 0u;
-              count_pruned(P);
-            }
-          }
-        }
-      }
-      if (fail) {
-        // walk failed: path ends, the first NEE's contribution still counts (render.cc:79)
+      c_vis = thr * (A + d2);
+      c_occ = thr * (A + V3(0.f));
+      if (!shadow) {
         float4 L4 = P.L[p];
-        P.L[p] = mk4(ld3(L4) + thr * (A + V3(0.f)), L4.w);
+        P.L[p] = mk4(ld3(L4) + c_occ, L4.w);
+      }
+      V3 t2 = new_thr * thr;
+      if (!is_black(t2)) {
+        qbit = doomed_bit(t2, rng.state, rng_inc);
+        if (!(qbit && !ENV && misses_all_lights(sc, s.pos, next_dir, 1e-3f))) {
+          alive = true;
+          P.ray_o[p] = mk4(s.pos, 1e-3f);
+          P.ray_d[p] = mk4(next_dir, kInf);
+          P.thr[p] = mk4(t2, pdf);
+          P.rng[p] = rng.state;
+        } else {
+          qbit = 0u;
+          count_pruned(P);
+        }
       }
     }
-    if (shadow) put_shadow(P, sh_pos, nee, c_vis, c_occ, p, kShSssExit, alive);
-    return (shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit;
+  }
+  if (fail) {
+    // walk failed: path ends, the first NEE's contribution still counts (render.cc:79)
+    float4 L4 = P.L[p];
+    P.L[p] = mk4(ld3(L4) + thr * (A + V3(0.f)), L4.w);
+  }
+  if (shadow) put_shadow(P, sh_pos, nee, c_vis, c_occ, p, kShSssExit, alive);
+  return (shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit;
+}
+// ENV: scenes with an environment; the body in the kernel template, like k_shade_hair's
+template <bool ENV>
+__global__ __launch_bounds__(kBlock) void k_sss_step(PathState P, DScene sc, uint64_t rng_inc) {
+  __shared__ float lds_lights[kLdsLightWords];
+  const bool lights_staged = stage_light_tables(sc, lds_lights);
+  if (lights_staged) __syncthreads();
+  const uint32_t n = P.counts[kCntSss];
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const uint32_t p = P.q_sss[i];
+    P.q_sss[i] = p | sss_step_path<ENV>(P, sc, p, rng_inc, nullptr, lights_staged ? lds_lights : nullptr);
   }
 }
-// (a macro for the same reason as PB_SHADE_HAIR_KERNEL)
-#define PB_SSS_STEP_KERNEL(ENV)                                                                      \
-  __shared__ float lds_lights[kLdsLightWords];                                                       \
-  const bool lights_staged = stage_light_tables(sc, lds_lights);                                    \
-  if (lights_staged) __syncthreads();                                                                \
-  const uint32_t n = P.counts[kCntSss];                                                              \
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {             \
-    const uint32_t p = P.q_sss[i];                                                                   \
-    P.q_sss[i] = p | sss_step_path<ENV>(P, sc, p, rng_inc, nullptr, lights_staged ? lds_lights : nullptr); \
-  }
-__global__ __launch_bounds__(kBlock) void k_sss_step(PathState P, DScene sc, uint64_t rng_inc) { PB_SSS_STEP_KERNEL(false) }
-// scenes with an environment
-__global__ __launch_bounds__(kBlock) void k_sss_step_env(PathState P, DScene sc, uint64_t rng_inc) { PB_SSS_STEP_KERNEL(true) }
-#undef PB_SSS_STEP_KERNEL
 
 // ------------------------------------------------------------------ k_sss_walk
 // Fast-forward of the random walks (RandomWalkSubsurface's loop, random-walk-sss.h:287-405).  A walk alternates a bounded
@@ -1830,34 +1821,19 @@ __global__ __launch_bounds__(kBlock) void k_hook_pv(DScene sc, const float4* __r
 }
 // One ray per thread, plain stack traversal (dtrace.h): an independent second implementation, selected with
 // PBRHIP_SIMPLE_TRAVERSAL=1, that must agree with the production traversal bit for bit.
-template <bool CURVES, bool WIDE>
-__global__ __launch_bounds__(kBlock) void k_hook_closest(DScene sc, const float4* __restrict__ rays, uint32_t n,
-                                                         HookHit* __restrict__ out, uint32_t* overflow_flag, uint32_t* spill) {
+template <bool ANY, bool CURVES, bool WIDE>
+__global__ __launch_bounds__(kBlock) void k_hook_simple(DScene sc, const float4* __restrict__ rays, uint32_t n, HookHit* __restrict__ hits,
+                                                        uint8_t* __restrict__ occ, uint32_t* overflow_flag, uint32_t* spill) {
   __shared__ uint32_t stk[kSimpleLdsStack * kBlock];
   TravStats st = {};
   uint32_t overflow = 0u;
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     float4 o4 = rays[2 * i], d4 = rays[2 * i + 1];
     Hit h;
-    traverse<false, false, CURVES, WIDE>(sc, ld3(o4), ld3(d4), o4.w, fminf(d4.w, INFINITY), h, stk + threadIdx.x, kBlock, st, &overflow,
-                                         spill + blockIdx.x * kBlock + threadIdx.x, gridDim.x * kBlock);
-    out[i] = hook_result(sc, ld3(o4), ld3(d4), h);
-  }
-  if (overflow) *overflow_flag = 1u;
-}
-template <bool CURVES, bool WIDE>
-__global__ __launch_bounds__(kBlock) void k_hook_any(DScene sc, const float4* __restrict__ rays, uint32_t n,
-                                                     uint8_t* __restrict__ out, uint32_t* overflow_flag, uint32_t* spill) {
-  __shared__ uint32_t stk[kSimpleLdsStack * kBlock];
-  TravStats st = {};
-  uint32_t overflow = 0u;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    float4 o4 = rays[2 * i], d4 = rays[2 * i + 1];
-    Hit h;
-    out[i] = traverse<true, false, CURVES, WIDE>(sc, ld3(o4), ld3(d4), o4.w, fminf(d4.w, INFINITY), h, stk + threadIdx.x, kBlock, st,
-                                                 &overflow, spill + blockIdx.x * kBlock + threadIdx.x, gridDim.x * kBlock)
-                 ? 1
-                 : 0;
+    const bool o = traverse<ANY, false, CURVES, WIDE>(sc, ld3(o4), ld3(d4), o4.w, fminf(d4.w, INFINITY), h, stk + threadIdx.x, kBlock, st, &overflow,
+                                                      spill + blockIdx.x * kBlock + threadIdx.x, gridDim.x * kBlock);
+    if (ANY) occ[i] = o ? 1 : 0;
+    else hits[i] = hook_result(sc, ld3(o4), ld3(d4), h);
   }
   if (overflow) *overflow_flag = 1u;
 }
@@ -1902,14 +1878,38 @@ __global__ void k_advance(uint32_t* counts, uint32_t* heads, uint32_t* ring, uin
 // ------------------------------------------------------------------ launchers
 // the Q tree serves the scenes whose tree was built on the host (PBRHIP_WIDE=0: never)
 static inline bool use_wide(const DScene& sc, const Knobs& k) { return sc.wide != nullptr && k.wide; }
-// launches KERNEL<..., CURVES, WIDE> for this scene: (curves, binary), (no curves, binary), (curves, Q), (no curves, Q)
-#define PB_LAUNCH_TRAV(KERNEL, PRE, curves, wide, ...)                                          \
-  do {                                                                                          \
-    if ((wide) && (curves)) hipLaunchKernelGGL((KERNEL<PRE, true, true>), __VA_ARGS__);         \
-    else if (wide) hipLaunchKernelGGL((KERNEL<PRE, false, true>), __VA_ARGS__);                 \
-    else if (curves) hipLaunchKernelGGL((KERNEL<PRE, true, false>), __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<PRE, false, false>), __VA_ARGS__);                          \
-  } while (0)
+// A runtime property of the scene becomes a template argument here and nowhere else: with_flags(f, a, b, ...) calls the generic lambda f
+// with one std::bool_constant per flag, which the lambda's launch names as a template argument (k_trace<st, c, w, first>).  Every
+// combination of the flags is an instance in the code object: a kernel that exists for fewer has a selector of its own below.
+template <class F>
+static inline void with_flags(F&& f) { f(); }
+template <class F, class... Bools>
+static inline void with_flags(F&& f, bool flag, Bools... rest) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// the shading mode of a scene (shade_principled_path): kShadePlain | kShadeMedia | kShadeFull by its materials, kShadeEnv on top
+template <class F>
+static inline void with_shade_mode(F&& f, bool media, bool textured, bool env) {
+  with_flags([&](auto e) {
+    constexpr int kEnv = e ? kShadeEnv : 0;
+    if (textured) f(std::integral_constant<int, kShadeFull | kEnv>{});
+    else if (media) f(std::integral_constant<int, kShadeMedia | kEnv>{});
+    else f(std::integral_constant<int, kShadePlain | kEnv>{});
+  }, env);
+}
+// k_tail's <MODE_, STATS>: the statistics build exists for kShadeFull (with and without kShadeEnv) only
+template <class F>
+static inline void with_tail_mode(F&& f, bool stats, bool media, bool textured, bool env) {
+  if (stats) with_flags([&](auto e) { f(std::integral_constant<int, kShadeFull | (e ? kShadeEnv : 0)>{}, std::true_type{}); }, env);
+  else with_shade_mode([&](auto mode) { f(mode, std::false_type{}); }, media, textured, env);
+}
+// the hooks' <CURVES, WIDE>: the tree the render of this scene walks, but the binary tree's hooks always carry the curve code
+template <class F>
+static inline void with_hook_tree(F&& f, const DScene& sc, const Knobs& k) {
+  if (use_wide(sc, k)) with_flags([&](auto c) { f(c, std::true_type{}); }, sc.num_curves != 0);
+  else f(std::true_type{}, std::false_type{});
+}
 bool trace_uses_wide(const DScene& sc, const Knobs& k) { return use_wide(sc, k); }
 #ifndef PB_TRACE_SMALL1_RAYS
 #define PB_TRACE_SMALL1_RAYS 16000000u  // launches of at most this many rays (upper bound): PB_TRACE_SMALL1_BLOCKS blocks per CU
@@ -1959,29 +1959,15 @@ void launch_trace(hipStream_t s, const PathState& P, const DScene& sc, uint32_t 
   if (P.first) {
     // a group's first launch: camera rays only, computed by the sink (TraceSinkT<.., FIRST>); always the phase-voting kernel
     if (trace_first_less(stats, curves)) cap = std::max(cap, 512u) - 256u;  // (its launch bounds: one block per CU fewer; never below one block per CU -- PBRHIP_TRACE_BLOCKS=1 used to make this 0)
-    dim3 g(blocks < 1u ? 1u : (blocks < cap ? blocks : cap));
-#define PB_LAUNCH_FIRST(ST)                                                                                      \
-  do {                                                                                                           \
-    if (wide && curves) hipLaunchKernelGGL((k_trace<ST, true, true, true>), g, dim3(kBlock), 0, s, P, sc);       \
-    else if (wide) hipLaunchKernelGGL((k_trace<ST, false, true, true>), g, dim3(kBlock), 0, s, P, sc);           \
-    else if (curves) hipLaunchKernelGGL((k_trace<ST, true, false, true>), g, dim3(kBlock), 0, s, P, sc);         \
-    else hipLaunchKernelGGL((k_trace<ST, false, false, true>), g, dim3(kBlock), 0, s, P, sc);                    \
-  } while (0)
-    if (stats) PB_LAUNCH_FIRST(true);
-    else PB_LAUNCH_FIRST(false);
-#undef PB_LAUNCH_FIRST
-    return;
-  }
-  if (wide && !curves && n_upper <= k.quad_rays) {
+  } else if (wide && !curves && n_upper <= k.quad_rays) {
     // a small launch: one ray per quad of lanes
     const dim3 gq(quad_grid(n_upper));
-    if (stats) hipLaunchKernelGGL((k_trace_quad<true>), gq, dim3(kBlock), 0, s, P, sc);
-    else hipLaunchKernelGGL((k_trace_quad<false>), gq, dim3(kBlock), 0, s, P, sc);
+    with_flags([&](auto st) { hipLaunchKernelGGL((k_trace_quad<st>), gq, dim3(kBlock), 0, s, P, sc); }, stats);
     return;
   }
   dim3 g(blocks < 1u ? 1u : (blocks < cap ? blocks : cap));
-  if (stats) PB_LAUNCH_TRAV(k_trace, true, curves, wide, g, dim3(kBlock), 0, s, P, sc);
-  else PB_LAUNCH_TRAV(k_trace, false, curves, wide, g, dim3(kBlock), 0, s, P, sc);
+  with_flags([&](auto st, auto c, auto w, auto first) { hipLaunchKernelGGL((k_trace<st, c, w, first>), g, dim3(kBlock), 0, s, P, sc); },
+             stats, curves, wide, P.first != 0u);
 }
 static inline uint32_t tiles_grid(uint32_t n_upper, int items_per_thread) {
   const uint32_t tile = (uint32_t)items_per_thread * kBlock;
@@ -1991,31 +1977,23 @@ static inline uint32_t tiles_grid(uint32_t n_upper, int items_per_thread) {
 // a scene with an environment (DScene::env_texels) runs the environment instances of the routing and shading kernels
 static inline bool has_env(const DScene& sc) { return sc.env_texels != nullptr; }
 void launch_classify(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper) {
-  if (has_env(sc)) hipLaunchKernelGGL(k_classify_env, dim3(tiles_grid(n_upper, kClassifyItems)), dim3(kBlock), 0, s, P, sc);
-  else hipLaunchKernelGGL(k_classify, dim3(tiles_grid(n_upper, kClassifyItems)), dim3(kBlock), 0, s, P, sc);
+  const dim3 g(tiles_grid(n_upper, kClassifyItems));
+  with_flags([&](auto env) { hipLaunchKernelGGL(k_classify<env>, g, dim3(kBlock), 0, s, P, sc); }, has_env(sc));
 }
 void launch_compact(hipStream_t s, const PathState& P, uint32_t n_upper) {
   hipLaunchKernelGGL(k_compact, dim3(tiles_grid(n_upper, kCompactItems)), dim3(kBlock), 0, s, P);
 }
 void launch_shade_principled(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool media, bool textured) {
   const dim3 g(grid_for(n_upper, kShadeGridCap));
-  if (has_env(sc)) {
-    if (textured) hipLaunchKernelGGL(k_shade_principled<kShadeFull | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    else if (media) hipLaunchKernelGGL(k_shade_principled<kShadeMedia | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    else hipLaunchKernelGGL(k_shade_principled<kShadePlain | kShadeEnv>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    return;
-  }
-  if (textured) hipLaunchKernelGGL(k_shade_principled<kShadeFull>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else if (media) hipLaunchKernelGGL(k_shade_principled<kShadeMedia>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else hipLaunchKernelGGL(k_shade_principled<kShadePlain>, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+  with_shade_mode([&](auto mode) { hipLaunchKernelGGL(k_shade_principled<mode>, g, dim3(kBlock), 0, s, P, sc, rng_inc); }, media, textured, has_env(sc));
 }
 void launch_shade_hair(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc) {
-  if (has_env(sc)) hipLaunchKernelGGL(k_shade_hair_env, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
-  else hipLaunchKernelGGL(k_shade_hair, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  const dim3 g(grid_for(n_upper, kShadeGridCap));
+  with_flags([&](auto env) { hipLaunchKernelGGL(k_shade_hair<env>, g, dim3(kBlock), 0, s, P, sc, rng_inc); }, has_env(sc));
 }
 void launch_sss_step(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc) {
-  if (has_env(sc)) hipLaunchKernelGGL(k_sss_step_env, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
-  else hipLaunchKernelGGL(k_sss_step, dim3(grid_for(n_upper, kShadeGridCap)), dim3(kBlock), 0, s, P, sc, rng_inc);
+  const dim3 g(grid_for(n_upper, kShadeGridCap));
+  with_flags([&](auto env) { hipLaunchKernelGGL(k_sss_step<env>, g, dim3(kBlock), 0, s, P, sc, rng_inc); }, has_env(sc));
 }
 void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, const Knobs& k) {
   const bool curves = sc.num_curves != 0;
@@ -2024,8 +2002,7 @@ void launch_sss_walk(hipStream_t s, const PathState& P, const DScene& sc, uint32
   const uint32_t cap = 256u * (stats ? (uint32_t)PB_WALK_WAVES : walk_blocks_per_cu(curves, wide));
   const uint32_t blocks = (n_upper + 15u) / 16u;
   dim3 g(blocks < 1u ? 1u : (blocks < cap ? blocks : cap));
-  if (stats) PB_LAUNCH_TRAV(k_sss_walk, true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else PB_LAUNCH_TRAV(k_sss_walk, false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+  with_flags([&](auto st, auto c, auto w) { hipLaunchKernelGGL((k_sss_walk<st, c, w>), g, dim3(kBlock), 0, s, P, sc, rng_inc); }, stats, curves, wide);
 }
 void launch_accumulate(hipStream_t s, const PathState& P, const uint32_t* pix_index, uint32_t npix, uint32_t npass,
                        float* rgba, uint32_t* count) {
@@ -2037,24 +2014,15 @@ void launch_accumulate(hipStream_t s, const PathState& P, const uint32_t* pix_in
 static_assert((size_t)(kStackDepth - kSimpleLdsStack) * PB_TAIL_BLOCKS * 256 <= kSpillWords, "k_tail's spill area (one stack per thread of its grid)");
 static_assert(trace_blocks_per_cu(false, true) * 256u <= kTraceGridCap && trace_blocks_per_cu(true, true) * 256u <= kTraceGridCap,
               "the Q tree's k_trace grids fit the spill area sized by kTraceGridCap");
-#define PB_COMMA ,
 void launch_tail(hipStream_t s, const PathState& P, const DScene& sc, uint32_t n_upper, uint64_t rng_inc, bool stats, bool media, bool textured,
                  const Knobs& k) {
   uint32_t blocks = (n_upper + 3u) / 4u;  // one path per wave while that fits, at most 2 blocks per CU
   dim3 g(blocks < 1u ? 1u : (blocks < PB_TAIL_BLOCKS ? blocks : PB_TAIL_BLOCKS));
   const bool curves = sc.num_curves != 0;
   const bool wide = use_wide(sc, k);
-  if (has_env(sc)) {
-    if (stats) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    else if (textured) PB_LAUNCH_TRAV(k_tail, kShadeFull | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    else if (media) PB_LAUNCH_TRAV(k_tail, kShadeMedia | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    else PB_LAUNCH_TRAV(k_tail, kShadePlain | kShadeEnv PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-    return;
-  }
-  if (stats) PB_LAUNCH_TRAV(k_tail, kShadeFull PB_COMMA true, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else if (textured) PB_LAUNCH_TRAV(k_tail, kShadeFull PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else if (media) PB_LAUNCH_TRAV(k_tail, kShadeMedia PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
-  else PB_LAUNCH_TRAV(k_tail, kShadePlain PB_COMMA false, curves, wide, g, dim3(kBlock), 0, s, P, sc, rng_inc);
+  with_tail_mode([&](auto mode, auto st) {
+    with_flags([&](auto c, auto w) { hipLaunchKernelGGL((k_tail<mode, st, c, w>), g, dim3(kBlock), 0, s, P, sc, rng_inc); }, curves, wide);
+  }, stats, media, textured, has_env(sc));
 }
 void launch_layer_pack(hipStream_t s, const uint32_t* pix, uint32_t npix, const float* rgba, const uint32_t* count, float* shard) {
   if (!npix) return;
@@ -2069,42 +2037,21 @@ void launch_layer_unpack_add(hipStream_t s, const uint32_t* pix, uint32_t npix, 
 }
 void launch_advance(hipStream_t s, const PathState& P, uint32_t* ring_slot, uint32_t stamp) { hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, s, P.counts, P.heads, ring_slot, stamp); }
 // counts: kCntNum zeroed words (queue head + overflow flag); spill: traversal-stack spill area
-void launch_hook_closest(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* out, uint32_t* counts,
-                         uint32_t* spill, const Knobs& k) {
-  // the variant of the traversal the render of this scene runs; the binary tree's hooks always carry the curve code
-  const bool wide = use_wide(sc, k), curves = !wide || sc.num_curves != 0;
-  if (k.simple_traversal) {
-    if (wide && curves) hipLaunchKernelGGL((k_hook_closest<true, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    else if (wide) hipLaunchKernelGGL((k_hook_closest<false, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    else hipLaunchKernelGGL((k_hook_closest<true, false>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    return;
-  }
-  if (wide && !curves && k.quad) {
-    hipLaunchKernelGGL((k_hook_quad<false>), dim3(quad_grid(n)), dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts + kCntOverflow, spill);
-    return;
-  }
-  const dim3 g(grid_for(n, kTraceGridCap));
-  if (wide && curves) hipLaunchKernelGGL((k_hook_pv<false, true, true>), g, dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts, spill);
-  else if (wide) hipLaunchKernelGGL((k_hook_pv<false, false, true>), g, dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts, spill);
-  else hipLaunchKernelGGL((k_hook_pv<false, true, false>), g, dim3(kBlock), 0, s, sc, rays, n, out, (uint8_t*)nullptr, counts, spill);
-}
-void launch_hook_any(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, uint8_t* out, uint32_t* counts,
-                     uint32_t* spill, const Knobs& k) {
-  const bool wide = use_wide(sc, k), curves = !wide || sc.num_curves != 0;
-  if (k.simple_traversal) {
-    if (wide && curves) hipLaunchKernelGGL((k_hook_any<true, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    else if (wide) hipLaunchKernelGGL((k_hook_any<false, true>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    else hipLaunchKernelGGL((k_hook_any<true, false>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, out, counts + kCntOverflow, spill);
-    return;
-  }
-  if (wide && !curves && k.quad) {
-    hipLaunchKernelGGL((k_hook_quad<true>), dim3(quad_grid(n)), dim3(kBlock), 0, s, sc, rays, n, (HookHit*)nullptr, out, counts + kCntOverflow, spill);
-    return;
-  }
-  const dim3 g(grid_for(n, kTraceGridCap));
-  if (wide && curves) hipLaunchKernelGGL((k_hook_pv<true, true, true>), g, dim3(kBlock), 0, s, sc, rays, n, (HookHit*)nullptr, out, counts, spill);
-  else if (wide) hipLaunchKernelGGL((k_hook_pv<true, false, true>), g, dim3(kBlock), 0, s, sc, rays, n, (HookHit*)nullptr, out, counts, spill);
-  else hipLaunchKernelGGL((k_hook_pv<true, true, false>), g, dim3(kBlock), 0, s, sc, rays, n, (HookHit*)nullptr, out, counts, spill);
+// occ != null: any-hit (n occlusion bytes), else closest-hit (n HookHit in hits); the other pointer is null
+void launch_hook(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n, HookHit* hits, uint8_t* occ, uint32_t* counts, uint32_t* spill,
+                 const Knobs& k) {
+  with_flags([&](auto any) {
+    if (k.simple_traversal) {
+      with_hook_tree([&](auto c, auto w) {
+        hipLaunchKernelGGL((k_hook_simple<any, c, w>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, sc, rays, n, hits, occ, counts + kCntOverflow, spill);
+      }, sc, k);
+    } else if (use_wide(sc, k) && sc.num_curves == 0 && k.quad) {
+      hipLaunchKernelGGL((k_hook_quad<any>), dim3(quad_grid(n)), dim3(kBlock), 0, s, sc, rays, n, hits, occ, counts + kCntOverflow, spill);
+    } else {
+      const dim3 g(grid_for(n, kTraceGridCap));
+      with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_hook_pv<any, c, w>), g, dim3(kBlock), 0, s, sc, rays, n, hits, occ, counts, spill); }, sc, k);
+    }
+  }, occ != nullptr);
 }
 
 }  // namespace pb

@@ -1826,8 +1826,7 @@ static int trace_hook(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, void* o
   HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
   HIPCHK(hipMemcpyAsync(s->hook_rays.p, rays, n * sizeof(pbrhip_ray), hipMemcpyHostToDevice, s->stream));
   HIPCHK(s->spill.reserve(kSpillWords));
-  if (any) launch_hook_any(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_occ.p, s->counts.p, s->spill.p, k);
-  else launch_hook_closest(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, s->hook_hits.p, s->counts.p, s->spill.p, k);
+  launch_hook(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, any ? nullptr : s->hook_hits.p, any ? s->hook_occ.p : nullptr, s->counts.p, s->spill.p, k);
   HIPCHK(hipGetLastError());
   if (any) HIPCHK(hipMemcpyAsync(out, s->hook_occ.p, n, hipMemcpyDeviceToHost, s->stream));
   else HIPCHK(hipMemcpyAsync(out, s->hook_hits.p, n * sizeof(pbrhip_hit), hipMemcpyDeviceToHost, s->stream));

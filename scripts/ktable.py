@@ -1,29 +1,52 @@
 #!/usr/bin/env python3
-"""VGPRs / scratch of the kernels of a built library: scripts/ktable.py [path/to/libpbrhip.so] [name prefix ...]"""
-import os, re, subprocess, sys, tempfile, shutil
-LLVM = "/opt/rocm/lib/llvm/bin"
-lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrlab_amd", "libpbrhip.so")
-tmp = tempfile.mkdtemp()
-try:
-    fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib], check=True, capture_output=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-finally:
-    shutil.rmtree(tmp, ignore_errors=True)
-table, cur, lds = {}, {}, 0
-for line in notes.splitlines():   # (the keys of a kernel's record come in alphabetical order: .group_segment_fixed_size BEFORE .name)
-    m = re.match(r"\s+\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\S+)", line)
-    if m:
-        if m.group(1) == "group_segment_fixed_size":
-            lds = int(m.group(2))
-        elif m.group(1) == "name":
-            cur = table.setdefault(m.group(2), {})
-            cur["group_segment_fixed_size"] = lds
-        else:
-            cur[m.group(1)] = int(m.group(2))
-names = subprocess.run(["c++filt"] + list(table), check=True, capture_output=True, text=True).stdout.split("\n")
-for d, v in sorted(zip(names, table.values())):
-    n = d.replace("void pb::", "").replace("pb::", "").split("(")[0]
-    if len(sys.argv) <= 2 or n.startswith(tuple(sys.argv[2:])):
-        print(f"{n:50s} vgpr {v.get('vgpr_count'):4d} scratch {v.get('private_segment_fixed_size'):4d} lds {v.get('group_segment_fixed_size'):6d}")
+"""The kernels of a built library, read from its gfx950 code object (tests/_codeobj.py):
+
+  scripts/ktable.py [libpbrhip.so] [name prefix ...]          registers / scratch / LDS of each kernel
+  scripts/ktable.py [libpbrhip.so] --diff OTHER.so [old=new ...]
+      OTHER's kernels against this library's, instruction by instruction (position-independent text) and by their metadata;
+      old=new renames a kernel of OTHER first.  Exit status 1 when a kernel differs or exists on one side only."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import _codeobj as CO
+
+
+def show(lib, prefixes):
+    for n, v in sorted(CO.kernel_table(lib).items()):
+        if not prefixes or n.startswith(prefixes):
+            print(f"{n:50s} vgpr {v['vgpr_count']:4d} sgpr {v['sgpr_count']:4d} scratch {v['private_segment_fixed_size']:4d} lds {v['group_segment_fixed_size']:6d}")
+
+
+def diff(lib, other, renames):
+    ren = dict(r.split("=", 1) for r in renames)
+    new_t, new_d = CO.kernel_table(lib), CO.disassembly(lib)
+    old_t = {ren.get(k, k): v for k, v in CO.kernel_table(other).items()}
+    old_d = {ren.get(k, k): v for k, v in CO.disassembly(other).items()}
+    only_old, only_new = sorted(set(old_t) - set(new_t)), sorted(set(new_t) - set(old_t))
+    lib, other = os.path.relpath(lib), os.path.relpath(other)
+    print(f"kernels: {len(old_t)} in {other}, {len(new_t)} in {lib}")
+    for side, names in ((other, only_old), (lib, only_new)):
+        for n in names:
+            print(f"only in {side}: {n}")
+    same = different = 0
+    for n in sorted(set(old_t) & set(new_t)):
+        meta = [f"{f} {old_t[n][f]} -> {new_t[n][f]}" for f in CO.FIELDS if old_t[n][f] != new_t[n][f]]
+        if old_d[n] == new_d[n] and not meta:
+            same += 1
+            continue
+        different += 1
+        moved = sum(1 for a, b in zip(old_d[n], new_d[n]) if a != b)
+        print(f"DIFF {n}: {len(old_d[n])} -> {len(new_d[n])} instructions, {moved} lines differ in place" + "".join("; " + m for m in meta))
+    print(f"identical: {same} different: {different}")
+    return 1 if different or only_old or only_new else 0
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    lib = args.pop(0) if args and args[0] != "--diff" else CO.LIB
+    if args and args[0] == "--diff":
+        if len(args) < 2:
+            sys.exit(__doc__)
+        sys.exit(diff(lib, args[1], args[2:]))
+    show(lib, tuple(args))

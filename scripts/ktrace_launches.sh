@@ -1,5 +1,6 @@
 #!/bin/bash
 # scripts/ktrace_launches.sh lib.so: per-launch k_trace durations (ms) of one C2 render (64 spp, one path group), WIDE=1 and WIDE=0
+# (kernels are matched by the name in front of their template arguments: k_classify is k_classify<false> and k_classify<true>)
 export TMPDIR=/tmp VARIANT=${VARIANT:-ggx} SPP=${SPP:-64} PBRHIP_STREAMS=1 REPS=1
 lib=$(realpath $1)
 for w in 1 0; do

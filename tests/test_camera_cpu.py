@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import _camera_analytic as CA
-from test_kernel_budgets import kernel_table, waves_per_simd
+from _codeobj import waves_per_simd
+from test_kernel_budgets import kernel_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "pbrlab_amd", "pbrlab-hip-cli")

@@ -3,7 +3,7 @@
 The environment is this project's own light: the reference leaves a miss black, so only the oracle (oracle/pbr_oracle.c: the miss,
 the NEE selection, the environment's estimate and shadow ray, each call site's normal and hemisphere rule, 1 - p_env on the area
 lights' NEE and emission-hit MIS) can hold the kernels that carry it -- k_shade_principled<4|5|6>, k_tail<4|5|6, ...>,
-k_classify_env, k_shade_hair_env, k_sss_step_env -- to something independent of them.  With the device's arithmetic
+k_classify<true>, k_shade_hair<true>, k_sss_step<true> -- to something independent of them.  With the device's arithmetic
 (MATH_DEVICE) every pixel's rgba and count must be the oracle's bits, not merely close, and the GPU's closest-hit and shadow ray
 counts the oracle's:
   - the five test_gpu_parity scenes x k_tail hand-overs (never / at once / mid-render) x two maps: a constant one on the scene with
