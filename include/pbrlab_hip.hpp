@@ -518,5 +518,62 @@ inline bool Render(const std::vector<const Scene*>& scenes, const uint32_t width
   return true;
 }
 
+// ---- first-hit feature buffers and the denoiser (not in the reference) ----
+// albedo: sum of albedo rgb | hits; normal_depth: sum of the viewer-facing shading normal | sum of the hit distance; count: samples
+struct FeatureLayer {
+  FeatureLayer() = default;
+  FeatureLayer(size_t w, size_t h) { Resize(w, h), Clear(); }
+  void Clear() {
+    std::fill(albedo.begin(), albedo.end(), 0.0f);
+    std::fill(normal_depth.begin(), normal_depth.end(), 0.0f);
+    std::fill(count.begin(), count.end(), 0u);
+  }
+  void Resize(size_t w, size_t h) {
+    width = w, height = h;
+    albedo.resize(w * h * 4);
+    normal_depth.resize(w * h * 4);
+    count.resize(w * h);
+  }
+  size_t width = 0, height = 0;
+  std::vector<float> albedo, normal_depth;
+  std::vector<uint32_t> count;
+};
+
+// pbrhip_render_features: the features of passes [first_pass, first_pass + num_sample) of the frame Render() makes of this scene.
+// Resizes *features unless no_clear, which accumulates on top of it.  Throws with pbrhip_last_error() on a library error.
+inline void RenderFeatures(const Scene& scene, const uint32_t width, const uint32_t height, const uint32_t num_sample, FeatureLayer* features,
+                           const uint32_t first_pass = 0, const bool no_clear = false) {
+  if (!no_clear || features->width != width || features->height != height) features->Resize(width, height);
+  scene.PushMaterialEdits();
+  pbrhip_render_desc d = {};
+  d.width = width, d.height = height, d.num_sample = num_sample, d.first_pass = first_pass;
+  d.seed_seq = 1234567890;  // Render()'s
+  d.tile_world = 1;
+  d.flags = no_clear ? PBRHIP_RENDER_NO_CLEAR : 0u;
+  if (pbrhip_render_features(scene.handle(), &d, features->albedo.data(), features->normal_depth.data(), features->count.data()) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderFeatures: ") + pbrhip_last_error());
+}
+
+struct DenoiseOptions {
+  uint32_t iterations = 0;  // 0: PBRHIP_DENOISE_ITERATIONS
+  float sigma_color = PBRHIP_DENOISE_SIGMA_COLOR, sigma_depth = PBRHIP_DENOISE_SIGMA_DEPTH;  // <= 0: that weight off
+  uint32_t normal_squarings = PBRHIP_DENOISE_NORMAL_SQUARINGS;
+  bool albedo = true;  // false: PBRHIP_DENOISE_NO_ALBEDO
+  int device = 0;
+};
+// pbrhip_denoise: the edge-avoiding A-trous filter of `layer` guided by `features` (nullptr: by colour alone) -> width x height x 4
+// floats, the denoised mean colour | 1.  Throws with pbrhip_last_error() on a library error.
+inline std::vector<float> Denoise(const RenderLayer& layer, const FeatureLayer* features, const DenoiseOptions& o = DenoiseOptions()) {
+  if (features && (features->width != layer.width || features->height != layer.height))
+    throw std::runtime_error("pbrlab::Denoise: features and layer differ in size");
+  std::vector<float> out(layer.width * layer.height * 4);
+  const int rc = pbrhip_denoise(o.device, uint32_t(layer.width), uint32_t(layer.height), layer.rgba.data(), layer.count.data(),
+                                features ? features->albedo.data() : nullptr, features ? features->normal_depth.data() : nullptr,
+                                features ? features->count.data() : nullptr, o.iterations, o.sigma_color, o.sigma_depth, o.normal_squarings,
+                                o.albedo ? 0u : PBRHIP_DENOISE_NO_ALBEDO, out.data());
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::Denoise: ") + pbrhip_last_error());
+  return out;
+}
+
 }  // namespace pbrlab
 #endif  // PBRLAB_HIP_HPP_

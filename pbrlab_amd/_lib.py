@@ -23,6 +23,7 @@ EXPORTS = [
     "pbrhip_render", "pbrhip_render_device", "pbrhip_trace_closest", "pbrhip_trace_any", "pbrhip_leaf_eval", "pbrhip_texture_fetch", "pbrhip_create_tiles",
     "pbrhip_render_multi", "pbrhip_scene_replicate", "pbrhip_comm_unique_id", "pbrhip_comm_create", "pbrhip_comm_destroy",
     "pbrhip_comm_reduce_layer", "pbrhip_comm_gather_layer",
+    "pbrhip_render_features", "pbrhip_render_features_device", "pbrhip_denoise", "pbrhip_denoise_device",
 ]
 
 
@@ -49,6 +50,9 @@ def lib():
         _lib.pbrhip_abi_version.restype = C.c_uint32
         _lib.pbrhip_math_mode.restype = C.c_uint32
         _lib.pbrhip_sizeof_render_stats.restype = C.c_size_t
+        vp, u32, f32 = C.c_void_p, C.c_uint32, C.c_float
+        _lib.pbrhip_render_features.argtypes = _lib.pbrhip_render_features_device.argtypes = [vp, vp, vp, vp, vp]
+        _lib.pbrhip_denoise.argtypes = _lib.pbrhip_denoise_device.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, u32, f32, f32, u32, u32, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -129,8 +129,13 @@ def device_count():
     return n.value
 
 
+_device = 0  # what set_device selected (Denoise runs there)
+
+
 def set_device(i):
+    global _device
     _chk(_lib.lib().pbrhip_set_device(int(i)))
+    _device = int(i)
 
 
 def create_tiles(width, height):
@@ -365,6 +370,98 @@ def Render(scene, width, height, num_sample, cancel_render_flag=None, layer=None
     _chk(L.pbrhip_render(scene.h, C.byref(desc), cancel, _ptr(layer.rgba), _ptr(layer.count, u32p), C.byref(fin),
                          C.byref(st)))
     return True, st.as_dict()
+
+
+# pbrhip_denoise's defaults (include/pbrhip.h PBRHIP_DENOISE_*)
+DENOISE_NO_ALBEDO = 1
+DENOISE_ITERATIONS, DENOISE_NORMAL_SQUARINGS, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_DEPTH = 5, 7, 0.5, 0.2
+
+
+class FeatureLayer:
+    """First-hit feature buffers (pbrhip_render_features): albedo (H, W, 4) = sum of albedo rgb | hits, normal_depth
+    (H, W, 4) = sum of the viewer-facing shading normal | sum of the hit distance, count (H, W) = samples."""
+
+    def __init__(self, w=0, h=0):
+        self.Resize(w, h)
+
+    def Resize(self, w, h):
+        self.width, self.height = int(w), int(h)
+        self.albedo = np.zeros((self.height, self.width, 4), np.float32)
+        self.normal_depth = np.zeros((self.height, self.width, 4), np.float32)
+        self.count = np.zeros((self.height, self.width), np.uint32)
+
+    def Clear(self):
+        self.albedo[...] = 0
+        self.normal_depth[...] = 0
+        self.count[...] = 0
+
+    def mean_albedo(self):
+        """(H, W, 3): the mean albedo over all samples, a miss counting as white (what the filter demodulates by); 1 without samples"""
+        m = self.count.astype(np.float64)[..., None]
+        a = self.albedo.astype(np.float64)
+        return np.where(m > 0, (a[..., :3] + (m - a[..., 3:4])) / np.maximum(m, 1), 1.0).astype(np.float32)
+
+    def mean_normal(self):
+        """(H, W, 3): the normalised normal sum; 0 where no sample hit"""
+        n = self.normal_depth[..., :3].astype(np.float64)
+        l = np.sqrt((n * n).sum(-1, keepdims=True))
+        return np.where(l > 0, n / np.where(l > 0, l, 1), 0.0).astype(np.float32)
+
+    def mean_depth(self):
+        """(H, W): the mean hit distance over the samples that hit; inf where none did"""
+        k = self.albedo[..., 3].astype(np.float64)
+        return np.where(k > 0, self.normal_depth[..., 3] / np.where(k > 0, k, 1), np.inf).astype(np.float32)
+
+
+def RenderFeatures(scene, width, height, num_sample, layer=None, *, first_pass=0, seed_seq=1234567890, tile_rank=0, tile_world=1,
+                   max_paths_in_flight=0, shard_block=0, no_clear=False, device_out=None):
+    """pbrhip_render_features: the first-hit features of passes [first_pass, first_pass + num_sample) of the frame Render makes from the
+    same arguments, into `layer` (a FeatureLayer; resized unless no_clear, which accumulates on top).  Returns the layer.
+    device_out: optional (albedo_ptr, normal_depth_ptr, count_ptr) DEVICE pointers (ints, 0 / None = not wanted) instead of a layer."""
+    L = _lib.lib()
+    desc = RenderDesc(width, height, num_sample, first_pass, seed_seq, tile_rank, tile_world, max_paths_in_flight,
+                      RENDER_NO_CLEAR if no_clear else 0, 0, 0, shard_block)
+    if device_out is not None:
+        _chk(L.pbrhip_render_features_device(scene.h, C.byref(desc), *[C.c_void_p(p or None) for p in device_out]))
+        return None
+    if layer is None:
+        layer = FeatureLayer()
+    if not no_clear or (layer.width, layer.height) != (width, height):
+        layer.Resize(width, height)
+    _chk(L.pbrhip_render_features(scene.h, C.byref(desc), layer.albedo.ctypes.data, layer.normal_depth.ctypes.data, layer.count.ctypes.data))
+    return layer
+
+
+def _denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo):
+    return (int(iterations), float(DENOISE_SIGMA_COLOR if sigma_color is None else sigma_color),
+            float(DENOISE_SIGMA_DEPTH if sigma_depth is None else sigma_depth), int(normal_squarings), 0 if albedo else DENOISE_NO_ALBEDO)
+
+
+def Denoise(layer, features=None, *, iterations=0, sigma_color=None, sigma_depth=None, normal_squarings=DENOISE_NORMAL_SQUARINGS,
+            albedo=True, device=None):
+    """pbrhip_denoise: the edge-avoiding A-trous filter of a RenderLayer guided by a FeatureLayer (None: by colour alone) -> (H, W, 4)
+    float32, the denoised mean colour | 1.  iterations 0 = 5; a sigma of None = the library's default, <= 0 = that weight off."""
+    h, w = layer.count.shape
+    if features is not None and features.count.shape != (h, w):
+        raise ValueError("features and layer differ in size")
+    rgba, count = np.ascontiguousarray(layer.rgba, np.float32), np.ascontiguousarray(layer.count, np.uint32)
+    f = (None, None, None)
+    if features is not None:
+        f = (np.ascontiguousarray(features.albedo, np.float32), np.ascontiguousarray(features.normal_depth, np.float32),
+             np.ascontiguousarray(features.count, np.uint32))
+    out = np.zeros((h, w, 4), np.float32)
+    _chk(_lib.lib().pbrhip_denoise(_device if device is None else int(device), w, h, rgba.ctypes.data, count.ctypes.data,
+                                   *[None if a is None else a.ctypes.data for a in f],
+                                   *_denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo), out.ctypes.data))
+    return out
+
+
+def DenoiseDevice(device, width, height, rgba_ptr, count_ptr, out_ptr, features=None, *, iterations=0, sigma_color=None, sigma_depth=None,
+                  normal_squarings=DENOISE_NORMAL_SQUARINGS, albedo=True):
+    """pbrhip_denoise_device: the same on DEVICE pointers (ints) of `device`; features = (albedo_ptr, normal_depth_ptr, count_ptr) or None."""
+    f = (None, None, None) if features is None else tuple(features)
+    _chk(_lib.lib().pbrhip_denoise_device(int(device), width, height, rgba_ptr, count_ptr, *f,
+                                          *_denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo), out_ptr))
 
 
 def _desc(width, height, num_sample, first_pass=0, seed_seq=1234567890, tile_rank=0, tile_world=1,

@@ -3,6 +3,7 @@
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
 //                  [--gpus N] [--bvh host|gpu] [--env FILE [--env-scale S]]
 //                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
+//                  [--aov PREFIX] [--denoise] [--feature-spp N]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
@@ -12,6 +13,11 @@
 // (.hdr, .exr or any LDR format pbrio_image_load reads), times --env-scale (default 1).  --eye / --lookat replace
 // the reference's camera with a look-at camera: --up (default 0,1,0), vertical --fov in degrees (default 30), a thin
 // lens of --lens-radius (default 0: a pinhole) focused at --focus along the view direction (default 0: |lookat - eye|).
+// --aov PREFIX writes the first-hit features: PREFIX.albedo.png (mean albedo, sRGB like the image), PREFIX.normal.png
+// (0.5 N + 0.5, linear) and PREFIX.depth.png ((z - z_min) / (z_max - z_min) over the covered pixels, background 1).  --denoise filters the
+// frame with the edge-avoiding A-trous filter before it is written.  Both use the features of the first --feature-spp passes (default:
+// min(spp, 16)), rendered on the first GPU.
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <cmath>
@@ -35,6 +41,9 @@ int main(int argc, char** argv) {
   float env_scale = 1.0f;
   bool have_eye = false, have_lookat = false;
   float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, 0}, up[3] = {0, 1, 0}, fov = 30.0f, lens_radius = 0.0f, focus = 0.0f;
+  const char* aov = nullptr;
+  bool denoise = false;
+  size_t feature_spp = 0;
   std::vector<const char*> files;
   files.push_back(argv[0]);
   for (int i = 1; i < argc; ++i) {
@@ -65,6 +74,9 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = int(number("--gpus", 1024));
     else if (a == "--bvh") bvh = std::string(value("--bvh")) == "gpu" ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
     else if (a == "--env") env = value("--env");
+    else if (a == "--aov") aov = value("--aov");
+    else if (a == "--denoise") denoise = true;
+    else if (a == "--feature-spp") feature_spp = number("--feature-spp", 0xFFFFFFFFul);
     else if (a == "--env-scale") {
       const char* v = value("--env-scale");
       char* end = nullptr;
@@ -108,6 +120,10 @@ int main(int argc, char** argv) {
   }
   if (have_eye != have_lookat) {
     std::cerr << (have_eye ? "--eye needs --lookat" : "--lookat needs --eye") << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (feature_spp && !aov && !denoise) {
+    std::cerr << "--feature-spp needs --aov or --denoise" << std::endl;
     return EXIT_FAILURE;
   }
   if (files.size() < 2) {
@@ -183,9 +199,60 @@ int main(int argc, char** argv) {
       return EXIT_FAILURE;
   }
 
-  const size_t slash = out.find_last_of('/');
-  const std::string dir = slash == std::string::npos ? "./" : out.substr(0, slash + 1);
-  const std::string name = slash == std::string::npos ? out : out.substr(slash + 1);
+  // a path as WritePNG takes it: directory (with the slash) + file name
+  auto split = [](const std::string& path, std::string* dir, std::string* name) {
+    const size_t slash = path.find_last_of('/');
+    *dir = slash == std::string::npos ? "./" : path.substr(0, slash + 1);
+    *name = slash == std::string::npos ? path : path.substr(slash + 1);
+  };
+  std::string dir, name;
+  const size_t npx = width * height;
+  if (aov || denoise) {
+    pbrlab::FeatureLayer feat;
+    const std::vector<uint32_t> ones(npx, 1u);
+    try {
+      pbrlab::RenderFeatures(scene, uint32_t(width), uint32_t(height), uint32_t(feature_spp ? feature_spp : std::min<size_t>(samples, 16)), &feat);
+      if (denoise) {  // the mean colour takes the layer's place: sum = mean, count = 1
+        layer.rgba = pbrlab::Denoise(layer, &feat);
+        layer.count = ones;
+      }
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return EXIT_FAILURE;
+    }
+    if (aov) {
+      std::vector<float> albedo(npx * 4, 1.0f);
+      std::vector<uint8_t> normal(npx * 3), depth(npx * 3);
+      auto byte = [](float x) { return uint8_t(std::min(255.0f, std::max(0.0f, x * 256.0f))); };
+      float zmin = INFINITY, zmax = -INFINITY;
+      for (size_t i = 0; i < npx; ++i)
+        if (feat.albedo[4 * i + 3] > 0.0f) {
+          const float z = feat.normal_depth[4 * i + 3] / feat.albedo[4 * i + 3];
+          zmin = std::min(zmin, z), zmax = std::max(zmax, z);
+        }
+      for (size_t i = 0; i < npx; ++i) {
+        const float m = float(feat.count[i]), k = feat.albedo[4 * i + 3];
+        const float* nd = &feat.normal_depth[4 * i];
+        const float len = std::sqrt(nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2]);
+        for (size_t c = 0; c < 3; ++c) {
+          if (m > 0.0f) albedo[4 * i + c] = (feat.albedo[4 * i + c] + (m - k)) / m;  // a miss counts as white
+          normal[3 * i + c] = byte(len > 0.0f ? 0.5f * nd[c] / len + 0.5f : 0.5f);
+          depth[3 * i + c] = byte(k > 0.0f && zmax > zmin ? (nd[3] / k - zmin) / (zmax - zmin) : (k > 0.0f ? 0.0f : 1.0f));
+        }
+      }
+      split(std::string(aov) + ".albedo.png", &dir, &name);
+      int rc = pbrio_write_layer_png(name.c_str(), dir.c_str(), albedo.data(), ones.data(), width, height);
+      split(std::string(aov) + ".normal.png", &dir, &name);
+      if (rc == PBRHIP_OK) rc = pbrio_write_png_u8(name.c_str(), dir.c_str(), normal.data(), width, height, 3);
+      split(std::string(aov) + ".depth.png", &dir, &name);
+      if (rc == PBRHIP_OK) rc = pbrio_write_png_u8(name.c_str(), dir.c_str(), depth.data(), width, height, 3);
+      if (rc != PBRHIP_OK) {
+        std::cerr << "--aov: " << pbrio_last_error() << std::endl;
+        return EXIT_FAILURE;
+      }
+    }
+  }
+  split(out, &dir, &name);
   if (pbrio_write_layer_png(name.c_str(), dir.c_str(), layer.rgba.data(), layer.count.data(), width, height) != PBRHIP_OK) {
     std::cerr << pbrio_last_error() << std::endl;
     return EXIT_FAILURE;

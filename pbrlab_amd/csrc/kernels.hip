@@ -19,6 +19,7 @@
 // k_accumulate (render.cc:175-183) bracket a chunk of passes.
 #include <type_traits>
 
+#include "dcamera.h"
 #include "dshade.h"
 #include "kernels.h"
 #include "dtrace_pv.h"
@@ -59,29 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_generate(PathState P, uint32_t npath
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < npaths; j += gridDim.x * kBlock) P.L[P.slot0 + j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
-// ------------------------------------------------------------------ the user camera
-// The camera ray of pixel (x, y) from a generator seeded for its sample: jx, jy, then (thin lens only) u1, u2 for the lens point
-// rho (cos phi, sin phi), rho = lens sqrt(u1), phi = 2 pi u2.  Direction: through the pixel's point on the focal plane.
-__device__ __forceinline__ void user_camera_ray(const UserCamera& c, uint32_t x, uint32_t y, uint32_t width, uint32_t height, Rng& rng, V3& o,
-                                                V3& d) {
-  const float jx = draw(rng);
-  const float jy = draw(rng);
-  const float sx = (2.0f * ((float)x + jx) / (float)width - 1.0f) * c.ha;
-  const float sy = (1.0f - 2.0f * ((float)y + jy) / (float)height) * c.h;
-  const V3 f(c.f[0], c.f[1], c.f[2]), r(c.r[0], c.r[1], c.r[2]), u(c.u[0], c.u[1], c.u[2]);
-  const V3 p = f + sx * r + sy * u;
-  o = V3(c.eye[0], c.eye[1], c.eye[2]);
-  if (c.lens > 0.0f) {
-    const float u1 = draw(rng);
-    const float u2 = draw(rng);
-    const float rho = c.lens * sqrtf(u1), phi = 2.0f * kPi * u2;
-    const V3 lo = (rho * cosf(phi)) * r + (rho * sinf(phi)) * u;
-    o = o + lo;
-    d = normalize_raw(c.focus * p - lo);
-  } else {
-    d = normalize_raw(p);
-  }
-}
+// ------------------------------------------------------------------ the user camera: user_camera_ray, dcamera.h
 // A user camera does not fit the implied first bounce (PathState::first: one origin for every path, nothing stored): its first rays are
 // materialised here, and the group's first bounce runs through the ordinary kernels, which load them.  pdf = +inf makes every MIS
 // weight of the first hit or miss power_heuristic(inf, finite) = 1, the depth-0 weight.  The default camera never comes here.

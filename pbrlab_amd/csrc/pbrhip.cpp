@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "env_tables.h"
+#include "feature_kernels.h"
 #include "scene_impl.h"
 
 using namespace pb;
@@ -1743,6 +1744,198 @@ extern "C" int pbrhip_render(pbrhip_scene* s, const pbrhip_render_desc* d, const
     HIPCHK(hipMemcpyAsync(count, s->own_count.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return PBRHIP_OK;
+  });
+}
+
+// ------------------------------------------------------------------ feature buffers and denoiser
+// What a first hit on a material adds to the albedo sum: rgb | the base-colour map's id (kNone: the rgb stands).  Principled: base_color.
+// Hair: base_color when it is coloured by RGB; for melanin the colour whose sigma_a under hair_param_to_bsdf's RGB mapping
+// (sigma_a = (log c / poly(beta_n))^2) is the material's: c = exp(-sqrt(sigma_a) poly(beta_n)), in double, rounded once.
+static float4 feature_albedo(const HostMaterial& hm) {
+  if (hm.kind == kMatPrincipled) return make_float4(hm.pr.base_color[0], hm.pr.base_color[1], hm.pr.base_color[2], __builtin_bit_cast(float, hm.pr.base_color_tex_id));
+  const float none = __builtin_bit_cast(float, kNone);
+  if (hm.hr.coloring_hair == 0) return make_float4(hm.hr.base_color[0], hm.hr.base_color[1], hm.hr.base_color[2], none);
+  const V3 sa = hair_param_to_bsdf(hm.hr).sigma_a;
+  const double bn = hm.hr.azimuthal_roughness;
+  const double poly = 5.969 - 0.215 * bn + 2.532 * bn * bn - 10.73 * bn * bn * bn + 5.574 * bn * bn * bn * bn + 0.245 * bn * bn * bn * bn * bn;
+  return make_float4((float)exp(-sqrt((double)sa.x) * poly), (float)exp(-sqrt((double)sa.y) * poly), (float)exp(-sqrt((double)sa.z) * poly), none);
+}
+
+// the body of pbrhip_render_features_device: device pointers on the scene's device, each may be null
+static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count) {
+  if (int rc = check_render_desc(s, d)) return rc;
+  if (d->num_sample == 0) return fail(PBRHIP_EINVAL, "render_features: no samples");
+  if ((uint64_t)d->first_pass + d->num_sample > (1ull << 32)) return fail(PBRHIP_EINVAL, "render_features: the passes do not fit 32 bits");
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const size_t npx_img = (size_t)d->width * d->height;
+  if (!(d->flags & PBRHIP_RENDER_NO_CLEAR)) {
+    if (d_albedo_hits) HIPCHK(hipMemsetAsync(d_albedo_hits, 0, npx_img * 4 * sizeof(float), st));
+    if (d_normal_depth) HIPCHK(hipMemsetAsync(d_normal_depth, 0, npx_img * 4 * sizeof(float), st));
+    if (d_count) HIPCHK(hipMemsetAsync(d_count, 0, npx_img * sizeof(uint32_t), st));
+  }
+  if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
+  const uint32_t npix = s->pk_npix;
+  if (npix == 0 || (!d_albedo_hits && !d_normal_depth && !d_count)) {
+    HIPCHK(hipStreamSynchronize(st));
+    return PBRHIP_OK;
+  }
+  std::vector<float4> albedo(std::max<size_t>(s->materials.size(), 1), make_float4(0.f, 0.f, 0.f, 0.f));
+  for (size_t i = 0; i < s->materials.size(); i++) albedo[i] = feature_albedo(s->materials[i]);  // (from the host model: material updates are seen)
+  HIPCHK(s->feat_albedo.upload(albedo, st));
+  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
+  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, st));
+  HIPCHK(s->spill.reserve(kSpillWords));
+  FeatureArgs a;
+  a.user = s->cam_set ? 1u : 0u;
+  a.ucam = s->cam_set ? make_user_camera(s, d->width, d->height) : UserCamera{};
+  a.cam = s->cam_set ? Camera{} : make_camera(s, d->width, d->height);
+  a.width = d->width, a.height = d->height, a.seed_seq = d->seed_seq;
+  a.pix = s->path_pix.p, a.npix = npix;
+  a.mat_albedo = s->feat_albedo.p;
+  a.albedo_hits = reinterpret_cast<float4*>(d_albedo_hits), a.normal_depth = reinterpret_cast<float4*>(d_normal_depth), a.count = d_count;
+  a.overflow = s->counts.p + kCntOverflow, a.spill = s->spill.p;
+  // max_paths_in_flight bounds the samples of one launch as it bounds the paths of a render's chunk; a pixel's sums continue from
+  // chunk to chunk in pass order, so the split is invisible in the result
+  uint32_t chunk = d->num_sample;
+  if (d->max_paths_in_flight) chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(d->num_sample, d->max_paths_in_flight / npix));
+  for (uint32_t done = 0; done < d->num_sample; done += chunk) {
+    a.first_pass = d->first_pass + done, a.npass = std::min(chunk, d->num_sample - done);
+    launch_features(st, s->dscene, a, k);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_render_features_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth,
+                                             uint32_t* d_count) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
+    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count);
+  });
+}
+
+extern "C" int pbrhip_render_features(pbrhip_scene* s, const pbrhip_render_desc* d, float* albedo_hits, float* normal_depth, uint32_t* count) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
+    if (int rc = check_render_desc(s, d)) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t npx = (size_t)d->width * d->height;
+    DevBuf<float> d_a, d_n;
+    DevBuf<uint32_t> d_c;
+    if (albedo_hits) HIPCHK(d_a.reserve(npx * 4));
+    if (normal_depth) HIPCHK(d_n.reserve(npx * 4));
+    if (count) HIPCHK(d_c.reserve(npx));
+    if (d->flags & PBRHIP_RENDER_NO_CLEAR) {
+      if (albedo_hits) HIPCHK(hipMemcpyAsync(d_a.p, albedo_hits, npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+      if (normal_depth) HIPCHK(hipMemcpyAsync(d_n.p, normal_depth, npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+      if (count) HIPCHK(hipMemcpyAsync(d_c.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    }
+    if (int rc = features_impl(s, d, d_a.p, d_n.p, d_c.p)) return rc;
+    if (albedo_hits) HIPCHK(hipMemcpyAsync(albedo_hits, d_a.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (normal_depth) HIPCHK(hipMemcpyAsync(normal_depth, d_n.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (count) HIPCHK(hipMemcpyAsync(count, d_c.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+// the checks both denoise entry points share; resolves the iteration default
+static int check_denoise(int device, uint32_t width, uint32_t height, const void* rgba, const void* count, const void* albedo_hits,
+                         const void* normal_depth, const void* feature_count, uint32_t* iterations, float sigma_color, float sigma_depth,
+                         uint32_t normal_squarings, uint32_t flags, const void* out_rgba) {
+  if (!rgba || !count || !out_rgba) return fail(PBRHIP_EINVAL, "denoise: NULL rgba, count or out_rgba");
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "denoise: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "denoise: image too large");
+  const int nfeat = (albedo_hits ? 1 : 0) + (normal_depth ? 1 : 0) + (feature_count ? 1 : 0);
+  if (nfeat != 0 && nfeat != 3) return fail(PBRHIP_EINVAL, "denoise: albedo_hits, normal_depth and feature_count come together or not at all");
+  if (sigma_color != sigma_color || sigma_depth != sigma_depth) return fail(PBRHIP_EINVAL, "denoise: a sigma is NaN");
+  if (*iterations > 8) return fail(PBRHIP_EINVAL, "denoise: %u iterations (at most 8)", *iterations);
+  if (normal_squarings > 16) return fail(PBRHIP_EINVAL, "denoise: %u normal squarings (at most 16)", normal_squarings);
+  if (flags & ~PBRHIP_DENOISE_NO_ALBEDO) return fail(PBRHIP_EINVAL, "denoise: unknown flags 0x%x", flags);
+  if (*iterations == 0) *iterations = PBRHIP_DENOISE_ITERATIONS;
+  int n = 0;
+  if (int rc = pbrhip_device_count(&n)) return rc;
+  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "denoise: device %d out of range (%d devices)", device, n);
+  return PBRHIP_OK;
+}
+
+// prepare + one launch per iteration on the device's null stream; the three temporaries (two colour images, one guide image) live
+// for the call
+static int denoise_impl(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
+                        const float* normal_depth, const uint32_t* feature_count, uint32_t iterations, float sigma_color, float sigma_depth,
+                        uint32_t normal_squarings, uint32_t flags, float* out_rgba) {
+  HIPCHK(hipSetDevice(device));
+  const size_t npx = (size_t)width * height;
+  DevBuf<float4> e0, e1, guide;
+  HIPCHK(e0.reserve(npx));
+  HIPCHK(e1.reserve(npx));
+  HIPCHK(guide.reserve(npx));
+  DenoiseArgs a;
+  a.width = width, a.height = height;
+  a.rgba = reinterpret_cast<const float4*>(rgba), a.count = count;
+  a.albedo_hits = reinterpret_cast<const float4*>(albedo_hits), a.normal_depth = reinterpret_cast<const float4*>(normal_depth), a.feature_count = feature_count;
+  a.no_albedo = (flags & PBRHIP_DENOISE_NO_ALBEDO) ? 1u : 0u;
+  a.sigma_color = sigma_color, a.sigma_depth = sigma_depth, a.normal_squarings = normal_squarings;
+  launch_denoise_prepare(nullptr, a, e0.p, guide.p);
+  HIPCHK(hipGetLastError());
+  for (uint32_t i = 0; i < iterations; i++) {
+    const bool last = i + 1 == iterations;
+    float4* const src = (i & 1u) ? e1.p : e0.p;
+    float4* const dst = last ? reinterpret_cast<float4*>(out_rgba) : ((i & 1u) ? e0.p : e1.p);
+    launch_denoise_iteration(nullptr, a, i, last, src, guide.p, dst);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_denoise_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                     const float* d_albedo_hits, const float* d_normal_depth, const uint32_t* d_feature_count, uint32_t iterations,
+                                     float sigma_color, float sigma_depth, uint32_t normal_squarings, uint32_t flags, float* d_out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_denoise(device, width, height, d_rgba, d_count, d_albedo_hits, d_normal_depth, d_feature_count, &iterations, sigma_color,
+                               sigma_depth, normal_squarings, flags, d_out_rgba))
+      return rc;
+    return denoise_impl(device, width, height, d_rgba, d_count, d_albedo_hits, d_normal_depth, d_feature_count, iterations, sigma_color, sigma_depth,
+                        normal_squarings, flags, d_out_rgba);
+  });
+}
+
+extern "C" int pbrhip_denoise(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
+                              const float* normal_depth, const uint32_t* feature_count, uint32_t iterations, float sigma_color, float sigma_depth,
+                              uint32_t normal_squarings, uint32_t flags, float* out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_denoise(device, width, height, rgba, count, albedo_hits, normal_depth, feature_count, &iterations, sigma_color, sigma_depth,
+                               normal_squarings, flags, out_rgba))
+      return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_rgba, d_a, d_n, d_out;
+    DevBuf<uint32_t> d_count, d_fc;
+    HIPCHK(d_rgba.reserve(npx * 4));
+    HIPCHK(d_count.reserve(npx));
+    HIPCHK(d_out.reserve(npx * 4));
+    HIPCHK(hipMemcpy(d_rgba.p, rgba, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (albedo_hits) {
+      HIPCHK(d_a.reserve(npx * 4));
+      HIPCHK(d_n.reserve(npx * 4));
+      HIPCHK(d_fc.reserve(npx));
+      HIPCHK(hipMemcpy(d_a.p, albedo_hits, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_n.p, normal_depth, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_fc.p, feature_count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (int rc = denoise_impl(device, width, height, d_rgba.p, d_count.p, d_a.p, d_n.p, d_fc.p, iterations, sigma_color, sigma_depth,
+                              normal_squarings, flags, d_out.p))
+      return rc;
+    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;
   });
 }

@@ -143,6 +143,7 @@ struct pbrhip_scene {
   pb::DevBuf<uint32_t> xchg_pix;                  // pixel lists of the ranks whose shards arrive here, concatenated
   std::vector<size_t> xk_off, xk_cnt;             // per rank: first entry in xchg_pix / number of pixels
   uint32_t xk_key[7] = {0, 0, 0, 0, 0, 0, 0};     // w, h, world, block, first rank, end rank, skipped rank
+  pb::DevBuf<float4> feat_albedo;                 // pbrhip_render_features: per material, albedo rgb | base-colour texture id (feature_kernels.h)
 
   size_t device_bytes() const {
     return d_nodes.n * sizeof(pb::BvhNode) + d_wide.n * sizeof(float4) + d_qhit.n * 4 + d_shade.n * sizeof(pb::ShadeRec) + d_materials.n * sizeof(pb::Material) +
