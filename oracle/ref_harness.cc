@@ -83,6 +83,16 @@ void ref_ggx_sample(const float wo[3], float ax, float ay, float u0, float u1, i
   out[0] = wi[0], out[1] = wi[1], out[2] = wi[2], out[3] = f, out[4] = pdf;
 }
 
+// n draws of MicrofacetGGXSample for one wo: u = n pairs (u0, u1), wi_out = n directions (zeros where the sampler writes none)
+void ref_ggx_sample_n(const float wo[3], float ax, float ay, int distrib, uint32_t n, const float* u, float* wi_out) {
+  for (uint32_t i = 0; i < n; i++) {
+    float3 wi(0.f);
+    float pdf = 0.f;
+    MicrofacetGGXSample(float3(wo), ax, ay, {u[2 * i], u[2 * i + 1]}, false, distrib, &wi, &pdf);
+    wi_out[3 * i] = wi[0], wi_out[3 * i + 1] = wi[1], wi_out[3 * i + 2] = wi[2];
+  }
+}
+
 // params: h, v0..v3, s, sigma_a[3], eta, alpha, tints[12], transparent_scale (23 floats)
 static void unpack_hair(const float* p, float* h, std::array<float, 4>* v, float* s, float3* sigma_a, float* eta,
                         float* alpha, std::array<float3, 4>* tints, float* ts) {

@@ -1,9 +1,10 @@
 """Float64 expectations for single-bounce scenes: what a pixel of the renderer should converge to, derived from the
 reference's rules (SURVEY.md §8(a')) and not from the oracle's code.  Test infrastructure only.
 
-Scope: untransformed triangle meshes; one receiver (a planar principled surface: Lambert, or metallic GGX with only the
-specular closure on); emitters and occluders with a black material; area lights with constant shading normals per face.
-A camera ray that hits such a receiver gathers light along exactly one bounce:
+Scope: untransformed triangle meshes; one receiver, a planar principled surface with any set of the non-subsurface closures
+(closure_set: Lambert, anisotropic GGX with its Fresnel tint, clearcoat; cycles-principled-shader.cc:244-412) in the shader's
+own tangent frame (branchless_onb); emitters and occluders with a black material; area lights with constant shading normals
+per face.  A camera ray that hits such a receiver gathers light along exactly one bounce:
 
   E(x) = sum over the light faces of  int_{V(x)}  f(w) Le (cos_p cos_l / d^2) [w_nee(y) + w_bsdf(y)] dA(y)     (Lambert)
 
@@ -15,6 +16,16 @@ with, from the rows of SURVEY §8(a'):
   w_bsdf  = q_bsdf^2 / (q_bsdf^2 + (p_A d^2 / |n_s.w|)^2), only for kFront hits   (Q2: the light's SHADING normal, and
             (w.n_g < 0 and w.n_s < 0)                                                 kFront needs both normals)
 so w_nee + w_bsdf != 1 wherever cos_p is not 1 (Q3's inconsistency).
+
+The closure set (lobes): f is the sum of the enabled closures; q_bsdf = q_rep = sum_k w_k pdf_k with the selection weights
+w_k of Q7 (selection_weights); the BSDF-sampled path draws wi with p_true = sum_k w_k p_k and carries f cos_p / q_rep, so
+  E(x) = sum over the light faces of  int_{V(x)}  f Le (cos_p cos_l / d^2) [w_nee + (p_true / q_rep) w_bsdf] dA(y)
+with both weights built from q_rep.  Lambert alone: p_true / q_rep = 1.  GGX alone: p_true / q_rep = cos_p (Q15, below).
+A modelled quirk (Q16): MicrofacetGGXSample draws from the GTR2 distribution of visible normals whatever `distrib` is, so
+the clearcoat is SAMPLED from GTR2 at its own alpha while its reported pdf is GTR1 with alpha^2 = 0.0625 inside G (Q8);
+ggx_vndf_pdf is that density, and tests/test_analytic_radiance.py::test_ggx_sampler_density_matches_model holds it to the
+reference's own sampler.  The sampler can also put wi below the surface; in these scenes nothing emits there
+(tests/_env_analytic.py models what an environment adds along such rays).
 
 Q15 (the GGX pdf, microfacet-ggx.h:233-238): MicrofacetGGXBsdfPdf returns pdf = G1o D / (4 cos_o cos_i), the density
 of its VNDF sampler G1o D / (4 cos_o) divided once more by cos_i.  For the GGX receiver the BSDF-sampled path then
@@ -124,17 +135,29 @@ def fresnel_dielectric_cos(c, eta):
     return np.where(g > 0, 0.5 * A * A * (1 + B * B), 1.0)
 
 
-def ggx_eval(wi, wo, ax, ay):
-    """GTR2 GGX reflection, microfacet-ggx.h:164-245 read in float64: returns (f, pdf) with the reference's pdf
-    G1o D / (4 cos_o cos_i) (Q15).  wi, wo: (...,3) in the local frame (z = normal)."""
-    wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
-    ax, ay = np.asarray(ax, np.float64), np.asarray(ay, np.float64)
+Y_WEIGHT = np.array([0.212671, 0.715160, 0.072169])     # RgbToY, pbrlab-util.h:48-51
+CUT_OFF = 1e-3                                           # kClosureWeightCutOff = kEps, pbrlab_math.h:10
+F32_EPS = float(np.finfo(np.float32).eps)
+
+
+def branchless_onb(n):
+    """shader-utils.h:44-50 in float64: the tangent frame (ex, ey) the shader builds around ez = n, n (...,3)"""
+    n = np.asarray(n, np.float64)
+    sign = np.copysign(1.0, n[..., 2])
+    a = -1.0 / (sign + n[..., 2])
+    b = n[..., 0] * n[..., 1] * a
+    ex = np.stack([1.0 + sign * n[..., 0] * n[..., 0] * a, sign * b, -sign * n[..., 0]], -1)
+    ey = np.stack([b, sign + n[..., 1] * n[..., 1] * a, -n[..., 1]], -1)
+    return ex, ey
+
+
+def _ggx_parts(wi, wo, ax, ay):
+    """the anisotropic GTR2 branch of microfacet-ggx.h:195-229 (it equals the isotropic one, :188-194, when ax == ay) for any
+    wi with wi.z + wo.z > 0: (D(m), G1o, G1(wi)) with m = the half vector; G1(wi) is 0 where wi.z <= 0"""
     co, ci = wo[..., 2], wi[..., 2]
-    ok = (co > 0) & (ci > 0)
-    co_, ci_ = np.where(ok, co, 1.0), np.where(ok, ci, 1.0)
     m = wi + wo
     m = m / np.linalg.norm(m, axis=-1, keepdims=True)
-    mz = np.where(ok, m[..., 2], 1.0)
+    mz = np.where(m[..., 2] > 0, m[..., 2], 1.0)
     sx, sy = -m[..., 0] / (mz * ax), -m[..., 1] / (mz * ay)
     sl = 1 + sx * sx + sy * sy
     D = 1.0 / (sl * sl * np.pi * ax * ay * mz ** 4)          # = alpha^2 / (pi c^4 (alpha^2 + tan^2)^2) when ax == ay
@@ -143,26 +166,44 @@ def ggx_eval(wi, wo, ax, ay):
         cp2 = w[..., 0] ** 2 + w[..., 1] ** 2
         a2 = np.where(cp2 > 0, (w[..., 0] ** 2 * ax * ax + w[..., 1] ** 2 * ay * ay) / np.where(cp2 > 0, cp2, 1.0), ax * ay)
         return 2 / (1 + np.sqrt(1 + a2 * (1 - c * c) / (c * c)))
-    G1o, G1i = g1(wo, co_), g1(wi, ci_)
+    return np.where(m[..., 2] > 0, D, 0.0), g1(wo, co), np.where(ci > 0, g1(wi, np.where(ci > 0, ci, 1.0)), 0.0), m
+
+
+def ggx_eval(wi, wo, ax, ay, distrib=2):
+    """Microfacet reflection, microfacet-ggx.h:164-245 read in float64: returns (f, pdf) with the reference's pdf
+    G1o D / (4 cos_o cos_i) (Q15).  wi, wo: (...,3) in the local frame (z = normal).  distrib = 2: GTR2 (GGX).  distrib = 1
+    (the clearcoat, Q8): where ax == ay, D is GTR1 (:48-53), both G1 take alpha^2 = 0.0625 whatever ax is, and f carries an
+    extra 0.25 (:236); where ax != ay the anisotropic GTR2 branch runs and only the 0.25 remains of distrib."""
+    wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
+    ax, ay = np.asarray(ax, np.float64), np.asarray(ay, np.float64)
+    co, ci = wo[..., 2], wi[..., 2]
+    ok = (co > 0) & (ci > 0)
+    wi_, wo_ = np.where(ok[..., None], wi, [0.0, 0.0, 1.0]), np.where(ok[..., None], wo, [0.0, 0.0, 1.0])
+    co_, ci_ = wo_[..., 2], wi_[..., 2]
+    D, G1o, G1i, m = _ggx_parts(wi_, wo_, ax, ay)
+    scale = 1.0
+    if distrib == 1:
+        iso = np.abs(ax - ay) < F32_EPS
+        a2 = np.minimum(ax * ax, 0.999999)                     # (alpha >= 1: D = 1 / pi, :49)
+        t = 1.0 + (a2 - 1.0) * m[..., 2] ** 2
+        D1 = np.where(ax >= 1.0, 1.0 / np.pi, (a2 - 1.0) / (np.pi * np.log(a2) * t))
+        g = lambda c: 2 / (1 + np.sqrt(1 + 0.0625 * (1 - c * c) / (c * c)))  # noqa: E731
+        D, G1o, G1i = np.where(iso, D1, D), np.where(iso, g(co_), G1o), np.where(iso, g(ci_), G1i)
+        scale = 0.25
     common = D * 0.25 / co_ / ci_
-    return np.where(ok, G1o * G1i * common, 0.0), np.where(ok, G1o * common, 0.0)
+    return np.where(ok, scale * G1o * G1i * common, 0.0), np.where(ok, G1o * common, 0.0)
 
 
-def _principled(mat):
-    """the closures cycles-principled-shader.cc:244-412 enables for the materials these scenes use"""
-    metallic, spec = float(mat["metallic"]), float(mat["specular"])
-    base = np.asarray(mat["base_color"], np.float64)
-    assert float(mat["subsurface"]) == 0 and float(mat["clearcoat"]) == 0 and float(mat["transmission"]) == 0
-    diffuse = (1 - metallic) * base if (1 - metallic) > 1e-3 and base.mean() > 1e-3 else None
-    specular = None
-    if spec > 1e-3 or metallic > 1e-3:
-        assert float(mat["anisotropic"]) == 0 and float(mat["specular_tint"]) == 0
-        ior = 2.0 / (1.0 - np.sqrt(0.08 * spec)) - 1.0
-        r2 = float(mat["roughness"]) ** 2
-        color = (1 - metallic) * 0.08 * spec + metallic * base
-        specular = dict(alpha=r2, ior=ior, color=color)
-    assert diffuse is None or specular is None, "one closure at a time: the selection weight would enter the pdf"
-    return diffuse, specular
+def ggx_vndf_pdf(wi, wo, ax, ay):
+    """The density (per solid angle of wi) MicrofacetGGXSample actually draws from, whatever `distrib` is
+    (microfacet-ggx.h:65-162, 247-286): MicrofacetSampleStretched draws a normal m from the GTR2 distribution of visible
+    normals G1o (m.wo) D(m) / cos_o and wi is wo's mirror image about m, so p(wi) = G1o D(m) / (4 cos_o).  That holds for
+    every wi with wi.z + wo.z > 0 (m.z > 0), below the surface as well: the sampler does not reject such wi."""
+    wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
+    ok = (wo[..., 2] > 0) & (wi[..., 2] + wo[..., 2] > 0)
+    wi_, wo_ = np.where(ok[..., None], wi, [0.0, 0.0, 1.0]), np.where(ok[..., None], wo, [0.0, 0.0, 1.0])
+    D, G1o, _, _ = _ggx_parts(wi_, wo_, np.asarray(ax, np.float64), np.asarray(ay, np.float64))
+    return np.where(ok, G1o * D * 0.25 / wo_[..., 2], 0.0)
 
 
 def specular_color(wi, wo, color, ior):
@@ -172,6 +213,100 @@ def specular_color(wi, wo, color, ior):
     f0 = fresnel_dielectric_cos(1.0, ior)
     fh = (fresnel_dielectric_cos(np.sum(h * wo, -1), ior) - f0) / (1.0 - f0)
     return color * (1 - fh[..., None]) + fh[..., None]
+
+
+def closure_set(mat):
+    """ParamToBsdf, cycles-principled-shader.cc:244-412, for a material without subsurface and without textures: the enabled
+    closures with their weights, or None per closure"""
+    sat = lambda v: min(max(float(v), 0.0), 1.0)  # noqa: E731
+    base = np.asarray(mat["base_color"], np.float64)
+    metallic, spec, transmission = float(mat["metallic"]), float(mat["specular"]), float(mat["transmission"])
+    assert float(mat["subsurface"]) == 0, "the random-walk closure is not modelled"
+    diffuse_w = (1 - sat(metallic)) * (1 - sat(transmission))                       # :326-327
+    final_transmission = sat(transmission) * (1 - sat(metallic))                    # :328-329
+    specular_w = 1 - final_transmission                                             # :330
+    out = dict(diffuse=None, specular=None, clearcoat=None)
+    if base.mean() > CUT_OFF and diffuse_w > CUT_OFF:                               # :338-342 (subsurface == 0 < cut-off)
+        out["diffuse"] = base * diffuse_w
+    if specular_w > CUT_OFF and (spec > CUT_OFF or metallic > CUT_OFF):             # :374-394
+        ior = 2.0 / (1.0 - np.sqrt(max(0.08 * spec, 0.0))) - 1.0
+        aspect = np.sqrt(max(1.0 - float(mat["anisotropic"]) * 0.9, 0.0))
+        r2 = float(mat["roughness"]) ** 2
+        y = float(Y_WEIGHT @ base)
+        rho_tint = base / y if y > 0 else np.zeros(3)
+        tint = float(mat["specular_tint"])
+        rho_specular = (1 - tint) * np.ones(3) + tint * rho_tint
+        color = (1 - metallic) * (0.08 * spec * rho_specular) + metallic * base
+        out["specular"] = dict(weight=specular_w, ax=r2 / aspect, ay=r2 * aspect, ior=ior, color=color)
+    cc = float(mat["clearcoat"])
+    if cc > CUT_OFF:                                                                # :397-409
+        out["clearcoat"] = dict(weight=0.25 * cc, alpha=float(mat["clearcoat_roughness"]) ** 2, ior=1.5, color=np.full(3, 0.04))
+    return out
+
+
+def selection_weights(cl, wo):
+    """FetchClosureSampleWeight, :63-112 (Q7): (w_diffuse, w_specular, w_clearcoat) per wo (...,3), each the luminance of the
+    closure's weight x SpecularColor(refl, wo) with refl = wo mirrored about the normal, normalised to sum 1"""
+    wo = np.asarray(wo, np.float64)
+    refl = wo * np.array([-1.0, -1.0, 1.0])
+    zero = np.zeros(wo.shape[:-1])
+    wd = zero + (float(Y_WEIGHT @ cl["diffuse"]) if cl["diffuse"] is not None else 0.0)
+    ws = wc = zero
+    if cl["specular"] is not None:
+        sp = cl["specular"]
+        ws = (sp["weight"] * specular_color(refl, wo, sp["color"], sp["ior"])) @ Y_WEIGHT
+    if cl["clearcoat"] is not None:
+        c = cl["clearcoat"]
+        wc = (c["weight"] * specular_color(refl, wo, c["color"], c["ior"])) @ Y_WEIGHT
+    s = wd + ws + wc
+    assert np.all(s > 0), "a receiver with no closure at all"
+    return wd / s, ws / s, wc / s
+
+
+def lobes(cl, wi, wo, sel=None, parts=False):
+    """EvalBsdf (:114-155) and what SampleBsdf (:169-242) draws, per pair of local directions (...,3):
+      f       the sum of the enabled closures, (...,3)
+      q_rep   the pdf the shader reports, sum_k w_k pdf_k (GGX and clearcoat with Q15's extra 1 / cos_i)
+      p_true  the density wi is actually drawn from, sum_k w_k p_k: Lambert cos_i / pi, GGX and the clearcoat the GTR2
+              density of ggx_vndf_pdf at their own alpha (the clearcoat REPORTS the GTR1 pdf but is SAMPLED from GTR2).
+    wi may lie below the surface (the GGX sampler can put it there): the GGX closures are then 0, while LambertBrdfPdf
+    (lambert.h:11-20) still returns f = 1 / pi and the NEGATIVE pdf cos_i / pi.
+    parts=True: the clearcoat's share of f is returned as a fourth value."""
+    wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
+    wd, ws, wc = sel if sel is not None else selection_weights(cl, wo)
+    shape = np.broadcast(wi[..., 0], wo[..., 0]).shape
+    f, q, p = np.zeros(shape + (3,)), np.zeros(shape), np.zeros(shape)
+    ci = np.broadcast_to(wi[..., 2], shape)
+    if cl["diffuse"] is not None:
+        f = f + cl["diffuse"] / np.pi
+        q = q + wd * ci / np.pi
+        p = p + wd * np.maximum(ci, 0.0) / np.pi
+    if cl["specular"] is not None:
+        sp = cl["specular"]
+        g, pdf = ggx_eval(wi, wo, sp["ax"], sp["ay"], 2)
+        f = f + sp["weight"] * specular_color(wi, wo, sp["color"], sp["ior"]) * g[..., None]
+        q = q + ws * pdf
+        p = p + ws * ggx_vndf_pdf(wi, wo, sp["ax"], sp["ay"])
+    if cl["clearcoat"] is not None:
+        c = cl["clearcoat"]
+        g, pdf = ggx_eval(wi, wo, c["alpha"], c["alpha"], 1)
+        f_cc = c["weight"] * specular_color(wi, wo, c["color"], c["ior"]) * g[..., None]
+        f = f + f_cc
+        q = q + wc * pdf
+        p = p + wc * ggx_vndf_pdf(wi, wo, c["alpha"], c["alpha"])
+    else:
+        f_cc = np.zeros_like(f)
+    return (f, q, p, f_cc) if parts else (f, q, p)
+
+
+def lobe_width(cl):
+    """the narrowest GGX alpha of the set (the angular scale on which f and the pdfs vary near the mirror direction), or None"""
+    a = []
+    if cl["specular"] is not None:
+        a += [cl["specular"]["ax"], cl["specular"]["ay"]]
+    if cl["clearcoat"] is not None:
+        a += [cl["clearcoat"]["alpha"]]
+    return min(a) if a else None
 
 
 # ------------------------------------------------------------------------------------------------- ray casting (float64)
@@ -298,9 +433,17 @@ def gauss_legendre01(n):
 class Expectation:
     """E(x) for points x on the receiver seen along camera directions, per RGB channel."""
 
-    def __init__(self, S: Scene, order=5, physical_mis=False):
-        self.S, self.order, self.physical_mis = S, order, physical_mis
-        self.diffuse, self.specular = _principled(S.meshes[S.receiver].material)
+    def __init__(self, S: Scene, order=5, physical_mis=False, lobe=None, alts=()):
+        """physical_mis: w_nee + w_bsdf replaced by 1.  lobe: see __call__'s refinement.  alts: mutations of the model that the
+        tests must reject, each evaluated alongside E at the same nodes and returned as three more channels, in this order:
+        "honest_pdf" (p_true := q_rep, a shader whose reported pdf were its sampling density), "clearcoat_unscaled" (the
+        clearcoat lobe without microfacet-ggx.h:236's 0.25)."""
+        assert all(a in ("honest_pdf", "clearcoat_unscaled") for a in alts)
+        self.S, self.order, self.physical_mis, self.alts = S, order, physical_mis, tuple(alts)
+        self.channels = 3 * (1 + len(self.alts))
+        self.closures = closure_set(S.meshes[S.receiver].material)
+        self.lobe = lobe                                   # None: triangles are refined by 1 / d^2 alone
+        self.width = lobe_width(self.closures) if lobe else None
         rv = np.asarray(S.meshes[S.receiver].verts, np.float64)
         rf = np.asarray(S.meshes[S.receiver].faces)
         n = np.cross(rv[rf[:, 1]] - rv[rf[:, 0]], rv[rf[:, 2]] - rv[rf[:, 0]])
@@ -386,7 +529,7 @@ class Expectation:
         S_, T_ = np.meshgrid(gs, gs, indexing="ij")
         W_ = np.outer(gw, gw).ravel()
         S_, T_ = S_.ravel(), T_.ravel()
-        out = np.zeros((N, 3))
+        out = np.zeros((N, self.channels))
         for fi, fc in enumerate(self.faces):
             o, e1, e2 = fc["e"]
             owner, tri, front = [], [], []
@@ -404,12 +547,23 @@ class Expectation:
             # 1/d^2 peaks near the foot of x on the light's plane: split a triangle into 4 while its longest edge exceeds
             # REFINE x its distance from x (estimated from the distance to the plane and the distance to the centroid less the edge),
             # at most MAX_SPLITS times
+            # A GGX lobe of width alpha varies on the angular scale alpha around the mirror direction and more slowly away from
+            # it: with lobe = c the triangle's angular size (edge / distance) is also held below c x (alpha + its angle from the mirror
+            # direction / 2)
             h = np.abs((x - o) @ fc["ng"])
             x2 = np.stack([(x - o) @ e1, (x - o) @ e2], -1)
+            mirror = 2.0 * np.sum(wo * n_r, -1, keepdims=True) * n_r - wo
             for _ in range(MAX_SPLITS):
                 edge = np.max(np.linalg.norm(tri - np.roll(tri, 1, axis=1), axis=-1), -1)
-                r = np.linalg.norm(tri.mean(1) - x2[owner], axis=-1)
-                big = edge > REFINE * np.sqrt(h[owner] ** 2 + np.maximum(r - edge, 0.0) ** 2)
+                cen = tri.mean(1)
+                r = np.linalg.norm(cen - x2[owner], axis=-1)
+                near = np.sqrt(h[owner] ** 2 + np.maximum(r - edge, 0.0) ** 2)
+                big = edge > REFINE * near
+                if self.width is not None:
+                    dc = o + cen[:, :1] * e1 + cen[:, 1:] * e2 - x[owner]
+                    dist = np.linalg.norm(dc, axis=-1)
+                    ang = np.arccos(np.clip(np.sum(dc * mirror[owner], -1) / dist, -1.0, 1.0))
+                    big |= edge > self.lobe * (self.width + 0.5 * np.maximum(ang - edge / near, 0.0)) * near
                 if not big.any():
                     break
                 t4 = tri[big]
@@ -422,6 +576,10 @@ class Expectation:
             for c0 in range(0, len(tri), CHUNK):
                 self._integrate(fc, tri[c0:c0 + CHUNK], owner[c0:c0 + CHUNK], front[c0:c0 + CHUNK], x, n_r, wo, S_, T_, W_, out)
         return out
+
+    def _lobes(self, wi, wo):
+        """(f, q_rep, p_true, the clearcoat's share of f) for local directions (M,Q,3): the receiver's closure set"""
+        return lobes(self.closures, wi, wo, parts=True)
 
     def _integrate(self, fc, tri, owner, front, x, n_r, wo, S_, T_, W_, out):
         o, e1, e2 = fc["e"]
@@ -441,29 +599,26 @@ class Expectation:
         pA = fc["pA"]
         q_nee = pA * d2 / (cos_l * cos_p)
         q_light = pA * d2 / ns_dot
-        if self.diffuse is not None:
-            f = (self.diffuse / np.pi)[None, None, :] * np.ones(cos_p.shape)[..., None]
-            q_bsdf = cos_p / np.pi
-            bsdf_cos = cos_p                               # f cos / pdf * pdf_true = f cos
-        else:
-            sp = self.specular
-            tloc = np.cross(nrm, np.array([0.0, 0.0, 1.0]) if abs(self.n_geo[2]) < 0.9 else np.array([1.0, 0.0, 0.0]))
-            tloc = tloc / np.linalg.norm(tloc, axis=-1, keepdims=True)
-            bloc = np.cross(nrm, tloc)
-            loc = lambda v: np.stack([np.sum(v * tloc, -1), np.sum(v * bloc, -1), np.sum(v * nrm, -1)], -1)  # noqa: E731
-            wi_l, wo_l = loc(w), loc(np.broadcast_to(wom, w.shape))
-            g, q_bsdf = ggx_eval(wi_l, wo_l, sp["alpha"], sp["alpha"])
-            f = specular_color(wi_l, wo_l, sp["color"], sp["ior"]) * g[..., None]
-            bsdf_cos = cos_p * cos_p                       # Q15: f cos / (pdf_true / cos) * pdf_true = f cos^2
+        ex, ey = branchless_onb(nrm)                             # the shader's own tangent frame: alpha_x lies along ex
+        loc = lambda v: np.stack([np.sum(v * ex, -1), np.sum(v * ey, -1), np.sum(v * nrm, -1)], -1)  # noqa: E731
+        f, q_bsdf, p_true, f_cc = self._lobes(loc(w), loc(np.broadcast_to(wom, w.shape)))
+        # the BSDF-sampled path: wi ~ p_true carries f cos / q_rep  ->  f cos (p_true / q_rep); Lambert alone: ratio 1,
+        # GGX alone (Q15): ratio cos
+        bsdf_cos = cos_p * p_true / q_bsdf
         if self.physical_mis:
             w_nee = np.ones_like(q_nee)
             w_bsdf = np.zeros_like(q_nee)
         else:
             w_nee = q_nee ** 2 / (q_nee ** 2 + q_bsdf ** 2)
             w_bsdf = np.where(front[:, None], q_bsdf ** 2 / (q_bsdf ** 2 + q_light ** 2), 0.0)
-        g_nee = (cos_p * cos_l / d2 * w_nee)[..., None] * f
-        g_bsdf = (bsdf_cos * cos_l / d2 * w_bsdf)[..., None] * f
-        val = np.sum((g_nee + g_bsdf) * wq[..., None], 1) * fc["le"]
+        k_nee, k_bsdf = cos_p * cos_l / d2 * w_nee, cos_l / d2 * w_bsdf
+        g = [(k_nee + bsdf_cos * k_bsdf)[..., None] * f]
+        for a in self.alts:
+            if a == "honest_pdf":
+                g.append((k_nee + cos_p * k_bsdf)[..., None] * f)
+            else:
+                g.append((k_nee + bsdf_cos * k_bsdf)[..., None] * (f + 3.0 * f_cc))
+        val = np.concatenate([np.sum(gi * wq[..., None], 1) * fc["le"] for gi in g], -1)
         np.add.at(out, owner, val)
 
 
@@ -534,7 +689,8 @@ def classify_and_expect(S: Scene, cam: Camera, expectation: Expectation, sub=2, 
     mesh, face, front = mesh.reshape(H, W, -1), face.reshape(H, W, -1), front.reshape(H, W, -1)
     emits = np.array([m.emission is not None for m in S.meshes] + [False])
     cls = np.full((H, W), PIX_MIXED)
-    value = np.zeros((H, W, 3))
+    nrep = getattr(expectation, "channels", 3) // 3            # E and the expectation's alternatives, three channels each
+    value = np.zeros((H, W, 3 * nrep))
     on_recv = np.all(mesh == S.receiver, -1)
     zero = np.all((mesh < 0) | ~emits[mesh] & (mesh != S.receiver) | emits[mesh] & ~front, -1)
     cls[zero] = PIX_ZERO
@@ -546,16 +702,26 @@ def classify_and_expect(S: Scene, cam: Camera, expectation: Expectation, sub=2, 
             same = np.all(em == em[k], 1)
             lit = np.all((mesh == mi) & front & same[np.where(mesh == mi, face, 0)], -1)
             cls[lit] = PIX_LIGHT
-            value[lit] = em[k]
+            value[lit] = np.tile(em[k], nrep)
     cls[on_recv] = PIX_RECEIVER
     # E over the footprints of the receiver pixels
     ys, xs = np.nonzero(on_recv)
     e, ev, pts, wo = pixel_mean(S, cam, expectation, xs, ys, sub, nodes=True)
     value[ys, xs] = e
     # where E is steep on the scale of a pixel (right next to an emitter) the rule is not trusted: such pixels are left out
-    steep = (ev.max(1) - ev.min(1)).max(1) > STEEP * np.abs(e).max(1)
+    steep = (ev[..., :3].max(1) - ev[..., :3].min(1)).max(1) > STEEP * np.abs(e[:, :3]).max(1)
     cls[ys[steep], xs[steep]] = PIX_MIXED
     return cls, value, (pts, wo)
+
+
+def on_receiver(S: Scene, cam: Camera, probe=6):
+    """(H,W) bool: the pixels whose whole (slightly widened) footprint sees the receiver, by classify_and_expect's probe rays"""
+    W, H = cam.width, cam.height
+    py, px = np.mgrid[0:H, 0:W]
+    js = np.linspace(-0.02, 1.02, probe)
+    jx, jy = np.meshgrid(js, js, indexing="ij")
+    d = cam.dirs(px[..., None].astype(np.float64), py[..., None].astype(np.float64), jx.ravel(), jy.ravel())
+    return np.all(cast(S, cam.org, d.reshape(-1, 3))[0].reshape(H, W, -1) == S.receiver, -1)
 
 
 def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False):
@@ -567,6 +733,6 @@ def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False):
     m, _, t, _ = cast(S, cam.org, d)
     assert np.all(m == S.receiver)
     pts = cam.org + t[:, None] * d
-    v = expectation(pts, -d).reshape(len(xs), sub * sub, 3)
+    v = expectation(pts, -d).reshape(len(xs), sub * sub, -1)
     e = np.einsum("pqc,q->pc", v, np.outer(gw, gw).ravel())
     return (e, v, pts, -d) if nodes else e

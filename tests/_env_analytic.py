@@ -2,8 +2,9 @@
 
 A Lambert floor with nothing above it (z = 0, normal +z) sees the whole upper hemisphere of the map, so the reflected radiance
 is the same at every floor point: E = (rho / pi) * integral of L(w) cos(w, n) over the hemisphere.  A white Lambert box open
-to a constant sky is a furnace: every pixel converges to L, however often its paths bounce.  A metallic GGX floor under a
-constant sky keeps the reference's skewed GGX pdf (Q15) on the BSDF side: GGXSkyExpectation."""
+to a constant sky is a furnace: every pixel converges to L, however often its paths bounce.  A principled floor (metallic GGX, or a
+mix of the Lambert, GGX and clearcoat closures) under a constant sky keeps the reference's skewed GGX pdf (Q15) and the clearcoat's
+sampler on the BSDF side: GGXSkyExpectation."""
 import numpy as np
 
 import _analytic as A
@@ -148,55 +149,75 @@ def sky_pixels(S, cam):
 GGX_METAL = dict(base_color=(0.9, 0.6, 0.3), metallic=1.0, roughness=0.7, specular=0.5, anisotropic=0.0)
 
 
-def ggx_floor_scene():
-    """floor_scene with the receiver of test_analytic_radiance's ggx_metallic case"""
+def ggx_floor_scene(mat=None):
+    """floor_scene with the receiver of test_analytic_radiance's ggx_metallic case, or with the principled material `mat`"""
     S = floor_scene()
-    return A.Scene([A.Mesh("floor", S.meshes[0].verts, S.meshes[0].faces, A.material(**GGX_METAL)), S.meshes[1]])
+    return A.Scene([A.Mesh("floor", S.meshes[0].verts, S.meshes[0].faces, A.material(**(mat or GGX_METAL))), S.meshes[1]])
 
 
 class GGXSkyExpectation:
-    """E(wo) for the metallic GGX floor (its only closure is the specular one) under a constant sky L, no area light (p_env = 1,
-    pdf_env = 1 / 4 pi).  With q = the reference's pdf G1o D / (4 cos_o cos_i) (Q15) and p = 1 / 4 pi:
+    """E(wo) for an isotropic principled floor (A.closure_set: any mix of the Lambert, GGX and clearcoat closures) under a constant
+    sky L, no area light (p_env = 1, pdf_env = 1 / 4 pi).  With (f, q, p_true) = A.lobes, q the pdf the shader reports (GGX and
+    clearcoat with Q15's extra 1 / cos_i) and p = 1 / 4 pi:
         NEE:  E f L cos_i / p x p^2 / (p^2 + q^2)   over the env sample  ->  int f L cos_i w_env dw
-        BSDF: the VNDF draws wi with density q cos_i and the path carries f cos_i / q, weighted q^2 / (q^2 + p^2) at the miss
-                                                                         ->  int f L cos_i^2 w_bsdf dw
-    q15=False: what a GGX whose pdf were its sampling density would converge to, int f L cos_i dw (the weights sum to 1).
+        BSDF: wi is drawn with density p_true and the path carries f cos_i / q, weighted q^2 / (q^2 + p^2) at the miss
+                                                                         ->  int f L cos_i (p_true / q) w_bsdf dw
+    (the metallic GGX floor alone: p_true / q = cos_i).  Below the floor (cos_i <= 0, reached by the GGX samplers only, with
+    density p_true) f is the Lambert closure's alone and q its negative pdf: the ray misses everything and adds the NEGATIVE
+    f |cos_i| / q L w_bsdf -- the lower part of the same integral, zero for a floor without a Lambert closure.
+    below=False: without that lower part (a sampler that never left the hemisphere).
+    q15=False: what a shader whose pdf were its sampling density would converge to, int f L cos_i dw (the weights sum to 1).
     The floor is isotropic, so E depends on cos_o alone: a Gauss-Legendre (cos_i) x trapezoid (phi, periodic) rule over the
-    hemisphere on a grid of cos_o, interpolated."""
+    hemisphere at Chebyshev nodes of cos_o, interpolated by their polynomial.  The lower part: Gauss-Legendre on cos_i in (-cos_o, 0) and in the azimuth (see at())."""
 
-    def __init__(self, S, L, q15=True, n_mu=96, n_phi=192, n_grid=400):
-        _, self.sp = A._principled(S.meshes[S.receiver].material)
-        self.L, self.q15 = np.asarray(L, np.float64), q15
+    def __init__(self, S, L, q15=True, n_mu=96, n_phi=192, n_grid=32, below=True):
+        self.cl = A.closure_set(S.meshes[S.receiver].material)
+        sp = self.cl["specular"]
+        assert sp is None or sp["ax"] == sp["ay"], "E must depend on cos_o alone"
+        self.L, self.q15, self.below = np.asarray(L, np.float64), q15, below
         self.n_mu, self.n_phi, self.n_grid = n_mu, n_phi, n_grid
         self.grid = None
 
-    def at(self, co, n_mu=None, n_phi=None):
+    def at(self, co, n_mu=None, n_phi=None, lower=None):
         """E for view cosines co (N,), (N, 3)"""
         n_mu, n_phi = n_mu or self.n_mu, n_phi or self.n_phi
+        lower = self.below if lower is None else lower
         mu, wmu = A.gauss_legendre01(n_mu)
         phi = (np.arange(n_phi) + 0.5) * 2.0 * np.pi / n_phi
-        M, P = np.meshgrid(mu, phi, indexing="ij")
-        st = np.sqrt(1.0 - M * M)
-        wi = np.stack([st * np.cos(P), st * np.sin(P), M], -1).reshape(-1, 3)
-        wq = (wmu[:, None] * np.full(n_phi, 2.0 * np.pi / n_phi)[None]).ravel()
         co = np.asarray(co, np.float64)
         wo = np.stack([np.sqrt(1.0 - co * co), np.zeros_like(co), co], -1)
-        a = self.sp["alpha"]
-        g, q = A.ggx_eval(wi[None], wo[:, None], a, a)                        # (N, Q)
-        f = A.specular_color(wi[None], np.broadcast_to(wo[:, None], (len(co), len(wi), 3)), self.sp["color"], self.sp["ior"]) * g[..., None]
-        ci = wi[None, :, 2]
-        if self.q15:
-            p = 1.0 / (4.0 * np.pi)
-            w_env, w_bsdf = p * p / (p * p + q * q), q * q / (q * q + p * p)
-            k = ci * w_env + ci * ci * w_bsdf
-        else:
-            k = np.broadcast_to(ci, q.shape)
-        return np.einsum("nqc,nq,q->nc", f, k, wq) * self.L
+        sel = tuple(w[:, None] for w in A.selection_weights(self.cl, wo))
+        p = 1.0 / (4.0 * np.pi)
+
+        def part(M, wq, phi, wphi):
+            """sum over directions with cos_i = M (N or 1, n_mu), weights wq (same), and azimuths phi, weights wphi"""
+            st = np.sqrt(1.0 - M * M)
+            wi = np.stack([st[..., None] * np.cos(phi), st[..., None] * np.sin(phi), M[..., None] * np.ones(n_phi)], -1)
+            wi = wi.reshape(M.shape[0], -1, 3)                                     # (N or 1, Q, 3)
+            w2 = (wq[..., None] * wphi).reshape(M.shape[0], -1)
+            f, q, pt = A.lobes(self.cl, wi, wo[:, None], sel=sel)
+            ci = wi[..., 2]
+            if self.q15:
+                w_env, w_bsdf = p * p / (p * p + q * q), q * q / (q * q + p * p)
+                ratio = np.where(q != 0, pt / np.where(q != 0, q, 1.0), 0.0)
+                k = np.where(ci > 0, ci * w_env, 0.0) + np.abs(ci) * ratio * w_bsdf
+            else:
+                k = np.where(ci > 0, ci, 0.0) * np.ones_like(q)
+            return np.einsum("nqc,nq,nq->nc", f, k, np.broadcast_to(w2, k.shape))
+        e = part(mu[None], wmu[None], phi, np.full(n_phi, 2.0 * np.pi / n_phi))
+        if lower and self.q15 and self.cl["diffuse"] is not None and A.lobe_width(self.cl) is not None:
+            # p_true's half vector is undefined at wi = -wo (cos_i = -cos_o, phi = pi), a corner of this part's domain, and the
+            # density's limit there depends on the direction of approach: Gauss-Legendre in t with phi = pi (1 + t^3) packs
+            # the azimuths around it (cos_i's own nodes already crowd towards -cos_o)
+            t, wt = np.polynomial.legendre.leggauss(n_phi)
+            e = e + part(-co[:, None] * mu[None], co[:, None] * wmu[None], np.pi * (1.0 + t ** 3), 3.0 * np.pi * t * t * wt)
+        return e * self.L
 
     def __call__(self, x, wo, order=None):
         co = np.abs(np.asarray(wo, np.float64)[:, 2])                         # the floor's normal is +z
         if self.grid is None:
-            self.grid = np.linspace(0.5, 1.0, self.n_grid)
-            self.table = np.concatenate([self.at(self.grid[i:i + 20]) for i in range(0, self.n_grid, 20)])
-        assert co.min() >= self.grid[0]
-        return np.stack([np.interp(co, self.grid, self.table[:, c]) for c in range(3)], -1)
+            # E is smooth in cos_o: the polynomial through its values at n_grid Chebyshev nodes of [0.5, 1]
+            self.grid = 0.75 + 0.25 * np.cos(np.pi * (np.arange(self.n_grid) + 0.5) / self.n_grid)
+            self.table = np.polynomial.chebyshev.chebfit(4.0 * self.grid - 3.0, self.at(self.grid), self.n_grid - 1)
+        assert co.min() >= 0.5
+        return np.polynomial.chebyshev.chebval(4.0 * co - 3.0, self.table).T

@@ -178,13 +178,14 @@ REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "ref_leaf_outputs.npz")
 _ref_outputs = None
 
 
-def ref_outputs(key, compute):
+def ref_outputs(key, compute, needs=()):
     """What the reference's own leaf code returns for one test's seeded inputs, as a dict of arrays: compute(ref()) where
     oracle/_ref/libref_leaf.so is built, else the same arrays read back from tests/golden/ref_leaf_outputs.npz (written by
     tests/golden/make_ref_outputs.py with the very compute functions the tests pass here).  A key missing from the file is
-    an error, never a skip."""
+    an error, never a skip.  needs: entry points of oracle/ref_harness.cc that compute calls and a library kept from an earlier
+    build (oracle/Makefile keeps a prebuilt one where the reference tree is absent) may lack: then the stored arrays are read too."""
     global _ref_outputs
-    if have_ref():
+    if have_ref() and all(hasattr(ref(), n) for n in needs):
         return {k: np.asarray(v) for k, v in compute(ref()).items()}
     if _ref_outputs is None:
         _ref_outputs = dict(np.load(REF_OUTPUTS))
@@ -208,6 +209,8 @@ def ref():
         R.ref_lambert_sample.argtypes = [C.c_float, C.c_float, fp]
         R.ref_ggx_eval.argtypes = [fp, fp, C.c_float, C.c_float, C.c_int, fp]
         R.ref_ggx_sample.argtypes = [fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp]
+        if hasattr(R, "ref_ggx_sample_n"):  # (a library built from an older oracle/ref_harness.cc lacks it: ref_outputs' `needs`)
+            R.ref_ggx_sample_n.argtypes = [fp, C.c_float, C.c_float, C.c_int, C.c_uint32, fp, fp]
         R.ref_hair_eval.argtypes = [fp, fp, fp, fp]
         R.ref_hair_sample.argtypes = [fp, fp, fp, fp]
         R.ref_uniform_sphere.argtypes = [C.c_float, C.c_float, fp]

@@ -242,6 +242,41 @@ for _d in (1, 2):
     ref_case(f"ggx{_d}")(lambda R, _d=_d: _ref_ggx(R, _d))
 
 
+# Where does the reference's GGX sampler put wi?  A jittered 1024 x 1024 grid of (u0, u1) through MicrofacetGGXSample, wi binned on
+# a (cos theta, phi) grid: tests/test_analytic_radiance.py::test_ggx_sampler_density_matches_model compares the counts with the
+# float64 density the radiance expectations assume.  (setting: alpha_x, alpha_y, distrib) x two wo each.
+GGX_HIST_SETTINGS = ((0.25, 0.25, 2), (0.6, 0.15, 2), (0.09, 0.09, 1))
+GGX_HIST_WO = ((0.9, 0.3), (0.45, 2.0))                      # (cos theta_o, phi_o)
+GGX_HIST_N, GGX_HIST_BINS = 1024, (16, 32)                   # the grid's side; bins in cos theta_i over (0, 1] and phi_i over (-pi, pi]
+
+
+def _ggx_hist_wo(k):
+    c, ph = GGX_HIST_WO[k]
+    s = np.sqrt(1.0 - c * c)
+    return np.float32([s * np.cos(ph), s * np.sin(ph), c])
+
+
+def _ref_ggx_hist(R):
+    n = GGX_HIST_N
+    rng = np.random.RandomState(11)
+    counts, below = [], []
+    for ax, ay, distrib in GGX_HIST_SETTINGS:
+        for k in range(len(GGX_HIST_WO)):
+            i, j = np.mgrid[0:n, 0:n]
+            u = np.stack([(i + rng.rand(n, n)) / n, (j + rng.rand(n, n)) / n], -1).reshape(-1, 2)
+            u = np.ascontiguousarray(np.minimum(u.astype(np.float32), np.nextafter(np.float32(1), np.float32(0))))
+            wi = np.zeros((n * n, 3), np.float32)
+            R.ref_ggx_sample_n(P(_ggx_hist_wo(k)), ax, ay, distrib, n * n, P(u), P(wi))
+            up = wi[:, 2] > 0
+            h, _, _ = np.histogram2d(wi[up, 2], np.arctan2(wi[up, 1], wi[up, 0]), bins=GGX_HIST_BINS, range=((0.0, 1.0), (-np.pi, np.pi)))
+            counts.append(h.astype(np.int64))
+            below.append(int((~up).sum()))
+    return {"counts": np.array(counts), "below": np.array(below, np.int64)}
+
+
+ref_case("ggx_sample_hist")(_ref_ggx_hist)
+
+
 @pytest.mark.parametrize("distrib", [1, 2])
 def test_ggx_bit_exact(distrib):
     L, want = O.lib(), reference(f"ggx{distrib}")
