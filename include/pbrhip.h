@@ -334,6 +334,19 @@ int pbrhip_comm_gather_layer(pbrhip_comm*, pbrhip_scene*, const pbrhip_render_de
  * array of rays: test hooks for hit-index parity */
 int pbrhip_trace_closest(pbrhip_scene*, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits);
 int pbrhip_trace_any(pbrhip_scene*, const pbrhip_ray* rays, size_t n, uint8_t* occluded);
+/* The GPU builder (PBRHIP_BVH_GPU_LBVH) on n bare boxes lo / hi (3 floats each) of kinds[i] (0 triangle, 1 curve piece), without a
+ * scene: a test hook.  nodes_out (host) receives max(n - 1, 1) traversal nodes of 64 bytes (lo[3][2], hi[3][2], c0, c1, pad[2]),
+ * order_out the primitive of every leaf slot, depth_out the stack depth a traversal needs.  It returns what the builder made however
+ * deep it is: replacing a tree deeper than the traversal stack by a host-built one is pbrhip_scene_commit's business.  The tree is
+ * defined exactly ("The tree, exactly"): per axis c = 0.5f * (lo + hi), cell = (uint)(q * 2097151.0f) with
+ * q = (c - min c) / (max c - min c) clamped to [0, 1] (0 on a flat axis), every step rounded to single precision; a 63-bit key with x
+ * in the highest bit of each triple; a stable sort; the radix tree over (key, position), equal keys continuing with the 32-bit
+ * positions (prefix 64 + clz(i ^ j)); node 0 the root, the children of a node that splits after position g being nodes g and g + 1;
+ * a subtree of at most two primitives of one kind stored as a leaf reference of its parent; boxes widened like every stored box;
+ * depth = height of the root + 1.  Boxes whose lo + hi overflows, or that are not finite, are outside that definition.
+ * NULL arguments or n >= 2^27: PBRHIP_EINVAL.  n == 0: PBRHIP_OK, nothing is written. */
+int pbrhip_lbvh_build(int device, const float* lo, const float* hi, const uint8_t* kinds, uint32_t n, void* nodes_out,
+                      uint32_t* order_out, uint32_t* depth_out);
 /* The camera ray the renderer traces for sample `pass` of pixel (x, y) of a width x height image (x_y_pass: n triples), evaluated on the
  * device: the user camera when one is set, else the reference's (which needs a committed scene: its box).  For tests and picking
  * (the ray of a pixel, for pbrhip_trace_closest). */

@@ -118,6 +118,26 @@ def leaf_eval(op, inputs, out_words):
     return out
 
 
+# BvhNode (csrc/dscene.h): both children's boxes interleaved [axis][child], two child references
+BVHNODE_DT = np.dtype([("lo", "<f4", (3, 2)), ("hi", "<f4", (3, 2)), ("c0", "<u4"), ("c1", "<u4"), ("pad", "<u4", 2)])
+
+
+def lbvh_build(lo, hi, kinds, device=None):
+    """pbrhip_lbvh_build (include/pbrhip.h): the GPU builder on (n, 3) float32 boxes lo / hi of kinds (n,) uint8 -> (nodes, order, depth):
+    max(n - 1, 1) BVHNODE_DT nodes, the primitive of every leaf slot, the stack depth the tree needs -- whatever that is.  A test hook."""
+    lo, hi = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (lo, hi))
+    kinds = np.ascontiguousarray(kinds, np.uint8).reshape(-1)
+    n = len(kinds)
+    if len(lo) != n or len(hi) != n:
+        raise ValueError("lo, hi and kinds differ in length")
+    nodes = np.zeros(max(n - 1, 1) if n else 0, BVHNODE_DT)
+    order = np.zeros(n, np.uint32)
+    depth = C.c_uint32(0)
+    _chk(_lib.lib().pbrhip_lbvh_build(_device if device is None else int(device), lo.ctypes.data, hi.ctypes.data, kinds.ctypes.data, n,
+                                      nodes.ctypes.data, order.ctypes.data, C.addressof(depth)))
+    return nodes, order, depth.value
+
+
 def math_mode():
     """'glibcf' (glibc's float functions restated bit for bit: the default) or 'f64r' (correctly rounded): pbrhip_math_mode()"""
     return {1: "f64r", 2: "glibcf"}[int(_lib.lib().pbrhip_math_mode())]

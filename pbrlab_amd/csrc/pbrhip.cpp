@@ -1961,6 +1961,41 @@ extern "C" int pbrhip_texture_fetch(pbrhip_scene* s, uint32_t texture_id, const 
   });
 }
 
+// the GPU builder on bare boxes, whatever depth it reaches (the fallback at kStackDepth is pbrhip_scene_commit's)
+extern "C" int pbrhip_lbvh_build(int device, const float* lo, const float* hi, const uint8_t* kinds, uint32_t n, void* nodes_out,
+                                 uint32_t* order_out, uint32_t* depth_out) {
+  return guarded([&]() -> int {
+    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "lbvh_build: too many boxes (%u)", n);
+    if (n == 0) return PBRHIP_OK;
+    if (!lo || !hi || !kinds || !nodes_out || !order_out || !depth_out) return fail(PBRHIP_EINVAL, "lbvh_build: NULL argument");
+    int ndev = 0;
+    if (int rc = pbrhip_device_count(&ndev)) return rc;
+    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "lbvh_build: device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    struct Stream {
+      hipStream_t s = nullptr;
+      ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+      }
+    } st;
+    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const size_t nn = n > 1 ? n - 1 : 1;
+    DevBuf<BvhNode> d_nodes;
+    HIPCHK(d_nodes.reserve(nn));
+    const std::vector<float> vlo(lo, lo + 3 * (size_t)n), vhi(hi, hi + 3 * (size_t)n);
+    const std::vector<uint8_t> vkinds(kinds, kinds + n);
+    std::vector<uint32_t> order;
+    uint32_t depth = 0;
+    HIPCHK(build_bvh_gpu(st.s, vlo, vhi, vkinds, d_nodes.p, &order, &depth));
+    HIPCHK(hipMemcpyAsync(nodes_out, d_nodes.p, nn * sizeof(BvhNode), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    memcpy(order_out, order.data(), sizeof(uint32_t) * n);
+    *depth_out = depth;
+    return PBRHIP_OK;
+  });
+}
+
 extern "C" int pbrhip_leaf_eval(uint32_t op, const float* in, size_t n, uint32_t in_words, float* out, uint32_t out_words) {
   return guarded([&]() -> int {
     if ((!in || !out) && n) return fail(PBRHIP_EINVAL, "leaf_eval: NULL argument");

@@ -640,6 +640,7 @@ def test_gpu_bvh_builder_errors_and_tiny_scenes(pa):
         s.AddMeshToLocalScene(ls, mesh)
         s.CreateInstance(ls, None)
         s.CommitScene()
+        assert s.info()["num_nodes"] == max(ntri - 1, 1)     # the GPU builder's tree, not a silent fallback to the host's
         rays = np.zeros(ntri, pa.api.RAY_DT)
         for k in range(ntri):
             c = v[f[k], :3].mean(axis=0)
