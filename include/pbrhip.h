@@ -196,7 +196,16 @@ int pbrhip_scene_commit(pbrhip_scene*);
  * Call before pbrhip_scene_commit.  (Environment override: PBRHIP_BVH=gpu|host.) */
 #define PBRHIP_BVH_HOST_SAH 0
 #define PBRHIP_BVH_GPU_LBVH 1
+/* GPU_LBVH_WIDE: the same tree, then collapsed on the GPU into the 4-wide quantised tree the production traversal reads (DESIGN.md
+ * section 8, "The collapse, exactly"): a GPU_LBVH commit plus a few kernels, rendered by the kernels a host-built scene runs, random
+ * walks' entry cuts included.  The binary tree stays (PBRHIP_WIDE=0 selects it).  A collapsed tree that cannot be kept (stack need
+ * beyond the traversal stack, a record index beyond its reference, a node that cannot be quantised) is dropped with one line on stderr
+ * and the scene is committed as by GPU_LBVH.  (Environment override: PBRHIP_BVH=gpu-wide.) */
+#define PBRHIP_BVH_GPU_LBVH_WIDE 2
 int pbrhip_scene_set_bvh_builder(pbrhip_scene*, int builder);
+/* The 4-wide quantised tree of a committed scene: its nodes (0: none -- PBRHIP_WIDE=0 at commit, builder GPU_LBVH, or a dropped tree),
+ * the exact traversal-stack need of a near-first traversal, and whether it was collapsed on the GPU.  Any pointer may be NULL. */
+int pbrhip_scene_wide_info(const pbrhip_scene*, uint64_t* wide_nodes, uint32_t* stack_need, int* built_on_gpu);
 /* Scene::FetchSceneAABB (scene.cc:251-259) */
 int pbrhip_scene_aabb(const pbrhip_scene*, float bmin[3], float bmax[3]);
 /* Scene::FetchMeshMaterialParameters + EditQueue edits between renders (pc/pc-common.cc:57-84): replace one
@@ -347,6 +356,16 @@ int pbrhip_trace_any(pbrhip_scene*, const pbrhip_ray* rays, size_t n, uint8_t* o
  * NULL arguments or n >= 2^27: PBRHIP_EINVAL.  n == 0: PBRHIP_OK, nothing is written. */
 int pbrhip_lbvh_build(int device, const float* lo, const float* hi, const uint8_t* kinds, uint32_t n, void* nodes_out,
                       uint32_t* order_out, uint32_t* depth_out);
+/* Builder GPU_LBVH_WIDE without a scene: a test hook.  lo / hi / kinds as for pbrhip_lbvh_build; slots: n records of 64 bytes, one per
+ * PRIMITIVE (four 16-byte words as a scene's slots: a triangle's corners, routing bits in .w of the third word; a curve piece's two end
+ * points xyzr, then its index in the cubic as the bits of the third word's .x).  sizes_out[6] receives: Q nodes, 16-byte words of
+ * triangle leaves, points, stack need, flags (1: every record index fits its reference, 2: every node was quantised), depth of the
+ * binary tree.  With qnodes_out == NULL only sizes_out (but the stack need) is written: call once for the sizes, then again with
+ * nodes_out (max(n - 1, 1) x 64 B), order_out (n), qnodes_out (sizes[0] x 64 B), tri_out (sizes[1] x 16 B), pts_out (sizes[2] x 16 B)
+ * and hit_out (sizes[2] words).  No fallback: whatever the collapse made is returned.  n == 0: sizes all zero. */
+int pbrhip_qtree_collapse(int device, const float* lo, const float* hi, const uint8_t* kinds, const void* slots, uint32_t n,
+                          void* nodes_out, uint32_t* order_out, void* qnodes_out, void* tri_out, void* pts_out, uint32_t* hit_out,
+                          uint32_t* sizes_out);
 /* The camera ray the renderer traces for sample `pass` of pixel (x, y) of a width x height image (x_y_pass: n triples), evaluated on the
  * device: the user camera when one is set, else the reference's (which needs a committed scene: its box).  For tests and picking
  * (the ray of a pixel, for pbrhip_trace_closest). */

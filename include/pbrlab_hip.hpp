@@ -354,6 +354,9 @@ public:
       Check(pbrhip_scene_attach_material_ids(h_, instance_id, uint32_t(g), ids[g].data(), uint32_t(ids[g].size())));
   }
   void CommitScene() { Check(pbrhip_scene_commit(h_)); }
+  // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
+  enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
+  void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }
   uint32_t CreateInstance(const uint32_t local_scene_id, const float transform[4][4]) {
     uint32_t id;
     Check(pbrhip_scene_create_instance(h_, local_scene_id, &transform[0][0], &id));

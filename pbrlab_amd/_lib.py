@@ -24,7 +24,7 @@ EXPORTS = [
     "pbrhip_render_multi", "pbrhip_scene_replicate", "pbrhip_comm_unique_id", "pbrhip_comm_create", "pbrhip_comm_destroy",
     "pbrhip_comm_reduce_layer", "pbrhip_comm_gather_layer",
     "pbrhip_render_features", "pbrhip_render_features_device", "pbrhip_denoise", "pbrhip_denoise_device",
-    "pbrhip_lbvh_build",
+    "pbrhip_lbvh_build", "pbrhip_scene_wide_info", "pbrhip_qtree_collapse",
 ]
 
 
@@ -55,6 +55,8 @@ def lib():
         _lib.pbrhip_render_features.argtypes = _lib.pbrhip_render_features_device.argtypes = [vp, vp, vp, vp, vp]
         _lib.pbrhip_denoise.argtypes = _lib.pbrhip_denoise_device.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, u32, f32, f32, u32, u32, vp]
         _lib.pbrhip_lbvh_build.argtypes = [C.c_int, vp, vp, vp, u32, vp, vp, vp]
+        _lib.pbrhip_qtree_collapse.argtypes = [C.c_int, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        _lib.pbrhip_scene_wide_info.argtypes = [vp, vp, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -46,7 +46,7 @@ class RenderDesc(C.Structure):
                 ("num_streams", C.c_uint32), ("tail_paths", C.c_uint32), ("shard_block", C.c_uint32)]
 
 
-BVH_HOST_SAH, BVH_GPU_LBVH = 0, 1
+BVH_HOST_SAH, BVH_GPU_LBVH, BVH_GPU_LBVH_WIDE = 0, 1, 2
 
 
 class RenderStats(C.Structure):
@@ -136,6 +136,34 @@ def lbvh_build(lo, hi, kinds, device=None):
     _chk(_lib.lib().pbrhip_lbvh_build(_device if device is None else int(device), lo.ctypes.data, hi.ctypes.data, kinds.ctypes.data, n,
                                       nodes.ctypes.data, order.ctypes.data, C.addressof(depth)))
     return nodes, order, depth.value
+
+
+# QNode (csrc/dscene.h): per axis an origin and a step, 8-bit bounds of four children (byte i of a word = child i), four references
+QNODE_DT = np.dtype([("org", "<f4", 3), ("sx", "<f4"), ("sy", "<f4"), ("sz", "<f4"), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("c", "<u4", 4)])
+
+
+def qtree_collapse(lo, hi, kinds, slots, device=None):
+    """pbrhip_qtree_collapse (include/pbrhip.h): builder BVH_GPU_LBVH_WIDE on bare boxes and per-primitive slot records (n, 4, 4) float32
+    -> dict(nodes, order, depth, qnodes (QNODE_DT), tri (words, 4), pts (points, 4), hit (points,) uint32, stack_need, fits, quantised).
+    No fallback: whatever the collapse made.  A test hook."""
+    lo, hi = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (lo, hi))
+    kinds = np.ascontiguousarray(kinds, np.uint8).reshape(-1)
+    slots = np.ascontiguousarray(slots, np.float32).reshape(-1, 4, 4)
+    n = len(kinds)
+    if len(lo) != n or len(hi) != n or len(slots) != n:
+        raise ValueError("lo, hi, kinds and slots differ in length")
+    dev = _device if device is None else int(device)
+    sizes = np.zeros(6, np.uint32)
+    head = (dev, lo.ctypes.data, hi.ctypes.data, kinds.ctypes.data, slots.ctypes.data, n)
+    _chk(_lib.lib().pbrhip_qtree_collapse(*head, None, None, None, None, None, None, sizes.ctypes.data))
+    nodes, order = np.zeros(max(n - 1, 1) if n else 0, BVHNODE_DT), np.zeros(n, np.uint32)
+    qnodes, tri = np.zeros(int(sizes[0]), QNODE_DT), np.zeros((int(sizes[1]), 4), np.float32)
+    pts, hit = np.zeros((int(sizes[2]), 4), np.float32), np.zeros(int(sizes[2]), np.uint32)
+    if n and sizes[4] & 1:
+        _chk(_lib.lib().pbrhip_qtree_collapse(*head, nodes.ctypes.data, order.ctypes.data, qnodes.ctypes.data, tri.ctypes.data,
+                                              pts.ctypes.data, hit.ctypes.data, sizes.ctypes.data))
+    return dict(nodes=nodes, order=order, depth=int(sizes[5]), qnodes=qnodes, tri=tri, pts=pts, hit=hit, stack_need=int(sizes[3]),
+                fits=bool(sizes[4] & 1), quantised=bool(sizes[4] & 2))
 
 
 def math_mode():
@@ -325,7 +353,7 @@ class Scene:
         _chk(self.L.pbrhip_scene_commit(self.h))
 
     def SetBvhBuilder(self, builder):
-        """BVH_HOST_SAH (default) or BVH_GPU_LBVH; before CommitScene (pbrhip_scene_set_bvh_builder)"""
+        """BVH_HOST_SAH (default), BVH_GPU_LBVH or BVH_GPU_LBVH_WIDE; before CommitScene (pbrhip_scene_set_bvh_builder)"""
         _chk(self.L.pbrhip_scene_set_bvh_builder(self.h, int(builder)))
 
     def FetchSceneAABB(self):
@@ -338,6 +366,12 @@ class Scene:
         dp = C.c_uint32()
         _chk(self.L.pbrhip_scene_info(self.h, C.byref(nn), C.byref(ns), C.byref(dp), C.byref(nb)))
         return dict(num_nodes=nn.value, num_slots=ns.value, depth=dp.value, device_bytes=nb.value)
+
+    def wide_info(self):
+        """pbrhip_scene_wide_info: the 4-wide quantised tree of the committed scene (wide_nodes 0: none)"""
+        nn, need, gpu = C.c_uint64(), C.c_uint32(), C.c_int()
+        _chk(self.L.pbrhip_scene_wide_info(self.h, C.byref(nn), C.byref(need), C.byref(gpu)))
+        return dict(wide_nodes=nn.value, stack_need=need.value, built_on_gpu=bool(gpu.value))
 
     # Raytracer::FirstHitTrace1 / AnyHit1 over ray arrays
     def trace_closest(self, rays):

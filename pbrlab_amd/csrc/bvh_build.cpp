@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "host_scene.h"
+#include "qquant.h"
 
 namespace pb {
 namespace {
@@ -278,50 +279,36 @@ void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const
   out->depth = depth;
 }
 
-// Quantises the boxes of up to four children into a QNode (dscene.h).  Per axis: step s = extent / 253, org = the node's
-// lower bound; a child's bounds are rounded outwards on that grid and
-// then checked -- and moved out further if need be -- with the expression the traversal evaluates, fmaf(q, s, org) in single
-// precision; when the grid is too fine for that arithmetic (a step below the resolution of org) the step doubles.
-struct QBox {
-  float lo[3], hi[3];
-};
-static bool quantise_node(const QBox* c, int n, QNode* nd) {
-  memset(nd, 0, sizeof(*nd));
-  uint32_t* qw[6] = {&nd->qlo_x, &nd->qlo_y, &nd->qlo_z, &nd->qhi_x, &nd->qhi_y, &nd->qhi_z};
-  for (int a = 0; a < 3; a++) {
-    float lo = std::numeric_limits<float>::infinity(), hi = -lo;
-    for (int i = 0; i < n; i++) lo = std::min(lo, c[i].lo[a]), hi = std::max(hi, c[i].hi[a]);
-    if (!(lo <= hi) || !std::isfinite(lo) || !std::isfinite(hi)) return false;
-    // (the step need not be a power of two: fmaf(q, s, org) rounds once whatever s is, and the result is checked below)
-    float sc = std::max(nextafterf((hi - lo) / 253.0f, std::numeric_limits<float>::infinity()), 1.1754944e-38f);
-    for (int tries = 0;; tries++) {
-      if (tries > 40 || !std::isfinite(sc)) return false;
-      const float org = lo;
-      bool ok = true;
-      uint32_t wl = 0, wh = 0;
-      for (int i = 0; i < 4 && ok; i++) {
-        if (i >= n) {  // unused child (reference kEmptyChild): never visited, any bytes will do
-          wl |= 255u << (8 * i);
-          continue;
-        }
-        int ql = (int)floor(((double)c[i].lo[a] - (double)org) / (double)sc);
-        int qh = (int)ceil(((double)c[i].hi[a] - (double)org) / (double)sc);
-        ql = std::max(0, std::min(255, ql)), qh = std::max(0, std::min(255, qh));
-        while (ql > 0 && !(fmaf((float)ql, sc, org) <= c[i].lo[a])) ql--;
-        while (qh < 255 && !(fmaf((float)qh, sc, org) >= c[i].hi[a])) qh++;
-        if (!(fmaf((float)ql, sc, org) <= c[i].lo[a] && fmaf((float)qh, sc, org) >= c[i].hi[a])) ok = false;
-        wl |= (uint32_t)ql << (8 * i), wh |= (uint32_t)qh << (8 * i);
-      }
-      if (ok) {
-        nd->org[a] = org;
-        (a == 0 ? nd->sx : (a == 1 ? nd->sy : nd->sz)) = sc;
-        *qw[a] = wl, *qw[3 + a] = wh;
-        break;
-      }
-      sc *= tries < 8 ? 1.03125f : 2.0f;
+// (the quantiser of a node -- quantise_node -- is qquant.h's: the collapse on the device, qtree_gpu.hip, shares it)
+
+// The exact stack need of a near-first traversal of a Q tree: the maximum over root-to-leaf paths of the sum of (children - 1).
+// need(node) = (children - 1) + max over inner children need(child); children need not follow their parent, so: depth first
+uint32_t qtree_stack_need(const std::vector<QNode>& N) {
+  if (N.empty()) return 0;
+  std::vector<uint32_t> need(N.size(), 0);
+  std::vector<uint8_t> state(N.size(), 0);  // 0 new, 1 open, 2 done
+  std::vector<uint32_t> todo{0u};
+  while (!todo.empty()) {
+    const uint32_t i = todo.back();
+    const QNode& nd = N[i];
+    if (state[i] == 0) {
+      state[i] = 1;
+      for (int k = 0; k < 4; k++)
+        if (!(nd.c[k] & kLeafBit) && nd.c[k] < N.size() && state[nd.c[k]] == 0) todo.push_back(nd.c[k]);
+      continue;
     }
+    todo.pop_back();
+    if (state[i] == 2) continue;
+    state[i] = 2;
+    uint32_t nc = 0, deepest = 0;
+    for (int k = 0; k < 4; k++) {
+      if (nd.c[k] == kEmptyChild) continue;
+      nc++;
+      if (!(nd.c[k] & kLeafBit) && nd.c[k] < N.size()) deepest = std::max(deepest, need[nd.c[k]]);
+    }
+    need[i] = (nc ? nc - 1u : 0u) + deepest;
   }
-  return true;
+  return need[0];
 }
 
 uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out) {
@@ -486,21 +473,8 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_
     }
     (*out)[it.out] = nd;
   }
-  // the stack a near-first traversal can need: on the way down every node leaves at most (children - 1) entries behind.
-  // need(node) = max over its inner children of (children - 1 + need(child)), at least (children - 1); children have
-  // larger indices than their parent, so one backward sweep does it
-  std::vector<uint32_t> need(out->size(), 0);
-  for (size_t i = out->size(); i-- > 0;) {
-    const QNode& nd = (*out)[i];
-    uint32_t nc = 0, deepest = 0;
-    for (int k = 0; k < 4; k++) {
-      if (nd.c[k] == kEmptyChild) continue;
-      nc++;
-      if (!(nd.c[k] & kLeafBit)) deepest = std::max(deepest, need[nd.c[k]]);
-    }
-    need[i] = (nc ? nc - 1u : 0u) + deepest;
-  }
-  return need[0];
+  // the stack a near-first traversal can need: on the way down every node leaves at most (children - 1) entries behind
+  return qtree_stack_need(*out);
 }
 
 void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out) {

@@ -105,4 +105,21 @@ hipError_t build_bvh_gpu(hipStream_t st, const std::vector<float>& lo, const std
                          const std::vector<uint8_t>& kinds, BvhNode* nodes_out, std::vector<uint32_t>* order_out,
                          uint32_t* depth_out);
 
+// The collapse of that tree into the Q tree ON THE DEVICE (qtree_gpu.hip; DESIGN.md section 8, "The collapse, exactly").  d_nodes: the
+// max(n - 1, 1) binary nodes build_bvh_gpu made, d_slots: the n 64-byte slots behind them (both device).  Once the sizes are known
+// `alloc(words of 16 B, hit codes, &wide, &hit)` provides the device memory of DScene::wide / q_hitcode; the layout is QLayout's:
+// nodes, then tri_words triangle words (q_tri0 = 4 * nodes), then pts points (q_pt0 = q_tri0 + tri_words).
+struct QCollapse {
+  uint32_t nodes = 0;      // Q nodes (heads)
+  size_t tri_words = 0, pts = 0;
+  uint32_t levels = 0;     // launches of the marking kernel
+  double alloc_ms = 0.0;   // host time spent in hipMalloc / hipFree of the working arrays and in `alloc`
+  bool fits = false;       // every record index fits its reference's bits (false: nothing was allocated or written)
+  bool quantised = false;  // every node could be quantised
+};
+hipError_t collapse_qtree_gpu(hipStream_t st, const BvhNode* d_nodes, uint32_t n, const float4* d_slots, bool tri_pairs,
+                              const std::function<hipError_t(size_t, size_t, float4**, uint32_t**)>& alloc, QCollapse* out);
+// the exact stack need of a near-first traversal (build_qtree's definition) of a Q tree whose children need not follow their parents
+uint32_t qtree_stack_need(const std::vector<QNode>& nodes);
+
 }  // namespace pb

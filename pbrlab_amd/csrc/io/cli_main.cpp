@@ -1,7 +1,7 @@
 // pbrlab-hip-cli -- pbrlab-cli (pc/pbrlab-cli.cc:16-60) on the MI355X path tracer.
 //
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
-//                  [--gpus N] [--bvh host|gpu] [--env FILE [--env-scale S]]
+//                  [--gpus N] [--bvh host|gpu|gpu-wide] [--env FILE [--env-scale S]]
 //                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
 //                  [--aov PREFIX] [--denoise] [--feature-spp N]
 //
@@ -9,7 +9,8 @@
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
 // GPU g % (GPUs present): one host thread per rank, the scene is ingested once and copied device-to-device, the shards
 // are gathered on the first GPU over xGMI inside the library (pbrhip_render_multi).  --bvh gpu builds the acceleration structure
-// on the GPU (faster commit, slightly slower traversal, same image).  --env FILE lights the scene with a lat-long environment map
+// on the GPU (faster commit, slightly slower traversal, same image); --bvh gpu-wide also collapses that tree
+// on the GPU into the 4-wide quantised tree the production kernels read.  --env FILE lights the scene with a lat-long environment map
 // (.hdr, .exr or any LDR format pbrio_image_load reads), times --env-scale (default 1).  --eye / --lookat replace
 // the reference's camera with a look-at camera: --up (default 0,1,0), vertical --fov in degrees (default 30), a thin
 // lens of --lens-radius (default 0: a pinhole) focused at --focus along the view direction (default 0: |lookat - eye|).
@@ -72,7 +73,10 @@ int main(int argc, char** argv) {
     else if (a == "--spp") samples = number("--spp", 0xFFFFFFFFul);
     else if (a == "--out") out = value("--out");
     else if (a == "--gpus") gpus = int(number("--gpus", 1024));
-    else if (a == "--bvh") bvh = std::string(value("--bvh")) == "gpu" ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+    else if (a == "--bvh") {
+      const std::string b = value("--bvh");
+      bvh = b == "gpu-wide" ? PBRHIP_BVH_GPU_LBVH_WIDE : (b == "gpu" ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH);
+    }
     else if (a == "--env") env = value("--env");
     else if (a == "--aov") aov = value("--aov");
     else if (a == "--denoise") denoise = true;

@@ -261,6 +261,7 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
     s->has_hair = src->has_hair, s->has_sss = src->has_sss, s->has_textured = src->has_textured;
     memcpy(s->bmin, src->bmin, sizeof(s->bmin)), memcpy(s->bmax, src->bmax, sizeof(s->bmax));
     s->bvh_depth = src->bvh_depth, s->bvh_builder = src->bvh_builder, s->bvh_built_on_gpu = src->bvh_built_on_gpu;
+    s->wide_stack_need = src->wide_stack_need, s->wide_built_on_gpu = src->wide_built_on_gpu;
     HIPCHK(hipSetDevice(device));
     if (device != src->device) {
       int can = 0;

@@ -73,7 +73,7 @@ Knobs pb::read_knobs() {
   auto u32 = [&](const char* name, uint32_t dflt) { const char* e = env(name); return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt; };
   auto not_zero = [&](const char* name) { const char* e = env(name); return !(e && atoi(e) == 0); };  // (atoi: a non-number is 0 too)
   Knobs k;
-  if (const char* e = env("PBRHIP_BVH")) k.bvh = strcmp(e, "gpu") == 0 ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH;
+  if (const char* e = env("PBRHIP_BVH")) k.bvh = strcmp(e, "gpu-wide") == 0 ? PBRHIP_BVH_GPU_LBVH_WIDE : (strcmp(e, "gpu") == 0 ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH);
   k.wide = not_zero("PBRHIP_WIDE");
   k.sss_entry = u32("PBRHIP_SSS_ENTRY", 1u) != 0u;
   k.sss_foreign = u32("PBRHIP_SSS_FOREIGN", 3u);
@@ -698,7 +698,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   bool gpu_built = false;
   uint32_t num_nodes = 0;
   const int builder = k.bvh >= 0 ? k.bvh : s->bvh_builder;
-  if (builder == PBRHIP_BVH_GPU_LBVH && np > 0) {
+  if ((builder == PBRHIP_BVH_GPU_LBVH || builder == PBRHIP_BVH_GPU_LBVH_WIDE) && np > 0) {
     HIPCHK(s->d_nodes.reserve(std::max<size_t>(np > 1 ? np - 1 : 1, 1) + np));  // nodes, then one 64-byte slot per primitive
     HIPCHK(build_bvh_gpu(s->stream, lo, hi, kinds, s->d_nodes.p, &bvh.slot_gid, &bvh.depth));
     if (bvh.depth > (uint32_t)kStackDepth) {
@@ -754,9 +754,47 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   // children per node with quantised boxes (64 B per node), followed by its own compact triangle leaves and curve records
   // (bvh_build.cpp::build_qlayout, dscene.h::QNode).
   QLayout q;
+  size_t q_tri_words = 0, q_pts = 0;
   if (!gpu_built && num_nodes && k.wide) {
     build_qlayout(bvh, slots, kinds, &q);
+    q_tri_words = q.tri.size(), q_pts = q.pts.size();
     if (k.debug) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
+  }
+  // PBRHIP_BVH_GPU_LBVH_WIDE: the GPU-built tree collapsed on the device (qtree_gpu.hip) straight into d_wide / d_qhit; the nodes come
+  // back (64 B each) for the stack need and the random walks' entries.  A tree that cannot be kept is dropped for the binary one.
+  bool wide_on_gpu = false;
+  if (gpu_built && builder == PBRHIP_BVH_GPU_LBVH_WIDE && k.wide) {
+    const bool tri_pairs = std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
+    QCollapse qc;
+    HIPCHK(hipStreamSynchronize(st));  // (the slots are on the device: what follows is the collapse's own time)
+    const auto t_start = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    auto alloc = [&](size_t words, size_t hits, float4** w, uint32_t** h) -> hipError_t {
+      hipError_t e = s->d_wide.reserve(words);
+      if (e == hipSuccess) e = s->d_qhit.reserve(hits);
+      *w = s->d_wide.p, *h = s->d_qhit.p;
+      return e;
+    };
+    HIPCHK(collapse_qtree_gpu(st, s->d_nodes.p, ns, reinterpret_cast<const float4*>(s->d_nodes.p + num_nodes), tri_pairs, alloc, &qc));
+    const double ms_collapse = ms_since(t_start);
+    const char* why = !qc.fits ? "a record index overflows its reference" : (!qc.quantised ? "a node cannot be quantised" : nullptr);
+    if (!why) {
+      q.nodes.resize(qc.nodes);
+      HIPCHK(hipMemcpyAsync(q.nodes.data(), s->d_wide.p, (size_t)qc.nodes * sizeof(QNode), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      q.stack_need = qtree_stack_need(q.nodes);
+      if (q.stack_need > (uint32_t)kStackDepth) why = "its traversal needs more than the stack";
+    }
+    if (k.debug)
+      fprintf(stderr, "pbrhip: commit: Q tree on the device: %u nodes in %u levels, collapse %.2f ms (of which allocation %.2f ms), download + stack need %.2f ms\n",
+              qc.nodes, qc.levels, ms_collapse, qc.alloc_ms, ms_since(t_start) - ms_collapse);
+    if (why) {
+      fprintf(stderr, "pbrhip: the Q tree of the GPU-built BVH is dropped (%s): rendering the binary tree\n", why);
+      q = QLayout();
+    } else {
+      wide_on_gpu = true;
+      q_tri_words = qc.tri_words, q_pts = qc.pts;
+    }
   }
   const std::vector<QNode>& wide = q.nodes;
   // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
@@ -769,15 +807,17 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
         ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * (size_t)g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * (size_t)g + a]);
     // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
     const uint32_t max_foreign = std::min(k.sss_foreign, kSssMaxForeign);
+    const auto t_entries = std::chrono::steady_clock::now();
     sss_entries = build_sss_entries(wide, ilo, ihi, max_foreign);
+    if (k.debug) fprintf(stderr, "pbrhip: commit: random walks' entries over %zu wide nodes: %.2f ms\n", wide.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entries).count());
     for (size_t i = 0; i < sss_entries.size() && k.debug; i++)
       if (sss_entries[i].entry) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, sss_entries[i].entry, sss_entries[i].nforeign);
   }
   if (sss_entries.empty()) s->d_sss_entries.release();
   else HIPCHK(s->d_sss_entries.upload(sss_entries, st));
   if (wide.empty()) s->d_wide.release(), s->d_qhit.release();
-  if (k.debug) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q.tri.size() / kTriPairWords, q.pts.size());
-  if (!wide.empty()) {
+  if (k.debug) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q_tri_words / kTriPairWords, q_pts);
+  if (!wide.empty() && !wide_on_gpu) {
     HIPCHK(s->d_wide.reserve(wide.size() * 4 + q.tri.size() + q.pts.size()));
     HIPCHK(hipMemcpyAsync(s->d_wide.p, wide.data(), wide.size() * sizeof(QNode), hipMemcpyHostToDevice, st));
     if (!q.tri.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4, q.tri.data(), q.tri.size() * 16, hipMemcpyHostToDevice, st));
@@ -804,7 +844,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   d.num_curves = 0;
   for (uint8_t kd : kinds) d.num_curves += kd ? 1u : 0u;
   d.wide = wide.empty() ? nullptr : s->d_wide.p, d.wide_nodes = (uint32_t)wide.size();
-  d.q_tri0 = (uint32_t)wide.size() * 4u, d.q_pt0 = d.q_tri0 + (uint32_t)q.tri.size(), d.q_hitcode = wide.empty() ? nullptr : s->d_qhit.p;
+  d.q_tri0 = (uint32_t)wide.size() * 4u, d.q_pt0 = d.q_tri0 + (uint32_t)q_tri_words, d.q_hitcode = wide.empty() ? nullptr : s->d_qhit.p;
   d.top_nodes = gpu_built ? 0u : std::min<uint32_t>(num_nodes, (uint32_t)kTopNodes);
   d.wide_top_nodes = std::min<uint32_t>((uint32_t)wide.size(), (uint32_t)kTopNodes);
   // light sampling works on the meshes' local positions (light-manager.h:128-136 "TODO transform"), the raytracer on the
@@ -813,7 +853,19 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   d.sss_entries = sss_entries.empty() ? nullptr : s->d_sss_entries.p, d.num_sss_entries = (uint32_t)sss_entries.size();
   d.lights_transformed = 0;
   for (const HostLight& L : s->lights) d.lights_transformed |= s->instances[L.instance_id].identity ? 0u : 1u;
+  s->wide_stack_need = wide.empty() ? 0u : q.stack_need, s->wide_built_on_gpu = wide_on_gpu;
   s->committed = true;
+  return PBRHIP_OK;
+  });
+}
+
+extern "C" int pbrhip_scene_wide_info(const pbrhip_scene* s, uint64_t* wide_nodes, uint32_t* stack_need, int* built_on_gpu) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  if (wide_nodes) *wide_nodes = s->dscene.wide_nodes;
+  if (stack_need) *stack_need = s->wide_stack_need;
+  if (built_on_gpu) *built_on_gpu = s->wide_built_on_gpu ? 1 : 0;
   return PBRHIP_OK;
   });
 }
@@ -821,7 +873,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
 extern "C" int pbrhip_scene_set_bvh_builder(pbrhip_scene* s, int builder) {
   return guarded([&]() -> int {
   if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
-  if (builder != PBRHIP_BVH_HOST_SAH && builder != PBRHIP_BVH_GPU_LBVH) return fail(PBRHIP_EINVAL, "unknown BVH builder %d", builder);
+  if (builder != PBRHIP_BVH_HOST_SAH && builder != PBRHIP_BVH_GPU_LBVH && builder != PBRHIP_BVH_GPU_LBVH_WIDE) return fail(PBRHIP_EINVAL, "unknown BVH builder %d", builder);
   if (s->committed) return fail(PBRHIP_ESTATE, "scene already committed");
   s->bvh_builder = builder;
   return PBRHIP_OK;
@@ -1992,6 +2044,70 @@ extern "C" int pbrhip_lbvh_build(int device, const float* lo, const float* hi, c
     HIPCHK(hipStreamSynchronize(st.s));
     memcpy(order_out, order.data(), sizeof(uint32_t) * n);
     *depth_out = depth;
+    return PBRHIP_OK;
+  });
+}
+
+// builder PBRHIP_BVH_GPU_LBVH_WIDE on bare boxes and slot records: the binary tree, then its collapse, whatever comes out (no fallback)
+extern "C" int pbrhip_qtree_collapse(int device, const float* lo, const float* hi, const uint8_t* kinds, const void* slots, uint32_t n,
+                                     void* nodes_out, uint32_t* order_out, void* qnodes_out, void* tri_out, void* pts_out,
+                                     uint32_t* hit_out, uint32_t* sizes_out) {
+  return guarded([&]() -> int {
+    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "qtree_collapse: too many boxes (%u)", n);
+    if (!sizes_out) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
+    if (n == 0) {
+      memset(sizes_out, 0, 6 * sizeof(uint32_t));
+      return PBRHIP_OK;
+    }
+    if (!lo || !hi || !kinds || !slots) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
+    if (qnodes_out && (!nodes_out || !order_out || !tri_out || !pts_out || !hit_out)) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
+    int ndev = 0;
+    if (int rc = pbrhip_device_count(&ndev)) return rc;
+    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "qtree_collapse: device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    struct Stream {
+      hipStream_t s = nullptr;
+      ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+      }
+    } st;
+    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const size_t nn = n > 1 ? n - 1 : 1;
+    DevBuf<BvhNode> d_nodes;  // nodes, then the slots in leaf order: the layout of a committed scene
+    HIPCHK(d_nodes.reserve(nn + n));
+    const std::vector<float> vlo(lo, lo + 3 * (size_t)n), vhi(hi, hi + 3 * (size_t)n);
+    const std::vector<uint8_t> vkinds(kinds, kinds + n);
+    std::vector<uint32_t> order;
+    uint32_t depth = 0;
+    HIPCHK(build_bvh_gpu(st.s, vlo, vhi, vkinds, d_nodes.p, &order, &depth));
+    std::vector<BvhNode> sl(n);  // (a slot is 64 bytes, like a node)
+    for (uint32_t k = 0; k < n; k++) memcpy(&sl[k], static_cast<const char*>(slots) + 64 * (size_t)order[k], 64);
+    HIPCHK(hipMemcpyAsync(d_nodes.p + nn, sl.data(), 64 * (size_t)n, hipMemcpyHostToDevice, st.s));
+    DevBuf<float4> d_wide;
+    DevBuf<uint32_t> d_hit;
+    auto alloc = [&](size_t words, size_t hits, float4** w, uint32_t** h) -> hipError_t {
+      hipError_t e = d_wide.reserve(words);
+      if (e == hipSuccess) e = d_hit.reserve(hits);
+      *w = d_wide.p, *h = d_hit.p;
+      return e;
+    };
+    const bool tri_pairs = std::all_of(vkinds.begin(), vkinds.end(), [](uint8_t kd) { return kd == 0; });
+    QCollapse qc;
+    HIPCHK(collapse_qtree_gpu(st.s, d_nodes.p, n, reinterpret_cast<const float4*>(d_nodes.p + nn), tri_pairs, alloc, &qc));
+    sizes_out[0] = qc.nodes, sizes_out[1] = (uint32_t)qc.tri_words, sizes_out[2] = (uint32_t)qc.pts, sizes_out[3] = 0;
+    sizes_out[4] = (qc.fits ? 1u : 0u) | (qc.quantised ? 2u : 0u), sizes_out[5] = depth;
+    if (!qc.fits || !qnodes_out) return PBRHIP_OK;  // (a call without output arrays reports the sizes)
+    std::vector<QNode> qn(qc.nodes);
+    HIPCHK(hipMemcpyAsync(nodes_out, d_nodes.p, nn * sizeof(BvhNode), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(qn.data(), d_wide.p, (size_t)qc.nodes * 64, hipMemcpyDeviceToHost, st.s));
+    if (qc.tri_words) HIPCHK(hipMemcpyAsync(tri_out, d_wide.p + (size_t)qc.nodes * 4, qc.tri_words * 16, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(pts_out, d_wide.p + (size_t)qc.nodes * 4 + qc.tri_words, qc.pts * 16, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(hit_out, d_hit.p, qc.pts * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    memcpy(qnodes_out, qn.data(), (size_t)qc.nodes * 64);
+    memcpy(order_out, order.data(), sizeof(uint32_t) * n);
+    sizes_out[3] = qtree_stack_need(qn);
     return PBRHIP_OK;
   });
 }

@@ -91,9 +91,11 @@ struct pbrhip_scene {
   uint32_t bvh_depth = 0;
   int bvh_builder = PBRHIP_BVH_HOST_SAH;
   bool bvh_built_on_gpu = false;
+  uint32_t wide_stack_need = 0;    // of the Q tree (0: none): pbrhip_scene_wide_info
+  bool wide_built_on_gpu = false;  // the Q tree was collapsed on the device (PBRHIP_BVH_GPU_LBVH_WIDE)
   // device scene
   pb::DevBuf<pb::BvhNode> d_nodes;
-  pb::DevBuf<float4> d_wide;  // the Q tree: quantised 4-wide nodes + its triangle slots + curve points (DScene::wide), host-built trees only
+  pb::DevBuf<float4> d_wide;  // the Q tree: quantised 4-wide nodes + its triangle slots + curve points (DScene::wide), built on the host, or on the device by qtree_gpu.hip
   pb::DevBuf<uint32_t> d_qhit;  // hit code per curve point of the Q tree (DScene::q_hitcode)
   pb::DevBuf<pb::ShadeRec> d_shade;
   pb::DevBuf<pb::Material> d_materials;
