@@ -28,7 +28,7 @@ extern "C" {
 #define PBRHIP_ENODEVICE (-3) /* no usable HIP device */
 #define PBRHIP_EHIP (-4)      /* a HIP runtime call failed */
 #define PBRHIP_EUNSUPPORTED (-5)
-#define PBRHIP_ESTATE (-6)    /* scene not committed / already committed */
+#define PBRHIP_ESTATE (-6)    /* scene not committed / already committed / stale (geometry edits pending: pbrhip_scene_refit) */
 #define PBRHIP_EOVERFLOW (-7) /* traversal stack overflow (BVH deeper than the kernel supports) */
 #define PBRHIP_ENOMEM (-8)    /* host allocation failed (std::bad_alloc) */
 #define PBRHIP_ECOMM (-9)     /* RCCL is unavailable or one of its calls failed */
@@ -212,6 +212,26 @@ int pbrhip_scene_aabb(const pbrhip_scene*, float bmin[3], float bmax[3]);
  * material's parameters in place on a committed scene */
 int pbrhip_scene_update_principled_material(pbrhip_scene*, uint32_t material_id, const pbrhip_principled_param*);
 int pbrhip_scene_update_hair_material(pbrhip_scene*, uint32_t material_id, const pbrhip_hair_param*);
+/* Geometry edits between renders ("The refit, exactly").  The update calls replace VALUES of the host model: a triangle
+ * mesh's vertices (and its normals; NULL: kept), a curve mesh's control points xyzr, an instance's transform (NULL: identity).  Indices,
+ * texcoords, materials and light attachments stay: the topology is fixed.  Counts must equal the mesh's own (else PBRHIP_ESIZE); a
+ * non-finite value, a mesh of the other kind, an id out of range or a matrix pbrhip_scene_create_instance would refuse: PBRHIP_EINVAL,
+ * and nothing changes.  Before the first commit they only edit the model.  On a committed scene every instance that shows the mesh (or
+ * the one instance) becomes dirty and the scene STALE: until pbrhip_scene_refit (or another pbrhip_scene_commit, which rebuilds from the
+ * model) every entry point that reads the device scene -- pbrhip_render*, pbrhip_render_features*, pbrhip_trace_*, pbrhip_camera_rays,
+ * pbrhip_scene_aabb, pbrhip_scene_replicate, pbrhip_comm_gather_layer -- returns PBRHIP_ESTATE.
+ * pbrhip_scene_refit brings the committed scene up to date ON THE DEVICE: the trees keep the topology their builder gave them and every
+ * stored box, leaf record, slot, ShadeRec, light table, the scene's bounds and the random walks' entries are recomputed, so that every
+ * observable (hits, pbrhip_scene_aabb, frames, feature buffers) equals, bit for bit, that of a fresh scene built from the edited model
+ * and committed with the same builder.  Only the tree's QUALITY is the old pose's: after large motions a commit traces faster.
+ * Uncommitted scene: PBRHIP_ESTATE; nothing pending: PBRHIP_OK, nothing happens.  A Q node that cannot be quantised (it cannot arise
+ * from finite vertices): PBRHIP_EHIP, the scene stays stale.  A replica made by pbrhip_scene_replicate holds no geometry: the update
+ * calls and pbrhip_scene_refit return PBRHIP_ESTATE on it -- refit the source scene and replicate it again. */
+int pbrhip_scene_update_triangle_mesh(pbrhip_scene*, uint32_t mesh_id, const float* vertices_xyzw, uint32_t num_vertices,
+                                      const float* normals_xyzw, uint32_t num_normals);
+int pbrhip_scene_update_curve_mesh(pbrhip_scene*, uint32_t mesh_id, const float* vertices_xyzr, uint32_t num_vertices);
+int pbrhip_scene_update_instance_transform(pbrhip_scene*, uint32_t instance_id, const float* transform4x4);
+int pbrhip_scene_refit(pbrhip_scene*);
 /* A lat-long environment light: rgb = width x height x 3 floats, row 0 = the top (+y up; a ray along -z sees the
  * middle of the map), nearest-sampled, times `scale`.  world_to_env: a 3x3 rotation, row-major, applied to world directions before
  * the lookup (NULL: identity).  A ray that leaves the scene collects it (with MIS), and NEE samples it by luminance x solid angle.
@@ -366,6 +386,13 @@ int pbrhip_lbvh_build(int device, const float* lo, const float* hi, const uint8_
 int pbrhip_qtree_collapse(int device, const float* lo, const float* hi, const uint8_t* kinds, const void* slots, uint32_t n,
                           void* nodes_out, uint32_t* order_out, void* qnodes_out, void* tri_out, void* pts_out, uint32_t* hit_out,
                           uint32_t* sizes_out);
+/* pbrhip_scene_refit's device work without a scene: a test hook.  slots: n x 64 B, the NEW slots in leaf order; nodes_inout: the
+ * max(n - 1, 1) binary nodes; qnodes_inout (num_qnodes x 64 B), tri_inout (tri_words x 16 B; tri_pairs: TriPair records, else 48-byte
+ * slots), pts_inout (num_points x 16 B) and hit (num_points words): the Q tree over them as pbrhip_qtree_collapse returns it;
+ * qnodes_inout == NULL: the binary tree only.  Uploads, runs the kernels pbrhip_scene_refit runs (plan, leaf records, both trees) and
+ * downloads.  A node that cannot be quantised or an index out of range: PBRHIP_EHIP.  n == 0: PBRHIP_OK, nothing is written. */
+int pbrhip_tree_refit(int device, uint32_t n, const void* slots, void* nodes_inout, void* qnodes_inout, uint32_t num_qnodes,
+                      void* tri_inout, uint32_t tri_words, int tri_pairs, void* pts_inout, const uint32_t* hit, uint32_t num_points);
 /* The camera ray the renderer traces for sample `pass` of pixel (x, y) of a width x height image (x_y_pass: n triples), evaluated on the
  * device: the user camera when one is set, else the reference's (which needs a committed scene: its box).  For tests and picking
  * (the ray of a pixel, for pbrhip_trace_closest). */

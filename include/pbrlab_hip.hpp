@@ -354,6 +354,21 @@ public:
       Check(pbrhip_scene_attach_material_ids(h_, instance_id, uint32_t(g), ids[g].data(), uint32_t(ids[g].size())));
   }
   void CommitScene() { Check(pbrhip_scene_commit(h_)); }
+  // Geometry edits between renders (pbrhip_scene_update_* / pbrhip_scene_refit; the reference has none): new VALUES for a mesh of this
+  // scene, as many as it was added with (normals empty: kept), or a new transform of an instance.  On a committed scene RefitScene()
+  // brings the trees up to date on the GPU before the next Render(); until then every call that reads the device scene throws.  The
+  // mesh objects this shim keeps for FetchMeshMaterialParameters are not touched: they hold no positions a render reads.
+  void UpdateTriangleMesh(const MeshPtr& mesh_ptr, const std::vector<float>& vertices_xyzw, const std::vector<float>& normals_xyzw = {}) {
+    Check(pbrhip_scene_update_triangle_mesh(h_, LibraryMeshId(mesh_ptr), vertices_xyzw.data(), uint32_t(vertices_xyzw.size() / 4),
+                                            normals_xyzw.empty() ? nullptr : normals_xyzw.data(), uint32_t(normals_xyzw.size() / 4)));
+  }
+  void UpdateCurveMesh(const MeshPtr& mesh_ptr, const std::vector<float>& vertices_xyzr) {
+    Check(pbrhip_scene_update_curve_mesh(h_, LibraryMeshId(mesh_ptr), vertices_xyzr.data(), uint32_t(vertices_xyzr.size() / 4)));
+  }
+  void UpdateInstanceTransform(const uint32_t instance_id, const float transform[4][4]) {
+    Check(pbrhip_scene_update_instance_transform(h_, instance_id, &transform[0][0]));
+  }
+  void RefitScene() { Check(pbrhip_scene_refit(h_)); }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
   void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }
@@ -417,8 +432,15 @@ private:
   static void Check(int rc) {
     if (rc != PBRHIP_OK) throw std::runtime_error(pbrhip_last_error());
   }
+  uint32_t LibraryMeshId(const MeshPtr& mesh_ptr) const {
+    const void* key = mesh_ptr.index() == kTriangleMesh ? static_cast<const void*>(std::get<kTriangleMesh>(mesh_ptr).get())
+                                                        : static_cast<const void*>(std::get<kCubicBezierCurveMesh>(mesh_ptr).get());
+    for (const auto& e : mesh_ids_)
+      if (e.first == key) return e.second;
+    throw std::runtime_error("the mesh was not added to this scene");
+  }
   pbrhip_scene* h_ = nullptr;
-  std::vector<std::shared_ptr<TriangleMesh>> triangle_meshes_;                  // scene.h:98
+  std::vector<std::shared_ptr<TriangleMesh>> triangle_meshes_;                 // scene.h:98
   std::vector<std::shared_ptr<CubicBezierCurveMesh>> cubic_bezier_curve_meshes_;  // scene.h:100
   std::vector<std::pair<const void*, uint32_t>> mesh_ids_;                      // mesh object -> the library's mesh id
   std::vector<MaterialParameter> material_params_;                              // scene.h:102

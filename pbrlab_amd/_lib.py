@@ -25,6 +25,8 @@ EXPORTS = [
     "pbrhip_comm_reduce_layer", "pbrhip_comm_gather_layer",
     "pbrhip_render_features", "pbrhip_render_features_device", "pbrhip_denoise", "pbrhip_denoise_device",
     "pbrhip_lbvh_build", "pbrhip_scene_wide_info", "pbrhip_qtree_collapse",
+    "pbrhip_scene_update_triangle_mesh", "pbrhip_scene_update_curve_mesh", "pbrhip_scene_update_instance_transform", "pbrhip_scene_refit",
+    "pbrhip_tree_refit",
 ]
 
 
@@ -57,6 +59,11 @@ def lib():
         _lib.pbrhip_lbvh_build.argtypes = [C.c_int, vp, vp, vp, u32, vp, vp, vp]
         _lib.pbrhip_qtree_collapse.argtypes = [C.c_int, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
         _lib.pbrhip_scene_wide_info.argtypes = [vp, vp, vp, vp]
+        _lib.pbrhip_scene_update_triangle_mesh.argtypes = [vp, u32, vp, u32, vp, u32]
+        _lib.pbrhip_scene_update_curve_mesh.argtypes = [vp, u32, vp, u32]
+        _lib.pbrhip_scene_update_instance_transform.argtypes = [vp, u32, vp]
+        _lib.pbrhip_scene_refit.argtypes = [vp]
+        _lib.pbrhip_tree_refit.argtypes = [C.c_int, u32, vp, vp, vp, u32, vp, u32, C.c_int, vp, vp, u32]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -166,6 +166,29 @@ def qtree_collapse(lo, hi, kinds, slots, device=None):
                 fits=bool(sizes[4] & 1), quantised=bool(sizes[4] & 2))
 
 
+def tree_refit(slots, nodes, qtree=None, device=None):
+    """pbrhip_tree_refit (include/pbrhip.h): pbrhip_scene_refit's kernels on a bare tree.  slots: the NEW (n, 4, 4) float32 slots in leaf
+    order; nodes: the max(n - 1, 1) BVHNODE_DT nodes; qtree: dict(qnodes, tri, pts, hit) as qtree_collapse returns it, or None for the
+    binary tree alone -> (nodes, dict(qnodes, tri, pts, hit) or None), refitted copies.  A test hook."""
+    slots = np.ascontiguousarray(slots, np.float32).reshape(-1, 4, 4)
+    n = len(slots)
+    nodes = np.array(nodes, BVHNODE_DT)
+    if len(nodes) != (max(n - 1, 1) if n else 0):
+        raise ValueError("nodes: max(n - 1, 1) of them")
+    dev = _device if device is None else int(device)
+    if qtree is None:
+        _chk(_lib.lib().pbrhip_tree_refit(dev, n, slots.ctypes.data, nodes.ctypes.data, None, 0, None, 0, 0, None, None, 0))
+        return nodes, None
+    qn, tri = np.array(qtree["qnodes"], QNODE_DT), np.array(qtree["tri"], np.float32).reshape(-1, 4)
+    pts, hit = np.array(qtree["pts"], np.float32).reshape(-1, 4), np.ascontiguousarray(qtree["hit"], np.uint32)
+    if len(hit) != len(pts):
+        raise ValueError("one hit code per point")
+    tri_pairs = int(len(pts) == 8)  # (no curve record at all: a triangle-only tree, whose triangle leaves are TriPairs)
+    _chk(_lib.lib().pbrhip_tree_refit(dev, n, slots.ctypes.data, nodes.ctypes.data, qn.ctypes.data, len(qn), tri.ctypes.data if len(tri) else None,
+                                      len(tri), tri_pairs, pts.ctypes.data, hit.ctypes.data, len(pts)))
+    return nodes, dict(qtree, qnodes=qn, tri=tri, pts=pts, hit=hit)
+
+
 def math_mode():
     """'glibcf' (glibc's float functions restated bit for bit: the default) or 'f64r' (correctly rounded): pbrhip_math_mode()"""
     return {1: "f64r", 2: "glibcf"}[int(_lib.lib().pbrhip_math_mode())]
@@ -273,6 +296,29 @@ class Scene:
             _chk(self.L.pbrhip_scene_update_principled_material(self.h, material_id, C.byref(p)))
         else:
             _chk(self.L.pbrhip_scene_update_hair_material(self.h, material_id, C.byref(p)))
+
+    def UpdateTriangleMesh(self, mesh_id, vertices, normals=None):
+        """pbrhip_scene_update_triangle_mesh: new vertices (and normals; None: kept) of a triangle mesh, counts as it was added.  On a
+        committed scene the scene is stale until RefitScene (or CommitScene)."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 4)
+        n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+        _chk(self.L.pbrhip_scene_update_triangle_mesh(self.h, mesh_id, v.ctypes.data, len(v), None if n is None else n.ctypes.data,
+                                                      0 if n is None else len(n)))
+
+    def UpdateCurveMesh(self, mesh_id, vertices_xyzr):
+        """pbrhip_scene_update_curve_mesh: new control points xyz + radius of a curve mesh, as many as it was added with"""
+        v = np.ascontiguousarray(vertices_xyzr, np.float32).reshape(-1, 4)
+        _chk(self.L.pbrhip_scene_update_curve_mesh(self.h, mesh_id, v.ctypes.data, len(v)))
+
+    def UpdateInstanceTransform(self, instance_id, transform=None):
+        """pbrhip_scene_update_instance_transform: a new 4x4 transform of an instance (None: identity), as CreateInstance takes it"""
+        t = None if transform is None else np.ascontiguousarray(transform, np.float32).reshape(16)
+        _chk(self.L.pbrhip_scene_update_instance_transform(self.h, instance_id, None if t is None else t.ctypes.data))
+
+    def RefitScene(self):
+        """pbrhip_scene_refit: the committed trees refitted on the GPU to the edited geometry; afterwards every observable equals that of
+        a fresh scene built from the edited model and committed with the same builder"""
+        _chk(self.L.pbrhip_scene_refit(self.h))
 
     def AddTexture(self, pixels):
         """Scene::AddTexture: pixels (H, W, C) float32."""

@@ -119,6 +119,43 @@ struct QCollapse {
 };
 hipError_t collapse_qtree_gpu(hipStream_t st, const BvhNode* d_nodes, uint32_t n, const float4* d_slots, bool tri_pairs,
                               const std::function<hipError_t(size_t, size_t, float4**, uint32_t**)>& alloc, QCollapse* out);
+// The refit of both trees ON THE DEVICE after vertex / transform edits (refit_gpu.hip; DESIGN.md section 8, "The refit, exactly"): the
+// topology stays, every stored box and every geometry word of a leaf record is recomputed from the slots behind the binary nodes.
+// The plan -- the nodes of either tree level by level -- is built at the first refit of a committed tree and kept until the next commit.
+struct RefitPlan {
+  uint32_t* d_list = nullptr;  // device: nb binary node indices by level, then nq Q node indices by level
+  float4* d_qbox = nullptr;    // device: the working arrays of a refit: the unwidened union of the slots below every Q node ...
+  float4* d_bbox = nullptr;    // ... and below every binary node (two 16-byte words each)
+  uint32_t* d_cnt = nullptr;   // device: level counter, failure flags
+  std::vector<uint32_t> bin_off, q_off;  // level l of a tree is list[off[l] .. off[l + 1])
+  bool built = false;
+  RefitPlan() = default;
+  RefitPlan(const RefitPlan&) = delete;
+  RefitPlan& operator=(const RefitPlan&) = delete;
+  ~RefitPlan() { release(); }
+  void release();
+};
+struct RefitTree {  // device pointers: nb binary nodes followed by ns slots; the Q tree as DScene::wide / q_hitcode lay it out (nq 0: none)
+  BvhNode* nodes = nullptr;
+  uint32_t nb = 0, ns = 0;
+  QNode* q = nullptr;
+  uint32_t nq = 0;
+  float4* tri = nullptr;
+  size_t tri_words = 0;
+  bool tri_pairs = false;
+  float4* pts = nullptr;
+  const uint32_t* hit = nullptr;
+  size_t npts = 0;
+};
+struct RefitTimes {
+  double plan_ms = 0.0, trees_ms = 0.0;  // the plan (first refit only); leaf records + both trees
+  uint32_t bin_levels = 0, q_levels = 0;
+  uint32_t failed = 0;  // bit 0: a Q node cannot be quantised; bit 1: an index of the tree is out of range
+};
+// `timed`: synchronise in front of the plan so that plan_ms is its own.  Synchronises the stream once, at the end.
+hipError_t refit_tree_gpu(hipStream_t st, const RefitTree& t, bool timed, RefitPlan* plan, RefitTimes* out);
+// d_packed: m slot indices padded to whole 16-byte words | m x 64 B slots | m x 128 B ShadeRecs, scattered to their places
+hipError_t scatter_slots_gpu(hipStream_t st, const float4* d_packed, uint32_t m, uint32_t ns, float4* d_slots, float4* d_shade);
 // the exact stack need of a near-first traversal (build_qtree's definition) of a Q tree whose children need not follow their parents
 uint32_t qtree_stack_need(const std::vector<QNode>& nodes);
 

@@ -192,6 +192,7 @@ extern "C" int pbrhip_comm_gather_layer(pbrhip_comm* c, pbrhip_scene* s, const p
                                         uint32_t* d_count, int root) {
   return guarded([&]() -> int {
     if (!c || !s || !d || !d_rgba || !d_count) return fail(PBRHIP_EINVAL, "gather_layer: NULL argument");
+    PB_NOT_STALE(s);
     if (root < 0 || root >= c->world) return fail(PBRHIP_EINVAL, "gather_layer: root %d of %d", root, c->world);
     const uint32_t world = d->tile_world ? d->tile_world : 1;
     if ((int)world != c->world || (int)d->tile_rank != c->rank)
@@ -245,6 +246,7 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
   return guarded([&]() -> int {
     if (!src || !out) return fail(PBRHIP_EINVAL, "scene_replicate: NULL argument");
     if (!src->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+    PB_NOT_STALE(src);
     int ndev = 0;
     if (int rc = pbrhip_device_count(&ndev)) return rc;
     if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "device %d out of range (%d devices)", device, ndev);
@@ -298,7 +300,7 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
       if (int r = set_environment(s, src->env_rgb.data(), src->env_w, src->env_h, src->env_scale, src->env_m)) return r;
     if (src->cam_set)
       if (int r = set_camera(s, src->cam_eye, src->cam_lookat, src->cam_up, src->cam_vfov, src->cam_lens, src->cam_focus)) return r;
-    s->committed = true;
+    s->committed = true, s->replica = true;
     *out = guard.release();
     return PBRHIP_OK;
   });
@@ -311,6 +313,7 @@ extern "C" int pbrhip_render_multi(pbrhip_scene* const* scenes, uint32_t n, cons
     if (!scenes || !n || !d || !rgba || !count) return fail(PBRHIP_EINVAL, "render_multi: NULL argument");
     for (uint32_t i = 0; i < n; i++)
       if (!scenes[i] || !scenes[i]->committed) return fail(PBRHIP_ESTATE, "render_multi: scene %u is not committed", i);
+    for (uint32_t i = 0; i < n; i++) PB_NOT_STALE(scenes[i]);
     for (uint32_t i = 0; i < n; i++)
       for (uint32_t j = 0; j < i; j++)
         if (scenes[i] == scenes[j]) return fail(PBRHIP_EINVAL, "render_multi: scene %u is listed twice (replicate it)", i);

@@ -281,27 +281,29 @@ extern "C" int pbrhip_scene_add_mesh_to_local_scene(pbrhip_scene* s, uint32_t lo
   return PBRHIP_OK;
   });
 }
+static const float kIdentity4x4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+// raytracer_impl.cc:49-84 hands the matrix to Embree (row-vector convention, v' = v * M, translation in the last
+// row); everything above the raytracer keeps working in the instance's local space (scene.cc:217,237 "TODO
+// transform").  A matrix that is not invertible has no such instance.
+static int check_transform(const float* m, const char* who) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(m[k])) return fail(PBRHIP_EINVAL, "%s: the transform has a non-finite entry", who);
+  const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
+                     (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
+  if (!(det != 0.0)) return fail(PBRHIP_EINVAL, "%s: the transform is singular", who);
+  return PBRHIP_OK;
+}
 extern "C" int pbrhip_scene_create_instance(pbrhip_scene* s, uint32_t local_scene_id, const float* transform,
                                             uint32_t* instance_id) {
   return guarded([&]() -> int {
   if (!s || !instance_id) return fail(PBRHIP_EINVAL, "create_instance: NULL argument");
   if (local_scene_id >= s->locals.size()) return fail(PBRHIP_EINVAL, "local scene %u out of range", local_scene_id);
-  static const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   HostInstance in;
   in.local_scene = local_scene_id;
-  memcpy(in.xf, transform ? transform : ident, sizeof(ident));
-  in.identity = memcmp(in.xf, ident, sizeof(ident)) == 0;
-  if (!in.identity) {
-    // raytracer_impl.cc:49-84 hands the matrix to Embree (row-vector convention, v' = v * M, translation in the last
-    // row); everything above the raytracer keeps working in the instance's local space (scene.cc:217,237 "TODO
-    // transform").  A matrix that is not invertible has no such instance.
-    const float* m = in.xf;
-    for (int k = 0; k < 16; k++)
-      if (!std::isfinite(m[k])) return fail(PBRHIP_EINVAL, "create_instance: the transform has a non-finite entry");
-    const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
-                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
-    if (!(det != 0.0)) return fail(PBRHIP_EINVAL, "create_instance: the transform is singular");
-  }
+  memcpy(in.xf, transform ? transform : kIdentity4x4, sizeof(kIdentity4x4));
+  in.identity = memcmp(in.xf, kIdentity4x4, sizeof(kIdentity4x4)) == 0;
+  if (!in.identity)
+    if (int rc = check_transform(in.xf, "create_instance")) return rc;
   // scene.cc:119-143: material ids are copied from the meshes when the instance is created
   for (uint32_t mid : s->locals[local_scene_id]) {
     const HostMesh& m = s->meshes[mid];
@@ -579,25 +581,18 @@ static void light_records(const pbrhip_scene* s, std::vector<LightHead>* heads, 
   }
 }
 
-// Leaf-ordered slots (traversal geometry, 64 B each) + one 128-byte ShadeRec per slot (everything shading needs).
-static int slots_and_shade(const pbrhip_scene* s, const std::vector<PrimRef>& prims, const std::vector<uint32_t>& slot_gid,
-                           const std::vector<LightHead>& heads, std::vector<float4>* slots, std::vector<ShadeRec>* shade) {
-  const uint32_t ns = (uint32_t)slot_gid.size();
-  slots->resize(4 * (size_t)ns);
-  shade->resize(ns);
-  for (uint32_t k = 0; k < ns; k++) {
-    uint32_t g = slot_gid[k];
-    const PrimRef& pr = prims[g];
+// One slot: the four 16-byte words `sl` and the ShadeRec `sr` of primitive `pr` with canonical id g (what pbrhip_scene_commit stages
+// for every slot and pbrhip_scene_refit for the dirty ones).
+static int slot_and_shade(const pbrhip_scene* s, const PrimRef& pr, uint32_t g, const std::vector<LightHead>& heads, float4* sl, ShadeRec& sr) {
+  {
     const HostInstance& in = s->instances[pr.instance_id];
     const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
     uint32_t mat = in.material_ids[pr.geom_id][pr.prim_id];
     if (mat != kNone && (mat >= s->materials.size() || mat >= 0x00FFFFFFu)) return fail(PBRHIP_EINVAL, "material id %u out of range", mat);
-    ShadeRec& sr = (*shade)[k];
     memset(&sr, 0, sizeof(sr));
     uint32_t flags = 0, lightrec = kNone;
     if (mat == kNone) flags |= kSlotMatNone;
     else if (s->materials[mat].kind == kMatHair) flags |= kSlotMatHair;
-    float4* sl = &(*slots)[4 * (size_t)k];
     for (int c = 0; c < 4; c++) sl[c] = make_float4(0, 0, 0, 0);
     if (pr.kind == 0) {
       for (int c = 0; c < 3; c++) {
@@ -659,6 +654,16 @@ static int slots_and_shade(const pbrhip_scene* s, const std::vector<PrimRef>& pr
     sl[2].w = __builtin_bit_cast(float, route);  // travels with the hit record (Hit::slot)
     sr.instance_id = pr.instance_id, sr.geom_id = pr.geom_id, sr.prim_id = pr.prim_id;
   }
+  return PBRHIP_OK;
+}
+// Leaf-ordered slots (traversal geometry, 64 B each) + one 128-byte ShadeRec per slot (everything shading needs).
+static int slots_and_shade(const pbrhip_scene* s, const std::vector<PrimRef>& prims, const std::vector<uint32_t>& slot_gid,
+                           const std::vector<LightHead>& heads, std::vector<float4>* slots, std::vector<ShadeRec>* shade) {
+  const uint32_t ns = (uint32_t)slot_gid.size();
+  slots->resize(4 * (size_t)ns);
+  shade->resize(ns);
+  for (uint32_t k = 0; k < ns; k++)
+    if (int rc = slot_and_shade(s, prims[slot_gid[k]], slot_gid[k], heads, &(*slots)[4 * (size_t)k], (*shade)[k])) return rc;
   return PBRHIP_OK;
 }
 
@@ -797,14 +802,18 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
     }
   }
   const std::vector<QNode>& wide = q.nodes;
-  // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
-  std::vector<SssEntry> sss_entries;
-  if (!wide.empty() && k.sss_entry) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
+  {  // the bounds of every instance's primitive boxes: what the random walks' entries are cut around (kept for pbrhip_scene_refit)
     const size_t ninst = s->instances.size();
-    std::vector<float> ilo(3 * ninst, INFINITY), ihi(3 * ninst, -INFINITY);
+    std::vector<float>&ilo = s->inst_lo, &ihi = s->inst_hi;
+    ilo.assign(3 * ninst, INFINITY), ihi.assign(3 * ninst, -INFINITY);
     for (uint32_t g = 0; g < np; g++)
       for (size_t a = 0, i = prims[g].instance_id; a < 3; a++)
         ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * (size_t)g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * (size_t)g + a]);
+  }
+  // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
+  std::vector<SssEntry> sss_entries;
+  if (!wide.empty() && k.sss_entry) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
+    const std::vector<float>&ilo = s->inst_lo, &ihi = s->inst_hi;
     // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
     const uint32_t max_foreign = std::min(k.sss_foreign, kSssMaxForeign);
     const auto t_entries = std::chrono::steady_clock::now();
@@ -854,6 +863,10 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   d.lights_transformed = 0;
   for (const HostLight& L : s->lights) d.lights_transformed |= s->instances[L.instance_id].identity ? 0u : 1u;
   s->wide_stack_need = wide.empty() ? 0u : q.stack_need, s->wide_built_on_gpu = wide_on_gpu;
+  // what pbrhip_scene_refit needs of this commit; the device scene is the model's again
+  s->slot_gid = std::move(bvh.slot_gid), s->light_heads = std::move(heads), s->q_points = wide.empty() ? 0 : q_pts;
+  s->rf_plan.release();
+  s->dirty_inst.assign(s->instances.size(), 0), s->stale = false;
   s->committed = true;
   return PBRHIP_OK;
   });
@@ -884,6 +897,7 @@ extern "C" int pbrhip_scene_aabb(const pbrhip_scene* s, float bmin[3], float bma
   return guarded([&]() -> int {
   if (!s || !bmin || !bmax) return fail(PBRHIP_EINVAL, "scene_aabb: NULL argument");
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
   memcpy(bmin, s->bmin, 12), memcpy(bmax, s->bmax, 12);
   return PBRHIP_OK;
   });
@@ -937,6 +951,196 @@ extern "C" int pbrhip_scene_update_hair_material(pbrhip_scene* s, uint32_t id, c
   memset(&m.pr, 0, sizeof(m.pr));
   memcpy(&m.hr, p, sizeof(m.hr));
   return update_material(s, id, m);
+  });
+}
+
+// ------------------------------------------------------------------ geometry edits and the refit ("The refit, exactly")
+static bool all_finite(const float* v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+// after an edit of the host model: on a committed scene every instance that shows the mesh (mesh_id) or the one instance is dirty
+static void mark_dirty(pbrhip_scene* s, uint32_t mesh_id, uint32_t instance_id) {
+  if (!s->committed) return;
+  s->dirty_inst.resize(s->instances.size(), 0);
+  for (uint32_t i = 0; i < s->instances.size(); i++) {
+    bool hit = i == instance_id;
+    if (mesh_id != kNone)
+      for (uint32_t m : s->locals[s->instances[i].local_scene]) hit = hit || m == mesh_id;
+    if (hit) s->dirty_inst[i] = 1, s->stale = true;
+  }
+}
+static int check_mesh_update(const pbrhip_scene* s, uint32_t mesh_id, int kind, const char* who) {
+  if (s->replica) return fail(PBRHIP_ESTATE, "%s: a replica holds no geometry (refit the source scene and replicate it again)", who);
+  if (mesh_id >= s->meshes.size()) return fail(PBRHIP_EINVAL, "%s: mesh %u out of range", who, mesh_id);
+  if (s->meshes[mesh_id].kind != kind) return fail(PBRHIP_EINVAL, "%s: mesh %u is of the other kind", who, mesh_id);
+  return PBRHIP_OK;
+}
+extern "C" int pbrhip_scene_update_triangle_mesh(pbrhip_scene* s, uint32_t mesh_id, const float* vertices_xyzw, uint32_t num_vertices,
+                                                 const float* normals_xyzw, uint32_t num_normals) {
+  return guarded([&]() -> int {
+  if (!s || (!vertices_xyzw && num_vertices)) return fail(PBRHIP_EINVAL, "update_triangle_mesh: NULL argument");
+  if (int rc = check_mesh_update(s, mesh_id, 0, "update_triangle_mesh")) return rc;
+  HostMesh& m = s->meshes[mesh_id];
+  if ((size_t)num_vertices * 4 != m.vertices.size()) return fail(PBRHIP_ESIZE, "update_triangle_mesh: %u vertices, the mesh has %zu", num_vertices, m.vertices.size() / 4);
+  if (normals_xyzw && (size_t)num_normals * 4 != m.normals.size()) return fail(PBRHIP_ESIZE, "update_triangle_mesh: %u normals, the mesh has %zu", num_normals, m.normals.size() / 4);
+  if (!all_finite(vertices_xyzw, (size_t)num_vertices * 4) || (normals_xyzw && !all_finite(normals_xyzw, (size_t)num_normals * 4)))
+    return fail(PBRHIP_EINVAL, "update_triangle_mesh: a value is not finite");
+  m.vertices.assign(vertices_xyzw, vertices_xyzw + (size_t)num_vertices * 4);
+  if (normals_xyzw) m.normals.assign(normals_xyzw, normals_xyzw + (size_t)num_normals * 4);
+  mark_dirty(s, mesh_id, kNone);
+  return PBRHIP_OK;
+  });
+}
+extern "C" int pbrhip_scene_update_curve_mesh(pbrhip_scene* s, uint32_t mesh_id, const float* vertices_xyzr, uint32_t num_vertices) {
+  return guarded([&]() -> int {
+  if (!s || (!vertices_xyzr && num_vertices)) return fail(PBRHIP_EINVAL, "update_curve_mesh: NULL argument");
+  if (int rc = check_mesh_update(s, mesh_id, 1, "update_curve_mesh")) return rc;
+  HostMesh& m = s->meshes[mesh_id];
+  if ((size_t)num_vertices * 4 != m.cverts.size()) return fail(PBRHIP_ESIZE, "update_curve_mesh: %u vertices, the mesh has %zu", num_vertices, m.cverts.size() / 4);
+  if (!all_finite(vertices_xyzr, (size_t)num_vertices * 4)) return fail(PBRHIP_EINVAL, "update_curve_mesh: a value is not finite");
+  m.cverts.assign(vertices_xyzr, vertices_xyzr + (size_t)num_vertices * 4);
+  mark_dirty(s, mesh_id, kNone);
+  return PBRHIP_OK;
+  });
+}
+extern "C" int pbrhip_scene_update_instance_transform(pbrhip_scene* s, uint32_t instance_id, const float* transform) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "update_instance_transform: scene is NULL");
+  if (s->replica) return fail(PBRHIP_ESTATE, "update_instance_transform: a replica holds no geometry (refit the source scene and replicate it again)");
+  if (instance_id >= s->instances.size()) return fail(PBRHIP_EINVAL, "update_instance_transform: instance %u out of range", instance_id);
+  const float* m = transform ? transform : kIdentity4x4;
+  const bool identity = memcmp(m, kIdentity4x4, sizeof(kIdentity4x4)) == 0;
+  if (!identity)
+    if (int rc = check_transform(m, "update_instance_transform")) return rc;
+  HostInstance& in = s->instances[instance_id];
+  memcpy(in.xf, m, sizeof(in.xf));
+  in.identity = identity;
+  mark_dirty(s, kNone, instance_id);
+  return PBRHIP_OK;
+  });
+}
+
+// the tight box of a staged slot: what prim_boxes computes for its primitive, from the very numbers the slot holds
+static void slot_tight_box(const float4* sl, bool curve, float lo[3], float hi[3]) {
+  const float a[3] = {sl[0].x, sl[0].y, sl[0].z}, b[3] = {sl[1].x, sl[1].y, sl[1].z}, c[3] = {sl[2].x, sl[2].y, sl[2].z};
+  const float r = std::max(fabsf(sl[0].w), fabsf(sl[1].w));
+  for (int k = 0; k < 3; k++) {
+    if (curve) lo[k] = std::min(a[k], b[k]) - r, hi[k] = std::max(a[k], b[k]) + r;
+    else lo[k] = std::min(std::min(a[k], b[k]), c[k]), hi[k] = std::max(std::max(a[k], b[k]), c[k]);
+  }
+}
+
+extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  if (s->replica) return fail(PBRHIP_ESTATE, "scene_refit: a replica holds no geometry (refit the source scene and replicate it again)");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  if (!s->stale) return PBRHIP_OK;
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  DScene& d = s->dscene;
+  const auto now = [] { return std::chrono::steady_clock::now(); };
+  const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+  const auto t_host = now();
+  const size_t ninst = s->instances.size();
+  s->dirty_inst.resize(ninst, 0);
+  // light tables: positions, areas and with them every probability (what commit runs, on the whole scene: the tables are small)
+  bool lights_dirty = false;
+  for (size_t i = 0; i < ninst; i++)
+    if (s->dirty_inst[i])
+      for (int has : s->instances[i].has_area_light) lights_dirty = lights_dirty || has != 0;
+  std::vector<LightRec> lrecs;
+  std::vector<float> lprim_cdf;
+  if (lights_dirty) {
+    for (uint32_t i = 0; i < ninst; i++) register_lights(s, i);
+    commit_lights(s);
+    light_records(s, &s->light_heads, &lrecs, &lprim_cdf);
+  }
+  // the dirty slots and their ShadeRecs, packed for one upload: index | 64 B | 128 B; the dirty instances' bounds from their new boxes
+  std::vector<PrimRef> prims;
+  if (int rc = flatten_prims(s, &prims)) return rc;
+  const uint32_t ns = d.num_slots;
+  if (s->slot_gid.size() != ns || prims.size() != ns) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
+  std::vector<uint32_t> dirty;
+  for (uint32_t slot = 0; slot < ns; slot++)
+    if (s->dirty_inst[prims[s->slot_gid[slot]].instance_id]) dirty.push_back(slot);
+  const uint32_t m = (uint32_t)dirty.size();
+  const size_t idx_words = ((size_t)m + 3) / 4;
+  std::vector<float4> packed(idx_words + 12 * (size_t)m, make_float4(0, 0, 0, 0));
+  std::vector<float> ilo = s->inst_lo, ihi = s->inst_hi;
+  for (size_t i = 0; i < ninst; i++)
+    if (s->dirty_inst[i])
+      for (int a = 0; a < 3; a++) ilo[3 * i + a] = INFINITY, ihi[3 * i + a] = -INFINITY;
+  for (uint32_t e = 0; e < m; e++) {
+    const uint32_t g = s->slot_gid[dirty[e]];
+    float4* sl = &packed[idx_words + 4 * (size_t)e];
+    ShadeRec sr;
+    if (int rc = slot_and_shade(s, prims[g], g, s->light_heads, sl, sr)) return rc;
+    reinterpret_cast<uint32_t*>(packed.data())[e] = dirty[e];
+    memcpy(&packed[idx_words + 4 * (size_t)m + 8 * (size_t)e], &sr, sizeof(sr));
+    float lo[3], hi[3];
+    slot_tight_box(sl, prims[g].kind != 0, lo, hi);
+    for (size_t a = 0, i = prims[g].instance_id; a < 3; a++) ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[a]);
+  }
+  float keep_min[3], keep_max[3];  // (a failed refit leaves the scene as stale as it was)
+  memcpy(keep_min, s->bmin, 12), memcpy(keep_max, s->bmax, 12);
+  scene_bounds(s);
+  const double ms_host = ms_since(t_host);
+
+  const auto t_up = now();
+  HIPCHK(s->rf_packed.upload(packed, st));
+  HIPCHK(scatter_slots_gpu(st, s->rf_packed.p, m, ns, reinterpret_cast<float4*>(s->d_nodes.p + d.num_nodes), reinterpret_cast<float4*>(s->d_shade.p)));
+  if (lights_dirty) {
+    HIPCHK(s->d_light_cdf.upload(s->light_cdf, st));
+    HIPCHK(s->d_heads.upload(s->light_heads, st));
+    HIPCHK(s->d_lprim_cdf.upload(lprim_cdf, st));
+    HIPCHK(s->d_lrecs.upload(lrecs, st));
+    HIPCHK(s->d_light_boxes.upload(light_boxes(s->light_heads, lrecs), st));
+  }
+  if (k.debug) HIPCHK(hipStreamSynchronize(st));
+  const double ms_upload = ms_since(t_up);
+
+  RefitTree t;
+  t.nodes = s->d_nodes.p, t.nb = d.num_nodes, t.ns = ns;
+  if (d.wide) {
+    t.q = reinterpret_cast<QNode*>(s->d_wide.p), t.nq = d.wide_nodes;
+    t.tri = s->d_wide.p + d.q_tri0, t.tri_words = d.q_pt0 - d.q_tri0, t.tri_pairs = d.num_curves == 0;
+    t.pts = s->d_wide.p + d.q_pt0, t.hit = s->d_qhit.p, t.npts = s->q_points;
+  }
+  RefitTimes rt;
+  HIPCHK(refit_tree_gpu(st, t, k.debug, &s->rf_plan, &rt));
+  if (rt.failed) {
+    memcpy(s->bmin, keep_min, 12), memcpy(s->bmax, keep_max, 12);
+    return fail(PBRHIP_EHIP, "scene_refit: %s; the scene stays stale (pbrhip_scene_commit rebuilds it)",
+                (rt.failed & 1u) ? "a node of the Q tree cannot be quantised" : "the committed tree holds an index out of range");
+  }
+  // the random walks' entries: a cut is only sound for the bounds it was made for
+  const auto t_entries = now();
+  if (d.wide && d.sss_entries) {
+    std::vector<QNode> wide(d.wide_nodes);
+    HIPCHK(hipMemcpyAsync(wide.data(), s->d_wide.p, wide.size() * sizeof(QNode), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const std::vector<SssEntry> entries = build_sss_entries(wide, ilo, ihi, std::min(k.sss_foreign, kSssMaxForeign));
+    HIPCHK(s->d_sss_entries.upload(entries, st));
+    HIPCHK(hipStreamSynchronize(st));
+    d.sss_entries = s->d_sss_entries.p, d.num_sss_entries = (uint32_t)entries.size();
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (k.debug)
+    fprintf(stderr, "pbrhip: refit: %u of %u slots dirty: host staging %.2f ms, upload + scatter %.2f ms, plan %.2f ms, pack + trees %.2f ms (%u + %u levels), Q-node download + walk entries %.2f ms\n",
+            m, ns, ms_host, ms_upload, rt.plan_ms, rt.trees_ms, rt.bin_levels, rt.q_levels, ms_since(t_entries));
+  if (lights_dirty) {
+    d.light_cdf = s->d_light_cdf.p, d.light_heads = s->d_heads.p, d.lprim_cdf = s->d_lprim_cdf.p, d.lrecs = s->d_lrecs.p, d.light_boxes = s->d_light_boxes.p;
+    d.num_lights = (uint32_t)s->lights.size(), d.num_lrecs = (uint32_t)lrecs.size();
+  }
+  d.lights_transformed = 0;
+  for (const HostLight& L : s->lights) d.lights_transformed |= s->instances[L.instance_id].identity ? 0u : 1u;
+  s->inst_lo = std::move(ilo), s->inst_hi = std::move(ihi);
+  s->dirty_inst.assign(ninst, 0), s->stale = false;
+  return PBRHIP_OK;
   });
 }
 
@@ -1311,6 +1515,7 @@ static std::vector<uint32_t> plan_groups(const Knobs& k, uint32_t np, uint32_t n
 
 static int check_render_desc(const pbrhip_scene* s, const pbrhip_render_desc* d) {
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
   if (d->width == 0 || d->height == 0) return fail(PBRHIP_EINVAL, "empty image");
   if ((uint64_t)d->width * d->height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "image too large");
   const uint32_t world = d->tile_world ? d->tile_world : 1;
@@ -2112,6 +2317,63 @@ extern "C" int pbrhip_qtree_collapse(int device, const float* lo, const float* h
   });
 }
 
+// pbrhip_scene_refit's kernels on bare trees: plan, leaf records, both trees (no scene)
+extern "C" int pbrhip_tree_refit(int device, uint32_t n, const void* slots, void* nodes_inout, void* qnodes_inout, uint32_t num_qnodes,
+                                 void* tri_inout, uint32_t tri_words, int tri_pairs, void* pts_inout, const uint32_t* hit, uint32_t num_points) {
+  return guarded([&]() -> int {
+    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "tree_refit: too many slots (%u)", n);
+    if (n == 0) return PBRHIP_OK;
+    if (!slots || !nodes_inout) return fail(PBRHIP_EINVAL, "tree_refit: NULL argument");
+    if (qnodes_inout && (num_qnodes == 0 || (tri_words && !tri_inout) || !pts_inout || !hit)) return fail(PBRHIP_EINVAL, "tree_refit: NULL argument");
+    if (qnodes_inout && (num_qnodes >= (1u << 27) || num_points >= (1u << 27) || tri_words >= 3u * (1u << 27))) return fail(PBRHIP_EINVAL, "tree_refit: a size is out of range");
+    int ndev = 0;
+    if (int rc = pbrhip_device_count(&ndev)) return rc;
+    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "tree_refit: device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    struct Stream {
+      hipStream_t s = nullptr;
+      ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+      }
+    } st;
+    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    const size_t nn = n > 1 ? n - 1 : 1;
+    const size_t nq = qnodes_inout ? num_qnodes : 0;
+    DevBuf<BvhNode> d_nodes;  // nodes, then the slots in leaf order: the layout of a committed scene
+    DevBuf<float4> d_wide;
+    DevBuf<uint32_t> d_hit;
+    HIPCHK(d_nodes.reserve(nn + n));
+    HIPCHK(hipMemcpyAsync(d_nodes.p, nodes_inout, nn * 64, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(d_nodes.p + nn, slots, (size_t)n * 64, hipMemcpyHostToDevice, st.s));
+    RefitTree t;
+    t.nodes = d_nodes.p, t.nb = (uint32_t)nn, t.ns = n;
+    if (nq) {
+      HIPCHK(d_wide.reserve(nq * 4 + tri_words + num_points));
+      HIPCHK(d_hit.reserve(num_points));
+      HIPCHK(hipMemcpyAsync(d_wide.p, qnodes_inout, nq * 64, hipMemcpyHostToDevice, st.s));
+      if (tri_words) HIPCHK(hipMemcpyAsync(d_wide.p + nq * 4, tri_inout, (size_t)tri_words * 16, hipMemcpyHostToDevice, st.s));
+      if (num_points) HIPCHK(hipMemcpyAsync(d_wide.p + nq * 4 + tri_words, pts_inout, (size_t)num_points * 16, hipMemcpyHostToDevice, st.s));
+      if (num_points) HIPCHK(hipMemcpyAsync(d_hit.p, hit, (size_t)num_points * 4, hipMemcpyHostToDevice, st.s));
+      t.q = reinterpret_cast<QNode*>(d_wide.p), t.nq = (uint32_t)nq;
+      t.tri = d_wide.p + nq * 4, t.tri_words = tri_words, t.tri_pairs = tri_pairs != 0;
+      t.pts = d_wide.p + nq * 4 + tri_words, t.hit = d_hit.p, t.npts = num_points;
+    }
+    RefitPlan plan;
+    RefitTimes rt;
+    HIPCHK(refit_tree_gpu(st.s, t, false, &plan, &rt));
+    if (rt.failed) return fail(PBRHIP_EHIP, "tree_refit: %s", (rt.failed & 1u) ? "a node of the Q tree cannot be quantised" : "the tree holds an index out of range");
+    HIPCHK(hipMemcpyAsync(nodes_inout, d_nodes.p, nn * 64, hipMemcpyDeviceToHost, st.s));
+    if (nq) {
+      HIPCHK(hipMemcpyAsync(qnodes_inout, d_wide.p, nq * 64, hipMemcpyDeviceToHost, st.s));
+      if (tri_words) HIPCHK(hipMemcpyAsync(tri_inout, d_wide.p + nq * 4, (size_t)tri_words * 16, hipMemcpyDeviceToHost, st.s));
+      if (num_points) HIPCHK(hipMemcpyAsync(pts_inout, d_wide.p + nq * 4 + tri_words, (size_t)num_points * 16, hipMemcpyDeviceToHost, st.s));
+    }
+    HIPCHK(hipStreamSynchronize(st.s));
+    return PBRHIP_OK;
+  });
+}
+
 extern "C" int pbrhip_leaf_eval(uint32_t op, const float* in, size_t n, uint32_t in_words, float* out, uint32_t out_words) {
   return guarded([&]() -> int {
     if ((!in || !out) && n) return fail(PBRHIP_EINVAL, "leaf_eval: NULL argument");
@@ -2137,6 +2399,7 @@ extern "C" int pbrhip_camera_rays(pbrhip_scene* s, uint32_t width, uint32_t heig
   if (!s || (!x_y_pass && n) || (!rays && n)) return fail(PBRHIP_EINVAL, "camera_rays: NULL argument");
   if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "camera_rays: zero image size");
   if (!s->cam_set && !s->committed) return fail(PBRHIP_ESTATE, "camera_rays: the reference camera needs a committed scene");
+  PB_NOT_STALE(s);
   if (n == 0) return PBRHIP_OK;
   if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
   for (size_t i = 0; i < n; i++)
@@ -2159,6 +2422,7 @@ static int trace_hook(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, void* o
   const char* name = any ? "trace_any" : "trace_closest";
   if (!s || (!rays && n) || (!out && n)) return fail(PBRHIP_EINVAL, "%s: NULL argument", name);
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
   if (n == 0) return PBRHIP_OK;
   if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
   const Knobs k = read_knobs();

@@ -44,6 +44,12 @@ static inline int guarded(F&& f) {
   }
 }
 
+// In front of the body of every entry point that reads the device scene: geometry edits are pending (pbrhip_scene_update_*)
+#define PB_NOT_STALE(s)                                                                                                   \
+  do {                                                                                                                    \
+    if ((s)->stale) return pb::fail(PBRHIP_ESTATE, "the scene has pending geometry edits: call pbrhip_scene_refit first"); \
+  } while (0)
+
 // ------------------------------------------------------------------ device buffers
 template <typename T>
 struct DevBuf {
@@ -93,6 +99,17 @@ struct pbrhip_scene {
   bool bvh_built_on_gpu = false;
   uint32_t wide_stack_need = 0;    // of the Q tree (0: none): pbrhip_scene_wide_info
   bool wide_built_on_gpu = false;  // the Q tree was collapsed on the device (PBRHIP_BVH_GPU_LBVH_WIDE)
+  // geometry edits on a committed scene (pbrhip_scene_update_triangle_mesh / _curve_mesh / _instance_transform) and what
+  // pbrhip_scene_refit needs of the last commit ("The refit, exactly")
+  bool stale = false;               // edits are pending: the device scene is not the model's until pbrhip_scene_refit or a commit
+  bool replica = false;             // made by pbrhip_scene_replicate: no host geometry, nothing to edit or refit
+  std::vector<uint8_t> dirty_inst;  // per instance: a mesh of its local scene or its transform changed since the device scene was made
+  std::vector<uint32_t> slot_gid;   // slot -> canonical primitive id, as the builder ordered the leaves
+  std::vector<pb::LightHead> light_heads;  // light -> its stretch of light records (fixed by the topology)
+  std::vector<float> inst_lo, inst_hi;     // per instance: the bounds of its primitives' boxes (what the random walks' entries are cut around)
+  size_t q_points = 0;              // points of the Q tree's curve records (DScene::q_hitcode's length)
+  pb::RefitPlan rf_plan;            // built at the first refit of a committed tree, dropped by the next commit
+  pb::DevBuf<float4> rf_packed;     // the dirty slots' upload: index | 64 B | 128 B (refit_gpu.hip::k_rf_scatter)
   // device scene
   pb::DevBuf<pb::BvhNode> d_nodes;
   pb::DevBuf<float4> d_wide;  // the Q tree: quantised 4-wide nodes + its triangle slots + curve points (DScene::wide), built on the host, or on the device by qtree_gpu.hip
