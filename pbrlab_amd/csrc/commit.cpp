@@ -1,0 +1,662 @@
+// commit.cpp -- from the host model to the device scene: the staging helpers (light tables, primitive boxes, slots and
+// ShadeRecs, materials), pbrhip_scene_commit, pbrhip_scene_refit and the device write of a material edit.  Host C++ only.
+#include <math.h>
+#include <string.h>
+
+#include <chrono>
+#include <limits>
+#include <numeric>
+
+#include "scene_impl.h"
+
+using namespace pb;
+
+static_assert(sizeof(LightRec) == 80, "light record layout");
+
+// ------------------------------------------------------------------ commit
+static V3 mesh_vertex(const HostMesh& m, uint32_t prim, int k) {
+  const float* p = m.vertices.data() + (size_t)m.vid[prim * 3 + k] * 4;
+  return V3(p[0], p[1], p[2]);
+}
+// What the raytracer sees of an instance (raytracer_impl.cc:61-81: the transform goes to Embree and nowhere else):
+// v' = v * M with the translation row, in this order of operations (the checker uses the same expression).
+static V3 xf_point(const float* m, V3 v) {
+  return V3(m[0] * v.x + m[4] * v.y + m[8] * v.z + m[12], m[1] * v.x + m[5] * v.y + m[9] * v.z + m[13],
+            m[2] * v.x + m[6] * v.y + m[10] * v.z + m[14]);
+}
+static V3 world_vertex(const HostInstance& in, const HostMesh& m, uint32_t prim, int k) {
+  const V3 v = mesh_vertex(m, prim, k);
+  return in.identity ? v : xf_point(in.xf, v);
+}
+// control points xyzr of curve `prim` as the raytracer sees them (the radius is not scaled)
+static void world_curve(const HostInstance& in, const HostMesh& m, uint32_t prim, float out[16]) {
+  const float* cps = m.cverts.data() + (size_t)m.cidx[prim] * 4;
+  for (int c = 0; c < 4; c++) {
+    V3 v(cps[4 * c], cps[4 * c + 1], cps[4 * c + 2]);
+    if (!in.identity) v = xf_point(in.xf, v);
+    out[4 * c] = v.x, out[4 * c + 1] = v.y, out[4 * c + 2] = v.z, out[4 * c + 3] = cps[4 * c + 3];
+  }
+}
+// TriangleMesh::FetchFaceArea (mesh/triangle-mesh.cc:113-124)
+static float face_area(const HostMesh& m, uint32_t prim) {
+  V3 p0 = mesh_vertex(m, prim, 0), p1 = mesh_vertex(m, prim, 1), p2 = mesh_vertex(m, prim, 2);
+  return length(cross(p1 - p0, p2 - p0)) * 0.5f;
+}
+
+// LightManager::RegisterInstanceMesh (light-manager.cc:79-184)
+static void register_lights(pbrhip_scene* s, uint32_t instance_id) {
+  HostInstance& in = s->instances[instance_id];
+  size_t ng = in.light_ids.size();
+  in.has_area_light.assign(ng, 0);
+  in.area_lights.assign(ng, HostAreaLight());
+  for (size_t g = 0; g < ng; g++) {
+    const std::vector<uint32_t>& ids = in.light_ids[g];
+    if (ids.empty()) continue;
+    const HostMesh& m = *inst_mesh(s, instance_id, (uint32_t)g);
+    if (m.kind != 0) continue;
+    uint32_t nf = m.nfaces;
+    bool have = false;
+    for (uint32_t f = 0; f < nf; f++) have = have || ids[f] != kNone;
+    if (!have) continue;
+    HostAreaLight& a = in.area_lights[g];
+    in.has_area_light[g] = 1;
+    a.light_param_ids = ids;
+    a.choose_prob.assign(nf, 0.f);
+    for (uint32_t f = 0; f < nf; f++) {
+      float intensity = 0.0f;
+      if (ids[f] != kNone) intensity = spectrum_norm(s->light_params[ids[f]]);
+      a.choose_prob[f] = intensity * face_area(m, f);
+    }
+    a.intensity_sum = std::accumulate(a.choose_prob.begin(), a.choose_prob.end(), 0.0f);
+    const float sum = a.intensity_sum;
+    for (float& v : a.choose_prob) v = v / sum;
+    a.cdf = a.choose_prob;
+    for (uint32_t f = 0; nf > 0 && f < nf - 1u; f++) a.cdf[f + 1u] += a.cdf[f];
+    a.area_pdf.assign(nf, 0.f);
+    for (uint32_t f = 0; f < nf; f++)
+      if (ids[f] != kNone) a.area_pdf[f] = 1.0f / face_area(m, f);
+  }
+}
+// LightManager::Commit (light-manager.cc:29-77)
+static void commit_lights(pbrhip_scene* s) {
+  s->lights.clear();
+  double intensity_sum = 0.0;
+  for (uint32_t i = 0; i < s->instances.size(); i++) {
+    HostInstance& in = s->instances[i];
+    for (uint32_t g = 0; g < in.area_lights.size(); g++) {
+      if (!in.has_area_light[g]) continue;
+      in.area_lights[g].global_id = (uint32_t)s->lights.size();
+      HostLight L;
+      L.choose_prob = in.area_lights[g].intensity_sum;
+      L.instance_id = i, L.geom_id = g;
+      intensity_sum += (double)L.choose_prob;
+      s->lights.push_back(L);
+    }
+  }
+  for (HostLight& L : s->lights) L.choose_prob = (float)((double)L.choose_prob / intensity_sum);
+  s->light_cdf.resize(s->lights.size());
+  for (size_t l = 0; l < s->lights.size(); l++) s->light_cdf[l] = s->lights[l].choose_prob;
+  for (size_t l = 0; !s->light_cdf.empty() && l < s->light_cdf.size() - 1u; l++) s->light_cdf[l + 1u] += s->light_cdf[l];
+}
+
+static Material make_material(const HostMaterial& hm) {
+  Material m;
+  memset(&m, 0, sizeof(m));
+  m.kind = hm.kind;
+  m.bsdf = default_bsdf();
+  if (hm.kind == kMatPrincipled) {
+    m.bsdf = param_to_bsdf(hm.pr);
+    m.param = hm.pr;
+    medium_coefficients(m.bsdf, m.sss_sigt, m.sss_sigs, m.sss_wthr);  // (only read when the subsurface closure is picked)
+    m.textured = (hm.pr.base_color_tex_id != kNone || hm.pr.subsurface_color_tex_id != kNone) ? 1u : 0u;
+  } else {
+    m.hair = hair_param_to_bsdf(hm.hr);
+  }
+  return m;
+}
+
+// End points of linear piece `sub` of a cubic Bezier (control points xyzr): B(sub/4) and B((sub+1)/4), evaluated with
+// the arithmetic of the intersection contract (Bernstein weights, products summed left to right, single precision,
+// no contraction) so that every back end tests the same segment.
+static void curve_piece(const float* cp, uint32_t sub, float a[4], float b[4]) {
+  for (uint32_t e = 0; e < 2; e++) {
+    const float u = (float)(sub + e) * 0.25f, s = 1.0f - u;
+    const float b0 = s * s * s, b1 = 3.0f * u * s * s, b2 = 3.0f * u * u * s, b3 = u * u * u;
+    for (int k = 0; k < 4; k++) (e ? b : a)[k] = ((cp[k] * b0 + cp[4 + k] * b1) + cp[8 + k] * b2) + cp[12 + k] * b3;
+  }
+}
+
+// Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.
+static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
+  for (uint32_t i = 0; i < s->instances.size(); i++)
+    for (uint32_t g = 0; g < s->instances[i].material_ids.size(); g++) {
+      const HostMesh& m = *inst_mesh(s, i, g);
+      if (s->instances[i].material_ids[g].size() != m.num_prims())
+        return fail(PBRHIP_ESIZE, "material param error (instance %u geom %u)", i, g);
+      for (uint32_t p = 0; p < m.num_prims(); p++)
+        for (uint32_t sub = 0; sub < (m.kind == 1 ? 4u : 1u); sub++) prims->push_back({i, g, p, (uint32_t)m.kind, sub});
+    }
+  return PBRHIP_OK;
+}
+
+// Scene bounds (rtcGetSceneBounds, raytracer_impl.cc:199-202; they place the camera): the union of the instances'
+// bounds.  An RTC_GEOMETRY_TYPE_INSTANCE (raytracer_impl.cc:61-81) reports the box of the transformed CORNERS of its local
+// scene's box -- larger than the box of the transformed geometry under rotation or shear; an instance whose matrix is
+// bit for bit the identity reports the local box.  Local box: triangles by their corners, curves by the hull of their
+// control points widened by the largest control radius.  (The tree is built over the transformed primitives.)
+static void scene_bounds(pbrhip_scene* s) {
+  const float inf = std::numeric_limits<float>::infinity();
+  float bmin[3] = {inf, inf, inf}, bmax[3] = {-inf, -inf, -inf};
+  for (uint32_t i = 0; i < s->instances.size(); i++) {
+    const HostInstance& inst = s->instances[i];
+    float ll[3] = {inf, inf, inf}, lh[3] = {-inf, -inf, -inf};
+    bool any = false;
+    for (uint32_t g = 0; g < inst.material_ids.size(); g++) {
+      const HostMesh& m = *inst_mesh(s, i, g);
+      for (uint32_t p = 0; p < m.num_prims(); p++) {
+        any = true;
+        if (m.kind == 0) {
+          for (int c = 0; c < 3; c++) {
+            const V3 v = mesh_vertex(m, p, c);
+            const float a[3] = {v.x, v.y, v.z};
+            for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], a[k]), lh[k] = fmaxf(lh[k], a[k]);
+          }
+        } else {
+          float r = 0.f, cl[3] = {inf, inf, inf}, ch[3] = {-inf, -inf, -inf};
+          for (int c = 0; c < 4; c++) {
+            const float* cp = m.cverts.data() + ((size_t)m.cidx[p] + c) * 4;
+            r = fmaxf(r, fabsf(cp[3]));
+            for (int k = 0; k < 3; k++) cl[k] = fminf(cl[k], cp[k]), ch[k] = fmaxf(ch[k], cp[k]);
+          }
+          for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], cl[k] - r), lh[k] = fmaxf(lh[k], ch[k] + r);
+        }
+      }
+    }
+    if (!any) continue;
+    if (inst.identity) {
+      for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], ll[k]), bmax[k] = fmaxf(bmax[k], lh[k]);
+    } else {
+      for (int c = 0; c < 8; c++) {
+        const V3 v = xf_point(inst.xf, V3((c & 1) ? lh[0] : ll[0], (c & 2) ? lh[1] : ll[1], (c & 4) ? lh[2] : ll[2]));
+        const float a[3] = {v.x, v.y, v.z};
+        for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], a[k]), bmax[k] = fmaxf(bmax[k], a[k]);
+      }
+    }
+  }
+  memcpy(s->bmin, bmin, sizeof(bmin));
+  memcpy(s->bmax, bmax, sizeof(bmax));
+}
+
+// The tight box of a slot's first three words: a triangle's corners, or the two end points (xyz, radius) of a curve piece widened by
+// the larger end radius (the ribbon between them never leaves that box, and a hit is reported at the depth of the axis point).
+static void slot_tight_box(const float4* sl, bool curve, float lo[3], float hi[3]) {
+  const float a[3] = {sl[0].x, sl[0].y, sl[0].z}, b[3] = {sl[1].x, sl[1].y, sl[1].z}, c[3] = {sl[2].x, sl[2].y, sl[2].z};
+  const float r = std::max(fabsf(sl[0].w), fabsf(sl[1].w));
+  for (int k = 0; k < 3; k++) {
+    if (curve) lo[k] = std::min(a[k], b[k]) - r, hi[k] = std::max(a[k], b[k]) + r;
+    else lo[k] = std::min(std::min(a[k], b[k]), c[k]), hi[k] = std::max(std::max(a[k], b[k]), c[k]);
+  }
+}
+// The box (world space) and kind of every primitive: what the tree is built over, from the numbers its slot will hold.
+static void prim_boxes(const pbrhip_scene* s, const std::vector<PrimRef>& prims, std::vector<float>* lo, std::vector<float>* hi,
+                       std::vector<uint8_t>* kinds) {
+  const uint32_t np = (uint32_t)prims.size();
+  lo->assign(3 * (size_t)np, 0.f), hi->assign(3 * (size_t)np, 0.f), kinds->assign(np, 0);
+  for (uint32_t g = 0; g < np; g++) {
+    const PrimRef& pr = prims[g];
+    const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
+    const HostInstance& inst = s->instances[pr.instance_id];
+    float4 sl[3] = {};
+    float cps[16], a[4], b[4];
+    (*kinds)[g] = (uint8_t)pr.kind;
+    if (pr.kind == 0) {
+      for (int c = 0; c < 3; c++) {
+        const V3 v = world_vertex(inst, m, pr.prim_id, c);
+        sl[c] = make_float4(v.x, v.y, v.z, 0.f);
+      }
+    } else {
+      world_curve(inst, m, pr.prim_id, cps);
+      curve_piece(cps, pr.sub, a, b);
+      sl[0] = make_float4(a[0], a[1], a[2], a[3]), sl[1] = make_float4(b[0], b[1], b[2], b[3]);
+    }
+    slot_tight_box(sl, pr.kind != 0, &(*lo)[3 * (size_t)g], &(*hi)[3 * (size_t)g]);
+  }
+}
+
+// Light records: one per (light, prim), concatenated; heads[l] is light l's stretch of them.
+static void light_records(const pbrhip_scene* s, std::vector<LightHead>* heads, std::vector<LightRec>* lrecs,
+                          std::vector<float>* lprim_cdf) {
+  heads->resize(s->lights.size());
+  for (size_t l = 0; l < s->lights.size(); l++) {
+    const HostLight& L = s->lights[l];
+    const HostAreaLight& a = s->instances[L.instance_id].area_lights[L.geom_id];
+    const HostMesh& m = *inst_mesh(s, L.instance_id, L.geom_id);
+    (*heads)[l].first = (uint32_t)lrecs->size();
+    (*heads)[l].count = m.nfaces;
+    for (uint32_t f = 0; f < m.nfaces; f++) {
+      LightRec r;
+      memset(&r, 0, sizeof(r));
+      V3 p0 = mesh_vertex(m, f, 0), p1 = mesh_vertex(m, f, 1), p2 = mesh_vertex(m, f, 2);
+      V3 n = vnormalize(cross(p1 - p0, p2 - p1));  // CalcGeometryNormal (triangle-mesh.cc:181-184)
+      r.p0[0] = p0.x, r.p0[1] = p0.y, r.p0[2] = p0.z;
+      r.p1[0] = p1.x, r.p1[1] = p1.y, r.p1[2] = p1.z;
+      r.p2[0] = p2.x, r.p2[1] = p2.y, r.p2[2] = p2.z;
+      r.normal[0] = n.x, r.normal[1] = n.y, r.normal[2] = n.z;
+      // light-manager.h:68-70,149-150: choose_light * choose_prim * prim_area_pdf, in that order
+      r.pdf = L.choose_prob * a.choose_prob[f] * a.area_pdf[f];
+      if (a.light_param_ids[f] != kNone) {
+        V3 e = s->light_params[a.light_param_ids[f]];
+        r.emission[0] = e.x, r.emission[1] = e.y, r.emission[2] = e.z;
+      }
+      lrecs->push_back(r);
+      lprim_cdf->push_back(a.cdf[f]);
+    }
+  }
+}
+
+// One slot: the four 16-byte words `sl` and the ShadeRec `sr` of primitive `pr` with canonical id g (what pbrhip_scene_commit stages
+// for every slot and pbrhip_scene_refit for the dirty ones).
+static int slot_and_shade(const pbrhip_scene* s, const PrimRef& pr, uint32_t g, const std::vector<LightHead>& heads, float4* sl, ShadeRec& sr) {
+  const HostInstance& in = s->instances[pr.instance_id];
+  const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
+  uint32_t mat = in.material_ids[pr.geom_id][pr.prim_id];
+  if (mat != kNone && (mat >= s->materials.size() || mat >= 0x00FFFFFFu)) return fail(PBRHIP_EINVAL, "material id %u out of range", mat);
+  memset(&sr, 0, sizeof(sr));
+  uint32_t flags = 0, lightrec = kNone;
+  if (mat == kNone) flags |= kSlotMatNone;
+  else if (s->materials[mat].kind == kMatHair) flags |= kSlotMatHair;
+  for (int c = 0; c < 4; c++) sl[c] = make_float4(0, 0, 0, 0);
+  if (pr.kind == 0) {
+    for (int c = 0; c < 3; c++) {
+      // traversal: what Embree sees (the transformed triangle); shading: the mesh's own corners -- the geometric normal
+      // Embree reports for an instance is in the instance's local space and pbrlab uses it as it is
+      const V3 w = world_vertex(in, m, pr.prim_id, c);
+      sl[c] = make_float4(w.x, w.y, w.z, 0.f);
+    }
+    {
+      // the two normals every hit on this triangle would otherwise compute from its corners (ShadeRec, dscene.h): the kernels'
+      // own functions, evaluated here
+      const V3 v0 = mesh_vertex(m, pr.prim_id, 0), v1 = mesh_vertex(m, pr.prim_id, 1), v2 = mesh_vertex(m, pr.prim_id, 2);
+      const V3 ng = normalize_raw(cross(v1 - v0, v2 - v0));
+      const V3 nf = vnormalize(cross(v1 - v0, v2 - v1));  // CalcGeometryNormal, triangle-mesh.cc:181-184
+      sr.ng[0] = ng.x, sr.ng[1] = ng.y, sr.ng[2] = ng.z;
+      sr.ns_flat[0] = nf.x, sr.ns_flat[1] = nf.y, sr.ns_flat[2] = nf.z;
+    }
+    uint32_t a = m.nid[pr.prim_id * 3 + 0], b = m.nid[pr.prim_id * 3 + 1], c = m.nid[pr.prim_id * 3 + 2];
+    if (a != kNone && b != kNone && c != kNone) {  // triangle-mesh.cc:81-84
+      flags |= kSlotHasNormals;
+      const uint32_t idx[3] = {a, b, c};
+      for (int q = 0; q < 3; q++) {
+        const float* n = m.normals.data() + (size_t)idx[q] * 4;
+        sr.n[3 * q + 0] = n[0], sr.n[3 * q + 1] = n[1], sr.n[3 * q + 2] = n[2];
+      }
+    }
+    if (in.has_area_light[pr.geom_id]) {
+      const HostAreaLight& al = in.area_lights[pr.geom_id];
+      if (al.light_param_ids[pr.prim_id] != kNone) lightrec = heads[al.global_id].first + pr.prim_id;
+    }
+    uint32_t ta = m.tid[pr.prim_id * 3 + 0], tb = m.tid[pr.prim_id * 3 + 1], tc = m.tid[pr.prim_id * 3 + 2];
+    if (ta != kNone && tb != kNone && tc != kNone) {  // triangle-mesh.cc:130-133
+      flags |= kSlotHasUV;
+      const uint32_t idx[3] = {ta, tb, tc};
+      for (int q = 0; q < 3; q++) {
+        sr.uv[2 * q + 0] = m.texcoords[(size_t)idx[q] * 2 + 0];
+        sr.uv[2 * q + 1] = m.texcoords[(size_t)idx[q] * 2 + 1];
+      }
+    }
+  } else {
+    flags |= kSlotIsCurve;
+    const float* cps = m.cverts.data() + (size_t)m.cidx[pr.prim_id] * 4;  // local: the tangent (= Ng) shading uses
+    float wcps[16];
+    world_curve(in, m, pr.prim_id, wcps);
+    float a[4], b[4];
+    curve_piece(wcps, pr.sub, a, b);
+    sl[0] = make_float4(a[0], a[1], a[2], a[3]);
+    sl[1] = make_float4(b[0], b[1], b[2], b[3]);
+    sl[2] = make_float4(__builtin_bit_cast(float, pr.sub), 0.f, 0.f, 0.f);
+    // shading needs the cubic itself (tangent = dP/du at the hit): control points xyzr in words 8..23 of the record
+    float* w = reinterpret_cast<float*>(&sr);
+    for (int c = 0; c < 16; c++) w[8 + c] = cps[c];
+  }
+  sr.gid = g, sr.lightrec = lightrec;
+  sr.matflags = (mat == kNone ? 0x00FFFFFFu : mat) | (flags << 24);
+  const uint32_t route = ((flags & kSlotMatHair) ? kHitHair : 0u) | ((flags & kSlotMatNone) ? kHitNoMaterial : 0u) |
+                         (lightrec != kNone ? kHitLight : 0u) |
+                         ((flags & (kSlotHasNormals | kSlotHasUV | kSlotIsCurve)) ? kHitMore : 0u);
+  sl[2].w = __builtin_bit_cast(float, route);  // travels with the hit record (Hit::slot)
+  sr.instance_id = pr.instance_id, sr.geom_id = pr.geom_id, sr.prim_id = pr.prim_id;
+  return PBRHIP_OK;
+}
+// One box per light over all primitives of its mesh, packed two per node (an odd last one is stored twice).
+static std::vector<BvhNode> light_boxes(const std::vector<LightHead>& heads, const std::vector<LightRec>& lrecs) {
+  std::vector<BvhNode> boxes((heads.size() + 1) / 2);
+  for (size_t l = 0; l < heads.size(); l++) {
+    float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t f = heads[l].first; f < heads[l].first + heads[l].count; f++)
+      for (const float* p : {lrecs[f].p0, lrecs[f].p1, lrecs[f].p2})
+        for (int a = 0; a < 3; a++) lo3[a] = std::min(lo3[a], p[a]), hi3[a] = std::max(hi3[a], p[a]);
+    BvhNode& nd = boxes[l / 2];
+    if (l % 2 == 0) memset(&nd, 0, sizeof(nd)), nd.set_box(1, lo3, hi3);
+    nd.set_box(int(l % 2), lo3, hi3);
+  }
+  return boxes;
+}
+
+// ------------------------------------------------------------------ the steps of commit and refit
+static double ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// Every host array a step stages.  Most are handed to hipMemcpyAsync from pageable memory: commit and refit own one of these until
+// their final hipStreamSynchronize, so that no staged array dies before the copy has read it.
+struct CommitStage {
+  std::vector<PrimRef> prims;  // canonical order: the index is the gid
+  std::vector<float> lo, hi, lprim_cdf;  // (lo, hi, kinds: what the tree is built over)
+  std::vector<uint8_t> kinds;
+  FlatBvh bvh;  // (built on the GPU: no nodes here, they are on the device)
+  std::vector<float4> slots;
+  std::vector<ShadeRec> shade;
+  std::vector<Material> mats;
+  QLayout q;  // built on the host: all of it; collapsed on the device, or refitted there: the nodes as they came back
+  std::vector<LightRec> lrecs;
+  std::vector<BvhNode> lboxes;
+  std::vector<SssEntry> walk_entries;
+};
+
+static void stage_lights(pbrhip_scene* s, CommitStage* cs) {  // the light tables of the whole model: they are small
+  for (uint32_t i = 0; i < s->instances.size(); i++) register_lights(s, i);
+  commit_lights(s);
+  light_records(s, &s->light_heads, &cs->lrecs, &cs->lprim_cdf);
+  cs->lboxes = light_boxes(s->light_heads, cs->lrecs);
+  s->num_lrecs = (uint32_t)cs->lrecs.size();
+  // light sampling works on the meshes' local positions (light-manager.h:128-136 "TODO transform"), the raytracer on the
+  // transformed ones: the doomed-path pretest against the light primitives (kernels.hip::misses_all_lights) is only the
+  // traversal's own test when the two coincide
+  s->lights_transformed = std::any_of(s->lights.begin(), s->lights.end(), [&](const HostLight& L) { return !s->instances[L.instance_id].identity; });
+}
+static int upload_lights(pbrhip_scene* s, const CommitStage& cs) {
+  HIPCHK(s->d_light_cdf.upload(s->light_cdf, s->stream));
+  HIPCHK(s->d_heads.upload(s->light_heads, s->stream));
+  HIPCHK(s->d_lprim_cdf.upload(cs.lprim_cdf, s->stream));
+  HIPCHK(s->d_lrecs.upload(cs.lrecs, s->stream));
+  HIPCHK(s->d_light_boxes.upload(cs.lboxes, s->stream));
+  return PBRHIP_OK;
+}
+
+static int build_binary_tree(pbrhip_scene* s, int builder, CommitStage* cs) {  // on the GPU into the scene's nodes, or on the host and uploaded
+  FlatBvh& bvh = cs->bvh;
+  const uint32_t np = (uint32_t)cs->prims.size();
+  s->bvh_built_on_gpu = false;
+  if ((builder == PBRHIP_BVH_GPU_LBVH || builder == PBRHIP_BVH_GPU_LBVH_WIDE) && np > 0) {
+    HIPCHK(s->tree.reserve_nodes(TreeBufs::lbvh_nodes(np), np));  // (one slot per primitive)
+    HIPCHK(build_bvh_gpu(s->stream, cs->lo, cs->hi, cs->kinds, s->tree.d_nodes.p, &bvh.slot_gid, &bvh.depth));
+    s->bvh_built_on_gpu = bvh.depth <= (uint32_t)kStackDepth;
+    if (!s->bvh_built_on_gpu) {
+      // a Morton-order tree over badly distributed primitives can be deeper than the traversal stack: use the SAH tree
+      fprintf(stderr, "pbrhip: GPU-built BVH is %u deep (stack %d): building on the host instead\n", bvh.depth, kStackDepth);
+      bvh = FlatBvh();
+    }
+  }
+  if (!s->bvh_built_on_gpu) build_bvh(cs->lo, cs->hi, cs->kinds, &bvh);
+  if (bvh.depth > (uint32_t)kStackDepth)
+    return fail(PBRHIP_EOVERFLOW, "BVH depth %u exceeds the traversal stack (%d)", bvh.depth, kStackDepth);
+  s->bvh_depth = bvh.depth;
+  if (!s->bvh_built_on_gpu) {
+    HIPCHK(s->tree.reserve_nodes((uint32_t)bvh.nodes.size(), (uint32_t)bvh.slot_gid.size()));
+    if (!bvh.nodes.empty()) HIPCHK(hipMemcpyAsync(s->tree.d_nodes.p, bvh.nodes.data(), bvh.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice, s->stream));
+  }
+  return PBRHIP_OK;
+}
+
+static int stage_slots_and_materials(pbrhip_scene* s, CommitStage* cs) {
+  const uint32_t ns = (uint32_t)cs->bvh.slot_gid.size();
+  if (ns > kHitSlotMask) return fail(PBRHIP_EINVAL, "%u traversal primitives: at most %u are supported", ns, kHitSlotMask);
+  // leaf-ordered slots (traversal geometry, 64 B each) + one 128-byte ShadeRec per slot (everything shading needs)
+  cs->slots.resize(4 * (size_t)ns), cs->shade.resize(ns);
+  for (uint32_t k = 0; k < ns; k++)
+    if (int rc = slot_and_shade(s, cs->prims[cs->bvh.slot_gid[k]], cs->bvh.slot_gid[k], s->light_heads, &cs->slots[4 * (size_t)k], cs->shade[k])) return rc;
+  std::vector<Material>& mats = cs->mats;
+  mats.resize(s->materials.size());
+  s->has_hair = s->has_sss = s->has_textured = false;
+  for (size_t i = 0; i < mats.size(); i++) {
+    const HostMaterial& hm = s->materials[i];
+    if (hm.kind == kMatPrincipled)
+      for (uint32_t t : {hm.pr.base_color_tex_id, hm.pr.subsurface_color_tex_id})
+        if (t != kNone && t >= s->tex_descs.size()) return fail(PBRHIP_EINVAL, "material %zu: texture id %u out of range", i, t);
+    mats[i] = make_material(s->materials[i]);
+    if (mats[i].textured) s->has_sss = s->has_textured = true;  // a subsurface_color / base_color map can switch the SSS closure on per hit
+    s->has_hair = s->has_hair || mats[i].kind == kMatHair;
+    s->has_sss = s->has_sss || (mats[i].kind == kMatPrincipled && mats[i].bsdf.enable_subsurface);
+  }
+  return PBRHIP_OK;
+}
+
+// The Q tree of the traversal kernels (dscene.h::QNode; PBRHIP_WIDE=0 at commit: none).  A host-built tree is collapsed on the host
+// (bvh_build.cpp::build_qlayout) and uploaded.  PBRHIP_BVH_GPU_LBVH_WIDE: the GPU-built tree is collapsed on the device (qtree_gpu.hip)
+// straight into the scene's buffers, and the nodes come back for the stack need and the walk entries.  A tree that cannot be kept is dropped.
+static int build_wide_tree(pbrhip_scene* s, const Knobs& k, int builder, CommitStage* cs) {
+  TreeBufs& t = s->tree;
+  QLayout& q = cs->q;
+  s->wide_built_on_gpu = false;
+  if (!s->bvh_built_on_gpu && t.num_nodes && k.wide) {
+    build_qlayout(cs->bvh, cs->slots, cs->kinds, &q);
+    if (k.debug) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
+  }
+  if (s->bvh_built_on_gpu && builder == PBRHIP_BVH_GPU_LBVH_WIDE && k.wide) {
+    const bool tri_pairs = all_triangles(cs->kinds);
+    QCollapse qc;
+    HIPCHK(hipStreamSynchronize(s->stream));  // (the slots are on the device: what follows is the collapse's own time)
+    const auto t_start = std::chrono::steady_clock::now();
+    HIPCHK(collapse_qtree_gpu(s->stream, t.d_nodes.p, t.num_slots, t.slots(), tri_pairs, [&](auto... a) { return t.alloc_wide(a...); }, &qc));
+    const double ms_collapse = ms_since(t_start);
+    const char* why = !qc.fits ? "a record index overflows its reference" : (!qc.quantised ? "a node cannot be quantised" : nullptr);
+    if (!why) {
+      q.nodes.resize(qc.nodes);
+      HIPCHK(hipMemcpyAsync(q.nodes.data(), t.d_wide.p, (size_t)qc.nodes * sizeof(QNode), hipMemcpyDeviceToHost, s->stream));
+      HIPCHK(hipStreamSynchronize(s->stream));
+      q.stack_need = qtree_stack_need(q.nodes);
+      if (q.stack_need > (uint32_t)kStackDepth) why = "its traversal needs more than the stack";
+    }
+    if (k.debug)
+      fprintf(stderr, "pbrhip: commit: Q tree on the device: %u nodes in %u levels, collapse %.2f ms (of which allocation %.2f ms), download + stack need %.2f ms\n",
+              qc.nodes, qc.levels, ms_collapse, qc.alloc_ms, ms_since(t_start) - ms_collapse);
+    if (why) {
+      fprintf(stderr, "pbrhip: the Q tree of the GPU-built BVH is dropped (%s): rendering the binary tree\n", why);
+      q = QLayout();
+    } else {
+      s->wide_built_on_gpu = true;
+      t.set_wide(qc.nodes, qc.tri_words, qc.pts);
+    }
+  }
+  if (!s->wide_built_on_gpu) HIPCHK(t.upload(q.nodes.data(), (uint32_t)q.nodes.size(), q.tri.data(), q.tri.size(), q.pts.data(), q.hit.data(), q.pts.size(), s->stream));
+  s->wide_stack_need = q.nodes.empty() ? 0u : q.stack_need;
+  return PBRHIP_OK;
+}
+
+// (the bounds of an instance's primitive boxes: what the random walks' entries are cut around)
+static void accumulate_instance_bounds(std::vector<float>& ilo, std::vector<float>& ihi, size_t inst, const float* lo, const float* hi) {
+  for (size_t a = 0; a < 3; a++) ilo[3 * inst + a] = std::min(ilo[3 * inst + a], lo[a]), ihi[3 * inst + a] = std::max(ihi[3 * inst + a], hi[a]);
+}
+
+// Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree (cs->q.nodes: its nodes on the host) around
+// the instance's bounds; none without a Q tree or with !want.  *ms (optional): what building them took, untouched if none were built.
+static int update_walk_entries(pbrhip_scene* s, const Knobs& k, bool want, const std::vector<float>& ilo, const std::vector<float>& ihi, CommitStage* cs, double* ms) {
+  cs->walk_entries.clear();
+  if (want && !cs->q.nodes.empty()) {
+    const auto t_entries = std::chrono::steady_clock::now();
+    // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
+    cs->walk_entries = build_sss_entries(cs->q.nodes, ilo, ihi, std::min(k.sss_foreign, kSssMaxForeign));
+    if (ms) *ms = ms_since(t_entries);
+  }
+  s->num_walk_entries = (uint32_t)cs->walk_entries.size();
+  if (cs->walk_entries.empty()) s->d_sss_entries.release();
+  else HIPCHK(s->d_sss_entries.upload(cs->walk_entries, s->stream));
+  return PBRHIP_OK;
+}
+
+void pb::bind_dscene(pbrhip_scene* s) {
+  DScene& d = s->dscene;
+  const TreeBufs& t = s->tree;
+  d.nodes = t.d_nodes.p, d.slots = t.slots(), d.num_nodes = t.num_nodes, d.num_slots = t.num_slots;
+  d.top_nodes = s->bvh_built_on_gpu ? 0u : std::min<uint32_t>(t.num_nodes, (uint32_t)kTopNodes);
+  d.wide = t.wide_nodes ? t.d_wide.p : nullptr, d.q_hitcode = t.wide_nodes ? t.d_qhit.p : nullptr, d.wide_nodes = t.wide_nodes;
+  d.q_tri0 = (uint32_t)t.tri0(), d.q_pt0 = (uint32_t)t.pt0();
+  d.wide_top_nodes = std::min<uint32_t>(t.wide_nodes, (uint32_t)kTopNodes);
+  d.shade = s->d_shade.p, d.num_curves = s->num_curves;
+  d.materials = s->d_materials.p, d.num_materials = (uint32_t)s->materials.size();
+  d.light_cdf = s->d_light_cdf.p, d.light_heads = s->d_heads.p, d.num_lights = (uint32_t)s->lights.size();
+  d.lprim_cdf = s->d_lprim_cdf.p, d.lrecs = s->d_lrecs.p, d.num_lrecs = s->num_lrecs;
+  d.light_boxes = s->d_light_boxes.p, d.lights_transformed = s->lights_transformed ? 1u : 0u;
+  d.tex_pixels = s->d_tex_pixels.p, d.textures = s->d_tex_descs.p, d.num_textures = (uint32_t)s->tex_descs.size();
+  d.sss_entries = s->num_walk_entries ? s->d_sss_entries.p : nullptr, d.num_sss_entries = s->num_walk_entries;
+}
+
+extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  const int builder = k.bvh >= 0 ? k.bvh : s->bvh_builder;
+  CommitStage cs;  // (outlives the synchronise below)
+  // the steps rewrite what the scene records and reallocate its device buffers: one that fails leaves the scene uncommitted, not
+  // bound to tables that were never uploaded or to freed memory
+  s->committed = false;
+  stage_lights(s, &cs);
+  if (int rc = flatten_prims(s, &cs.prims)) return rc;
+  const uint32_t np = (uint32_t)cs.prims.size();
+  if (np >= (1u << 27)) return fail(PBRHIP_EUNSUPPORTED, "too many primitives (%u)", np);
+  prim_boxes(s, cs.prims, &cs.lo, &cs.hi, &cs.kinds);
+  scene_bounds(s);
+  s->num_curves = (uint32_t)(cs.kinds.size() - std::count(cs.kinds.begin(), cs.kinds.end(), 0));
+  if (int rc = build_binary_tree(s, builder, &cs)) return rc;
+  if (int rc = stage_slots_and_materials(s, &cs)) return rc;
+  const TreeBufs& t = s->tree;
+  if (t.num_slots) HIPCHK(hipMemcpyAsync(t.slots(), cs.slots.data(), (size_t)t.num_slots * 64, hipMemcpyHostToDevice, s->stream));
+  if (int rc = build_wide_tree(s, k, builder, &cs)) return rc;
+  s->inst_lo.assign(3 * s->instances.size(), INFINITY), s->inst_hi.assign(3 * s->instances.size(), -INFINITY);  // (kept for pbrhip_scene_refit)
+  for (size_t g = 0; g < cs.prims.size(); g++) accumulate_instance_bounds(s->inst_lo, s->inst_hi, cs.prims[g].instance_id, &cs.lo[3 * g], &cs.hi[3 * g]);
+  double ms_entries = -1.0;  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
+  if (int rc = update_walk_entries(s, k, k.sss_entry, s->inst_lo, s->inst_hi, &cs, &ms_entries)) return rc;
+  if (k.debug) {
+    if (ms_entries >= 0.0) fprintf(stderr, "pbrhip: commit: random walks' entries over %zu wide nodes: %.2f ms\n", cs.q.nodes.size(), ms_entries);
+    for (size_t i = 0; i < cs.walk_entries.size(); i++)
+      if (cs.walk_entries[i].entry) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, cs.walk_entries[i].entry, cs.walk_entries[i].nforeign);
+    fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", t.num_nodes, (size_t)t.wide_nodes, (size_t)t.num_slots, t.tri_words / kTriPairWords, t.points);
+  }
+  HIPCHK(s->d_shade.upload(cs.shade, s->stream));
+  HIPCHK(s->d_materials.upload(cs.mats, s->stream));
+  if (int rc = upload_lights(s, cs)) return rc;
+  HIPCHK(s->d_tex_pixels.upload(s->tex_pixels, s->stream));
+  HIPCHK(s->d_tex_descs.upload(s->tex_descs, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  bind_dscene(s);
+  // what pbrhip_scene_refit needs of this commit; the device scene is the model's again
+  s->slot_gid = std::move(cs.bvh.slot_gid);
+  s->rf_plan.release();
+  s->dirty_inst.assign(s->instances.size(), 0), s->stale = false;
+  s->committed = true;
+  return PBRHIP_OK;
+  });
+}
+
+int pb::update_material(pbrhip_scene* s, uint32_t id, const HostMaterial& hm) {
+  // validate everything first: a rejected call leaves the host material, has_sss and the device copy as they were
+  if (id >= s->materials.size()) return fail(PBRHIP_EINVAL, "material id %u out of range", id);
+  if (s->materials[id].kind != hm.kind) return fail(PBRHIP_EINVAL, "material %u is of the other kind", id);
+  if (s->committed && hm.kind == kMatPrincipled)
+    for (uint32_t t : {hm.pr.base_color_tex_id, hm.pr.subsurface_color_tex_id})
+      if (t != kNone && t >= s->tex_descs.size()) return fail(PBRHIP_EINVAL, "texture id %u out of range", t);
+  if (s->committed) {
+    HIPCHK(hipSetDevice(s->device));
+    const Material m = make_material(hm);
+    HIPCHK(hipMemcpyAsync(s->d_materials.p + id, &m, sizeof(m), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->has_sss = s->has_sss || (m.kind == kMatPrincipled && (m.bsdf.enable_subsurface || m.textured));
+    s->has_textured = s->has_textured || (m.kind == kMatPrincipled && m.textured);
+  }
+  s->materials[id] = hm;
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
+  if (s->replica) return fail(PBRHIP_ESTATE, "scene_refit: a replica holds no geometry (refit the source scene and replicate it again)");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  if (!s->stale) return PBRHIP_OK;
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const TreeBufs& t = s->tree;
+  const auto t_host = std::chrono::steady_clock::now();
+  const size_t ninst = s->instances.size();
+  s->dirty_inst.resize(ninst, 0);
+  CommitStage cs;  // (outlives the last synchronise)
+  // light tables: positions, areas and with them every probability
+  bool lights_dirty = false;
+  for (size_t i = 0; i < ninst; i++)
+    if (s->dirty_inst[i])
+      for (int has : s->instances[i].has_area_light) lights_dirty = lights_dirty || has != 0;
+  if (lights_dirty) stage_lights(s, &cs);
+  // the dirty slots and their ShadeRecs, packed for one upload: index | 64 B | 128 B; the dirty instances' bounds from their new boxes
+  if (int rc = flatten_prims(s, &cs.prims)) return rc;
+  const uint32_t ns = t.num_slots;
+  if (s->slot_gid.size() != ns || cs.prims.size() != ns) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
+  std::vector<uint32_t> dirty;
+  for (uint32_t slot = 0; slot < ns; slot++)
+    if (s->dirty_inst[cs.prims[s->slot_gid[slot]].instance_id]) dirty.push_back(slot);
+  const uint32_t m = (uint32_t)dirty.size();
+  const size_t idx_words = ((size_t)m + 3) / 4;
+  std::vector<float4> packed(idx_words + 12 * (size_t)m, make_float4(0, 0, 0, 0));
+  std::vector<float> ilo = s->inst_lo, ihi = s->inst_hi;
+  for (size_t i = 0; i < ninst; i++)
+    if (s->dirty_inst[i])
+      for (int a = 0; a < 3; a++) ilo[3 * i + a] = INFINITY, ihi[3 * i + a] = -INFINITY;
+  for (uint32_t e = 0; e < m; e++) {
+    const uint32_t g = s->slot_gid[dirty[e]];
+    float4* sl = &packed[idx_words + 4 * (size_t)e];
+    ShadeRec sr;
+    if (int rc = slot_and_shade(s, cs.prims[g], g, s->light_heads, sl, sr)) return rc;
+    reinterpret_cast<uint32_t*>(packed.data())[e] = dirty[e];
+    memcpy(&packed[idx_words + 4 * (size_t)m + 8 * (size_t)e], &sr, sizeof(sr));
+    float lo[3], hi[3];
+    slot_tight_box(sl, cs.prims[g].kind != 0, lo, hi);
+    accumulate_instance_bounds(ilo, ihi, cs.prims[g].instance_id, lo, hi);
+  }
+  float keep_min[3], keep_max[3];  // (a failed refit leaves the scene as stale as it was)
+  memcpy(keep_min, s->bmin, 12), memcpy(keep_max, s->bmax, 12);
+  scene_bounds(s);
+  const double ms_host = ms_since(t_host);
+
+  const auto t_up = std::chrono::steady_clock::now();
+  HIPCHK(s->rf_packed.upload(packed, st));
+  HIPCHK(scatter_slots_gpu(st, s->rf_packed.p, m, ns, t.slots(), reinterpret_cast<float4*>(s->d_shade.p)));
+  if (lights_dirty)
+    if (int rc = upload_lights(s, cs)) return rc;
+  if (k.debug) HIPCHK(hipStreamSynchronize(st));
+  const double ms_upload = ms_since(t_up);
+
+  RefitTimes rt;
+  HIPCHK(refit_tree_gpu(st, t.refit_tree(s->num_curves == 0), k.debug, &s->rf_plan, &rt));
+  if (rt.failed) {
+    memcpy(s->bmin, keep_min, 12), memcpy(s->bmax, keep_max, 12);
+    return fail(PBRHIP_EHIP, "scene_refit: %s; the scene stays stale (pbrhip_scene_commit rebuilds it)",
+                (rt.failed & 1u) ? "a node of the Q tree cannot be quantised" : "the committed tree holds an index out of range");
+  }
+  const auto t_entries = std::chrono::steady_clock::now();
+  if (t.wide_nodes && s->num_walk_entries) {  // (the scene has them: made again for the new bounds, over the refitted nodes)
+    cs.q.nodes.resize(t.wide_nodes);
+    HIPCHK(hipMemcpyAsync(cs.q.nodes.data(), t.d_wide.p, cs.q.nodes.size() * sizeof(QNode), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = update_walk_entries(s, k, true, ilo, ihi, &cs, nullptr)) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (k.debug)
+    fprintf(stderr, "pbrhip: refit: %u of %u slots dirty: host staging %.2f ms, upload + scatter %.2f ms, plan %.2f ms, pack + trees %.2f ms (%u + %u levels), Q-node download + walk entries %.2f ms\n",
+            m, ns, ms_host, ms_upload, rt.plan_ms, rt.trees_ms, rt.bin_levels, rt.q_levels, ms_since(t_entries));
+  bind_dscene(s);
+  s->inst_lo = std::move(ilo), s->inst_hi = std::move(ihi);
+  s->dirty_inst.assign(ninst, 0), s->stale = false;
+  return PBRHIP_OK;
+  });
+}

@@ -247,11 +247,8 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
     if (!src || !out) return fail(PBRHIP_EINVAL, "scene_replicate: NULL argument");
     if (!src->committed) return fail(PBRHIP_ESTATE, "scene not committed");
     PB_NOT_STALE(src);
-    int ndev = 0;
-    if (int rc = pbrhip_device_count(&ndev)) return rc;
-    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "device %d out of range (%d devices)", device, ndev);
     const int keep = current_device();
-    if (int rc = pbrhip_set_device(device)) return rc;
+    if (int rc = pbrhip_set_device(device)) return rc;  // ("device %d out of range (%d devices)")
     pbrhip_scene* s = nullptr;
     int rc = pbrhip_scene_create(&s);
     (void)pbrhip_set_device(keep);
@@ -272,30 +269,15 @@ extern "C" int pbrhip_scene_replicate(const pbrhip_scene* src, int device, pbrhi
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
       }
     }
-    if (int r = copy_buf(s->d_nodes, device, src->d_nodes, src->device)) return r;
-    if (int r = copy_buf(s->d_wide, device, src->d_wide, src->device)) return r;
-    if (int r = copy_buf(s->d_qhit, device, src->d_qhit, src->device)) return r;
-    if (int r = copy_buf(s->d_shade, device, src->d_shade, src->device)) return r;
-    if (int r = copy_buf(s->d_materials, device, src->d_materials, src->device)) return r;
-    if (int r = copy_buf(s->d_light_cdf, device, src->d_light_cdf, src->device)) return r;
-    if (int r = copy_buf(s->d_lprim_cdf, device, src->d_lprim_cdf, src->device)) return r;
-    if (int r = copy_buf(s->d_tex_pixels, device, src->d_tex_pixels, src->device)) return r;
-    if (int r = copy_buf(s->d_tex_descs, device, src->d_tex_descs, src->device)) return r;
-    if (int r = copy_buf(s->d_heads, device, src->d_heads, src->device)) return r;
-    if (int r = copy_buf(s->d_lrecs, device, src->d_lrecs, src->device)) return r;
-    if (int r = copy_buf(s->d_light_boxes, device, src->d_light_boxes, src->device)) return r;
-    if (int r = copy_buf(s->d_sss_entries, device, src->d_sss_entries, src->device)) return r;
+    int rc_copy = PBRHIP_OK;
+    pbrhip_scene::each_scene_buf([&](bool, auto& dst, const auto& from) { rc_copy = rc_copy ? rc_copy : copy_buf(dst, device, from, src->device); }, *s, *src);
+    if (rc_copy) return rc_copy;
     HIPCHK(hipDeviceSynchronize());
-    DScene& dd = s->dscene;
-    dd = src->dscene;
-    dd.nodes = s->d_nodes.p, dd.slots = reinterpret_cast<const float4*>(s->d_nodes.p + dd.num_nodes), dd.shade = s->d_shade.p;
-    dd.wide = src->dscene.wide ? s->d_wide.p : nullptr;
-    dd.q_hitcode = src->dscene.wide ? s->d_qhit.p : nullptr;
-    dd.materials = s->d_materials.p, dd.light_cdf = s->d_light_cdf.p, dd.light_heads = s->d_heads.p;
-    dd.lprim_cdf = s->d_lprim_cdf.p, dd.lrecs = s->d_lrecs.p, dd.light_boxes = s->d_light_boxes.p;
-    dd.sss_entries = src->dscene.sss_entries ? s->d_sss_entries.p : nullptr;
-    dd.tex_pixels = s->d_tex_pixels.p, dd.textures = s->d_tex_descs.p;
-    dd.env_texels = nullptr, dd.env_alias = nullptr, dd.env_w = dd.env_h = 0;  // (the environment is rebuilt on this device)
+    // what bind_dscene reads beside the buffers (the environment is rebuilt on this device, below)
+    s->tree.counts_from(src->tree);
+    s->num_curves = src->num_curves, s->num_lrecs = src->num_lrecs, s->num_walk_entries = src->num_walk_entries;
+    s->lights_transformed = src->lights_transformed;
+    bind_dscene(s);
     if (!src->env_rgb.empty())
       if (int r = set_environment(s, src->env_rgb.data(), src->env_w, src->env_h, src->env_scale, src->env_m)) return r;
     if (src->cam_set)

@@ -1,5 +1,5 @@
-// pbrhip.cpp -- C ABI (include/pbrhip.h): host scene store, commit (light tables, BVH, upload) and the
-// wavefront render loop that drives kernels.hip.  Host C++ only; device code lives in kernels.hip.
+// pbrhip.cpp -- C ABI (include/pbrhip.h): host scene store, model edits, getters, environment, camera and the wavefront render loop
+// that drives kernels.hip.  Commit and refit live in commit.cpp, the test hooks in hooks.cpp.  Host C++ only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -10,7 +10,6 @@
 #include <algorithm>
 #include <chrono>
 #include <memory>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -23,9 +22,6 @@ using namespace pb;
 
 static_assert(sizeof(pbrhip_principled_param) == sizeof(PrincipledParam), "param layout");
 static_assert(sizeof(pbrhip_hair_param) == sizeof(HairParam), "param layout");
-static_assert(sizeof(pbrhip_hit) == sizeof(HookHit), "hit layout");
-static_assert(sizeof(pbrhip_ray) == 32, "ray layout");
-static_assert(sizeof(LightRec) == 80, "light record layout");
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -315,10 +311,6 @@ extern "C" int pbrhip_scene_create_instance(pbrhip_scene* s, uint32_t local_scen
   return PBRHIP_OK;
   });
 }
-static const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id) {
-  const HostInstance& in = s->instances[instance_id];
-  return &s->meshes[s->locals[in.local_scene][geom_id]];
-}
 extern "C" int pbrhip_scene_attach_light_ids(pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id,
                                              const uint32_t* ids, uint32_t n) {
   return guarded([&]() -> int {
@@ -340,534 +332,6 @@ extern "C" int pbrhip_scene_attach_material_ids(pbrhip_scene* s, uint32_t instan
     return fail(PBRHIP_EINVAL, "instance %u / geom %u out of range", instance_id, geom_id);
   if (n != inst_mesh(s, instance_id, geom_id)->num_prims()) return fail(PBRHIP_ESIZE, "material param error");
   s->instances[instance_id].material_ids[geom_id].assign(ids, ids + n);
-  return PBRHIP_OK;
-  });
-}
-
-// ------------------------------------------------------------------ commit
-static V3 mesh_vertex(const HostMesh& m, uint32_t prim, int k) {
-  const float* p = m.vertices.data() + (size_t)m.vid[prim * 3 + k] * 4;
-  return V3(p[0], p[1], p[2]);
-}
-// What the raytracer sees of an instance (raytracer_impl.cc:61-81: the transform goes to Embree and nowhere else):
-// v' = v * M with the translation row, in this order of operations (the checker uses the same expression).
-static V3 xf_point(const float* m, V3 v) {
-  return V3(m[0] * v.x + m[4] * v.y + m[8] * v.z + m[12], m[1] * v.x + m[5] * v.y + m[9] * v.z + m[13],
-            m[2] * v.x + m[6] * v.y + m[10] * v.z + m[14]);
-}
-static V3 world_vertex(const HostInstance& in, const HostMesh& m, uint32_t prim, int k) {
-  const V3 v = mesh_vertex(m, prim, k);
-  return in.identity ? v : xf_point(in.xf, v);
-}
-// control points xyzr of curve `prim` as the raytracer sees them (the radius is not scaled)
-static void world_curve(const HostInstance& in, const HostMesh& m, uint32_t prim, float out[16]) {
-  const float* cps = m.cverts.data() + (size_t)m.cidx[prim] * 4;
-  for (int c = 0; c < 4; c++) {
-    V3 v(cps[4 * c], cps[4 * c + 1], cps[4 * c + 2]);
-    if (!in.identity) v = xf_point(in.xf, v);
-    out[4 * c] = v.x, out[4 * c + 1] = v.y, out[4 * c + 2] = v.z, out[4 * c + 3] = cps[4 * c + 3];
-  }
-}
-// TriangleMesh::FetchFaceArea (mesh/triangle-mesh.cc:113-124)
-static float face_area(const HostMesh& m, uint32_t prim) {
-  V3 p0 = mesh_vertex(m, prim, 0), p1 = mesh_vertex(m, prim, 1), p2 = mesh_vertex(m, prim, 2);
-  return length(cross(p1 - p0, p2 - p0)) * 0.5f;
-}
-
-// LightManager::RegisterInstanceMesh (light-manager.cc:79-184)
-static void register_lights(pbrhip_scene* s, uint32_t instance_id) {
-  HostInstance& in = s->instances[instance_id];
-  size_t ng = in.light_ids.size();
-  in.has_area_light.assign(ng, 0);
-  in.area_lights.assign(ng, HostAreaLight());
-  for (size_t g = 0; g < ng; g++) {
-    const std::vector<uint32_t>& ids = in.light_ids[g];
-    if (ids.empty()) continue;
-    const HostMesh& m = *inst_mesh(s, instance_id, (uint32_t)g);
-    if (m.kind != 0) continue;
-    uint32_t nf = m.nfaces;
-    bool have = false;
-    for (uint32_t f = 0; f < nf; f++) have = have || ids[f] != kNone;
-    if (!have) continue;
-    HostAreaLight& a = in.area_lights[g];
-    in.has_area_light[g] = 1;
-    a.light_param_ids = ids;
-    a.choose_prob.assign(nf, 0.f);
-    for (uint32_t f = 0; f < nf; f++) {
-      float intensity = 0.0f;
-      if (ids[f] != kNone) intensity = spectrum_norm(s->light_params[ids[f]]);
-      a.choose_prob[f] = intensity * face_area(m, f);
-    }
-    a.intensity_sum = std::accumulate(a.choose_prob.begin(), a.choose_prob.end(), 0.0f);
-    const float sum = a.intensity_sum;
-    for (float& v : a.choose_prob) v = v / sum;
-    a.cdf = a.choose_prob;
-    for (uint32_t f = 0; nf > 0 && f < nf - 1u; f++) a.cdf[f + 1u] += a.cdf[f];
-    a.area_pdf.assign(nf, 0.f);
-    for (uint32_t f = 0; f < nf; f++)
-      if (ids[f] != kNone) a.area_pdf[f] = 1.0f / face_area(m, f);
-  }
-}
-// LightManager::Commit (light-manager.cc:29-77)
-static void commit_lights(pbrhip_scene* s) {
-  s->lights.clear();
-  double intensity_sum = 0.0;
-  for (uint32_t i = 0; i < s->instances.size(); i++) {
-    HostInstance& in = s->instances[i];
-    for (uint32_t g = 0; g < in.area_lights.size(); g++) {
-      if (!in.has_area_light[g]) continue;
-      in.area_lights[g].global_id = (uint32_t)s->lights.size();
-      HostLight L;
-      L.choose_prob = in.area_lights[g].intensity_sum;
-      L.instance_id = i, L.geom_id = g;
-      intensity_sum += (double)L.choose_prob;
-      s->lights.push_back(L);
-    }
-  }
-  for (HostLight& L : s->lights) L.choose_prob = (float)((double)L.choose_prob / intensity_sum);
-  s->light_cdf.resize(s->lights.size());
-  for (size_t l = 0; l < s->lights.size(); l++) s->light_cdf[l] = s->lights[l].choose_prob;
-  for (size_t l = 0; !s->light_cdf.empty() && l < s->light_cdf.size() - 1u; l++) s->light_cdf[l + 1u] += s->light_cdf[l];
-}
-
-static Material make_material(const HostMaterial& hm) {
-  Material m;
-  memset(&m, 0, sizeof(m));
-  m.kind = hm.kind;
-  m.bsdf = default_bsdf();
-  if (hm.kind == kMatPrincipled) {
-    m.bsdf = param_to_bsdf(hm.pr);
-    m.param = hm.pr;
-    medium_coefficients(m.bsdf, m.sss_sigt, m.sss_sigs, m.sss_wthr);  // (only read when the subsurface closure is picked)
-    m.textured = (hm.pr.base_color_tex_id != kNone || hm.pr.subsurface_color_tex_id != kNone) ? 1u : 0u;
-  } else {
-    m.hair = hair_param_to_bsdf(hm.hr);
-  }
-  return m;
-}
-
-// End points of linear piece `sub` of a cubic Bezier (control points xyzr): B(sub/4) and B((sub+1)/4), evaluated with
-// the arithmetic of the intersection contract (Bernstein weights, products summed left to right, single precision,
-// no contraction) so that every back end tests the same segment.
-static void curve_piece(const float* cp, uint32_t sub, float a[4], float b[4]) {
-  for (uint32_t e = 0; e < 2; e++) {
-    const float u = (float)(sub + e) * 0.25f, s = 1.0f - u;
-    const float b0 = s * s * s, b1 = 3.0f * u * s * s, b2 = 3.0f * u * u * s, b3 = u * u * u;
-    for (int k = 0; k < 4; k++) (e ? b : a)[k] = ((cp[k] * b0 + cp[4 + k] * b1) + cp[8 + k] * b2) + cp[12 + k] * b3;
-  }
-}
-
-// Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.
-static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
-  for (uint32_t i = 0; i < s->instances.size(); i++)
-    for (uint32_t g = 0; g < s->instances[i].material_ids.size(); g++) {
-      const HostMesh& m = *inst_mesh(s, i, g);
-      if (s->instances[i].material_ids[g].size() != m.num_prims())
-        return fail(PBRHIP_ESIZE, "material param error (instance %u geom %u)", i, g);
-      for (uint32_t p = 0; p < m.num_prims(); p++)
-        for (uint32_t sub = 0; sub < (m.kind == 1 ? 4u : 1u); sub++) prims->push_back({i, g, p, (uint32_t)m.kind, sub});
-    }
-  return PBRHIP_OK;
-}
-
-// Scene bounds (rtcGetSceneBounds, raytracer_impl.cc:199-202; they place the camera): the union of the instances'
-// bounds.  An RTC_GEOMETRY_TYPE_INSTANCE (raytracer_impl.cc:61-81) reports the box of the transformed CORNERS of its local
-// scene's box -- larger than the box of the transformed geometry under rotation or shear; an instance whose matrix is
-// bit for bit the identity reports the local box.  Local box: triangles by their corners, curves by the hull of their
-// control points widened by the largest control radius.  (The tree is built over the transformed primitives.)
-static void scene_bounds(pbrhip_scene* s) {
-  const float inf = std::numeric_limits<float>::infinity();
-  float bmin[3] = {inf, inf, inf}, bmax[3] = {-inf, -inf, -inf};
-  for (uint32_t i = 0; i < s->instances.size(); i++) {
-    const HostInstance& inst = s->instances[i];
-    float ll[3] = {inf, inf, inf}, lh[3] = {-inf, -inf, -inf};
-    bool any = false;
-    for (uint32_t g = 0; g < inst.material_ids.size(); g++) {
-      const HostMesh& m = *inst_mesh(s, i, g);
-      for (uint32_t p = 0; p < m.num_prims(); p++) {
-        any = true;
-        if (m.kind == 0) {
-          for (int c = 0; c < 3; c++) {
-            const V3 v = mesh_vertex(m, p, c);
-            const float a[3] = {v.x, v.y, v.z};
-            for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], a[k]), lh[k] = fmaxf(lh[k], a[k]);
-          }
-        } else {
-          float r = 0.f, cl[3] = {inf, inf, inf}, ch[3] = {-inf, -inf, -inf};
-          for (int c = 0; c < 4; c++) {
-            const float* cp = m.cverts.data() + ((size_t)m.cidx[p] + c) * 4;
-            r = fmaxf(r, fabsf(cp[3]));
-            for (int k = 0; k < 3; k++) cl[k] = fminf(cl[k], cp[k]), ch[k] = fmaxf(ch[k], cp[k]);
-          }
-          for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], cl[k] - r), lh[k] = fmaxf(lh[k], ch[k] + r);
-        }
-      }
-    }
-    if (!any) continue;
-    if (inst.identity) {
-      for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], ll[k]), bmax[k] = fmaxf(bmax[k], lh[k]);
-    } else {
-      for (int c = 0; c < 8; c++) {
-        const V3 v = xf_point(inst.xf, V3((c & 1) ? lh[0] : ll[0], (c & 2) ? lh[1] : ll[1], (c & 4) ? lh[2] : ll[2]));
-        const float a[3] = {v.x, v.y, v.z};
-        for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], a[k]), bmax[k] = fmaxf(bmax[k], a[k]);
-      }
-    }
-  }
-  memcpy(s->bmin, bmin, sizeof(bmin));
-  memcpy(s->bmax, bmax, sizeof(bmax));
-}
-
-// The box (world space) and kind of every primitive: what the tree is built over.
-static void prim_boxes(const pbrhip_scene* s, const std::vector<PrimRef>& prims, std::vector<float>* lo, std::vector<float>* hi,
-                       std::vector<uint8_t>* kinds) {
-  const float inf = std::numeric_limits<float>::infinity();
-  const uint32_t np = (uint32_t)prims.size();
-  lo->assign(3 * (size_t)np, 0.f), hi->assign(3 * (size_t)np, 0.f), kinds->assign(np, 0);
-  for (uint32_t g = 0; g < np; g++) {
-    const PrimRef& pr = prims[g];
-    const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
-    const HostInstance& inst = s->instances[pr.instance_id];
-    float l[3] = {inf, inf, inf}, h[3] = {-inf, -inf, -inf};
-    (*kinds)[g] = (uint8_t)pr.kind;
-    if (pr.kind == 0) {
-      for (int c = 0; c < 3; c++) {
-        V3 v = world_vertex(inst, m, pr.prim_id, c);
-        float a[3] = {v.x, v.y, v.z};
-        for (int k = 0; k < 3; k++) l[k] = std::min(l[k], a[k]), h[k] = std::max(h[k], a[k]);
-      }
-    } else {
-      float cps[16];
-      world_curve(inst, m, pr.prim_id, cps);
-      // BVH box of this piece: its two end points widened by the larger end radius (the ribbon between them never
-      // leaves that box, and a hit is reported at the depth of the axis point)
-      float a[4], b[4];
-      curve_piece(cps, pr.sub, a, b);
-      const float r = std::max(fabsf(a[3]), fabsf(b[3]));
-      for (int k = 0; k < 3; k++) l[k] = std::min(a[k], b[k]) - r, h[k] = std::max(a[k], b[k]) + r;
-    }
-    for (int k = 0; k < 3; k++) (*lo)[3 * g + k] = l[k], (*hi)[3 * g + k] = h[k];
-  }
-}
-
-// Light records: one per (light, prim), concatenated; heads[l] is light l's stretch of them.
-static void light_records(const pbrhip_scene* s, std::vector<LightHead>* heads, std::vector<LightRec>* lrecs,
-                          std::vector<float>* lprim_cdf) {
-  heads->resize(s->lights.size());
-  for (size_t l = 0; l < s->lights.size(); l++) {
-    const HostLight& L = s->lights[l];
-    const HostAreaLight& a = s->instances[L.instance_id].area_lights[L.geom_id];
-    const HostMesh& m = *inst_mesh(s, L.instance_id, L.geom_id);
-    (*heads)[l].first = (uint32_t)lrecs->size();
-    (*heads)[l].count = m.nfaces;
-    for (uint32_t f = 0; f < m.nfaces; f++) {
-      LightRec r;
-      memset(&r, 0, sizeof(r));
-      V3 p0 = mesh_vertex(m, f, 0), p1 = mesh_vertex(m, f, 1), p2 = mesh_vertex(m, f, 2);
-      V3 n = vnormalize(cross(p1 - p0, p2 - p1));  // CalcGeometryNormal (triangle-mesh.cc:181-184)
-      r.p0[0] = p0.x, r.p0[1] = p0.y, r.p0[2] = p0.z;
-      r.p1[0] = p1.x, r.p1[1] = p1.y, r.p1[2] = p1.z;
-      r.p2[0] = p2.x, r.p2[1] = p2.y, r.p2[2] = p2.z;
-      r.normal[0] = n.x, r.normal[1] = n.y, r.normal[2] = n.z;
-      // light-manager.h:68-70,149-150: choose_light * choose_prim * prim_area_pdf, in that order
-      r.pdf = L.choose_prob * a.choose_prob[f] * a.area_pdf[f];
-      if (a.light_param_ids[f] != kNone) {
-        V3 e = s->light_params[a.light_param_ids[f]];
-        r.emission[0] = e.x, r.emission[1] = e.y, r.emission[2] = e.z;
-      }
-      lrecs->push_back(r);
-      lprim_cdf->push_back(a.cdf[f]);
-    }
-  }
-}
-
-// One slot: the four 16-byte words `sl` and the ShadeRec `sr` of primitive `pr` with canonical id g (what pbrhip_scene_commit stages
-// for every slot and pbrhip_scene_refit for the dirty ones).
-static int slot_and_shade(const pbrhip_scene* s, const PrimRef& pr, uint32_t g, const std::vector<LightHead>& heads, float4* sl, ShadeRec& sr) {
-  {
-    const HostInstance& in = s->instances[pr.instance_id];
-    const HostMesh& m = *inst_mesh(s, pr.instance_id, pr.geom_id);
-    uint32_t mat = in.material_ids[pr.geom_id][pr.prim_id];
-    if (mat != kNone && (mat >= s->materials.size() || mat >= 0x00FFFFFFu)) return fail(PBRHIP_EINVAL, "material id %u out of range", mat);
-    memset(&sr, 0, sizeof(sr));
-    uint32_t flags = 0, lightrec = kNone;
-    if (mat == kNone) flags |= kSlotMatNone;
-    else if (s->materials[mat].kind == kMatHair) flags |= kSlotMatHair;
-    for (int c = 0; c < 4; c++) sl[c] = make_float4(0, 0, 0, 0);
-    if (pr.kind == 0) {
-      for (int c = 0; c < 3; c++) {
-        // traversal: what Embree sees (the transformed triangle); shading: the mesh's own corners -- the geometric normal
-        // Embree reports for an instance is in the instance's local space and pbrlab uses it as it is
-        const V3 w = world_vertex(in, m, pr.prim_id, c);
-        sl[c] = make_float4(w.x, w.y, w.z, 0.f);
-      }
-      {
-        // the two normals every hit on this triangle would otherwise compute from its corners (ShadeRec, dscene.h): the kernels'
-        // own functions, evaluated here
-        const V3 v0 = mesh_vertex(m, pr.prim_id, 0), v1 = mesh_vertex(m, pr.prim_id, 1), v2 = mesh_vertex(m, pr.prim_id, 2);
-        const V3 ng = normalize_raw(cross(v1 - v0, v2 - v0));
-        const V3 nf = vnormalize(cross(v1 - v0, v2 - v1));  // CalcGeometryNormal, triangle-mesh.cc:181-184
-        sr.ng[0] = ng.x, sr.ng[1] = ng.y, sr.ng[2] = ng.z;
-        sr.ns_flat[0] = nf.x, sr.ns_flat[1] = nf.y, sr.ns_flat[2] = nf.z;
-      }
-      uint32_t a = m.nid[pr.prim_id * 3 + 0], b = m.nid[pr.prim_id * 3 + 1], c = m.nid[pr.prim_id * 3 + 2];
-      if (a != kNone && b != kNone && c != kNone) {  // triangle-mesh.cc:81-84
-        flags |= kSlotHasNormals;
-        const uint32_t idx[3] = {a, b, c};
-        for (int q = 0; q < 3; q++) {
-          const float* n = m.normals.data() + (size_t)idx[q] * 4;
-          sr.n[3 * q + 0] = n[0], sr.n[3 * q + 1] = n[1], sr.n[3 * q + 2] = n[2];
-        }
-      }
-      if (in.has_area_light[pr.geom_id]) {
-        const HostAreaLight& al = in.area_lights[pr.geom_id];
-        if (al.light_param_ids[pr.prim_id] != kNone) lightrec = heads[al.global_id].first + pr.prim_id;
-      }
-      uint32_t ta = m.tid[pr.prim_id * 3 + 0], tb = m.tid[pr.prim_id * 3 + 1], tc = m.tid[pr.prim_id * 3 + 2];
-      if (ta != kNone && tb != kNone && tc != kNone) {  // triangle-mesh.cc:130-133
-        flags |= kSlotHasUV;
-        const uint32_t idx[3] = {ta, tb, tc};
-        for (int q = 0; q < 3; q++) {
-          sr.uv[2 * q + 0] = m.texcoords[(size_t)idx[q] * 2 + 0];
-          sr.uv[2 * q + 1] = m.texcoords[(size_t)idx[q] * 2 + 1];
-        }
-      }
-    } else {
-      flags |= kSlotIsCurve;
-      const float* cps = m.cverts.data() + (size_t)m.cidx[pr.prim_id] * 4;  // local: the tangent (= Ng) shading uses
-      float wcps[16];
-      world_curve(in, m, pr.prim_id, wcps);
-      float a[4], b[4];
-      curve_piece(wcps, pr.sub, a, b);
-      sl[0] = make_float4(a[0], a[1], a[2], a[3]);
-      sl[1] = make_float4(b[0], b[1], b[2], b[3]);
-      sl[2] = make_float4(__builtin_bit_cast(float, pr.sub), 0.f, 0.f, 0.f);
-      // shading needs the cubic itself (tangent = dP/du at the hit): control points xyzr in words 8..23 of the record
-      float* w = reinterpret_cast<float*>(&sr);
-      for (int c = 0; c < 16; c++) w[8 + c] = cps[c];
-    }
-    sr.gid = g, sr.lightrec = lightrec;
-    sr.matflags = (mat == kNone ? 0x00FFFFFFu : mat) | (flags << 24);
-    const uint32_t route = ((flags & kSlotMatHair) ? kHitHair : 0u) | ((flags & kSlotMatNone) ? kHitNoMaterial : 0u) |
-                           (lightrec != kNone ? kHitLight : 0u) |
-                           ((flags & (kSlotHasNormals | kSlotHasUV | kSlotIsCurve)) ? kHitMore : 0u);
-    sl[2].w = __builtin_bit_cast(float, route);  // travels with the hit record (Hit::slot)
-    sr.instance_id = pr.instance_id, sr.geom_id = pr.geom_id, sr.prim_id = pr.prim_id;
-  }
-  return PBRHIP_OK;
-}
-// Leaf-ordered slots (traversal geometry, 64 B each) + one 128-byte ShadeRec per slot (everything shading needs).
-static int slots_and_shade(const pbrhip_scene* s, const std::vector<PrimRef>& prims, const std::vector<uint32_t>& slot_gid,
-                           const std::vector<LightHead>& heads, std::vector<float4>* slots, std::vector<ShadeRec>* shade) {
-  const uint32_t ns = (uint32_t)slot_gid.size();
-  slots->resize(4 * (size_t)ns);
-  shade->resize(ns);
-  for (uint32_t k = 0; k < ns; k++)
-    if (int rc = slot_and_shade(s, prims[slot_gid[k]], slot_gid[k], heads, &(*slots)[4 * (size_t)k], (*shade)[k])) return rc;
-  return PBRHIP_OK;
-}
-
-// One box per light over all primitives of its mesh, packed two per node (an odd last one is stored twice).
-static std::vector<BvhNode> light_boxes(const std::vector<LightHead>& heads, const std::vector<LightRec>& lrecs) {
-  std::vector<BvhNode> boxes((heads.size() + 1) / 2);
-  for (size_t l = 0; l < heads.size(); l++) {
-    float lo3[3] = {INFINITY, INFINITY, INFINITY}, hi3[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t f = heads[l].first; f < heads[l].first + heads[l].count; f++)
-      for (const float* p : {lrecs[f].p0, lrecs[f].p1, lrecs[f].p2})
-        for (int a = 0; a < 3; a++) lo3[a] = std::min(lo3[a], p[a]), hi3[a] = std::max(hi3[a], p[a]);
-    BvhNode& nd = boxes[l / 2];
-    if (l % 2 == 0) memset(&nd, 0, sizeof(nd)), nd.set_box(1, lo3, hi3);
-    nd.set_box(int(l % 2), lo3, hi3);
-  }
-  return boxes;
-}
-
-extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
-  return guarded([&]() -> int {
-  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
-  const Knobs k = read_knobs();
-  HIPCHK(hipSetDevice(s->device));
-  for (uint32_t i = 0; i < s->instances.size(); i++) register_lights(s, i);
-  commit_lights(s);
-
-  std::vector<PrimRef> prims;
-  if (int rc = flatten_prims(s, &prims)) return rc;
-  uint32_t np = (uint32_t)prims.size();
-  if (np >= (1u << 27)) return fail(PBRHIP_EUNSUPPORTED, "too many primitives (%u)", np);
-  std::vector<float> lo, hi;
-  std::vector<uint8_t> kinds;
-  prim_boxes(s, prims, &lo, &hi, &kinds);
-  scene_bounds(s);
-
-  FlatBvh bvh;
-  bool gpu_built = false;
-  uint32_t num_nodes = 0;
-  const int builder = k.bvh >= 0 ? k.bvh : s->bvh_builder;
-  if ((builder == PBRHIP_BVH_GPU_LBVH || builder == PBRHIP_BVH_GPU_LBVH_WIDE) && np > 0) {
-    HIPCHK(s->d_nodes.reserve(std::max<size_t>(np > 1 ? np - 1 : 1, 1) + np));  // nodes, then one 64-byte slot per primitive
-    HIPCHK(build_bvh_gpu(s->stream, lo, hi, kinds, s->d_nodes.p, &bvh.slot_gid, &bvh.depth));
-    if (bvh.depth > (uint32_t)kStackDepth) {
-      // a Morton-order tree over badly distributed primitives can be deeper than the traversal stack: use the SAH tree
-      fprintf(stderr, "pbrhip: GPU-built BVH is %u deep (stack %d): building on the host instead\n", bvh.depth, kStackDepth);
-      bvh = FlatBvh();
-    } else {
-      gpu_built = true;
-      num_nodes = np > 1 ? np - 1 : 1;
-    }
-  }
-  if (!gpu_built) {
-    build_bvh(lo, hi, kinds, &bvh);
-    num_nodes = (uint32_t)bvh.nodes.size();
-  }
-  s->bvh_built_on_gpu = gpu_built;
-  if (bvh.depth > (uint32_t)kStackDepth)
-    return fail(PBRHIP_EOVERFLOW, "BVH depth %u exceeds the traversal stack (%d)", bvh.depth, kStackDepth);
-  s->bvh_depth = bvh.depth;
-
-  std::vector<LightHead> heads;
-  std::vector<LightRec> lrecs;
-  std::vector<float> lprim_cdf;
-  light_records(s, &heads, &lrecs, &lprim_cdf);
-  const uint32_t ns = (uint32_t)bvh.slot_gid.size();
-  if (ns > kHitSlotMask) return fail(PBRHIP_EINVAL, "%u traversal primitives: at most %u are supported", ns, kHitSlotMask);
-  std::vector<float4> slots;
-  std::vector<ShadeRec> shade;
-  if (int rc = slots_and_shade(s, prims, bvh.slot_gid, heads, &slots, &shade)) return rc;
-  std::vector<Material> mats(s->materials.size());
-  s->has_hair = s->has_sss = s->has_textured = false;
-  for (size_t i = 0; i < mats.size(); i++) {
-    const HostMaterial& hm = s->materials[i];
-    if (hm.kind == kMatPrincipled)
-      for (uint32_t t : {hm.pr.base_color_tex_id, hm.pr.subsurface_color_tex_id})
-        if (t != kNone && t >= s->tex_descs.size()) return fail(PBRHIP_EINVAL, "material %zu: texture id %u out of range", i, t);
-    mats[i] = make_material(s->materials[i]);
-    if (mats[i].textured) s->has_sss = s->has_textured = true;  // a subsurface_color / base_color map can switch the SSS closure on per hit
-    s->has_hair = s->has_hair || mats[i].kind == kMatHair;
-    s->has_sss = s->has_sss || (mats[i].kind == kMatPrincipled && mats[i].bsdf.enable_subsurface);
-  }
-
-  hipStream_t st = s->stream;
-  // nodes and primitive slots share one allocation (both are 64-byte items: the traversal addresses either as
-  // base + index * 64, with slot k at index num_nodes + k)
-  static_assert(sizeof(BvhNode) == 64 && sizeof(float4) == 16, "node / slot footprint");
-  if (!gpu_built) {
-    HIPCHK(s->d_nodes.reserve((size_t)num_nodes + ns));
-    if (num_nodes) HIPCHK(hipMemcpyAsync(s->d_nodes.p, bvh.nodes.data(), (size_t)num_nodes * sizeof(BvhNode), hipMemcpyHostToDevice, st));
-  }
-  if (ns) HIPCHK(hipMemcpyAsync(s->d_nodes.p + num_nodes, slots.data(), (size_t)ns * 64, hipMemcpyHostToDevice, st));
-  // The Q tree of the traversal kernels (host-built trees; PBRHIP_WIDE=0 at commit: none): the binary tree collapsed to four
-  // children per node with quantised boxes (64 B per node), followed by its own compact triangle leaves and curve records
-  // (bvh_build.cpp::build_qlayout, dscene.h::QNode).
-  QLayout q;
-  size_t q_tri_words = 0, q_pts = 0;
-  if (!gpu_built && num_nodes && k.wide) {
-    build_qlayout(bvh, slots, kinds, &q);
-    q_tri_words = q.tri.size(), q_pts = q.pts.size();
-    if (k.debug) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
-  }
-  // PBRHIP_BVH_GPU_LBVH_WIDE: the GPU-built tree collapsed on the device (qtree_gpu.hip) straight into d_wide / d_qhit; the nodes come
-  // back (64 B each) for the stack need and the random walks' entries.  A tree that cannot be kept is dropped for the binary one.
-  bool wide_on_gpu = false;
-  if (gpu_built && builder == PBRHIP_BVH_GPU_LBVH_WIDE && k.wide) {
-    const bool tri_pairs = std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
-    QCollapse qc;
-    HIPCHK(hipStreamSynchronize(st));  // (the slots are on the device: what follows is the collapse's own time)
-    const auto t_start = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    auto alloc = [&](size_t words, size_t hits, float4** w, uint32_t** h) -> hipError_t {
-      hipError_t e = s->d_wide.reserve(words);
-      if (e == hipSuccess) e = s->d_qhit.reserve(hits);
-      *w = s->d_wide.p, *h = s->d_qhit.p;
-      return e;
-    };
-    HIPCHK(collapse_qtree_gpu(st, s->d_nodes.p, ns, reinterpret_cast<const float4*>(s->d_nodes.p + num_nodes), tri_pairs, alloc, &qc));
-    const double ms_collapse = ms_since(t_start);
-    const char* why = !qc.fits ? "a record index overflows its reference" : (!qc.quantised ? "a node cannot be quantised" : nullptr);
-    if (!why) {
-      q.nodes.resize(qc.nodes);
-      HIPCHK(hipMemcpyAsync(q.nodes.data(), s->d_wide.p, (size_t)qc.nodes * sizeof(QNode), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      q.stack_need = qtree_stack_need(q.nodes);
-      if (q.stack_need > (uint32_t)kStackDepth) why = "its traversal needs more than the stack";
-    }
-    if (k.debug)
-      fprintf(stderr, "pbrhip: commit: Q tree on the device: %u nodes in %u levels, collapse %.2f ms (of which allocation %.2f ms), download + stack need %.2f ms\n",
-              qc.nodes, qc.levels, ms_collapse, qc.alloc_ms, ms_since(t_start) - ms_collapse);
-    if (why) {
-      fprintf(stderr, "pbrhip: the Q tree of the GPU-built BVH is dropped (%s): rendering the binary tree\n", why);
-      q = QLayout();
-    } else {
-      wide_on_gpu = true;
-      q_tri_words = qc.tri_words, q_pts = qc.pts;
-    }
-  }
-  const std::vector<QNode>& wide = q.nodes;
-  {  // the bounds of every instance's primitive boxes: what the random walks' entries are cut around (kept for pbrhip_scene_refit)
-    const size_t ninst = s->instances.size();
-    std::vector<float>&ilo = s->inst_lo, &ihi = s->inst_hi;
-    ilo.assign(3 * ninst, INFINITY), ihi.assign(3 * ninst, -INFINITY);
-    for (uint32_t g = 0; g < np; g++)
-      for (size_t a = 0, i = prims[g].instance_id; a < 3; a++)
-        ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[3 * (size_t)g + a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[3 * (size_t)g + a]);
-  }
-  // Where the random walks' rays start (dscene.h::SssEntry): per instance, the cut of the Q tree around its bounds
-  std::vector<SssEntry> sss_entries;
-  if (!wide.empty() && k.sss_entry) {  // (whatever the materials are now: pbrhip_scene_update_* can switch subsurface on later)
-    const std::vector<float>&ilo = s->inst_lo, &ihi = s->inst_hi;
-    // (every foreign reference costs each walk ray a slab test: a deeper entry is only worth so many)
-    const uint32_t max_foreign = std::min(k.sss_foreign, kSssMaxForeign);
-    const auto t_entries = std::chrono::steady_clock::now();
-    sss_entries = build_sss_entries(wide, ilo, ihi, max_foreign);
-    if (k.debug) fprintf(stderr, "pbrhip: commit: random walks' entries over %zu wide nodes: %.2f ms\n", wide.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entries).count());
-    for (size_t i = 0; i < sss_entries.size() && k.debug; i++)
-      if (sss_entries[i].entry) fprintf(stderr, "pbrhip: commit: instance %zu: random walks start at Q node %u with %u foreign references\n", i, sss_entries[i].entry, sss_entries[i].nforeign);
-  }
-  if (sss_entries.empty()) s->d_sss_entries.release();
-  else HIPCHK(s->d_sss_entries.upload(sss_entries, st));
-  if (wide.empty()) s->d_wide.release(), s->d_qhit.release();
-  if (k.debug) fprintf(stderr, "pbrhip: commit: %u binary nodes, %zu wide nodes, %zu slots, %zu triangle leaves + %zu points in the Q tree\n", num_nodes, wide.size(), (size_t)ns, q_tri_words / kTriPairWords, q_pts);
-  if (!wide.empty() && !wide_on_gpu) {
-    HIPCHK(s->d_wide.reserve(wide.size() * 4 + q.tri.size() + q.pts.size()));
-    HIPCHK(hipMemcpyAsync(s->d_wide.p, wide.data(), wide.size() * sizeof(QNode), hipMemcpyHostToDevice, st));
-    if (!q.tri.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4, q.tri.data(), q.tri.size() * 16, hipMemcpyHostToDevice, st));
-    if (!q.pts.empty()) HIPCHK(hipMemcpyAsync(s->d_wide.p + wide.size() * 4 + q.tri.size(), q.pts.data(), q.pts.size() * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(s->d_qhit.upload(q.hit, st));
-  }
-  HIPCHK(s->d_shade.upload(shade, st));
-  HIPCHK(s->d_materials.upload(mats, st));
-  HIPCHK(s->d_light_cdf.upload(s->light_cdf, st));
-  HIPCHK(s->d_heads.upload(heads, st));
-  HIPCHK(s->d_lprim_cdf.upload(lprim_cdf, st));
-  HIPCHK(s->d_lrecs.upload(lrecs, st));
-  HIPCHK(s->d_light_boxes.upload(light_boxes(heads, lrecs), st));
-  HIPCHK(s->d_tex_pixels.upload(s->tex_pixels, st));
-  HIPCHK(s->d_tex_descs.upload(s->tex_descs, st));
-  HIPCHK(hipStreamSynchronize(st));
-  DScene& d = s->dscene;
-  d.nodes = s->d_nodes.p, d.slots = reinterpret_cast<const float4*>(s->d_nodes.p + num_nodes), d.shade = s->d_shade.p;
-  d.materials = s->d_materials.p, d.light_cdf = s->d_light_cdf.p;
-  d.light_heads = s->d_heads.p, d.lprim_cdf = s->d_lprim_cdf.p, d.lrecs = s->d_lrecs.p, d.light_boxes = s->d_light_boxes.p;
-  d.num_nodes = num_nodes, d.num_slots = ns, d.num_lights = (uint32_t)s->lights.size(), d.num_lrecs = (uint32_t)lrecs.size();
-  d.num_materials = (uint32_t)mats.size();
-  d.tex_pixels = s->d_tex_pixels.p, d.textures = s->d_tex_descs.p, d.num_textures = (uint32_t)s->tex_descs.size();
-  d.num_curves = 0;
-  for (uint8_t kd : kinds) d.num_curves += kd ? 1u : 0u;
-  d.wide = wide.empty() ? nullptr : s->d_wide.p, d.wide_nodes = (uint32_t)wide.size();
-  d.q_tri0 = (uint32_t)wide.size() * 4u, d.q_pt0 = d.q_tri0 + (uint32_t)q_tri_words, d.q_hitcode = wide.empty() ? nullptr : s->d_qhit.p;
-  d.top_nodes = gpu_built ? 0u : std::min<uint32_t>(num_nodes, (uint32_t)kTopNodes);
-  d.wide_top_nodes = std::min<uint32_t>((uint32_t)wide.size(), (uint32_t)kTopNodes);
-  // light sampling works on the meshes' local positions (light-manager.h:128-136 "TODO transform"), the raytracer on the
-  // transformed ones: the doomed-path pretest against the light primitives (kernels.hip::misses_all_lights) is only the
-  // traversal's own test when the two coincide
-  d.sss_entries = sss_entries.empty() ? nullptr : s->d_sss_entries.p, d.num_sss_entries = (uint32_t)sss_entries.size();
-  d.lights_transformed = 0;
-  for (const HostLight& L : s->lights) d.lights_transformed |= s->instances[L.instance_id].identity ? 0u : 1u;
-  s->wide_stack_need = wide.empty() ? 0u : q.stack_need, s->wide_built_on_gpu = wide_on_gpu;
-  // what pbrhip_scene_refit needs of this commit; the device scene is the model's again
-  s->slot_gid = std::move(bvh.slot_gid), s->light_heads = std::move(heads), s->q_points = wide.empty() ? 0 : q_pts;
-  s->rf_plan.release();
-  s->dirty_inst.assign(s->instances.size(), 0), s->stale = false;
-  s->committed = true;
   return PBRHIP_OK;
   });
 }
@@ -914,24 +378,6 @@ extern "C" int pbrhip_scene_info(const pbrhip_scene* s, uint64_t* num_nodes, uin
   });
 }
 
-static int update_material(pbrhip_scene* s, uint32_t id, const HostMaterial& hm) {
-  // validate everything first: a rejected call leaves the host material, has_sss and the device copy as they were
-  if (id >= s->materials.size()) return fail(PBRHIP_EINVAL, "material id %u out of range", id);
-  if (s->materials[id].kind != hm.kind) return fail(PBRHIP_EINVAL, "material %u is of the other kind", id);
-  if (s->committed && hm.kind == kMatPrincipled)
-    for (uint32_t t : {hm.pr.base_color_tex_id, hm.pr.subsurface_color_tex_id})
-      if (t != kNone && t >= s->tex_descs.size()) return fail(PBRHIP_EINVAL, "texture id %u out of range", t);
-  if (s->committed) {
-    HIPCHK(hipSetDevice(s->device));
-    const Material m = make_material(hm);
-    HIPCHK(hipMemcpyAsync(s->d_materials.p + id, &m, sizeof(m), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->has_sss = s->has_sss || (m.kind == kMatPrincipled && (m.bsdf.enable_subsurface || m.textured));
-    s->has_textured = s->has_textured || (m.kind == kMatPrincipled && m.textured);
-  }
-  s->materials[id] = hm;
-  return PBRHIP_OK;
-}
 extern "C" int pbrhip_scene_update_principled_material(pbrhip_scene* s, uint32_t id, const pbrhip_principled_param* p) {
   return guarded([&]() -> int {
   if (!s || !p) return fail(PBRHIP_EINVAL, "update_material: NULL argument");
@@ -1018,128 +464,6 @@ extern "C" int pbrhip_scene_update_instance_transform(pbrhip_scene* s, uint32_t 
   memcpy(in.xf, m, sizeof(in.xf));
   in.identity = identity;
   mark_dirty(s, kNone, instance_id);
-  return PBRHIP_OK;
-  });
-}
-
-// the tight box of a staged slot: what prim_boxes computes for its primitive, from the very numbers the slot holds
-static void slot_tight_box(const float4* sl, bool curve, float lo[3], float hi[3]) {
-  const float a[3] = {sl[0].x, sl[0].y, sl[0].z}, b[3] = {sl[1].x, sl[1].y, sl[1].z}, c[3] = {sl[2].x, sl[2].y, sl[2].z};
-  const float r = std::max(fabsf(sl[0].w), fabsf(sl[1].w));
-  for (int k = 0; k < 3; k++) {
-    if (curve) lo[k] = std::min(a[k], b[k]) - r, hi[k] = std::max(a[k], b[k]) + r;
-    else lo[k] = std::min(std::min(a[k], b[k]), c[k]), hi[k] = std::max(std::max(a[k], b[k]), c[k]);
-  }
-}
-
-extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
-  return guarded([&]() -> int {
-  if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
-  if (s->replica) return fail(PBRHIP_ESTATE, "scene_refit: a replica holds no geometry (refit the source scene and replicate it again)");
-  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-  if (!s->stale) return PBRHIP_OK;
-  const Knobs k = read_knobs();
-  HIPCHK(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  DScene& d = s->dscene;
-  const auto now = [] { return std::chrono::steady_clock::now(); };
-  const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  const auto t_host = now();
-  const size_t ninst = s->instances.size();
-  s->dirty_inst.resize(ninst, 0);
-  // light tables: positions, areas and with them every probability (what commit runs, on the whole scene: the tables are small)
-  bool lights_dirty = false;
-  for (size_t i = 0; i < ninst; i++)
-    if (s->dirty_inst[i])
-      for (int has : s->instances[i].has_area_light) lights_dirty = lights_dirty || has != 0;
-  std::vector<LightRec> lrecs;
-  std::vector<float> lprim_cdf;
-  if (lights_dirty) {
-    for (uint32_t i = 0; i < ninst; i++) register_lights(s, i);
-    commit_lights(s);
-    light_records(s, &s->light_heads, &lrecs, &lprim_cdf);
-  }
-  // the dirty slots and their ShadeRecs, packed for one upload: index | 64 B | 128 B; the dirty instances' bounds from their new boxes
-  std::vector<PrimRef> prims;
-  if (int rc = flatten_prims(s, &prims)) return rc;
-  const uint32_t ns = d.num_slots;
-  if (s->slot_gid.size() != ns || prims.size() != ns) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
-  std::vector<uint32_t> dirty;
-  for (uint32_t slot = 0; slot < ns; slot++)
-    if (s->dirty_inst[prims[s->slot_gid[slot]].instance_id]) dirty.push_back(slot);
-  const uint32_t m = (uint32_t)dirty.size();
-  const size_t idx_words = ((size_t)m + 3) / 4;
-  std::vector<float4> packed(idx_words + 12 * (size_t)m, make_float4(0, 0, 0, 0));
-  std::vector<float> ilo = s->inst_lo, ihi = s->inst_hi;
-  for (size_t i = 0; i < ninst; i++)
-    if (s->dirty_inst[i])
-      for (int a = 0; a < 3; a++) ilo[3 * i + a] = INFINITY, ihi[3 * i + a] = -INFINITY;
-  for (uint32_t e = 0; e < m; e++) {
-    const uint32_t g = s->slot_gid[dirty[e]];
-    float4* sl = &packed[idx_words + 4 * (size_t)e];
-    ShadeRec sr;
-    if (int rc = slot_and_shade(s, prims[g], g, s->light_heads, sl, sr)) return rc;
-    reinterpret_cast<uint32_t*>(packed.data())[e] = dirty[e];
-    memcpy(&packed[idx_words + 4 * (size_t)m + 8 * (size_t)e], &sr, sizeof(sr));
-    float lo[3], hi[3];
-    slot_tight_box(sl, prims[g].kind != 0, lo, hi);
-    for (size_t a = 0, i = prims[g].instance_id; a < 3; a++) ilo[3 * i + a] = std::min(ilo[3 * i + a], lo[a]), ihi[3 * i + a] = std::max(ihi[3 * i + a], hi[a]);
-  }
-  float keep_min[3], keep_max[3];  // (a failed refit leaves the scene as stale as it was)
-  memcpy(keep_min, s->bmin, 12), memcpy(keep_max, s->bmax, 12);
-  scene_bounds(s);
-  const double ms_host = ms_since(t_host);
-
-  const auto t_up = now();
-  HIPCHK(s->rf_packed.upload(packed, st));
-  HIPCHK(scatter_slots_gpu(st, s->rf_packed.p, m, ns, reinterpret_cast<float4*>(s->d_nodes.p + d.num_nodes), reinterpret_cast<float4*>(s->d_shade.p)));
-  if (lights_dirty) {
-    HIPCHK(s->d_light_cdf.upload(s->light_cdf, st));
-    HIPCHK(s->d_heads.upload(s->light_heads, st));
-    HIPCHK(s->d_lprim_cdf.upload(lprim_cdf, st));
-    HIPCHK(s->d_lrecs.upload(lrecs, st));
-    HIPCHK(s->d_light_boxes.upload(light_boxes(s->light_heads, lrecs), st));
-  }
-  if (k.debug) HIPCHK(hipStreamSynchronize(st));
-  const double ms_upload = ms_since(t_up);
-
-  RefitTree t;
-  t.nodes = s->d_nodes.p, t.nb = d.num_nodes, t.ns = ns;
-  if (d.wide) {
-    t.q = reinterpret_cast<QNode*>(s->d_wide.p), t.nq = d.wide_nodes;
-    t.tri = s->d_wide.p + d.q_tri0, t.tri_words = d.q_pt0 - d.q_tri0, t.tri_pairs = d.num_curves == 0;
-    t.pts = s->d_wide.p + d.q_pt0, t.hit = s->d_qhit.p, t.npts = s->q_points;
-  }
-  RefitTimes rt;
-  HIPCHK(refit_tree_gpu(st, t, k.debug, &s->rf_plan, &rt));
-  if (rt.failed) {
-    memcpy(s->bmin, keep_min, 12), memcpy(s->bmax, keep_max, 12);
-    return fail(PBRHIP_EHIP, "scene_refit: %s; the scene stays stale (pbrhip_scene_commit rebuilds it)",
-                (rt.failed & 1u) ? "a node of the Q tree cannot be quantised" : "the committed tree holds an index out of range");
-  }
-  // the random walks' entries: a cut is only sound for the bounds it was made for
-  const auto t_entries = now();
-  if (d.wide && d.sss_entries) {
-    std::vector<QNode> wide(d.wide_nodes);
-    HIPCHK(hipMemcpyAsync(wide.data(), s->d_wide.p, wide.size() * sizeof(QNode), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const std::vector<SssEntry> entries = build_sss_entries(wide, ilo, ihi, std::min(k.sss_foreign, kSssMaxForeign));
-    HIPCHK(s->d_sss_entries.upload(entries, st));
-    HIPCHK(hipStreamSynchronize(st));
-    d.sss_entries = s->d_sss_entries.p, d.num_sss_entries = (uint32_t)entries.size();
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  if (k.debug)
-    fprintf(stderr, "pbrhip: refit: %u of %u slots dirty: host staging %.2f ms, upload + scatter %.2f ms, plan %.2f ms, pack + trees %.2f ms (%u + %u levels), Q-node download + walk entries %.2f ms\n",
-            m, ns, ms_host, ms_upload, rt.plan_ms, rt.trees_ms, rt.bin_levels, rt.q_levels, ms_since(t_entries));
-  if (lights_dirty) {
-    d.light_cdf = s->d_light_cdf.p, d.light_heads = s->d_heads.p, d.lprim_cdf = s->d_lprim_cdf.p, d.lrecs = s->d_lrecs.p, d.light_boxes = s->d_light_boxes.p;
-    d.num_lights = (uint32_t)s->lights.size(), d.num_lrecs = (uint32_t)lrecs.size();
-  }
-  d.lights_transformed = 0;
-  for (const HostLight& L : s->lights) d.lights_transformed |= s->instances[L.instance_id].identity ? 0u : 1u;
-  s->inst_lo = std::move(ilo), s->inst_hi = std::move(ihi);
-  s->dirty_inst.assign(ninst, 0), s->stale = false;
   return PBRHIP_OK;
   });
 }
@@ -1233,7 +557,7 @@ extern "C" int pbrhip_scene_set_camera(pbrhip_scene* s, const float eye[3], cons
   });
 }
 // the frame of the scene's user camera for a width x height image, in double, rounded once (dscene.h::UserCamera)
-static UserCamera make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
+UserCamera pb::make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
   double f[3], r[3], u[3], up[3];
   for (int k = 0; k < 3; k++) f[k] = (double)s->cam_lookat[k] - s->cam_eye[k], up[k] = s->cam_up[k];
   const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
@@ -1270,7 +594,7 @@ extern "C" int pbrhip_create_tiles(uint32_t width, uint32_t height, uint32_t* ou
 }
 
 // camera of RenderingTile (render.cc:132-158)
-static Camera make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
+Camera pb::make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
   const float *bmin = s->bmin, *bmax = s->bmax;
   float hs, vs;
   if (bmax[0] - bmin[0] > bmax[1] - bmin[1]) {
@@ -1366,7 +690,6 @@ struct Timer {
   }
 };
 }  // namespace
-
 
 void pb::shard_pixels(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t block, std::vector<uint32_t>* out) {
   if (block == 0) block = 64;  // CreateTiles' tile (pbrhip_create_tiles enumerates the same blocks in the same order)
@@ -2195,257 +1518,4 @@ extern "C" int pbrhip_denoise(int device, uint32_t width, uint32_t height, const
     HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;
   });
-}
-
-// ------------------------------------------------------------------ test hooks
-extern "C" int pbrhip_texture_fetch(pbrhip_scene* s, uint32_t texture_id, const float* uv, size_t n, float* rgb) {
-  return guarded([&]() -> int {
-    if (!s || ((!uv || !rgb) && n)) return fail(PBRHIP_EINVAL, "texture_fetch: NULL argument");
-    if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-    if (texture_id >= s->tex_descs.size()) return fail(PBRHIP_EINVAL, "texture_fetch: texture id %u out of range", texture_id);
-    if (n > (1u << 24)) return fail(PBRHIP_EINVAL, "texture_fetch: too many coordinates");
-    if (!n) return PBRHIP_OK;
-    HIPCHK(hipSetDevice(s->device));
-    DevBuf<float> d_uv, d_rgb;
-    HIPCHK(d_uv.reserve(2 * n));
-    HIPCHK(d_rgb.reserve(3 * n));
-    HIPCHK(hipMemcpyAsync(d_uv.p, uv, 2 * n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    launch_texture_fetch(s->stream, s->dscene, texture_id, d_uv.p, (uint32_t)n, d_rgb.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
-// the GPU builder on bare boxes, whatever depth it reaches (the fallback at kStackDepth is pbrhip_scene_commit's)
-extern "C" int pbrhip_lbvh_build(int device, const float* lo, const float* hi, const uint8_t* kinds, uint32_t n, void* nodes_out,
-                                 uint32_t* order_out, uint32_t* depth_out) {
-  return guarded([&]() -> int {
-    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "lbvh_build: too many boxes (%u)", n);
-    if (n == 0) return PBRHIP_OK;
-    if (!lo || !hi || !kinds || !nodes_out || !order_out || !depth_out) return fail(PBRHIP_EINVAL, "lbvh_build: NULL argument");
-    int ndev = 0;
-    if (int rc = pbrhip_device_count(&ndev)) return rc;
-    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "lbvh_build: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
-    struct Stream {
-      hipStream_t s = nullptr;
-      ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-      }
-    } st;
-    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    const size_t nn = n > 1 ? n - 1 : 1;
-    DevBuf<BvhNode> d_nodes;
-    HIPCHK(d_nodes.reserve(nn));
-    const std::vector<float> vlo(lo, lo + 3 * (size_t)n), vhi(hi, hi + 3 * (size_t)n);
-    const std::vector<uint8_t> vkinds(kinds, kinds + n);
-    std::vector<uint32_t> order;
-    uint32_t depth = 0;
-    HIPCHK(build_bvh_gpu(st.s, vlo, vhi, vkinds, d_nodes.p, &order, &depth));
-    HIPCHK(hipMemcpyAsync(nodes_out, d_nodes.p, nn * sizeof(BvhNode), hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipStreamSynchronize(st.s));
-    memcpy(order_out, order.data(), sizeof(uint32_t) * n);
-    *depth_out = depth;
-    return PBRHIP_OK;
-  });
-}
-
-// builder PBRHIP_BVH_GPU_LBVH_WIDE on bare boxes and slot records: the binary tree, then its collapse, whatever comes out (no fallback)
-extern "C" int pbrhip_qtree_collapse(int device, const float* lo, const float* hi, const uint8_t* kinds, const void* slots, uint32_t n,
-                                     void* nodes_out, uint32_t* order_out, void* qnodes_out, void* tri_out, void* pts_out,
-                                     uint32_t* hit_out, uint32_t* sizes_out) {
-  return guarded([&]() -> int {
-    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "qtree_collapse: too many boxes (%u)", n);
-    if (!sizes_out) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
-    if (n == 0) {
-      memset(sizes_out, 0, 6 * sizeof(uint32_t));
-      return PBRHIP_OK;
-    }
-    if (!lo || !hi || !kinds || !slots) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
-    if (qnodes_out && (!nodes_out || !order_out || !tri_out || !pts_out || !hit_out)) return fail(PBRHIP_EINVAL, "qtree_collapse: NULL argument");
-    int ndev = 0;
-    if (int rc = pbrhip_device_count(&ndev)) return rc;
-    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "qtree_collapse: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
-    struct Stream {
-      hipStream_t s = nullptr;
-      ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-      }
-    } st;
-    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    const size_t nn = n > 1 ? n - 1 : 1;
-    DevBuf<BvhNode> d_nodes;  // nodes, then the slots in leaf order: the layout of a committed scene
-    HIPCHK(d_nodes.reserve(nn + n));
-    const std::vector<float> vlo(lo, lo + 3 * (size_t)n), vhi(hi, hi + 3 * (size_t)n);
-    const std::vector<uint8_t> vkinds(kinds, kinds + n);
-    std::vector<uint32_t> order;
-    uint32_t depth = 0;
-    HIPCHK(build_bvh_gpu(st.s, vlo, vhi, vkinds, d_nodes.p, &order, &depth));
-    std::vector<BvhNode> sl(n);  // (a slot is 64 bytes, like a node)
-    for (uint32_t k = 0; k < n; k++) memcpy(&sl[k], static_cast<const char*>(slots) + 64 * (size_t)order[k], 64);
-    HIPCHK(hipMemcpyAsync(d_nodes.p + nn, sl.data(), 64 * (size_t)n, hipMemcpyHostToDevice, st.s));
-    DevBuf<float4> d_wide;
-    DevBuf<uint32_t> d_hit;
-    auto alloc = [&](size_t words, size_t hits, float4** w, uint32_t** h) -> hipError_t {
-      hipError_t e = d_wide.reserve(words);
-      if (e == hipSuccess) e = d_hit.reserve(hits);
-      *w = d_wide.p, *h = d_hit.p;
-      return e;
-    };
-    const bool tri_pairs = std::all_of(vkinds.begin(), vkinds.end(), [](uint8_t kd) { return kd == 0; });
-    QCollapse qc;
-    HIPCHK(collapse_qtree_gpu(st.s, d_nodes.p, n, reinterpret_cast<const float4*>(d_nodes.p + nn), tri_pairs, alloc, &qc));
-    sizes_out[0] = qc.nodes, sizes_out[1] = (uint32_t)qc.tri_words, sizes_out[2] = (uint32_t)qc.pts, sizes_out[3] = 0;
-    sizes_out[4] = (qc.fits ? 1u : 0u) | (qc.quantised ? 2u : 0u), sizes_out[5] = depth;
-    if (!qc.fits || !qnodes_out) return PBRHIP_OK;  // (a call without output arrays reports the sizes)
-    std::vector<QNode> qn(qc.nodes);
-    HIPCHK(hipMemcpyAsync(nodes_out, d_nodes.p, nn * sizeof(BvhNode), hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipMemcpyAsync(qn.data(), d_wide.p, (size_t)qc.nodes * 64, hipMemcpyDeviceToHost, st.s));
-    if (qc.tri_words) HIPCHK(hipMemcpyAsync(tri_out, d_wide.p + (size_t)qc.nodes * 4, qc.tri_words * 16, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipMemcpyAsync(pts_out, d_wide.p + (size_t)qc.nodes * 4 + qc.tri_words, qc.pts * 16, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipMemcpyAsync(hit_out, d_hit.p, qc.pts * 4, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipStreamSynchronize(st.s));
-    memcpy(qnodes_out, qn.data(), (size_t)qc.nodes * 64);
-    memcpy(order_out, order.data(), sizeof(uint32_t) * n);
-    sizes_out[3] = qtree_stack_need(qn);
-    return PBRHIP_OK;
-  });
-}
-
-// pbrhip_scene_refit's kernels on bare trees: plan, leaf records, both trees (no scene)
-extern "C" int pbrhip_tree_refit(int device, uint32_t n, const void* slots, void* nodes_inout, void* qnodes_inout, uint32_t num_qnodes,
-                                 void* tri_inout, uint32_t tri_words, int tri_pairs, void* pts_inout, const uint32_t* hit, uint32_t num_points) {
-  return guarded([&]() -> int {
-    if (n >= (1u << 27)) return fail(PBRHIP_EINVAL, "tree_refit: too many slots (%u)", n);
-    if (n == 0) return PBRHIP_OK;
-    if (!slots || !nodes_inout) return fail(PBRHIP_EINVAL, "tree_refit: NULL argument");
-    if (qnodes_inout && (num_qnodes == 0 || (tri_words && !tri_inout) || !pts_inout || !hit)) return fail(PBRHIP_EINVAL, "tree_refit: NULL argument");
-    if (qnodes_inout && (num_qnodes >= (1u << 27) || num_points >= (1u << 27) || tri_words >= 3u * (1u << 27))) return fail(PBRHIP_EINVAL, "tree_refit: a size is out of range");
-    int ndev = 0;
-    if (int rc = pbrhip_device_count(&ndev)) return rc;
-    if (ndev <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(PBRHIP_EINVAL, "tree_refit: device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
-    struct Stream {
-      hipStream_t s = nullptr;
-      ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-      }
-    } st;
-    HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    const size_t nn = n > 1 ? n - 1 : 1;
-    const size_t nq = qnodes_inout ? num_qnodes : 0;
-    DevBuf<BvhNode> d_nodes;  // nodes, then the slots in leaf order: the layout of a committed scene
-    DevBuf<float4> d_wide;
-    DevBuf<uint32_t> d_hit;
-    HIPCHK(d_nodes.reserve(nn + n));
-    HIPCHK(hipMemcpyAsync(d_nodes.p, nodes_inout, nn * 64, hipMemcpyHostToDevice, st.s));
-    HIPCHK(hipMemcpyAsync(d_nodes.p + nn, slots, (size_t)n * 64, hipMemcpyHostToDevice, st.s));
-    RefitTree t;
-    t.nodes = d_nodes.p, t.nb = (uint32_t)nn, t.ns = n;
-    if (nq) {
-      HIPCHK(d_wide.reserve(nq * 4 + tri_words + num_points));
-      HIPCHK(d_hit.reserve(num_points));
-      HIPCHK(hipMemcpyAsync(d_wide.p, qnodes_inout, nq * 64, hipMemcpyHostToDevice, st.s));
-      if (tri_words) HIPCHK(hipMemcpyAsync(d_wide.p + nq * 4, tri_inout, (size_t)tri_words * 16, hipMemcpyHostToDevice, st.s));
-      if (num_points) HIPCHK(hipMemcpyAsync(d_wide.p + nq * 4 + tri_words, pts_inout, (size_t)num_points * 16, hipMemcpyHostToDevice, st.s));
-      if (num_points) HIPCHK(hipMemcpyAsync(d_hit.p, hit, (size_t)num_points * 4, hipMemcpyHostToDevice, st.s));
-      t.q = reinterpret_cast<QNode*>(d_wide.p), t.nq = (uint32_t)nq;
-      t.tri = d_wide.p + nq * 4, t.tri_words = tri_words, t.tri_pairs = tri_pairs != 0;
-      t.pts = d_wide.p + nq * 4 + tri_words, t.hit = d_hit.p, t.npts = num_points;
-    }
-    RefitPlan plan;
-    RefitTimes rt;
-    HIPCHK(refit_tree_gpu(st.s, t, false, &plan, &rt));
-    if (rt.failed) return fail(PBRHIP_EHIP, "tree_refit: %s", (rt.failed & 1u) ? "a node of the Q tree cannot be quantised" : "the tree holds an index out of range");
-    HIPCHK(hipMemcpyAsync(nodes_inout, d_nodes.p, nn * 64, hipMemcpyDeviceToHost, st.s));
-    if (nq) {
-      HIPCHK(hipMemcpyAsync(qnodes_inout, d_wide.p, nq * 64, hipMemcpyDeviceToHost, st.s));
-      if (tri_words) HIPCHK(hipMemcpyAsync(tri_inout, d_wide.p + nq * 4, (size_t)tri_words * 16, hipMemcpyDeviceToHost, st.s));
-      if (num_points) HIPCHK(hipMemcpyAsync(pts_inout, d_wide.p + nq * 4 + tri_words, (size_t)num_points * 16, hipMemcpyDeviceToHost, st.s));
-    }
-    HIPCHK(hipStreamSynchronize(st.s));
-    return PBRHIP_OK;
-  });
-}
-
-extern "C" int pbrhip_leaf_eval(uint32_t op, const float* in, size_t n, uint32_t in_words, float* out, uint32_t out_words) {
-  return guarded([&]() -> int {
-    if ((!in || !out) && n) return fail(PBRHIP_EINVAL, "leaf_eval: NULL argument");
-    if (op > 10u || in_words == 0 || out_words == 0 || n > (1u << 24)) return fail(PBRHIP_EINVAL, "leaf_eval: bad operation or sizes");
-    static const uint32_t need_in[11] = {4, 3, 2, 2, 2, 2, 2, 9, 8, 29, 30}, need_out[11] = {1, 1, 1, 1, 5, 3, 2, 2, 5, 4, 7};
-    if (in_words < need_in[op] || out_words < need_out[op]) return fail(PBRHIP_EINVAL, "leaf_eval: operation %u needs %u words in, %u out", op, need_in[op], need_out[op]);
-    if (!n) return PBRHIP_OK;
-    DevBuf<float> d_in, d_out;
-    HIPCHK(d_in.reserve(n * in_words));
-    HIPCHK(d_out.reserve(n * out_words));
-    HIPCHK(hipMemcpy(d_in.p, in, n * in_words * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_out.p, 0, n * out_words * sizeof(float)));
-    launch_leaf_eval(nullptr, op, d_in.p, (uint32_t)n, in_words, d_out.p, out_words);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_out.p, n * out_words * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-extern "C" int pbrhip_camera_rays(pbrhip_scene* s, uint32_t width, uint32_t height, uint64_t seed_seq, const uint32_t* x_y_pass, size_t n,
-                                  pbrhip_ray* rays) {
-  return guarded([&]() -> int {
-  if (!s || (!x_y_pass && n) || (!rays && n)) return fail(PBRHIP_EINVAL, "camera_rays: NULL argument");
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "camera_rays: zero image size");
-  if (!s->cam_set && !s->committed) return fail(PBRHIP_ESTATE, "camera_rays: the reference camera needs a committed scene");
-  PB_NOT_STALE(s);
-  if (n == 0) return PBRHIP_OK;
-  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
-  for (size_t i = 0; i < n; i++)
-    if (x_y_pass[3 * i] >= width || x_y_pass[3 * i + 1] >= height) return fail(PBRHIP_EINVAL, "camera_rays: pixel %zu is outside the image", i);
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(s->hook_rays.reserve(2 * n));
-  HIPCHK(s->hook_xyp.reserve(3 * n));
-  HIPCHK(hipMemcpyAsync(s->hook_xyp.p, x_y_pass, 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  const UserCamera uc = s->cam_set ? make_user_camera(s, width, height) : UserCamera{};
-  const Camera dc = s->cam_set ? Camera{} : make_camera(s, width, height);
-  launch_camera_rays(s->stream, uc, dc, s->cam_set, width, height, seed_seq, s->hook_xyp.p, (uint32_t)n, s->hook_rays.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(rays, s->hook_rays.p, n * sizeof(pbrhip_ray), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return PBRHIP_OK;
-  });
-}
-// the body of pbrhip_trace_closest (any = false: `out` receives n pbrhip_hit) and pbrhip_trace_any (any: n occlusion bytes)
-static int trace_hook(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, void* out, bool any) {
-  const char* name = any ? "trace_any" : "trace_closest";
-  if (!s || (!rays && n) || (!out && n)) return fail(PBRHIP_EINVAL, "%s: NULL argument", name);
-  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-  PB_NOT_STALE(s);
-  if (n == 0) return PBRHIP_OK;
-  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "too many rays");
-  const Knobs k = read_knobs();
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(s->hook_rays.reserve(2 * n));
-  if (any) HIPCHK(s->hook_occ.reserve(n));
-  else HIPCHK(s->hook_hits.reserve(n));
-  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
-  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
-  HIPCHK(hipMemcpyAsync(s->hook_rays.p, rays, n * sizeof(pbrhip_ray), hipMemcpyHostToDevice, s->stream));
-  HIPCHK(s->spill.reserve(kSpillWords));
-  launch_hook(s->stream, s->dscene, s->hook_rays.p, (uint32_t)n, any ? nullptr : s->hook_hits.p, any ? s->hook_occ.p : nullptr, s->counts.p, s->spill.p, k);
-  HIPCHK(hipGetLastError());
-  if (any) HIPCHK(hipMemcpyAsync(out, s->hook_occ.p, n, hipMemcpyDeviceToHost, s->stream));
-  else HIPCHK(hipMemcpyAsync(out, s->hook_hits.p, n * sizeof(pbrhip_hit), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-  return PBRHIP_OK;
-}
-extern "C" int pbrhip_trace_closest(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, pbrhip_hit* hits) {
-  return guarded([&]() -> int { return trace_hook(s, rays, n, hits, false); });
-}
-extern "C" int pbrhip_trace_any(pbrhip_scene* s, const pbrhip_ray* rays, size_t n, uint8_t* occluded) {
-  return guarded([&]() -> int { return trace_hook(s, rays, n, occluded, true); });
 }

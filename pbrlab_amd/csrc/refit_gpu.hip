@@ -3,7 +3,7 @@
 // recomputed from the moved slots ("The refit, exactly"; tests/_refit_model.py restates it):
 //
 //   tight box    of a slot: a triangle's float min / max of its three corners; a curve piece's min(a, b) - r and max(a, b) + r with
-//                r = max(|a.w|, |b.w|) -- what pbrhip.cpp::prim_boxes computes from the very numbers the slot holds
+//                r = max(|a.w|, |b.w|) -- what commit.cpp::slot_tight_box computes from the very numbers the slot holds
 //   W(box)       BvhNode::widen_lo / widen_hi per bound
 //   binary tree  every child reference but kEmptyChild: W(union of the tight boxes of the slots below it), as both builders store it.  The
 //                union of a subtree is kept UNWIDENED in a working array (six floats per node) and widened where it is stored: the union

@@ -77,6 +77,63 @@ struct DevBuf {
   }
 };
 
+// The binary tree with its slots and the Q tree on the device, and the one place that says how they are laid out: d_nodes holds
+// num_nodes nodes, then num_slots slots (64-byte items both); d_wide holds wide_nodes Q nodes of four 16-byte words (0: no Q tree),
+// then tri_words words of triangle leaves, then `points` curve points (DScene::q_tri0, q_pt0); d_qhit one hit code per point.
+struct TreeBufs {
+  uint32_t num_nodes = 0, num_slots = 0, wide_nodes = 0;
+  size_t tri_words = 0, points = 0;
+  static_assert(sizeof(BvhNode) == 64 && sizeof(QNode) == 64 && sizeof(float4) == 16, "node / slot footprint");
+  DevBuf<BvhNode> d_nodes;
+  DevBuf<float4> d_wide;  // filled from the host (upload), or on the device by qtree_gpu.hip (alloc_wide, then set_wide)
+  DevBuf<uint32_t> d_qhit;
+
+  static uint32_t lbvh_nodes(uint32_t n) { return n > 1 ? n - 1 : 1; }  // the nodes build_bvh_gpu makes over n primitives
+  hipError_t reserve_nodes(uint32_t nodes, uint32_t slots) {
+    num_nodes = nodes, num_slots = slots;
+    return d_nodes.reserve((size_t)nodes + slots);
+  }
+  float4* slots() const { return reinterpret_cast<float4*>(d_nodes.p + num_nodes); }
+  size_t tri0() const { return (size_t)wide_nodes * 4; }
+  size_t pt0() const { return tri0() + tri_words; }
+  float4* tri() const { return d_wide.p + tri0(); }
+  float4* pts() const { return d_wide.p + pt0(); }
+  void set_wide(uint32_t nodes, size_t tri_words_, size_t points_) { wide_nodes = nodes, tri_words = tri_words_, points = points_; }
+  void counts_from(const TreeBufs& o) { num_nodes = o.num_nodes, num_slots = o.num_slots, set_wide(o.wide_nodes, o.tri_words, o.points); }  // (a replica)
+  hipError_t alloc_wide(size_t words, size_t hits, float4** w, uint32_t** h) {  // what collapse_qtree_gpu asks for once it knows the sizes
+    hipError_t e = d_wide.reserve(words);
+    if (e == hipSuccess) e = d_qhit.reserve(hits);
+    *w = d_wide.p, *h = d_qhit.p;
+    return e;
+  }
+  // The Q tree from host arrays (a QLayout's, or a hook's).  No nodes: no Q tree, the buffers are released; tri_words and points
+  // are recorded all the same, because commit's debug line and DScene::q_pt0 report what build_qlayout made before it gave up.
+  hipError_t upload(const void* qn, uint32_t nodes, const void* tri_, size_t tw, const void* pts_, const uint32_t* hit, size_t np, hipStream_t st) {
+    set_wide(nodes, tw, np);
+    if (!nodes) {
+      d_wide.release(), d_qhit.release();
+      return hipSuccess;
+    }
+    hipError_t e = d_wide.reserve(pt0() + np);
+    if (e == hipSuccess) e = d_qhit.reserve(np);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_wide.p, qn, (size_t)nodes * 64, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && tw) e = hipMemcpyAsync(tri(), tri_, tw * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && np) e = hipMemcpyAsync(pts(), pts_, np * 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && np) e = hipMemcpyAsync(d_qhit.p, hit, np * 4, hipMemcpyHostToDevice, st);
+    return e;
+  }
+  RefitTree refit_tree(bool tri_pairs) const {  // (nq 0: no Q tree, and nothing else of it is read)
+    RefitTree r;
+    r.nodes = d_nodes.p, r.nb = num_nodes, r.ns = num_slots, r.tri_pairs = tri_pairs;
+    r.q = reinterpret_cast<QNode*>(d_wide.p), r.nq = wide_nodes, r.hit = d_qhit.p, r.npts = points;
+    r.tri = tri(), r.tri_words = tri_words, r.pts = pts();
+    return r;
+  }
+};
+inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
+  return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
+}
+
 }  // namespace pb
 
 struct pbrhip_scene {
@@ -107,13 +164,13 @@ struct pbrhip_scene {
   std::vector<uint32_t> slot_gid;   // slot -> canonical primitive id, as the builder ordered the leaves
   std::vector<pb::LightHead> light_heads;  // light -> its stretch of light records (fixed by the topology)
   std::vector<float> inst_lo, inst_hi;     // per instance: the bounds of its primitives' boxes (what the random walks' entries are cut around)
-  size_t q_points = 0;              // points of the Q tree's curve records (DScene::q_hitcode's length)
+  // what bind_dscene needs beside the buffers (recorded by commit and refit, carried over by pbrhip_scene_replicate)
+  uint32_t num_curves = 0, num_lrecs = 0, num_walk_entries = 0;  // curve pieces among the slots; light records; entries in d_sss_entries (0: none)
+  bool lights_transformed = false;  // DScene::lights_transformed
   pb::RefitPlan rf_plan;            // built at the first refit of a committed tree, dropped by the next commit
   pb::DevBuf<float4> rf_packed;     // the dirty slots' upload: index | 64 B | 128 B (refit_gpu.hip::k_rf_scatter)
   // device scene
-  pb::DevBuf<pb::BvhNode> d_nodes;
-  pb::DevBuf<float4> d_wide;  // the Q tree: quantised 4-wide nodes + its triangle slots + curve points (DScene::wide), built on the host, or on the device by qtree_gpu.hip
-  pb::DevBuf<uint32_t> d_qhit;  // hit code per curve point of the Q tree (DScene::q_hitcode)
+  pb::TreeBufs tree;
   pb::DevBuf<pb::ShadeRec> d_shade;
   pb::DevBuf<pb::Material> d_materials;
   pb::DevBuf<float> d_light_cdf, d_lprim_cdf, d_tex_pixels;
@@ -164,9 +221,18 @@ struct pbrhip_scene {
   uint32_t xk_key[7] = {0, 0, 0, 0, 0, 0, 0};     // w, h, world, block, first rank, end rank, skipped rank
   pb::DevBuf<float4> feat_albedo;                 // pbrhip_render_features: per material, albedo rgb | base-colour texture id (feature_kernels.h)
 
+  // The buffers of the device scene, each named once.  `s.member...` expands over the scenes given: f(counted, buffer) for one scene,
+  // f(counted, buffer, its counterpart) for two.  `counted`: in pbrhip_scene_info's device bytes.  (Not the environment's tables.)
+  template <typename F, typename... S>
+  static void each_scene_buf(F&& f, S&... s) {
+    f(true, s.tree.d_nodes...), f(true, s.tree.d_wide...), f(true, s.tree.d_qhit...), f(true, s.d_shade...), f(true, s.d_materials...), f(true, s.d_lrecs...);
+    f(false, s.d_light_cdf...), f(false, s.d_lprim_cdf...), f(false, s.d_tex_pixels...), f(false, s.d_tex_descs...), f(false, s.d_heads...);
+    f(false, s.d_light_boxes...), f(false, s.d_sss_entries...);
+  }
   size_t device_bytes() const {
-    return d_nodes.n * sizeof(pb::BvhNode) + d_wide.n * sizeof(float4) + d_qhit.n * 4 + d_shade.n * sizeof(pb::ShadeRec) + d_materials.n * sizeof(pb::Material) +
-           d_lrecs.n * sizeof(pb::LightRec);
+    size_t bytes = 0;
+    each_scene_buf([&](bool counted, const auto& b) { bytes += counted ? b.n * sizeof(*b.p) : 0; }, *this);
+    return bytes;
   }
 };
 
@@ -181,4 +247,13 @@ int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const flo
 // the body of pbrhip_render_device (device pointers on the scene's device)
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
                 uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats);
+void bind_dscene(pbrhip_scene* s);  // points every DScene member that comes from a scene buffer at it, with its count (commit.cpp)
+inline const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id) {  // (per primitive in commit's loops: inline)
+  const HostInstance& in = s->instances[instance_id];
+  return &s->meshes[s->locals[in.local_scene][geom_id]];
+}
+int update_material(pbrhip_scene* s, uint32_t id, const HostMaterial& hm);  // pbrhip_scene_update_*_material's body (commit.cpp)
+// the scene's cameras for a width x height image (pbrhip.cpp; pbrhip_camera_rays launches them too)
+UserCamera make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
+Camera make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
 }  // namespace pb
