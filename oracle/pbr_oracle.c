@@ -136,6 +136,9 @@ struct orc_scene {
   uint32_t *env_keep, *env_alias;
   uint32_t env_w, env_h;
   float env_m[9]; /* world_to_env, row-major */
+  /* the look-at pinhole as the caller set it; cam_set == 0: the reference's camera */
+  int cam_set;
+  float cam_eye[3], cam_lookat[3], cam_up[3], cam_vfov;
 };
 
 static void* xrealloc(void* p, size_t n) {
@@ -840,6 +843,28 @@ int orc_commit(orc_scene* s) {
   s->committed = 1;
   return 0;
 }
+/* pbrhip.cpp::set_camera's checks, for a pinhole */
+int orc_scene_set_camera(orc_scene* s, const float eye[3], const float lookat[3], const float up[3], float vfov_degrees,
+                         float lens_radius) {
+  if (!eye) {
+    s->cam_set = 0;
+    return 0;
+  }
+  if (!lookat || !up) return -1;
+  for (int k = 0; k < 3; k++)
+    if (!isfinite(eye[k]) || !isfinite(lookat[k]) || !isfinite(up[k])) return -1;
+  if (!isfinite(vfov_degrees) || !(vfov_degrees > 0.0f && vfov_degrees < 180.0f)) return -1;
+  if (!(lens_radius == 0.0f)) return -1; /* the thin lens draws its point with the device's cosf / sinf */
+  const double fx = (double)lookat[0] - eye[0], fy = (double)lookat[1] - eye[1], fz = (double)lookat[2] - eye[2];
+  const double fl = sqrt(fx * fx + fy * fy + fz * fz), ul = sqrt((double)up[0] * up[0] + (double)up[1] * up[1] + (double)up[2] * up[2]);
+  if (!(fl > 0.0)) return -1;
+  const double cx = fy * up[2] - fz * up[1], cy = fz * up[0] - fx * up[2], cz = fx * up[1] - fy * up[0];
+  if (!(ul > 0.0) || sqrt(cx * cx + cy * cy + cz * cz) <= 1e-6 * fl * ul) return -1;
+  memcpy(s->cam_eye, eye, sizeof(s->cam_eye)), memcpy(s->cam_lookat, lookat, sizeof(s->cam_lookat)), memcpy(s->cam_up, up, sizeof(s->cam_up));
+  s->cam_vfov = vfov_degrees, s->cam_set = 1;
+  return 0;
+}
+
 void orc_scene_aabb(const orc_scene* s, float bmin[3], float bmax[3]) {
   memcpy(bmin, s->bmin, sizeof(float) * 3);
   memcpy(bmax, s->bmax, sizeof(float) * 3);
@@ -1995,9 +2020,37 @@ static f3 get_radiance(orc_ctx* c, const orc_rayf* input_ray, orc_rng* rng) {
 typedef struct {
   f3 org;
   float x_corner, y_corner, z_corner, dx, dy;
+  /* the look-at pinhole (dscene.h::UserCamera): user != 0, org = the eye */
+  int user;
+  uint32_t width, height;
+  f3 f, r, u;
+  float h, ha;
 } orc_camera;
 
+/* pbrhip.cpp::make_user_camera: the frame in double, rounded once */
+static orc_camera make_user_camera(const orc_scene* s, uint32_t width, uint32_t height) {
+  double f[3], r[3], u[3], up[3];
+  for (int k = 0; k < 3; k++) f[k] = (double)s->cam_lookat[k] - s->cam_eye[k], up[k] = s->cam_up[k];
+  const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+  for (int k = 0; k < 3; k++) f[k] /= fl;
+  r[0] = f[1] * up[2] - f[2] * up[1], r[1] = f[2] * up[0] - f[0] * up[2], r[2] = f[0] * up[1] - f[1] * up[0];
+  const double rl = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  for (int k = 0; k < 3; k++) r[k] /= rl;
+  u[0] = r[1] * f[2] - r[2] * f[1], u[1] = r[2] * f[0] - r[0] * f[2], u[2] = r[0] * f[1] - r[1] * f[0];
+  orc_camera c;
+  memset(&c, 0, sizeof(c));
+  c.user = 1, c.width = width, c.height = height;
+  c.org = f3_make(s->cam_eye[0], s->cam_eye[1], s->cam_eye[2]);
+  c.f = f3_make((float)f[0], (float)f[1], (float)f[2]);
+  c.r = f3_make((float)r[0], (float)r[1], (float)r[2]);
+  c.u = f3_make((float)u[0], (float)u[1], (float)u[2]);
+  const double h = tan((double)s->cam_vfov * M_PI / 360.0);
+  c.h = (float)h, c.ha = (float)(h * width / height);
+  return c;
+}
+
 static orc_camera make_camera(const orc_scene* s, uint32_t width, uint32_t height) {
+  if (s->cam_set) return make_user_camera(s, width, height);
   const float *bmin = s->bmin, *bmax = s->bmax;
   float hs, vs;
   if (bmax[0] - bmin[0] > bmax[1] - bmin[1]) {
@@ -2008,6 +2061,7 @@ static orc_camera make_camera(const orc_scene* s, uint32_t width, uint32_t heigh
     hs = vs * (float)width / (float)height;
   }
   orc_camera cam;
+  memset(&cam, 0, sizeof(cam));
   cam.org = f3_make((bmax[0] + bmin[0]) * 0.5f, (bmax[1] + bmin[1]) * 0.5f, bmax[2] + hs * 0.5f * sqrtf(3.f));
   cam.x_corner = (bmax[0] + bmin[0]) * 0.5f - hs * 0.5f;
   cam.y_corner = (bmax[1] + bmin[1]) * 0.5f + vs * 0.5f;
@@ -2020,6 +2074,17 @@ static orc_camera make_camera(const orc_scene* s, uint32_t width, uint32_t heigh
 static orc_rayf camera_ray(const orc_camera* cam, uint32_t x, uint32_t y, orc_rng* rng) {
   float jx = orc_rng_draw(rng);
   float jy = orc_rng_draw(rng);
+  if (cam->user) { /* dcamera.h::user_camera_ray, the pinhole branch */
+    const float sx = (2.0f * ((float)x + jx) / (float)cam->width - 1.0f) * cam->ha;
+    const float sy = (1.0f - 2.0f * ((float)y + jy) / (float)cam->height) * cam->h;
+    const f3 p = f3_add(f3_add(cam->f, f3_scale(cam->r, sx)), f3_scale(cam->u, sy));
+    orc_rayf r;
+    r.dir = f3_normalize_raw(p);
+    r.org = cam->org;
+    r.min_t = 0.0f;
+    r.max_t = ORC_INF;
+    return r;
+  }
   f3 target = f3_make(cam->x_corner + cam->dx * ((float)x + jx), cam->y_corner - cam->dy * ((float)y + jy), cam->z_corner);
   orc_rayf r;
   r.dir = f3_normalize_raw(f3_sub(target, cam->org));
@@ -2297,6 +2362,9 @@ void orc_kat_hair_sample(const float wo[3], const float* params, const float us[
   float pdf = 0.f;
   f3 f = orc_hair_sample(f3_make(wo[0], wo[1], wo[2]), &b, us, &wi, &pdf);
   out[0] = wi.x, out[1] = wi.y, out[2] = wi.z, out[3] = f.x, out[4] = f.y, out[5] = f.z, out[6] = pdf;
+}
+void orc_kat_hair_sample_n(const float wo[3], const float* params, const float* us, uint32_t n, float* out) {
+  for (uint32_t i = 0; i < n; i++) orc_kat_hair_sample(wo, params, us + (size_t)i * 4, out + (size_t)i * 7);
 }
 void orc_kat_uniform_sphere(float u1, float u2, float out[3]) {
   f3 v = orc_uniform_sample_sphere(u1, u2);

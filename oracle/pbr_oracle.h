@@ -97,6 +97,13 @@ int orc_commit(orc_scene*);
  * map removes it: the scene then renders exactly as without.  Valid before or after orc_commit.  Returns 0, or -1 (the environment
  * is left as it was) for a zero size, a texel or scale that is negative / NaN / infinite, or a matrix that is not a rotation. */
 int orc_scene_set_environment(orc_scene*, const float* rgb, uint32_t w, uint32_t h, float scale, const float world_to_env[9]);
+/* pbrhip_scene_set_camera's pinhole: the frame f = normalize(lookat - eye), r = normalize(f x up), u = r x f in
+ * double, rounded once; the ray of a sample is dcamera.h::user_camera_ray's pinhole branch, operation for operation.  Honoured by
+ * orc_camera_ray, orc_render / orc_render_jobs and orc_sample_trace.  eye == NULL: the reference's camera again.  Valid before or
+ * after orc_commit.  Returns 0, or -1 (the camera is left as it was) for what pbrhip_scene_set_camera refuses and for
+ * lens_radius != 0: the thin lens calls the device's cosf / sinf, which the host does not reproduce. */
+int orc_scene_set_camera(orc_scene*, const float eye[3], const float lookat[3], const float up[3], float vfov_degrees,
+                         float lens_radius);
 void orc_scene_aabb(const orc_scene*, float bmin[3], float bmax[3]);
 uint32_t orc_bvh_depth(const orc_scene*);
 
@@ -147,6 +154,8 @@ void orc_kat_ggx_sample(const float wo[3], float ax, float ay, float u0, float u
 /* hair: params = h, v0..v3, s, sigma_a[3], eta, alpha, tints[12], transparent_scale (23 floats) */
 void orc_kat_hair_eval(const float wi[3], const float wo[3], const float* params, float out[4]);
 void orc_kat_hair_sample(const float wo[3], const float* params, const float us[4], float out[7]);
+/* the same for n quadruples of uniforms (n x 4 in, n x 7 out): one wo and one parameter set */
+void orc_kat_hair_sample_n(const float wo[3], const float* params, const float* us, uint32_t n, float* out);
 void orc_kat_uniform_sphere(float u1, float u2, float out[3]);
 void orc_kat_triangle_sampler(float u1, float u2, float out[2]);
 /* ParamToBsdf (cycles-principled-shader.cc:244-412) dump: 34 floats, see pbr_oracle.c */

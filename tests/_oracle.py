@@ -127,6 +127,7 @@ def lib():
         L.orc_attach_material_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
         L.orc_commit.argtypes = [C.c_void_p]
         L.orc_scene_set_environment.argtypes = [C.c_void_p, fp, C.c_uint32, C.c_uint32, C.c_float, fp]
+        L.orc_scene_set_camera.argtypes = [C.c_void_p, fp, fp, fp, C.c_float, C.c_float]
         L.orc_scene_aabb.argtypes = [C.c_void_p, fp, fp]
         L.orc_bvh_depth.argtypes = [C.c_void_p]
         L.orc_bvh_depth.restype = C.c_uint32
@@ -154,6 +155,7 @@ def lib():
         L.orc_kat_ggx_sample.argtypes = [fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp]
         L.orc_kat_hair_eval.argtypes = [fp, fp, fp, fp]
         L.orc_kat_hair_sample.argtypes = [fp, fp, fp, fp]
+        L.orc_kat_hair_sample_n.argtypes = [fp, fp, fp, C.c_uint32, fp]
         L.orc_kat_uniform_sphere.argtypes = [C.c_float, C.c_float, fp]
         L.orc_kat_triangle_sampler.argtypes = [C.c_float, C.c_float, fp]
         L.orc_kat_param_to_bsdf.argtypes = [C.POINTER(PrincipledParam), fp]
@@ -325,6 +327,15 @@ class OracleScene:
         m = None if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(9)
         if self.L.orc_scene_set_environment(self.h, _ptr(px), px.shape[1], px.shape[0], float(scale), _ptr(m)) != 0:
             raise ValueError("orc_scene_set_environment: invalid map, scale or rotation")
+
+    def SetCamera(self, eye, lookat=None, up=(0.0, 1.0, 0.0), fov=30.0, lens_radius=0.0):
+        """pbrlab_amd.Scene.SetCamera on the oracle, pinhole only: eye None = the reference's camera again"""
+        if eye is None:
+            self.L.orc_scene_set_camera(self.h, None, None, None, 0.0, 0.0)
+            return
+        e, a, u = f32(*eye), f32(*lookat), f32(*up)
+        if self.L.orc_scene_set_camera(self.h, _ptr(e), _ptr(a), _ptr(u), float(fov), float(lens_radius)) != 0:
+            raise ValueError("orc_scene_set_camera: invalid camera (a lens radius > 0 is not supported)")
 
     def FetchSceneAABB(self):
         lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)

@@ -174,6 +174,21 @@ def render_batches(backend, S, pa=None, spp=SPP):
     return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
 
 
+def group_stats(means, groups, val, skip_nan=False):
+    """z per (group of pixels, channel) and the Bonferroni t bar.  means: (K,H,W,3) batch means, groups: (H,W) bool masks.
+    skip_nan: a batch mean leaves out the pixels that are NaN in that batch (the caller bounds and explains their number)."""
+    z = []
+    for g in groups:
+        bm = np.nanmean(means[:, g], 1) if skip_nan else means[:, g].mean(1)                                   # (K,3)
+        se = bm.std(0, ddof=1) / np.sqrt(len(means))
+        d = bm.mean(0) - val[g].mean(0)
+        # a cell no light reaches (every batch mean 0, SE 0) passes only when E is 0 there as well
+        z.append(np.where(se > 0, d / np.where(se > 0, se, 1.0), np.where(d == 0, 0.0, np.inf)))
+    z = np.array(z)                                                # (groups, 3)
+    bar = A.student_t_bar(P_FAIL / z.size, len(means) - 1)
+    return z, bar
+
+
 def cell_stats(means, cls, val):
     """z per (cell, channel) and for the whole receiver, and the Bonferroni t bar.  means: (K,H,W,3) batch means."""
     rec = cls == A.PIX_RECEIVER
@@ -185,16 +200,7 @@ def cell_stats(means, cls, val):
             if m.sum() >= MIN_CELL_PIXELS:
                 groups.append(m)
     groups.append(rec)
-    z = []
-    for g in groups:
-        bm = means[:, g].mean(1)                                   # (K,3)
-        se = bm.std(0, ddof=1) / np.sqrt(K)
-        d = bm.mean(0) - val[g].mean(0)
-        # a cell no light reaches (every batch mean 0, SE 0) passes only when E is 0 there as well
-        z.append(np.where(se > 0, d / np.where(se > 0, se, 1.0), np.where(d == 0, 0.0, np.inf)))
-    z = np.array(z)                                                # (cells + 1, 3)
-    bar = A.student_t_bar(P_FAIL / z.size, K - 1)
-    return z, bar
+    return group_stats(means, groups, val)
 
 
 def _pa():

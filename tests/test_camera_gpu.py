@@ -333,3 +333,74 @@ def test_camera_shim_caller_renders():
     TC.test_camera_shim_caller_compiles()
     r = subprocess.run([TC.EXE], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "camera ok" in r.stdout, r.stdout + r.stderr
+
+
+# ---- the oracle's pinhole (orc_scene_set_camera): the same frame and the same ray, so rays and whole frames are compared bit for bit
+PINHOLES = {  # name -> eye, lookat, up, fov
+    "head_on": ((0.0, 0.0, 4.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 35.0),
+    "oblique": CAMERAS["oblique"][:4],
+    "zoom": ((0.031, -0.022, 0.035), (0.0005, 0.0002, -0.0003), (0.1, 0.2, 1.0), 0.35),   # vfov < 1 degree
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(PINHOLES))
+def test_pinhole_rays_are_the_oracle_pinhole(name):
+    pa = _pa()
+    eye, at, up, fov = PINHOLES[name]
+    sg, so = pa.Scene(), O.OracleScene()
+    sg.SetCamera(eye, at, up, fov)
+    so.SetCamera(eye, at, up, fov)
+    rng = np.random.RandomState(3)
+    for (W, H) in ((64, 48), (37, 91)):
+        pix = np.stack([rng.randint(0, W, 300), rng.randint(0, H, 300)], 1)
+        for p, seed in ((0, 1234567890), (17, 2718281828)):
+            want = so.camera_rays(W, H, pix, p=p, seed_seq=seed)
+            got = sg.CameraRays(W, H, np.concatenate([pix, np.full((len(pix), 1), p)], 1), seed_seq=seed)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, W, H, p, seed)
+            assert len(np.unique(want["dir"], axis=0)) == len(np.unique(pix, axis=0))  # (float32 still tells the pixels of the zoom apart)
+    with pytest.raises(ValueError):
+        so.SetCamera(eye, at, up, fov, lens_radius=0.05)
+    assert np.array_equal(so.camera_rays(W, H, pix, p=p, seed_seq=seed).view(np.uint32), want.view(np.uint32)), "a refused call changed the camera"
+    sg.close()
+
+
+def _oblique_inside(s):
+    """an oblique pinhole inside the scene's box, looking across it"""
+    bmin, bmax = (np.array(v, np.float64) for v in s.FetchSceneAABB())
+    c, e = 0.5 * (bmin + bmax), bmax - bmin
+    return c + np.array([0.31, 0.12, 0.42]) * e, c - np.array([0.12, 0.07, 0.05]) * e, (0.1, 1.0, 0.05), 58.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tail", [0xFFFFFFFF, 0])
+@pytest.mark.parametrize("name", ["lambert", "hair"])
+def test_frames_through_an_oblique_pinhole_are_the_oracle_frames(name, tail):
+    """the first user-camera frames compared bit for bit with anything: every kernel behind k_generate_camera against the oracle"""
+    from golden.make_golden import golden_scenes
+    pa = _pa()
+    desc = golden_scenes()[name]
+    sg, so = pa.scene_from_desc(desc), O.oracle_scene_from_desc(desc)
+    cam = _oblique_inside(so)
+    W, H, spp = 64, 48, 4
+    layer = pa.RenderLayer()
+    plain = pa.RenderLayer()
+    pa.Render(sg, W, H, spp, layer=plain, tail_paths=tail)
+    sg.SetCamera(*cam)
+    so.SetCamera(*cam)
+    ok, st = pa.Render(sg, W, H, spp, layer=layer, flags=pa.api.RENDER_STATS, tail_paths=tail)
+    assert (st["n_tail"] == 0) == (tail == 0xFFFFFFFF)
+    rgba, cnt, ost = so.render(W, H, spp, threads=4, math_mode=O.MATH_DEVICE)
+    got = np.array(layer.rgba, np.float32).reshape(H, W, 4)
+    assert (cnt == spp).all() and np.array_equal(np.array(layer.count, np.uint32).reshape(H, W), cnt)
+    assert np.array_equal(got.view(np.uint32), rgba.view(np.uint32)), int((got != rgba).any(-1).sum())
+    assert (st["closest_rays"] + st["tail_closest_rays"] + st["pruned_rays"], st["shadow_rays"] + st["tail_shadow_rays"]) == \
+        (ost["closest_rays"], ost["shadow_rays"])
+    assert (rgba[..., :3].sum(-1) > 0).mean() > 0.5 and not np.array_equal(got, np.array(plain.rgba, np.float32).reshape(H, W, 4))
+    if name == "hair":
+        assert ost["curves_tested"] > 0
+    so.SetCamera(None)
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "oracle_images.npz"))
+    back = so.render(64, 64, 4, threads=4, math_mode=O.MATH_LIBM)[0]
+    assert np.array_equal(back, fx[f"{name}_libm_rgba"]) or not O.libm_is_glibcf(), "a reset camera is not the reference's camera"
+    sg.close()
