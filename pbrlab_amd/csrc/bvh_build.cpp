@@ -1,13 +1,15 @@
 // bvh_build.cpp -- host BVH2 builder + flatten (replaces Embree's rtcCommitScene,
 // src/raytracer/raytracer_impl.cc:136-147,181-192).  Binned SAH (48 bins), leaves of <= kMaxLeaf
 // primitives of a single kind, 64-byte nodes that carry both children's boxes so that one node fetch
-// decides both descents.  Large subtrees are built on worker threads.
+// decides both descents.  Large subtrees are built on worker threads.  Optionally (BvhBuildOptions) the largest subtrees of a
+// triangle-only tree are re-inserted where the tree grows least before it is flattened; the Q collapse's own cost decides whether a pass is kept.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <deque>
 #include <functional>
 #include <future>
@@ -201,13 +203,342 @@ uint32_t leaf_ref(const TNode& n) {
   return kLeafBit | (n.kind ? kCurveBit : 0u) | (n.first << 3) | (n.count - 1u);
 }
 
+// The binary tree as a tree of boxes whose leaves are the Q tree's leaf references: what the collapse's dynamic programme reads.
+struct QV {
+  float lo[3], hi[3];
+  int32_t l = -1, r = -1;  // children, or -1: leaf
+  uint32_t ref = 0;        // leaf: the Q tree's reference
+  uint32_t prims = 0;      // leaf: primitives behind the reference
+};
+
+// ... of a flattened tree.  Children follow their parent.
+void qv_of_nodes(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QV>* out) {
+  std::vector<QV>& T = *out;
+  T.clear();
+  T.reserve(N2.size() * 2 + 1);
+  struct Todo {
+    uint32_t node2;
+    int32_t v;
+  };
+  std::vector<Todo> todo;
+  T.emplace_back();
+  todo.push_back({0u, 0});
+  while (!todo.empty()) {
+    const Todo t = todo.back();
+    todo.pop_back();
+    const BvhNode& b = N2[t.node2];
+    int32_t kids[2] = {-1, -1};
+    int nk = 0;
+    for (int k = 0; k < 2; k++) {
+      const uint32_t ref = k ? b.c1 : b.c0;
+      if (ref == kEmptyChild) continue;
+      const int32_t v = (int32_t)T.size();
+      T.emplace_back();
+      for (int a = 0; a < 3; a++) T[v].lo[a] = b.lo[a][k], T[v].hi[a] = b.hi[a][k];
+      kids[nk++] = v;
+      if (ref & kLeafBit) T[v].ref = map_leaf(ref), T[v].prims = (ref & 7u) + 1u;
+      else todo.push_back({ref, v});
+    }
+    // vertex t.v takes the node's children; a node with one child (a scene of one leaf) passes it through
+    if (nk == 2) T[t.v].l = kids[0], T[t.v].r = kids[1];
+    else if (nk == 1) T[t.v].l = kids[0], T[t.v].r = -1;
+  }
+  // the root's own box: the union of its children
+  for (int a = 0; a < 3; a++) {
+    T[0].lo[a] = std::numeric_limits<float>::infinity(), T[0].hi[a] = -T[0].lo[a];
+    for (int32_t k : {T[0].l, T[0].r})
+      if (k >= 0) T[0].lo[a] = std::min(T[0].lo[a], T[k].lo[a]), T[0].hi[a] = std::max(T[0].hi[a], T[k].hi[a]);
+  }
+}
+
+// Which descendants become the (up to four) children of the Q node of a vertex v is chosen bottom-up over the surface-area
+// cost, with the box a child really presents to a ray: its box rounded outwards on the 8-bit grid of v (step = extent of v /
+// 253 ).  That looseness is what matters for thin primitives in big nodes -- a wall triangle of
+// the Cornell box as a child of a node two units wide is a slab 0.016 thick, and every ray that starts on the wall tests it:
+// with plain areas the collapse put such leaves high up and a shadow ray tested 2.7 triangles instead of 0.9.
+//   below[v] = min over the frontiers F below v, |F| <= 4, of  sum_{u in F} qarea(u | v) * (u leaf ? prims : 1) + below[u]
+// A vertex has at most a dozen frontiers (each inner member may be replaced by its two children while there is room).
+// One vertex of that programme: below[vi] and the chosen frontier choice[4 vi ..], from the values of the vertices under it.
+void qdp_vertex(const std::vector<QV>& T, size_t vi, std::vector<double>& below, std::vector<int32_t>& choice) {
+  using V = QV;
+  auto area = [](const V& v) {
+    const float dx = v.hi[0] - v.lo[0], dy = v.hi[1] - v.lo[1], dz = v.hi[2] - v.lo[2];
+    const float a = dx * dy + dy * dz + dz * dx;
+    return a >= 0.f && std::isfinite(a) ? (double)a : 0.0;
+  };
+  constexpr double kCostNode = 1.0, kCostPrim = 1.0;
+  auto qarea = [&](const V& u, const V& v) {
+    double e[3];
+    for (int a = 0; a < 3; a++) {
+      const double ext = (double)v.hi[a] - (double)v.lo[a];
+      const double st = std::max(ext / 253.0, 1e-37);
+      const double ql = floor(((double)u.lo[a] - (double)v.lo[a]) / st), qh = ceil(((double)u.hi[a] - (double)v.lo[a]) / st);
+      e[a] = std::max(qh - ql, 0.0) * st;
+    }
+    const double a = e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
+    return std::isfinite(a) ? a : 0.0;
+  };
+  const V& v = T[vi];
+  for (int m = 0; m < 4; m++) choice[vi * 4 + m] = -1;
+  below[vi] = 0.0;
+  if (v.l < 0) return;  // leaf: nothing below
+  if (v.r < 0) {        // pass-through (the root of a scene with one leaf or one subtree)
+    choice[vi * 4] = v.l;
+    below[vi] = T[v.l].l < 0 ? area(T[v.l]) * kCostPrim * T[v.l].prims : area(T[v.l]) * kCostNode + below[v.l];
+    return;
+  }
+  // enumerate the frontiers: start from {l, r}; replace inner members by their children while the size stays <= 4
+  int32_t fronts[16][4];
+  int sizes[16], nf = 0;
+  fronts[0][0] = v.l, fronts[0][1] = v.r, sizes[0] = 2, nf = 1;
+  for (int i = 0; i < nf && nf < 16; i++) {
+    if (sizes[i] >= 4) continue;
+    for (int m = 0; m < sizes[i] && nf < 16; m++) {
+      const V& u = T[fronts[i][m]];
+      if (u.l < 0 || u.r < 0) continue;
+      int32_t g[4];
+      int n = 0;
+      for (int j = 0; j < sizes[i]; j++) {
+        if (j == m) g[n++] = u.l, g[n++] = u.r;
+        else g[n++] = fronts[i][j];
+      }
+      std::sort(g, g + n);
+      bool dup = false;
+      for (int q = 0; q < nf && !dup; q++) dup = sizes[q] == n && std::equal(g, g + n, fronts[q]);
+      if (dup) continue;
+      std::copy(g, g + n, fronts[nf]), sizes[nf] = n, nf++;
+    }
+  }
+  // (the frontiers draw their members from at most 2 + 4 + 8 vertices: each one's term is worked out once)
+  int32_t term_of[16];
+  double term[16];
+  int nt = 0;
+  auto member = [&](int32_t ui) {
+    for (int k = 0; k < nt; k++)
+      if (term_of[k] == ui) return term[k];
+    const V& u = T[ui];
+    term_of[nt] = ui, term[nt] = u.l < 0 ? qarea(u, v) * kCostPrim * u.prims : qarea(u, v) * kCostNode + below[ui];
+    return term[nt++];
+  };
+  double best = 1e300;
+  int bi = 0;
+  for (int i = 0; i < nf; i++) {
+    double c = 0.0;
+    for (int m = 0; m < sizes[i]; m++) c += member(fronts[i][m]);
+    if (c < best) best = c, bi = i;
+  }
+  below[vi] = best;
+  for (int m = 0; m < sizes[bi]; m++) choice[vi * 4 + m] = fronts[bi][m];
+}
+
+// The stack need of the Q node of vertex vi, from its chosen frontier and the needs of the vertices under it (build_qtree's definition).
+uint32_t qdp_need(const std::vector<QV>& T, size_t vi, const std::vector<int32_t>& choice, const std::vector<uint32_t>& need) {
+  uint32_t nc = 0, deepest = 0;
+  for (int m = 0; m < 4; m++) {
+    const int32_t u = choice[vi * 4 + m];
+    if (u < 0) continue;
+    nc++;
+    if (T[u].l >= 0) deepest = std::max(deepest, need[u]);
+  }
+  return (nc ? nc - 1u : 0u) + deepest;
+}
+
+
+// Subtree re-insertion on the build-time tree.  A top-down split decides near the root with the least knowledge:
+// a dozen wall triangles among half a million small ones end up in nodes that span the room.  A pass takes the largest nodes, one
+// after the other, out of the tree and puts each back where the tree grows least; leaves move as they are (ranges, kinds and the
+// order array never change).  Whether a pass is kept is decided by what the Q collapse would pay for the tree, not by the binary
+// surface-area sum: that one keeps falling while the collapsed tree gets worse.
+struct Reinserter {
+  std::vector<TNode>& T;
+  int32_t root;
+  const BvhBuildOptions& opt;
+  std::vector<int32_t> parent;
+  // the collapse's programme per pool node: a move dirties the two paths from its ends to the root and nothing else
+  std::vector<QV> qv;
+  std::vector<double> below;
+  std::vector<int32_t> choice;
+  std::vector<uint32_t> need;
+  std::vector<uint8_t> dirty;
+  struct Move {
+    int32_t n, sibling;  // n was taken from beside `sibling`
+  };
+  std::vector<Move> log;  // the moves of the running pass, for undoing it
+
+  static Box unite(const Box& a, const Box& b) {
+    Box u = a;
+    u.grow(b);
+    return u;
+  }
+  void replace_child(int32_t g, int32_t from, int32_t to) { (T[g].left == from ? T[g].left : T[g].right) = to; }
+  // boxes upwards from i, each the exact union of its two children; above the first one that stays as it is nothing changes
+  void refit_up(int32_t i) {
+    for (; i >= 0; i = parent[i]) {
+      const Box b = unite(T[T[i].left].box, T[T[i].right].box);
+      if (memcmp(&b, &T[i].box, sizeof(Box)) == 0) break;
+      T[i].box = b;
+    }
+  }
+  void mark_up(int32_t i) {
+    if (dirty.empty()) return;
+    for (; i >= 0; i = parent[i]) dirty[i] = 1;
+  }
+  // n leaves the tree together with its parent p, whose other child takes p's place; returns p
+  int32_t unlink(int32_t n) {
+    const int32_t p = parent[n], g = parent[p], s = T[p].left == n ? T[p].right : T[p].left;
+    parent[s] = g;
+    if (g < 0) root = s;
+    else replace_child(g, p, s), refit_up(g);
+    return p;
+  }
+  // p, which holds n on one side, takes x's place and x on its other side
+  void link(int32_t p, int32_t n, int32_t x) {
+    const int32_t g = parent[x];
+    (T[p].left == n ? T[p].right : T[p].left) = x;
+    parent[x] = p, parent[p] = g;
+    T[p].box = unite(T[x].box, T[n].box);
+    if (g < 0) root = p;
+    else replace_child(g, x, p), refit_up(g);
+  }
+
+  // One pass over the opt.reinsert_top largest nodes, in descending order of area (ties: the lower index).  Returns the moves made.
+  uint32_t pass() {
+    std::vector<std::pair<float, int32_t>> cand;
+    cand.reserve(T.size());
+    for (int32_t i = 0; i < (int32_t)T.size(); i++)
+      if (i != root && parent[i] != root) cand.push_back({T[i].box.area(), i});
+    const size_t K = std::min<size_t>(opt.reinsert_top, cand.size());
+    auto larger = [](const std::pair<float, int32_t>& a, const std::pair<float, int32_t>& b) {
+      return a.first > b.first || (a.first == b.first && a.second < b.second);
+    };
+    if (K < cand.size()) std::nth_element(cand.begin(), cand.begin() + (ptrdiff_t)K, cand.end(), larger);
+    std::sort(cand.begin(), cand.begin() + (ptrdiff_t)K, larger);
+    using Entry = std::pair<double, int32_t>;  // (area growth of the ancestors, node): the least first, ties to the lower index
+    std::vector<Entry> heap;
+    uint32_t moves = 0;
+    for (size_t c = 0; c < K; c++) {
+      const int32_t n = cand[c].second;
+      if (n == root || parent[n] == root) continue;  // (an earlier move of this pass put it there)
+      const int32_t s = T[parent[n]].left == n ? T[parent[n]].right : T[parent[n]].left;
+      const int32_t p = unlink(n);
+      const Box nb = T[n].box;
+      const double an = nb.area();
+      // where it was: the position to beat
+      double best = unite(T[s].box, nb).area();
+      for (int32_t a = parent[s]; a >= 0; a = parent[a]) best += (double)unite(T[a].box, nb).area() - (double)T[a].box.area();
+      int32_t bx = s;
+      // best first from the root; a subtree whose ancestors alone grow by as much as the best position costs is left out
+      heap.clear();
+      heap.push_back({0.0, root});
+      while (!heap.empty()) {
+        std::pop_heap(heap.begin(), heap.end(), std::greater<Entry>());
+        const Entry e = heap.back();
+        heap.pop_back();
+        if (!(e.first + an < best)) break;
+        const int32_t x = e.second;
+        const double total = e.first + (double)unite(T[x].box, nb).area();
+        if (total < best) best = total, bx = x;
+        const double grown = total - (double)T[x].box.area();
+        if (T[x].left >= 0 && grown + an < best) {
+          heap.push_back({grown, T[x].left}), std::push_heap(heap.begin(), heap.end(), std::greater<Entry>());
+          heap.push_back({grown, T[x].right}), std::push_heap(heap.begin(), heap.end(), std::greater<Entry>());
+        }
+      }
+      const int32_t g = parent[s];
+      link(p, n, bx);
+      if (bx == s) continue;  // (back where it was: the boxes are the same unions again)
+      mark_up(g), mark_up(p);
+      log.push_back({n, s});
+      moves++;
+    }
+    return moves;
+  }
+  void undo_pass() {
+    for (size_t i = log.size(); i-- > 0;) link(unlink(log[i].n), log[i].n, log[i].sibling);
+    log.clear();
+  }
+
+  // below[root] of the collapse's programme: the vertices a move has dirtied, children first
+  double evaluate() {
+    std::vector<int32_t> todo{root}, pre;
+    while (!todo.empty()) {
+      const int32_t i = todo.back();
+      todo.pop_back();
+      if (!dirty[i]) continue;
+      pre.push_back(i);
+      if (T[i].left >= 0) todo.push_back(T[i].left), todo.push_back(T[i].right);
+    }
+    for (size_t k = pre.size(); k-- > 0;) {
+      const int32_t i = pre[k];
+      const TNode& t = T[i];
+      QV& q = qv[i];
+      for (int a = 0; a < 3; a++) q.lo[a] = BvhNode::widen_lo(t.box.lo[a]), q.hi[a] = BvhNode::widen_hi(t.box.hi[a]);  // (the boxes the flattened tree stores)
+      q.l = t.left, q.r = t.right, q.prims = t.left < 0 ? t.count : 0u;
+      qdp_vertex(qv, (size_t)i, below, choice);
+      need[i] = qdp_need(qv, (size_t)i, choice, need);
+      dirty[i] = 0;
+    }
+    return below[root];
+  }
+  double inner_area() const {  // the binary tree's surface-area sum (every pool node is in the tree)
+    double sum = 0.0;
+    for (const TNode& t : T)
+      if (t.left >= 0) sum += (double)t.box.area();
+    return sum;
+  }
+  // TNode::depth of every node; returns the deepest inner node's (what the flattened tree reports: FlatBvh::depth)
+  uint32_t set_depths() {
+    uint32_t deepest = 0;
+    std::vector<int32_t> todo{root};
+    T[root].depth = 1;
+    while (!todo.empty()) {
+      const int32_t i = todo.back();
+      todo.pop_back();
+      if (T[i].left < 0) continue;
+      deepest = std::max(deepest, T[i].depth);
+      T[T[i].left].depth = T[T[i].right].depth = T[i].depth + 1;
+      todo.push_back(T[i].left), todo.push_back(T[i].right);
+    }
+    return deepest;
+  }
+
+  void run(FlatBvh* out) {
+    if (T[root].left < 0) return;
+    parent.assign(T.size(), -1);
+    for (int32_t i = 0; i < (int32_t)T.size(); i++)
+      if (T[i].left >= 0) parent[T[i].left] = parent[T[i].right] = i;
+    bool by_q = opt.for_qtree;
+    double cost = 0.0;
+    if (by_q) {
+      qv.resize(T.size()), below.assign(T.size(), 0.0), choice.assign(T.size() * 4, -1), need.assign(T.size(), 0u), dirty.assign(T.size(), 1);
+      cost = evaluate();
+      by_q = need[root] <= (uint32_t)kStackDepth;  // (a Q tree that is dropped anyway: the binary tree is what gets walked)
+      if (!by_q) dirty.clear();
+    }
+    if (!by_q) cost = inner_area();
+    out->reinsert_cost0 = out->reinsert_cost = cost;
+    for (uint32_t k = 0; k < opt.reinsert_passes; k++) {
+      const uint32_t moves = pass();
+      if (moves == 0) break;
+      const double c = by_q ? evaluate() : inner_area();
+      const bool fits = set_depths() <= (uint32_t)kStackDepth && (!by_q || need[root] <= (uint32_t)kStackDepth);
+      if (!(c < cost) || !fits) {  // the first pass that does not pay, or that the traversal stack cannot hold, is taken back
+        undo_pass();
+        break;
+      }
+      log.clear();
+      cost = c;
+      out->reinsert_cost = c, out->reinsert_passes++, out->reinsert_moves += moves;
+    }
+    set_depths();
+  }
+};
+
 }  // namespace
 
 void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const std::vector<uint8_t>& kinds,
-               FlatBvh* out) {
-  out->nodes.clear();
-  out->slot_gid.clear();
-  out->depth = 0;
+               FlatBvh* out, const BvhBuildOptions& opt) {
+  *out = FlatBvh();
   uint32_t n = (uint32_t)kinds.size();
   if (n == 0) return;
   Builder b;
@@ -220,7 +551,17 @@ void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const
   }
   Builder::Pool pool;
   pool.nodes.reserve(2 * (size_t)n / 2 + 16);
+  const auto t_build = std::chrono::steady_clock::now();
   int32_t root = b.build(pool, 0, n, 1);
+  const auto t_reinsert = std::chrono::steady_clock::now();
+  out->build_ms = std::chrono::duration<double, std::milli>(t_reinsert - t_build).count();
+  // (triangle-only scenes: a tree with curve leaves stays as the builder left it -- host_scene.h::BvhBuildOptions)
+  if (opt.reinsert_passes > 0 && opt.reinsert_top > 0 && std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; })) {
+    Reinserter re{pool.nodes, root, opt};
+    re.run(out);
+    root = re.root;
+    out->reinsert_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_reinsert).count();
+  }
 
   // flatten: internal nodes get consecutive indices; node 0 is always internal
   const std::vector<TNode>& T = pool.nodes;
@@ -311,123 +652,34 @@ uint32_t qtree_stack_need(const std::vector<QNode>& N) {
   return need[0];
 }
 
+double qtree_cost(const std::vector<BvhNode>& N2, uint32_t* stack_need) {
+  if (stack_need) *stack_need = 0;
+  if (N2.empty()) return 0.0;
+  std::vector<QV> T;
+  qv_of_nodes(N2, [](uint32_t ref) { return ref; }, &T);
+  const size_t nv = T.size();
+  std::vector<double> below(nv, 0.0);
+  std::vector<int32_t> choice(nv * 4, -1);
+  std::vector<uint32_t> need(nv, 0u);
+  for (size_t vi = nv; vi-- > 0;) {  // (children follow their parent)
+    qdp_vertex(T, vi, below, choice);
+    need[vi] = qdp_need(T, vi, choice, need);
+  }
+  // (a pass-through root whose only child is inner gets a node of its own under the root's: one child, nothing left behind)
+  if (stack_need) *stack_need = need[0];
+  return below[0];
+}
+
 uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out) {
   out->clear();
   if (N2.empty()) return 0;
-  // The binary tree as a tree of boxes whose leaves are the Q tree's leaf references.  Children follow their parent.
-  struct V {
-    float lo[3], hi[3];
-    int32_t l = -1, r = -1;  // children, or -1: leaf
-    uint32_t ref = 0;        // leaf: the Q tree's reference
-    uint32_t prims = 0;      // leaf: primitives behind the reference
-  };
+  using V = QV;
   std::vector<V> T;
-  T.reserve(N2.size() * 2 + 1);
-  {
-    struct Todo {
-      uint32_t node2;
-      int32_t v;
-    };
-    std::vector<Todo> todo;
-    T.emplace_back();
-    todo.push_back({0u, 0});
-    while (!todo.empty()) {
-      const Todo t = todo.back();
-      todo.pop_back();
-      const BvhNode& b = N2[t.node2];
-      int32_t kids[2] = {-1, -1};
-      int nk = 0;
-      for (int k = 0; k < 2; k++) {
-        const uint32_t ref = k ? b.c1 : b.c0;
-        if (ref == kEmptyChild) continue;
-        const int32_t v = (int32_t)T.size();
-        T.emplace_back();
-        for (int a = 0; a < 3; a++) T[v].lo[a] = b.lo[a][k], T[v].hi[a] = b.hi[a][k];
-        kids[nk++] = v;
-        if (ref & kLeafBit) T[v].ref = map_leaf(ref), T[v].prims = (ref & 7u) + 1u;
-        else todo.push_back({ref, v});
-      }
-      // vertex t.v takes the node's children; a node with one child (a scene of one leaf) passes it through
-      if (nk == 2) T[t.v].l = kids[0], T[t.v].r = kids[1];
-      else if (nk == 1) T[t.v].l = kids[0], T[t.v].r = -1;
-    }
-    // the root's own box: the union of its children
-    for (int a = 0; a < 3; a++) {
-      T[0].lo[a] = std::numeric_limits<float>::infinity(), T[0].hi[a] = -T[0].lo[a];
-      for (int32_t k : {T[0].l, T[0].r})
-        if (k >= 0) T[0].lo[a] = std::min(T[0].lo[a], T[k].lo[a]), T[0].hi[a] = std::max(T[0].hi[a], T[k].hi[a]);
-    }
-  }
-  auto area = [](const V& v) {
-    const float dx = v.hi[0] - v.lo[0], dy = v.hi[1] - v.lo[1], dz = v.hi[2] - v.lo[2];
-    const float a = dx * dy + dy * dz + dz * dx;
-    return a >= 0.f && std::isfinite(a) ? (double)a : 0.0;
-  };
-  // Which descendants become the (up to four) children of the Q node of a vertex v is chosen bottom-up over the surface-area
-  // cost, with the box a child really presents to a ray: its box rounded outwards on the 8-bit grid of v (step = extent of v /
-  // 253 ).  That looseness is what matters for thin primitives in big nodes -- a wall triangle of
-  // the Cornell box as a child of a node two units wide is a slab 0.016 thick, and every ray that starts on the wall tests it:
-  // with plain areas the collapse put such leaves high up and a shadow ray tested 2.7 triangles instead of 0.9.
-  //   below[v] = min over the frontiers F below v, |F| <= 4, of  sum_{u in F} qarea(u | v) * (u leaf ? prims : 1) + below[u]
-  // A vertex has at most a dozen frontiers (each inner member may be replaced by its two children while there is room).
-  constexpr double kCostNode = 1.0, kCostPrim = 1.0;
+  qv_of_nodes(N2, map_leaf, &T);
   const size_t nv = T.size();
   std::vector<double> below(nv, 0.0);
   std::vector<int32_t> choice(nv * 4, -1);  // the chosen frontier of v
-  auto qarea = [&](const V& u, const V& v) {
-    double e[3];
-    for (int a = 0; a < 3; a++) {
-      const double ext = (double)v.hi[a] - (double)v.lo[a];
-      const double st = std::max(ext / 253.0, 1e-37);
-      const double ql = floor(((double)u.lo[a] - (double)v.lo[a]) / st), qh = ceil(((double)u.hi[a] - (double)v.lo[a]) / st);
-      e[a] = std::max(qh - ql, 0.0) * st;
-    }
-    const double a = e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
-    return std::isfinite(a) ? a : 0.0;
-  };
-  for (size_t vi = nv; vi-- > 0;) {
-    const V& v = T[vi];
-    if (v.l < 0) continue;  // leaf: nothing below
-    if (v.r < 0) {          // pass-through (the root of a scene with one leaf or one subtree)
-      choice[vi * 4] = v.l;
-      below[vi] = T[v.l].l < 0 ? area(T[v.l]) * kCostPrim * T[v.l].prims : area(T[v.l]) * kCostNode + below[v.l];
-      continue;
-    }
-    // enumerate the frontiers: start from {l, r}; replace inner members by their children while the size stays <= 4
-    int32_t fronts[16][4];
-    int sizes[16], nf = 0;
-    fronts[0][0] = v.l, fronts[0][1] = v.r, sizes[0] = 2, nf = 1;
-    for (int i = 0; i < nf && nf < 16; i++) {
-      if (sizes[i] >= 4) continue;
-      for (int m = 0; m < sizes[i] && nf < 16; m++) {
-        const V& u = T[fronts[i][m]];
-        if (u.l < 0 || u.r < 0) continue;
-        int32_t g[4];
-        int n = 0;
-        for (int j = 0; j < sizes[i]; j++) {
-          if (j == m) g[n++] = u.l, g[n++] = u.r;
-          else g[n++] = fronts[i][j];
-        }
-        std::sort(g, g + n);
-        bool dup = false;
-        for (int q = 0; q < nf && !dup; q++) dup = sizes[q] == n && std::equal(g, g + n, fronts[q]);
-        if (dup) continue;
-        std::copy(g, g + n, fronts[nf]), sizes[nf] = n, nf++;
-      }
-    }
-    double best = 1e300;
-    int bi = 0;
-    for (int i = 0; i < nf; i++) {
-      double c = 0.0;
-      for (int m = 0; m < sizes[i]; m++) {
-        const V& u = T[fronts[i][m]];
-        c += u.l < 0 ? qarea(u, v) * kCostPrim * u.prims : qarea(u, v) * kCostNode + below[fronts[i][m]];
-      }
-      if (c < best) best = c, bi = i;
-    }
-    below[vi] = best;
-    for (int m = 0; m < sizes[bi]; m++) choice[vi * 4 + m] = fronts[bi][m];
-  }
+  for (size_t vi = nv; vi-- > 0;) qdp_vertex(T, vi, below, choice);
   // emit: the Q node of vertex v has its chosen frontier as children
   struct Item {
     int32_t v;

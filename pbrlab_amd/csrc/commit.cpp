@@ -383,7 +383,7 @@ static int upload_lights(pbrhip_scene* s, const CommitStage& cs) {
   return PBRHIP_OK;
 }
 
-static int build_binary_tree(pbrhip_scene* s, int builder, CommitStage* cs) {  // on the GPU into the scene's nodes, or on the host and uploaded
+static int build_binary_tree(pbrhip_scene* s, const Knobs& k, int builder, CommitStage* cs) {  // on the GPU into the scene's nodes, or on the host and uploaded
   FlatBvh& bvh = cs->bvh;
   const uint32_t np = (uint32_t)cs->prims.size();
   s->bvh_built_on_gpu = false;
@@ -397,7 +397,15 @@ static int build_binary_tree(pbrhip_scene* s, int builder, CommitStage* cs) {  /
       bvh = FlatBvh();
     }
   }
-  if (!s->bvh_built_on_gpu) build_bvh(cs->lo, cs->hi, cs->kinds, &bvh);
+  if (!s->bvh_built_on_gpu) {
+    BvhBuildOptions opt;
+    opt.reinsert_passes = k.bvh_reinsert ? kReinsertPasses : 0u, opt.reinsert_top = k.bvh_reinsert_top;
+    opt.for_qtree = k.wide;  // (no Q tree at this commit: the binary tree is what the rays walk)
+    build_bvh(cs->lo, cs->hi, cs->kinds, &bvh, opt);
+    if (k.debug)
+      fprintf(stderr, "pbrhip: commit: host BVH: top-down build %.2f ms; re-insertion %.2f ms: %u passes kept, %u subtrees moved, %s %.6g -> %.6g\n", bvh.build_ms,
+              bvh.reinsert_ms, bvh.reinsert_passes, bvh.reinsert_moves, k.wide ? "collapse cost" : "inner area", bvh.reinsert_cost0, bvh.reinsert_cost);
+  }
   if (bvh.depth > (uint32_t)kStackDepth)
     return fail(PBRHIP_EOVERFLOW, "BVH depth %u exceeds the traversal stack (%d)", bvh.depth, kStackDepth);
   s->bvh_depth = bvh.depth;
@@ -528,7 +536,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   prim_boxes(s, cs.prims, &cs.lo, &cs.hi, &cs.kinds);
   scene_bounds(s);
   s->num_curves = (uint32_t)(cs.kinds.size() - std::count(cs.kinds.begin(), cs.kinds.end(), 0));
-  if (int rc = build_binary_tree(s, builder, &cs)) return rc;
+  if (int rc = build_binary_tree(s, k, builder, &cs)) return rc;
   if (int rc = stage_slots_and_materials(s, &cs)) return rc;
   const TreeBufs& t = s->tree;
   if (t.num_slots) HIPCHK(hipMemcpyAsync(t.slots(), cs.slots.data(), (size_t)t.num_slots * 64, hipMemcpyHostToDevice, s->stream));

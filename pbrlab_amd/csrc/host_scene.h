@@ -65,12 +65,33 @@ struct FlatBvh {
   std::vector<BvhNode> nodes;
   std::vector<uint32_t> slot_gid;  // leaf order -> gid
   uint32_t depth = 0;
+  // what the re-insertion passes did (BvhBuildOptions; all zero when they are off)
+  uint32_t reinsert_passes = 0, reinsert_moves = 0;  // passes kept, subtrees moved by them
+  double reinsert_cost0 = 0.0, reinsert_cost = 0.0;  // the deciding cost of the builder's tree and of the kept one
+  double build_ms = 0.0, reinsert_ms = 0.0;          // the top-down build; the passes with their evaluations
+};
+
+// Subtree re-insertion on the build-time tree: up to `reinsert_passes` passes, each over the `reinsert_top`
+// largest nodes by box area; a pass is kept only while it lowers the cost the Q collapse itself would pay (for_qtree; the binary
+// surface-area sum otherwise, or when the builder's own tree already needs more Q stack than there is) and the tree still fits the
+// traversal stack.  0 passes: the builder's tree, byte for byte.  Sets with curves get no pass whatever the options say: the passes
+// gained 3 % on the hair scene, but a frame of a small hair scene with nearly every ray suspended did not end once on such a tree and
+// the reason is not known; triangle-only trees are what the flagship scenes have.
+constexpr uint32_t kReinsertPasses = 4, kReinsertTop = 20000;
+struct BvhBuildOptions {
+  uint32_t reinsert_passes = 0;
+  uint32_t reinsert_top = kReinsertTop;
+  bool for_qtree = true;
 };
 
 // Binned-SAH BVH2 over primitive boxes; leaves hold <= kMaxLeaf primitives of ONE kind.
 // boxes: lo/hi per primitive (3 floats each); kinds: 0 triangle / 1 curve.
 void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const std::vector<uint8_t>& kinds,
-               FlatBvh* out);
+               FlatBvh* out, const BvhBuildOptions& opt = BvhBuildOptions());
+
+// What the collapse below pays for a binary tree -- below[root] of its dynamic programme -- without emitting a node, and the exact
+// stack need of the Q tree it would emit.
+double qtree_cost(const std::vector<BvhNode>& nodes, uint32_t* stack_need);
 
 // The binary tree collapsed to four children per node with quantised boxes (dscene.h::QNode).  Which descendants of a
 // binary node become the children of its Q node -- a frontier of at most four subtrees below it -- is chosen bottom-up by

@@ -16,6 +16,8 @@ struct Knobs {
   // scene commit
   int bvh = -1;                 // PBRHIP_BVH: -1 (unset) = the scene's builder; "gpu" = the LBVH built on the GPU, any other value = the host's SAH tree
   bool wide = true;             // PBRHIP_WIDE: a value that atoi reads as 0 (any non-number too) = no Q tree: none is built at commit, none is walked at render
+  bool bvh_reinsert = true;     // PBRHIP_BVH_REINSERT (1): 0 = the host builder's tree as its top-down splits leave it, no subtree re-insertion (host_scene.h::BvhBuildOptions; triangle-only scenes, the others never get it)
+  uint32_t bvh_reinsert_top = 20000;  // PBRHIP_BVH_REINSERT_TOP (kReinsertTop): the largest nodes by box area that a re-insertion pass takes out and puts back; 0 = none
   bool sss_entry = true;        // PBRHIP_SSS_ENTRY (1): 0 = random walks start at the root, not at the cut of the Q tree around their instance
   uint32_t sss_foreign = 3;     // PBRHIP_SSS_FOREIGN (3): foreign references allowed in a walk's entry cut (at most kSssMaxForeign)
   bool debug = false;           // PBRHIP_DEBUG: set = commit and render print sizes and free memory on stderr

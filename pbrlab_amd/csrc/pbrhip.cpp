@@ -71,6 +71,8 @@ Knobs pb::read_knobs() {
   Knobs k;
   if (const char* e = env("PBRHIP_BVH")) k.bvh = strcmp(e, "gpu-wide") == 0 ? PBRHIP_BVH_GPU_LBVH_WIDE : (strcmp(e, "gpu") == 0 ? PBRHIP_BVH_GPU_LBVH : PBRHIP_BVH_HOST_SAH);
   k.wide = not_zero("PBRHIP_WIDE");
+  k.bvh_reinsert = u32("PBRHIP_BVH_REINSERT", 1u) != 0u;
+  k.bvh_reinsert_top = u32("PBRHIP_BVH_REINSERT_TOP", kReinsertTop);
   k.sss_entry = u32("PBRHIP_SSS_ENTRY", 1u) != 0u;
   k.sss_foreign = u32("PBRHIP_SSS_FOREIGN", 3u);
   k.debug = env("PBRHIP_DEBUG") != nullptr;

@@ -31,7 +31,10 @@ int main() {
       kinds[i] = (uint8_t)(it % 3 != 0 && rng() % 4 == 0);  // (every third case: triangles only)
     }
     FlatBvh b;
-    build_bvh(lo, hi, kinds, &b);
+    BvhBuildOptions opt;  // (every other case: with subtree re-insertion -- it runs on the triangle-only cases -- over few to all of the nodes, decided by the Q collapse's cost or by the binary tree's)
+    opt.reinsert_passes = it % 2 ? kReinsertPasses : 0u, opt.reinsert_top = 8u + 13u * (uint32_t)it, opt.for_qtree = it % 4 == 1;
+    build_bvh(lo, hi, kinds, &b, opt);
+    if (b.depth > (uint32_t)kStackDepth) return printf("FAIL: depth %u\n", b.depth), 1;
     if (n == 0) { if (!b.nodes.empty()) return printf("FAIL: nodes for empty input\n"), 1; continue; }
     std::vector<int> seen(n, 0);
     if (b.slot_gid.size() != n) return printf("FAIL: slot count\n"), 1;
