@@ -509,7 +509,6 @@ void pb::bind_dscene(pbrhip_scene* s) {
   d.top_nodes = s->bvh_built_on_gpu ? 0u : std::min<uint32_t>(t.num_nodes, (uint32_t)kTopNodes);
   d.wide = t.wide_nodes ? t.d_wide.p : nullptr, d.q_hitcode = t.wide_nodes ? t.d_qhit.p : nullptr, d.wide_nodes = t.wide_nodes;
   d.q_tri0 = (uint32_t)t.tri0(), d.q_pt0 = (uint32_t)t.pt0();
-  d.wide_top_nodes = std::min<uint32_t>(t.wide_nodes, (uint32_t)kTopNodes);
   d.shade = s->d_shade.p, d.num_curves = s->num_curves;
   d.materials = s->d_materials.p, d.num_materials = (uint32_t)s->materials.size();
   d.light_cdf = s->d_light_cdf.p, d.light_heads = s->d_heads.p, d.num_lights = (uint32_t)s->lights.size();

@@ -36,14 +36,18 @@ constexpr int kSimpleLdsStack = 40;          // of which the one-ray-per-lane tr
 #define PB_TOP_NODES 64
 #endif
 constexpr int kTopNodes = PB_TOP_NODES;
-// ... and the Q tree's kernels.  0 since round 4: with the packed two-triangle leaf test the triangle kernel is at its register
-// budget and the staging branch costs it a spill; same-box A/B on C2 (k_trace ms per frame, two runs each): no staging 33.9 / 33.6,
-// 64 nodes 35.1 / 34.8, 128 nodes 34.9 / 35.0, 256 nodes (12 stack entries in LDS) 34.8 / 35.3 -- the top of the tree is served by
-// the vector L1 either way (profiles/README.md).
-#ifndef PB_TOP_NODES_WIDE
-#define PB_TOP_NODES_WIDE 0
-#endif
-constexpr int kTopNodesWide = PB_TOP_NODES_WIDE;
+// (The Q tree's top is not staged: with the packed two-triangle leaf test the triangle kernel is at its register budget and the
+// staging branch costs it a spill; same-box A/B on C2 (k_trace ms per frame, two runs each): no staging 33.9 / 33.6, 64 nodes
+// 35.1 / 34.8, 128 nodes 34.9 / 35.0, 256 nodes (12 stack entries in LDS) 34.8 / 35.3 -- the top of the tree is served by the
+// vector L1 either way (profiles/README.md).)
+// Words of the suspend record of a resumable ray (kernels.h::PathState::susp_turns): a header, then the whole traversal stack.  The layout
+// is dtrace_pv.h's, which packs and unpacks it.
+constexpr int kSuspHeaderWords = 8;
+constexpr uint32_t kSuspWords = (uint32_t)(kSuspHeaderWords + kStackDepth);
+static_assert(kStackDepth <= 64, "a suspend record holds the whole traversal stack (72 words at most)");
+// words between two heads of a ray queue (k_trace's, dtrace_pv.h): each in a 256-byte block of its own (atomics on one cache line
+// serialise: eight heads in ONE line were twice as slow as one head)
+constexpr uint32_t kHeadStride = 64;
 
 // Both children's boxes, interleaved [axis][child] so that the two children's values of one bound sit in an aligned
 // register pair after the 16-byte loads: the slab test runs on v_pk_add_f32 / v_pk_mul_f32 (two children per instruction).
@@ -256,7 +260,6 @@ struct DScene {
   uint32_t q_tri0, q_pt0;       // 16-byte index of triangle leaf record 0 / point 0 in `wide`
   const uint32_t* q_hitcode;    // per point p: the hit code of piece p (slot | routing bits)
   uint32_t top_nodes;           // nodes 0 .. top_nodes-1 are the breadth-first top of the tree (<= kTopNodes; 0: not numbered that way)
-  uint32_t wide_top_nodes;      // the same for the Q tree
   uint32_t lights_transformed;  // an emissive instance has a transform: lrecs / light_boxes are not what the raytracer sees
   const SssEntry* sss_entries;  // per instance (num_sss_entries), or null: where its random walks' rays start
   uint32_t num_sss_entries;

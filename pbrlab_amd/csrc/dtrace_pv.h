@@ -3,12 +3,22 @@
 // Why: a one-ray-per-lane while/if traversal on gfx950 measured 9.6 active lanes per VALU instruction (15 %)
 // -- lanes at a leaf idle while others walk nodes, and finished rays idle until the slowest lane of the wave
 // ends (profiles/README.md, round 1a).  Here every lane owns a small state machine
-//     IDLE -> NODE(internal node) <-> TRI(one triangle of a leaf) [<-> CURVE]
-// whose next work item (a 64-byte node or a 64-byte primitive slot -- same footprint) is prefetched into
-// registers as soon as it is known.  Each iteration the WAVE votes (ballot + popcount) for the phase with the
+//     IDLE -> NODE(internal node) <-> TRI(one leaf item of triangles) [<-> CURVE]
+// whose next work item is prefetched into registers (D0..D4) as soon as it is known: a 64-byte node of either tree; of the binary
+// tree a 64-byte primitive slot; of the Q tree an 80-byte TriPair (triangle-only scenes), a 48-byte triangle slot or a 64-byte
+// curve record (dscene.h).  Each iteration the WAVE votes (ballot + popcount) for the phase with the
 // most lanes and executes only that phase's code, so at least half of the busy lanes advance per iteration and
 // the two code paths never serialise.  When enough lanes are idle they are refilled from the ray queue
 // (persistent threads): the wave grabs rays in batches with one atomicAdd and deals them out by ballot rank.
+//
+// One turn of trace_pv's loop, in the order of the text: the refill (queue grab, delivery of the finished rays, new rays -- split, plain
+// or walking, by the sink -- and their start: resume, root or walk entry), else the drain check, the vote and the voted phase's turn
+// (node: wide / binary; leaf: TriPair / curve record / slot), then the common tail: pop / finish / decode, and the ONE load site.
+// The turns stay in one function body on purpose.  Measured on the code object (scripts/ktable.py --diff --histogram against the build
+// before): the per-lane state as one struct changed registers or instruction mix of 24 of the 27 k_trace / k_sss_walk / k_hook_pv
+// instantiations (12 bytes of scratch in k_trace<false, false, true, true>); the suspend record's packing and unpacking as functions
+// changed every k_trace (the same 12 bytes); the tie rule as a function, and the RayFrame store as a function, changed the
+// instantiations with CURVES; the queue grab as a lambda doubled its loop.  The RayFrame read as a function (frame_load) changed nothing.
 //
 // The intersection contract is dtrace.h's (same tests, same tie rule), so results are bit-identical to the
 // simple traversal used by the test hooks.
@@ -26,7 +36,6 @@ constexpr uint32_t kPvBatch = PB_BATCH;   // rays grabbed per atomicAdd, at most
 #define PB_BATCH_HEADS 256  // (A/B, eight heads: 64 / 128 / 256 rays: eighth of C2 7.86 / 7.86 / 7.78 ms, frame 46.5 / 45.4 / 44.8; one head with 512: 8.49 / 44.8 -- profiles/README.md)
 #endif
 constexpr uint32_t kPvBatchHeads = PB_BATCH_HEADS;  // ... when the queue has several heads (k_trace)
-constexpr uint32_t kPvHeadStride = 64;  // == kernels.h::kHeadStride: words between two heads (a cache line of its own each)
 #ifndef PB_GUIDE
 #define PB_GUIDE 2
 #endif
@@ -72,39 +81,70 @@ constexpr int kPvRefillIdleCurves = PB_REFILL_CURVES;  // the same for scenes wi
 // or two lanes that happen to finish in an iteration -- the delivery code costs the same however few lanes run it.
 enum : uint32_t { kStIdle = 0, kStNode = 1, kStTri = 2, kStCurve = 3, kStDone = 4, kStDoneOccluded = 5 };
 
-// Sink: what to do with a finished ray.  closest: store the hit record; shadow: resolve the contribution.
+// Sink: where rays come from and what to do with a finished one.  Every sink declares
+//   static constexpr bool kWalk, kSplit, kSuspend           which select its refill (kSplit and kSuspend count only without kWalk)
+// and has
 //   bool load(uint32_t idx, uint32_t& tag, V3& o, V3& d, float& tmin, float& tmax)   returns "any-hit ray"
-//   void done(uint32_t tag, const Hit& h, bool occluded)
-// A WALKING sink (Sink::kWalk, the random walk of subsurface scattering: k_sss_walk) chains rays: its queue entries arrive
+//   void done(uint32_t tag, const Hit& h, bool occluded)                             closest: store the hit record; shadow: resolve the contribution
+// A WALKING sink (kWalk, the random walk of subsurface scattering: k_sss_walk) chains rays: its queue entries arrive
 // with a hit that is already known, and every finished ray is followed by the next one of the same walk:
 //   void start(uint32_t idx, uint32_t& tag, Hit& h, V3& o, V3& d)                     the entry's ray and its known hit
 //   bool next(uint32_t tag, const Hit& h, V3& o, V3& d, float& tmin, float& tmax)     one step; true = trace this ray next
+//   void entry(sc, o, d, inv, tmin, tmax, uint32_t& next, push)                       Q tree: where the ray starts below the root
+// A SPLITTING sink (kSplit) also offers load and done in two halves each: load_entry / load_ray, done_issue (-> Sink::Pending) / done_finish.
 // MODE: 0 = every ray wants its closest hit, 1 = every ray is an any-hit (shadow) ray, 2 = per ray (load()'s
 // return value): closest-hit rays of bounce k+1 and shadow rays of bounce k share one launch and one drain.
-// Traversal stack: the first kPvLdsStack entries of each lane live in LDS (stk_base[i * stride]), deeper ones
-// spill to a per-thread global area (spill[(i - kPvLdsStack) * spill_stride]); keeping the LDS part small is
-// what lets 6 blocks (24 waves) share a CU.
-// a sink with `static constexpr bool kSplit = true` (and no walk) offers done_issue / done_finish / load_entry / load_ray
-template <typename Sink, typename = void>
-struct SinkSplits { static constexpr bool value = false; };
-template <typename Sink>
-struct SinkSplits<Sink, decltype((void)Sink::kSplit)> { static constexpr bool value = Sink::kSplit && !Sink::kWalk; };
-template <typename Sink>
-__device__ constexpr bool sink_splits() { return SinkSplits<Sink>::value; }
-// a sink with `static constexpr bool kSuspend = true` takes part in the suspension of long rays (kernels.h::PathState::susp_turns):
+// A SUSPENDING sink (kSuspend) takes part in the suspension of long rays (kernels.h::PathState::susp_turns):
 //   uint32_t susp_turns();  uint32_t* susp_out();  const uint32_t* susp_in();  static constexpr bool kResumes (its queue can hold suspended rays)
 //   bool suspendable(uint32_t tag)                                   a closest-hit ray whose path can skip a shading round
 //   void suspended(uint32_t tag, uint32_t rec, V3 o, V3 d)           marks the path: its ray's state is record `rec` of susp_out
 //   uint32_t resume_index(uint32_t tag)                              the record of a ray whose load() returned a tag with kTagResume
 // Tag bits of such a sink: kTagShadow (its own), kTagNoSuspend, kTagResume; the low 28 bits are the path slot.
-template <typename Sink, typename = void>
-struct SinkSuspends { static constexpr bool value = false; };
-template <typename Sink>
-struct SinkSuspends<Sink, decltype((void)Sink::kSuspend)> { static constexpr bool value = Sink::kSuspend && !Sink::kWalk; };
-template <typename Sink>
-__device__ constexpr bool sink_suspends() { return SinkSuspends<Sink>::value; }
+// The suspend record of a ray, kSuspWords words (dscene.h): hit t, u, v, slot | cur | state, rem << 8, sp << 16 | 2 unused | the stack.
+// The prefetched item is not kept: the resuming lane fetches it again.
+constexpr int kSuspCur = 4, kSuspMeta = 5, kSuspStack = kSuspHeaderWords;
 constexpr uint32_t kTagShadow = 0x80000000u, kTagNoSuspend = 0x40000000u, kTagResume = 0x20000000u, kTagHeld = 0x10000000u;
-constexpr uint32_t kSuspRecWords = 72;  // == kernels.h::kSuspWords: hit (4 words) | cur, state | rem << 8 | sp << 16, 0, 0 | the stack
+
+// Traversal stack of one lane, and THE rule of where an entry lives: the first LDS entries in LDS (lds[i * stride]), deeper ones
+// in a per-thread global area (spill[(i - LDS) * spill_stride]), none at or past kStackDepth (the overflow flag is raised: the
+// launch's result is discarded).  Keeping the LDS part small is what lets 6 blocks (24 waves) share a CU.
+template <int LDS>
+struct PvStack {
+  uint32_t* lds;
+  uint32_t stride;
+  uint32_t* spill;
+  uint32_t spill_stride;
+  uint32_t* overflow;
+  // index of entry pos in lds / in spill
+  template <typename I>
+  __device__ __forceinline__ uint32_t lds_at(I pos) const { return (uint32_t)pos * stride; }
+  template <typename I>
+  __device__ __forceinline__ uint32_t spill_at(I pos) const { return (uint32_t)(pos - (I)LDS) * spill_stride; }
+  // CHECKED = false: the caller knows that pos < kStackDepth
+  template <bool CHECKED = true, typename I>
+  __device__ __forceinline__ void put(I pos, uint32_t ref) const {
+    if (pos < (I)LDS) lds[lds_at(pos)] = ref;
+    else if (!CHECKED || pos < (I)kStackDepth) spill[spill_at(pos)] = ref;
+    else *overflow = 1u;
+  }
+  template <typename I>
+  __device__ __forceinline__ uint32_t get(I pos) const { return pos < (I)LDS ? lds[lds_at(pos)] : spill[spill_at(pos)]; }
+  __device__ __forceinline__ void push(int& sp, uint32_t ref) const {
+    if (sp < LDS) lds[lds_at(sp)] = ref, sp++;
+    else if (sp < kStackDepth) spill[spill_at(sp)] = ref, sp++;
+    else *overflow = 1u;
+  }
+};
+
+// the ray's RayFrame from LDS (10 words per lane, frame[k * stride]; trace_pv stores it when the ray is fetched)
+__device__ __forceinline__ RayFrame frame_load(const float* frame, uint32_t stride) {
+  RayFrame f;
+  f.dn = V3(frame[0], frame[stride], frame[2 * stride]), f.bx = V3(frame[3 * stride], frame[4 * stride], frame[5 * stride]);
+  f.by = V3(frame[6 * stride], frame[7 * stride], frame[8 * stride]), f.inv_len = frame[9 * stride];
+  return f;
+}
+// bucket of the step histograms (TravStats::hist / ahist): up to 16 steps, then one per doubling
+__device__ __forceinline__ int step_bucket(uint32_t steps) { return steps <= 16u ? 0 : (28 - __clz(steps - 1u) > 7 ? 7 : 28 - __clz(steps - 1u)); }
 
 // WIDE: the Q tree (sc.wide: QNode, dscene.h: four children per 64-byte node with quantised boxes, compact triangle slots,
 // curve leaves as 64-byte records of 16-byte points) instead of the binary one -- half the dependent fetches per ray and half the bytes
@@ -116,14 +156,16 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
                                          uint32_t* overflow, float* frame = nullptr, const float4* top = nullptr,
                                          uint32_t ntop = 0) {
   constexpr uint32_t nheads = NHEADS;
+  constexpr bool kSplits = Sink::kSplit && !Sink::kWalk, kSuspends = Sink::kSuspend && !Sink::kWalk;
   // NHEADS (round 6): the queue [0, n) is cut into nheads equal ranges, head[h] counts inside range h; a wave draws from the head of its
   // block (block b: head b % nheads -- blocks go round the XCDs) and, when that range is dealt, from the next ones.  Why: ONE counter
   // sustains ~88 atomics per microsecond, which is what made the batches 512 rays -- ~0.4 ms of work for one wave -- and the waves that
   // drew their last batch late found the queue empty up to 0.3 ms after the first wave had (per-wave timelines: profiles/README.md);
   // eight counters take eight times the rate, so the batches can be a quarter of that.
-  // top / ntop: LDS copy of nodes 0 .. ntop-1 (the breadth-first top of the tree, 64 bytes each), or none
+  // top / ntop (binary tree): LDS copy of nodes 0 .. ntop-1 (the breadth-first top of the tree, 64 bytes each), or none
   // frame (CURVES): 10 words per lane in LDS (frame[k * stride]), the ray's RayFrame, written when the ray is fetched
   constexpr int kLds = pv_lds_stack<CURVES, WIDE>();  // stack entries of this lane that live in LDS
+  const PvStack<kLds> stk = {stk_base, stride, spill, spill_stride, overflow};
   const uint32_t lane = __lane_id();
   // number of set bits of a wave mask below this lane (v_mbcnt: no per-lane mask has to stay in registers)
   auto rank_in = [](unsigned long long m) {
@@ -188,6 +230,12 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
   const float4* const items = WIDE ? sc.wide : reinterpret_cast<const float4*>(sc.nodes);
   const uint32_t slot0 = sc.num_nodes;  // binary tree: item index of slot 0
 
+  // STATS: the lane's ray is finished (any: as an any-hit ray)
+  auto note_finished = [&](bool any) {
+    const int b = step_bucket(steps);
+    if (any) st.ahist[b]++, st.amax_steps = steps > st.amax_steps ? steps : st.amax_steps;
+    else st.hist[b]++, st.max_steps = steps > st.max_steps ? steps : st.max_steps;
+  };
   unsigned long long t_turn = STATS ? __builtin_readcyclecounter() : 0ull;  // STATS: the turn's cycles go to what it did
   int did = -1;
   uint32_t drain_turns = 0u;  // loop turns since this wave found the queue empty (wave-uniform)
@@ -213,12 +261,13 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
       // ---- refill idle lanes from the queue
       const unsigned long long t_refill = STATS ? wall_clock64() : 0ull;
       did = 3;
+      // ---- refill, queue grab: the wave's next batch when its last one is dealt
       if (!exhausted && batch_cur == batch_end) {
         for (;;) {  // (wave-uniform: the next head when this one's range is dealt)
           // range of head hsel: [hsel * nq, + nq) -- the last one takes the remainder; the head counts inside its range
           const uint32_t nq = n / nheads, lo_h = hsel * nq, len_h = hsel + 1u == nheads ? n - lo_h : nq;
           uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(head + hsel * kPvHeadStride, batch);
+          if (lane == 0) base = atomicAdd(head + hsel * kHeadStride, batch);
           base = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl((int)base, 0));
           if (base < len_h) {  // (a head that has overshot its range keeps growing by what later visitors add: far below 2^32)
             const uint32_t end = (base + batch) < len_h ? base + batch : len_h;
@@ -243,7 +292,8 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
       bool fresh = false;  // the lane has a new ray in (o, d, tmin, hit.t)
       uint32_t taken = 0u;  // queue entries handed out in this refill
       if (WIDE && CURVES && state >= kStDone) hit.slot = q_final_code(sc, hit.slot);  // a curve hit of the Q tree gets its hit code here, with the other lanes' 
-      if constexpr (sink_splits<Sink>()) {
+      // ---- refill, delivery and new rays: split / walking / plain, by the sink
+      if constexpr (kSplits) {
         // A splitting sink hands out its loads first and uses them afterwards: what the delivery of the finished rays needs
         // (done_issue) and the queue entries of the new rays (load_entry) are in flight together, one memory round trip
         // instead of three before the new rays' own loads.
@@ -301,6 +351,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
       }
       taken = take;
       }
+      // ---- refill, start of a new ray: reciprocals and frame; resume, or root / walk entry
       if (fresh) {
         inv = V3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
         if (WIDE) inv4 = make_float4(inv.x, inv.y, inv.z, 0.f);
@@ -311,21 +362,17 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           for (int k = 0; k < 10; k++) frame[(uint32_t)k * stride] = w[k];
         }
         bool resumed = false;
-        if constexpr (sink_suspends<Sink>()) resumed = Sink::kResumes && (tag & kTagResume) != 0u;
+        if constexpr (kSuspends) resumed = Sink::kResumes && (tag & kTagResume) != 0u;
         if (resumed) {
           // a ray suspended by the previous launch: it goes on where it stopped (its item is fetched again at the load site below)
-          if constexpr (sink_suspends<Sink>()) {
+          if constexpr (kSuspends) {
             tag &= ~kTagResume;
-            const uint32_t* rec = sink.susp_in() + (size_t)sink.resume_index(tag) * kSuspRecWords;
+            const uint32_t* rec = sink.susp_in() + (size_t)sink.resume_index(tag) * kSuspWords;
             hit.t = __uint_as_float(rec[0]), hit.u = __uint_as_float(rec[1]), hit.v = __uint_as_float(rec[2]), hit.slot = rec[3];
-            cur = rec[4];
-            const uint32_t meta = rec[5];
+            cur = rec[kSuspCur];
+            const uint32_t meta = rec[kSuspMeta];
             state = meta & 255u, rem = (meta >> 8) & 255u, sp = (int)(meta >> 16);
-            for (int i = 0; i < sp; i++) {
-              const uint32_t v = rec[8 + i];
-              if (i < kLds) stk_base[(uint32_t)i * stride] = v;
-              else spill[(uint32_t)(i - kLds) * spill_stride] = v;
-            }
+            for (int i = 0; i < sp; i++) stk.template put<false>(i, rec[kSuspStack + i]);  // (sp <= kStackDepth when it was stored)
             steps = 0, need_load = true;
           }
         } else {
@@ -335,6 +382,8 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           if constexpr (Sink::kWalk && WIDE) {
             // a random walk's ray starts below the root where its instance has an entry (dscene.h::SssEntry): `next` becomes the entry node
             // and the foreign references the ray's interval meets go on the stack
+            // (written out, not stk.put, not even stk.lds_at / spill_at: with either the refill of both Q-tree k_sss_walk comes out six to
+            // eight instructions longer; the stack is empty here and an entry has at most kSssMaxForeign foreign references, so no depth check)
             sink.entry(sc, o, d, inv, tmin, hit.t, next, [&](uint32_t ref) {
               if (sp < kLds) stk_base[(uint32_t)sp * stride] = ref;
               else spill[(uint32_t)(sp - kLds) * spill_stride] = ref;
@@ -350,8 +399,9 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
         if (lane == 0) st.it_refill++, st.refill_ticks += (uint32_t)(wall_clock64() - t_refill);
       }
     } else {
+      // ---- drain check
       if (n_idle == 64) break;  // queue exhausted and every lane done
-      if constexpr (sink_suspends<Sink>()) {
+      if constexpr (kSuspends) {
         // The drain: the queue is empty, this wave's last rays are finishing one by one and the chip runs nearly empty while they
         // do.  After susp_turns more turns the wave stops as soon as every ray it still traces can be suspended (closest-hit rays:
         // below); the launch that follows takes them up again in its bulk phase.
@@ -364,7 +414,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
       unsigned long long tri_mask = __ballot(state == kStTri);
       int n_node = __popcll(node_mask), n_tri = __popcll(tri_mask);
       int n_curve = CURVES ? __popcll(__ballot(state == kStCurve)) : 0;
-      // vote: the phase that advances the most lanes per instruction issued (a node step is cheaper than a primitive step)
+      // ---- vote: the phase that advances the most lanes per instruction issued (a node step is cheaper than a primitive step)
       const int w_node = n_node * PB_W_NODE, w_tri = n_tri * PB_W_TRI, w_curve = n_curve * PB_W_CURVE;
       const int phase = (w_node >= w_tri && w_node >= w_curve) ? 0 : ((!CURVES || w_tri >= w_curve) ? 1 : 2);
       did = phase;
@@ -374,25 +424,9 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
         else st.it_curve++, st.ln_curve += n_curve;
       }
       if (phase == 0) {
-        // ---- NODE phase
+        // ---- NODE turn: wide, else binary
         if (WIDE && state == kStNode) {
           if (STATS) (any_ray ? st.anodes : st.nodes)++, steps++;
-#ifdef PB_DIAG_EXTRA_VALU  // diagnostic build: PB_DIAG_EXTRA_VALU dependent fma more per node turn (is the kernel bound by its VALU instructions?)
-          {
-            float x = D0.x;
-#pragma unroll
-            for (int k2 = 0; k2 < PB_DIAG_EXTRA_VALU; k2++) asm volatile("v_fma_f32 %0, %0, %0, %1" : "+v"(x) : "v"(D0.y));
-            if (x == 1.2345e-30f) tmin = x;
-          }
-#endif
-#ifdef PB_DIAG_EXTRA_LOAD  // diagnostic build: one more 16-byte load per lane and node turn (the node's own first word: an L1 hit)
-          {
-            const float4* qd = items + cur;
-            asm volatile("" : "+v"(qd));
-            const float4 x = *qd;
-            if (x.x == 1.2345e-30f) tmin = x.y;
-          }
-#endif
           uint32_t k[4];
           wide_node_keys(D0, D1, D2, D3w, o, inv4, tmin, hit.t, k);
           auto ref_of = [&](uint32_t key) { return wide_ref(D3w, key); };
@@ -404,27 +438,16 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
             if (sp + 3 <= kLds) {
               // (an entry written for a child that was not hit lies above the new top or is overwritten by the next one)
               uint32_t p = (uint32_t)sp;
-              stk_base[p * stride] = ref_of(k[3]);
+              stk.lds[stk.lds_at(p)] = ref_of(k[3]);
               p += (k[3] != kWideMiss) ? 1u : 0u;
-              stk_base[p * stride] = ref_of(k[2]);
+              stk.lds[stk.lds_at(p)] = ref_of(k[2]);
               p += (k[2] != kWideMiss) ? 1u : 0u;
-              stk_base[p * stride] = ref_of(k[1]);
+              stk.lds[stk.lds_at(p)] = ref_of(k[1]);
               sp = (int)p + 1;
             } else {
 #pragma unroll
-              for (int j = 3; j >= 1; j--) {
-                if (k[j] == kWideMiss) continue;
-                const uint32_t farc = ref_of(k[j]);
-                if (sp < kLds) {
-                  stk_base[(uint32_t)sp * stride] = farc;
-                  sp++;
-                } else if (sp < kStackDepth) {
-                  spill[(uint32_t)(sp - kLds) * spill_stride] = farc;
-                  sp++;
-                } else {
-                  *overflow = 1u;
-                }
-              }
+              for (int j = 3; j >= 1; j--)
+                if (k[j] != kWideMiss) stk.push(sp, ref_of(k[j]));
             }
           } else if (k[1] != kWideMiss) {
             const uint32_t r3 = ref_of(k[3]), r2 = ref_of(k[2]), r1 = ref_of(k[1]);
@@ -433,19 +456,14 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
             // every node turn (hair: trees 14-16 levels deep, up to three entries per level)
             if (__ballot(p1 >= (uint32_t)kLds) == 0ull) {
               // (an entry written for a child that was not hit lies above the new top or is overwritten by the next one)
-              stk_base[p3 * stride] = r3;
-              stk_base[p2 * stride] = r2;
-              stk_base[p1 * stride] = r1;
+              stk.lds[stk.lds_at(p3)] = r3;
+              stk.lds[stk.lds_at(p2)] = r2;
+              stk.lds[stk.lds_at(p1)] = r1;
               sp = (int)p1 + 1;
             } else {
-              auto put = [&](uint32_t pos, uint32_t ref) {
-                if (pos < (uint32_t)kLds) stk_base[pos * stride] = ref;
-                else if (pos < (uint32_t)kStackDepth) spill[(pos - (uint32_t)kLds) * spill_stride] = ref;
-                else *overflow = 1u;
-              };
-              if (k[3] != kWideMiss) put(p3, r3);
-              if (k[2] != kWideMiss) put(p2, r2);
-              put(p1, r1);
+              if (k[3] != kWideMiss) stk.put(p3, r3);
+              if (k[2] != kWideMiss) stk.put(p2, r2);
+              stk.put(p1, r1);
               sp = (int)(p1 + 1u < (uint32_t)kStackDepth ? p1 + 1u : (uint32_t)kStackDepth);
             }
           }
@@ -460,20 +478,10 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           advance = true;
           have_next = h0 || h1;
           next = nearc;
-          if (h0 && h1) {
-            if (sp < kLds) {
-              stk_base[(uint32_t)sp * stride] = farc;
-              sp++;
-            } else if (sp < kStackDepth) {
-              spill[(uint32_t)(sp - kLds) * spill_stride] = farc;
-              sp++;
-            } else {
-              *overflow = 1u;
-            }
-          }
+          if (h0 && h1) stk.push(sp, farc);
         }
       } else {
-        // ---- TRI / CURVE phase: one primitive per lane
+        // ---- TRI / CURVE turn (one primitive per lane): TriPair, else curve record, else slot
         const bool is_tri = state == kStTri, is_curve = CURVES && state == kStCurve;
         const bool mine = (phase == 1) ? is_tri : is_curve;
         if (WIDE && !CURVES && mine) {
@@ -484,7 +492,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           if (STATS) (any_ray ? st.atris : st.tris) += nt;
           if (occ) {
             state = kStDoneOccluded;
-            if (STATS) st.ahist[steps <= 16u ? 0 : (28 - __clz(steps - 1u) > 7 ? 7 : 28 - __clz(steps - 1u))]++, st.amax_steps = steps > st.amax_steps ? steps : st.amax_steps;
+            if (STATS) note_finished(true);
           } else {
             advance = true;  // leaf done: pop
           }
@@ -493,9 +501,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           // (D2, D3w) (rem & kCurvePairBit: a second piece; the pieces' indices in their cubics are the low bits of cur and of rem).
           // Both pieces in this one turn (88-91 registers: five blocks per CU; one piece per turn: 4-7 % slower, profiles/README.md).
           const bool two = (rem & kCurvePairBit) != 0u;
-          RayFrame f;
-          f.dn = V3(frame[0], frame[stride], frame[2 * stride]), f.bx = V3(frame[3 * stride], frame[4 * stride], frame[5 * stride]);
-          f.by = V3(frame[6 * stride], frame[7 * stride], frame[8 * stride]), f.inv_len = frame[9 * stride];
+          const RayFrame f = frame_load(frame, stride);
           const V3 i3(inv4.x, inv4.y, inv4.z);
           const uint32_t pt = (cur & ~3u) - sc.q_pt0;  // point index of the first piece
           bool occ = false;
@@ -521,7 +527,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           }
           if (occ) {
             state = kStDoneOccluded;
-            if (STATS) st.ahist[steps <= 16u ? 0 : (28 - __clz(steps - 1u) > 7 ? 7 : 28 - __clz(steps - 1u))]++, st.amax_steps = steps > st.amax_steps ? steps : st.amax_steps;
+            if (STATS) note_finished(true);
           } else {
             advance = true;  // leaf done: pop
           }
@@ -534,9 +540,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
             ok = tri_test(ld3(D0), ld3(D1), ld3(D2), o, d, WIDE ? V3(inv4.x, inv4.y, inv4.z) : inv, tmin, t, u, v) && (t <= hit.t);
           } else {
             if (STATS) (any_ray ? st.acurves : st.curves)++;
-            RayFrame f;
-            f.dn = V3(frame[0], frame[stride], frame[2 * stride]), f.bx = V3(frame[3 * stride], frame[4 * stride], frame[5 * stride]);
-            f.by = V3(frame[6 * stride], frame[7 * stride], frame[8 * stride]), f.inv_len = frame[9 * stride];
+            const RayFrame f = frame_load(frame, stride);
             // (a 64-byte curve slot of the binary tree: its piece index in its cubic in D2.x; the Q tree's curve records are tested above)
             ok = segment_test(D0, D1, __float_as_uint(D2.x), o, f, WIDE ? V3(inv4.x, inv4.y, inv4.z) : inv, tmin, hit.t, t, u, v);
           }
@@ -549,7 +553,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
           }
           if (any_ray && ok) {
             state = kStDoneOccluded;
-            if (STATS) st.ahist[steps <= 16u ? 0 : (28 - __clz(steps - 1u) > 7 ? 7 : 28 - __clz(steps - 1u))]++, st.amax_steps = steps > st.amax_steps ? steps : st.amax_steps;
+            if (STATS) note_finished(true);
           } else if (rem != 0u) {  // next primitive of the same leaf
             rem--, cur += WIDE ? 3u : 1u;
             need_load = true;
@@ -565,17 +569,13 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
         if (sp == 0) {
           state = kStDone;
           advance = false;
-          if (STATS) {
-            const int b = steps <= 16u ? 0 : (28 - __clz(steps - 1u) > 7 ? 7 : 28 - __clz(steps - 1u));
-            if (any_ray) st.ahist[b]++, st.amax_steps = steps > st.amax_steps ? steps : st.amax_steps;
-            else st.hist[b]++, st.max_steps = steps > st.max_steps ? steps : st.max_steps;
-          }
+          if (STATS) note_finished(any_ray);
         } else {
           sp--;
           // the LDS read is unconditional (a clamped index), the spill read the rare exception: one ds_read instead of a
           // flat load behind an address select
-          next = stk_base[(uint32_t)(sp < kLds ? sp : kLds - 1) * stride];
-          if (sp >= kLds) next = spill[(uint32_t)(sp - kLds) * spill_stride];
+          next = stk.lds[stk.lds_at(sp < kLds ? sp : kLds - 1)];
+          if (sp >= kLds) next = stk.spill[stk.spill_at(sp)];
         }
       }
       if (advance) {
@@ -593,19 +593,15 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
         }
       }
     }
+    // ---- the load site
     if (WIDE && need_load) {
-      if (!CURVES && kTopNodesWide > 0 && cur < 4u * ntop) {  // the top of the Q tree (triangle-only scenes): every ray passes through it
-        const float4* g = top + cur;
-        D0 = g[0], D1 = g[1], D2 = g[2], D3w = g[3];
-      } else {
-        // (a curve record: four words; the low bits of its address carry a piece index)
-        const bool at_rec = CURVES && state == kStCurve;
-        const float4* g = items + (at_rec ? (cur & ~3u) : cur);
-        D0 = g[0], D1 = g[1];
-        if (!CURVES || state != kStCurve || at_rec) D2 = g[2];
-        if (!CURVES || state == kStNode || at_rec) D3w = g[3];
-        if (!CURVES && state == kStTri) D4 = g[4];
-      }
+      // (a curve record: four words; the low bits of its address carry a piece index)
+      const bool at_rec = CURVES && state == kStCurve;
+      const float4* g = items + (at_rec ? (cur & ~3u) : cur);
+      D0 = g[0], D1 = g[1];
+      if (!CURVES || state != kStCurve || at_rec) D2 = g[2];
+      if (!CURVES || state == kStNode || at_rec) D3w = g[3];
+      if (!CURVES && state == kStTri) D4 = g[4];
     } else if (need_load) {
       if (kTopNodes > 0 && cur < ntop) {  // the top of the tree: every ray passes through it
         const float4* g = top + cur * 4u;
@@ -618,23 +614,24 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
       }
     }
   }
+  // ---- after the loop: leftover deliveries, then the suspension
   if constexpr (!Sink::kWalk) {
     if (state >= kStDone) {  // rays that finished after the queue ran dry
       if (WIDE && CURVES) hit.slot = q_final_code(sc, hit.slot);
       sink.done(tag, hit, state == kStDoneOccluded);
     }
   }
-  if constexpr (sink_suspends<Sink>()) {
+  if constexpr (kSuspends) {
     // SUSPEND what is still being traced (the wave left its loop at the end of the drain): the stack, the current item and the hit
     // held so far go to the lane's record (one per resident thread: no counter), the path is marked (sink.suspended: its hit code
     // becomes kHitSuspended) and the ray goes on -- from this very point, so its hit is what it would have been -- in the next
     // iteration's launch.  The prefetched item is not kept (the resuming lane fetches it again), so this costs the loop no register.
     if (state >= kStNode && state <= kStCurve) {
       const uint32_t j = wave_id * 64u + __lane_id();
-      uint32_t* rec = sink.susp_out() + (size_t)j * kSuspRecWords;
+      uint32_t* rec = sink.susp_out() + (size_t)j * kSuspWords;
       rec[0] = __float_as_uint(hit.t), rec[1] = __float_as_uint(hit.u), rec[2] = __float_as_uint(hit.v), rec[3] = hit.slot;
-      rec[4] = cur, rec[5] = state | (rem << 8) | ((uint32_t)sp << 16);
-      for (int i = 0; i < sp; i++) rec[8 + i] = i < kLds ? stk_base[(uint32_t)i * stride] : spill[(uint32_t)(i - kLds) * spill_stride];
+      rec[kSuspCur] = cur, rec[kSuspMeta] = state | (rem << 8) | ((uint32_t)sp << 16);
+      for (int i = 0; i < sp; i++) rec[kSuspStack + i] = stk.get(i);
       sink.suspended(tag, j, o, d);
       if (STATS) (any_ray ? st.suspended_any : st.suspended)++;
     }

@@ -88,8 +88,6 @@ struct PathState {
   PathView<uint4, 4> rng4;         // rec + 3 as one 16-byte word: generator state (x, y) | hold (z) | -
   PathView<uint32_t, 16> hold;     // rec + 3, third word: 1 while the path's shadow ray is suspended -- the path's next shading waits for it (above)
 };
-constexpr uint32_t kSuspWords = 72;  // hit (4) | cur, state | rem << 8 | sp << 16, -, - (4) | stack (kStackDepth = 64)
-static_assert(kStackDepth <= 64, "a suspend record holds the whole traversal stack");
 
 enum : uint32_t { kFlagNotFirst = 1u };
 // queue entry = path slot | in-medium bit | "the Russian roulette at the head of this path's next shading fails" bit
@@ -175,7 +173,6 @@ constexpr int kMaxGroups = 8;
 #define PB_TRACE_HEADS 8
 #endif
 constexpr uint32_t kTraceHeads = PB_TRACE_HEADS;  // heads of k_trace's ray queue: one per XCD (block b draws from head b % 8 first)
-constexpr uint32_t kHeadStride = 64;  // words between two heads: each in a 256-byte block of its own (atomics on one cache line serialise: eight heads in ONE line were twice as slow as one head)
 constexpr uint32_t kRingSlots = 16;  // iterations of one group the host may have enqueued and not yet heard of
 constexpr uint32_t kWaveLogWaves = 8192, kWaveLogLaunches = 64;  // PBRHIP_WAVE_LOG buffer: launches x waves x 4 words  // concurrent path groups (one HIP stream each)
 

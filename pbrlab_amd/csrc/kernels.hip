@@ -322,13 +322,12 @@ template <bool STATS, bool CURVES, bool WIDE = false, bool FIRST = false>
 __global__ __launch_bounds__(kBlock, trace_blocks_per_cu(CURVES, WIDE) - (FIRST ? trace_first_less(STATS, CURVES) : 0u)) void k_trace(PathState P, DScene sc) {
   __shared__ uint32_t stk[pv_lds_stack<CURVES, WIDE>() * kBlock];
   __shared__ float frm[CURVES ? 10 * kBlock : 1];
-  // the top of the tree in LDS (triangle-only scenes: with the ribbon frames of curve scenes it would cost a block per CU)
-  constexpr int kTopHere = WIDE ? kTopNodesWide : kTopNodes;
-  constexpr bool kStageTop = !CURVES && kTopHere > 0;
-  __shared__ float4 top[kStageTop ? kTopHere * 4 : 1];
-  const uint32_t ntop = kStageTop ? (WIDE ? (sc.wide_top_nodes < (uint32_t)kTopHere ? sc.wide_top_nodes : (uint32_t)kTopHere) : sc.top_nodes) : 0u;
+  // the top of the binary tree in LDS (triangle-only scenes: with the ribbon frames of curve scenes it would cost a block per CU)
+  constexpr bool kStageTop = !CURVES && !WIDE && kTopNodes > 0;
+  __shared__ float4 top[kStageTop ? kTopNodes * 4 : 1];
+  const uint32_t ntop = kStageTop ? sc.top_nodes : 0u;
   if (kStageTop) {
-    const float4* src = WIDE ? sc.wide : reinterpret_cast<const float4*>(sc.nodes);  // (binary node and Q node: 64 bytes each)
+    const float4* src = reinterpret_cast<const float4*>(sc.nodes);
     for (uint32_t i = threadIdx.x; i < ntop * 4u; i += kBlock) top[i] = src[i];
     __syncthreads();
   }
@@ -1293,7 +1292,7 @@ __global__ __launch_bounds__(kBlock) void k_sss_step(PathState P, DScene sc, uin
 constexpr uint32_t kWalkCap = PB_WALK_CAP;
 constexpr uint32_t kWalkWords = 22;  // words of walk state per lane in LDS (WalkSink)
 struct WalkSink {
-  static constexpr bool kWalk = true;
+  static constexpr bool kWalk = true, kSplit = false, kSuspend = false;
   const PathState& P;
   uint64_t rng_inc;
   // What a walk carries besides its ray (which the traversal holds in registers anyway) lives in LDS, kWalkWords words per
@@ -1770,7 +1769,7 @@ __device__ __forceinline__ HookHit hook_result(const DScene& sc, V3 o, V3 d, con
   return r;
 }
 struct HookSink {
-  static constexpr bool kWalk = false;
+  static constexpr bool kWalk = false, kSplit = false, kSuspend = false;
   const DScene& sc;
   const float4* rays;
   HookHit* hits;
