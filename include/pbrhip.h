@@ -232,6 +232,26 @@ int pbrhip_scene_update_triangle_mesh(pbrhip_scene*, uint32_t mesh_id, const flo
 int pbrhip_scene_update_curve_mesh(pbrhip_scene*, uint32_t mesh_id, const float* vertices_xyzr, uint32_t num_vertices);
 int pbrhip_scene_update_instance_transform(pbrhip_scene*, uint32_t instance_id, const float* transform4x4);
 int pbrhip_scene_refit(pbrhip_scene*);
+/* The same mesh edits from DEVICE memory, for a simulation that holds its vertices on the scene's GPU (a torch tensor's data_ptr()):
+ * d_vertices_xyzw / d_normals_xyzw / d_vertices_xyzr are device pointers of the scene's device (anything else, host memory included:
+ * PBRHIP_EINVAL), 16-byte aligned; `stream` is the caller's hipStream_t (NULL: the null stream).  The library reads the arrays only
+ * after the work already enqueued on that stream (an event and a stream wait, no device-wide synchronise), checks them for non-finite
+ * values on the device, and holds its own copy when the call returns: the caller may overwrite the buffer.  Counts, refusals and their
+ * codes are the host calls'; after a refusal nothing has changed.  The host model receives the values inside the call (a download), so
+ * pbrhip_scene_commit, the light tables and the host calls keep working.  Before the first commit the call only edits the model.
+ * The first successful call on a committed scene switches the scene to DEVICE GEOMETRY MODE until the next commit: every mesh's
+ * position, normal and index arrays are uploaded once, the host update calls refresh that copy as well, and pbrhip_scene_refit
+ * re-derives the dirty instances' slots, ShadeRecs and bounds on the device from it ("Staging on the device")
+ * instead of staging them on the host -- with the same functions, so the refitted scene is the same, bit for bit.  (One freedom: a
+ * scene bound taken over both +0 and -0 is -0 as a minimum and +0 as a maximum; the host's chain of fminf gives either.)  A scene that
+ * never makes these calls allocates nothing for them. */
+int pbrhip_scene_update_triangle_mesh_device(pbrhip_scene*, uint32_t mesh_id, const void* d_vertices_xyzw, uint32_t num_vertices,
+                                             const void* d_normals_xyzw, uint32_t num_normals, void* stream);
+int pbrhip_scene_update_curve_mesh_device(pbrhip_scene*, uint32_t mesh_id, const void* d_vertices_xyzr, uint32_t num_vertices, void* stream);
+/* A test hook: the committed scene's slots (64 bytes each, leaf order) and ShadeRecs (128 bytes each) as the device holds them, so that
+ * a stale word no ray happens to see can still be found.  num_slots receives the count; with both output pointers NULL nothing else
+ * happens.  Uncommitted or stale scene: PBRHIP_ESTATE. */
+int pbrhip_scene_read_slots(pbrhip_scene*, void* slots_out, void* shade_out, uint32_t* num_slots);
 /* A lat-long environment light: rgb = width x height x 3 floats, row 0 = the top (+y up; a ray along -z sees the
  * middle of the map), nearest-sampled, times `scale`.  world_to_env: a 3x3 rotation, row-major, applied to world directions before
  * the lookup (NULL: identity).  A ray that leaves the scene collects it (with MIS), and NEE samples it by luminance x solid angle.

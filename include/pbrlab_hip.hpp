@@ -368,6 +368,16 @@ public:
   void UpdateInstanceTransform(const uint32_t instance_id, const float transform[4][4]) {
     Check(pbrhip_scene_update_instance_transform(h_, instance_id, &transform[0][0]));
   }
+  // The same edits from device memory of the scene's GPU (pbrhip_scene_update_*_mesh_device): `count` 16-byte elements at each pointer
+  // (d_normals_xyzw null: kept), read after the work already enqueued on `stream` (a hipStream_t; null: the null stream).  The library has
+  // its own copy when the call returns; from the first such call on a committed scene RefitScene() stages on the GPU as well.
+  void UpdateTriangleMeshDevice(const MeshPtr& mesh_ptr, const void* d_vertices_xyzw, uint32_t num_vertices, const void* d_normals_xyzw = nullptr,
+                                uint32_t num_normals = 0, void* stream = nullptr) {
+    Check(pbrhip_scene_update_triangle_mesh_device(h_, LibraryMeshId(mesh_ptr), d_vertices_xyzw, num_vertices, d_normals_xyzw, num_normals, stream));
+  }
+  void UpdateCurveMeshDevice(const MeshPtr& mesh_ptr, const void* d_vertices_xyzr, uint32_t num_vertices, void* stream = nullptr) {
+    Check(pbrhip_scene_update_curve_mesh_device(h_, LibraryMeshId(mesh_ptr), d_vertices_xyzr, num_vertices, stream));
+  }
   void RefitScene() { Check(pbrhip_scene_refit(h_)); }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };

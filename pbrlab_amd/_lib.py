@@ -27,6 +27,7 @@ EXPORTS = [
     "pbrhip_lbvh_build", "pbrhip_scene_wide_info", "pbrhip_qtree_collapse",
     "pbrhip_scene_update_triangle_mesh", "pbrhip_scene_update_curve_mesh", "pbrhip_scene_update_instance_transform", "pbrhip_scene_refit",
     "pbrhip_tree_refit",
+    "pbrhip_scene_update_triangle_mesh_device", "pbrhip_scene_update_curve_mesh_device", "pbrhip_scene_read_slots",
 ]
 
 
@@ -63,6 +64,9 @@ def lib():
         _lib.pbrhip_scene_update_curve_mesh.argtypes = [vp, u32, vp, u32]
         _lib.pbrhip_scene_update_instance_transform.argtypes = [vp, u32, vp]
         _lib.pbrhip_scene_refit.argtypes = [vp]
+        _lib.pbrhip_scene_update_triangle_mesh_device.argtypes = [vp, u32, vp, u32, vp, u32, vp]
+        _lib.pbrhip_scene_update_curve_mesh_device.argtypes = [vp, u32, vp, u32, vp]
+        _lib.pbrhip_scene_read_slots.argtypes = [vp, vp, vp, vp]
         _lib.pbrhip_tree_refit.argtypes = [C.c_int, u32, vp, vp, vp, u32, vp, u32, C.c_int, vp, vp, u32]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()

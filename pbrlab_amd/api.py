@@ -85,6 +85,45 @@ def _ptr(a, t=fp):
     return None if a is None else a.ctypes.data_as(t)
 
 
+def _device_array(a, scene):
+    """An argument of the *Device update calls -> (pointer, count): None, a (pointer, count) pair, or an object with data_ptr() as a
+    torch tensor has -- float32, contiguous, (n, 4), on the scene's device, else TypeError / ValueError here, before any C call."""
+    if a is None:
+        return None, 0
+    if isinstance(a, (tuple, list)):
+        if len(a) != 2:
+            raise TypeError("a device array is a tensor or a (pointer, count) pair")
+        return C.c_void_p(None if a[0] is None else int(a[0])), int(a[1])
+    if not hasattr(a, "data_ptr"):
+        raise TypeError(f"{type(a).__name__} is no device array: pass a tensor on the scene's device (data_ptr()) or a (pointer, count) pair")
+    if not str(getattr(a, "dtype", "")).endswith("float32"):
+        raise TypeError(f"a device array must be float32, not {getattr(a, 'dtype', None)}")
+    shape = tuple(getattr(a, "shape", ()))
+    if len(shape) != 2 or shape[1] != 4:
+        raise ValueError(f"a device array must have the shape (n, 4), not {shape}")
+    if not a.is_contiguous():
+        raise ValueError("a device array must be contiguous")
+    dev = getattr(a, "device", None)
+    if getattr(dev, "type", None) != "cuda":
+        raise ValueError(f"a device array must be in GPU memory, not on {dev}")
+    want = getattr(scene, "device", None)
+    if want is not None and dev.index is not None and dev.index != want:
+        raise ValueError(f"the array is on device {dev.index}, the scene on device {want}")
+    return C.c_void_p(int(a.data_ptr())), int(shape[0])
+
+
+def _device_stream(stream, *arrays):
+    """The hipStream_t of a *Device update call: as given (an integer, or an object with cuda_stream); None: torch's current stream when
+    an argument is a tensor (torch is then the caller's: this module does not import it otherwise), else the null stream."""
+    if stream is None:
+        if any(type(a).__module__.partition(".")[0] == "torch" for a in arrays):
+            import torch
+            stream = torch.cuda.current_stream()
+        else:
+            return None
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
 def _fill(struct, d):
     for k, _ in struct._fields_:
         v = d[k]
@@ -244,6 +283,7 @@ class Scene:
         h = C.c_void_p()
         _chk(self.L.pbrhip_scene_create(C.byref(h)))
         self.h = h
+        self.device = _device
 
     def close(self):
         if getattr(self, "h", None):
@@ -314,6 +354,29 @@ class Scene:
         """pbrhip_scene_update_instance_transform: a new 4x4 transform of an instance (None: identity), as CreateInstance takes it"""
         t = None if transform is None else np.ascontiguousarray(transform, np.float32).reshape(16)
         _chk(self.L.pbrhip_scene_update_instance_transform(self.h, instance_id, None if t is None else t.ctypes.data))
+
+    def UpdateTriangleMeshDevice(self, mesh_id, vertices, normals=None, stream=None):
+        """pbrhip_scene_update_triangle_mesh_device: UpdateTriangleMesh from device memory of the scene's GPU.  vertices / normals: a
+        float32, contiguous (n, 4) tensor on that device (anything with data_ptr(), as a torch tensor has), or a (pointer, count) pair;
+        normals None: kept.  stream: the hipStream_t the arrays are produced on (None: with tensors torch's current stream, else the
+        null stream); they are read after the work already enqueued there, and the library has its own copy when the call returns.
+        From the first such call on a committed scene RefitScene stages on the GPU as well."""
+        (vp, vn), (np_, nn), stream = _device_array(vertices, self), _device_array(normals, self), _device_stream(stream, vertices, normals)
+        _chk(self.L.pbrhip_scene_update_triangle_mesh_device(self.h, mesh_id, vp, vn, np_, nn, stream))
+
+    def UpdateCurveMeshDevice(self, mesh_id, vertices_xyzr, stream=None):
+        """pbrhip_scene_update_curve_mesh_device: UpdateCurveMesh from device memory; arguments as UpdateTriangleMeshDevice's"""
+        (vp, vn), stream = _device_array(vertices_xyzr, self), _device_stream(stream, vertices_xyzr)
+        _chk(self.L.pbrhip_scene_update_curve_mesh_device(self.h, mesh_id, vp, vn, stream))
+
+    def read_slots(self):
+        """pbrhip_scene_read_slots, a test hook: the committed scene's slots (n, 4, 4) float32 in leaf order and its ShadeRecs (n, 32)
+        uint32 as the device holds them"""
+        n = C.c_uint32()
+        _chk(self.L.pbrhip_scene_read_slots(self.h, None, None, C.byref(n)))
+        slots, shade = np.zeros((n.value, 4, 4), np.float32), np.zeros((n.value, 32), np.uint32)
+        _chk(self.L.pbrhip_scene_read_slots(self.h, slots.ctypes.data, shade.ctypes.data, C.byref(n)))
+        return slots, shade
 
     def RefitScene(self):
         """pbrhip_scene_refit: the committed trees refitted on the GPU to the edited geometry; afterwards every observable equals that of
@@ -577,6 +640,7 @@ def replicate(scene, device):
     h = C.c_void_p()
     _chk(out.L.pbrhip_scene_replicate(scene.h, int(device), C.byref(h)))
     out.h = h
+    out.device = int(device)
     return out
 
 

@@ -1,5 +1,6 @@
 // commit.cpp -- from the host model to the device scene: the staging helpers (light tables, primitive boxes, slots and
-// ShadeRecs, materials), pbrhip_scene_commit, pbrhip_scene_refit and the device write of a material edit.  Host C++ only.
+// ShadeRecs, materials), pbrhip_scene_commit, pbrhip_scene_refit with its two ways of staging (on the host, or -- device geometry mode,
+// geom_gpu.h -- on the device), the host side of that mode and the device write of a material edit.  Host C++ only.
 #include <math.h>
 #include <string.h>
 
@@ -7,6 +8,7 @@
 #include <limits>
 #include <numeric>
 
+#include "geom_math.h"
 #include "scene_impl.h"
 
 using namespace pb;
@@ -17,12 +19,6 @@ static_assert(sizeof(LightRec) == 80, "light record layout");
 static V3 mesh_vertex(const HostMesh& m, uint32_t prim, int k) {
   const float* p = m.vertices.data() + (size_t)m.vid[prim * 3 + k] * 4;
   return V3(p[0], p[1], p[2]);
-}
-// What the raytracer sees of an instance (raytracer_impl.cc:61-81: the transform goes to Embree and nowhere else):
-// v' = v * M with the translation row, in this order of operations (the checker uses the same expression).
-static V3 xf_point(const float* m, V3 v) {
-  return V3(m[0] * v.x + m[4] * v.y + m[8] * v.z + m[12], m[1] * v.x + m[5] * v.y + m[9] * v.z + m[13],
-            m[2] * v.x + m[6] * v.y + m[10] * v.z + m[14]);
 }
 static V3 world_vertex(const HostInstance& in, const HostMesh& m, uint32_t prim, int k) {
   const V3 v = mesh_vertex(m, prim, k);
@@ -115,17 +111,6 @@ static Material make_material(const HostMaterial& hm) {
   return m;
 }
 
-// End points of linear piece `sub` of a cubic Bezier (control points xyzr): B(sub/4) and B((sub+1)/4), evaluated with
-// the arithmetic of the intersection contract (Bernstein weights, products summed left to right, single precision,
-// no contraction) so that every back end tests the same segment.
-static void curve_piece(const float* cp, uint32_t sub, float a[4], float b[4]) {
-  for (uint32_t e = 0; e < 2; e++) {
-    const float u = (float)(sub + e) * 0.25f, s = 1.0f - u;
-    const float b0 = s * s * s, b1 = 3.0f * u * s * s, b2 = 3.0f * u * u * s, b3 = u * u * u;
-    for (int k = 0; k < 4; k++) (e ? b : a)[k] = ((cp[k] * b0 + cp[4 + k] * b1) + cp[8 + k] * b2) + cp[12 + k] * b3;
-  }
-}
-
 // Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.
 static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
   for (uint32_t i = 0; i < s->instances.size(); i++)
@@ -144,44 +129,53 @@ static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
 // scene's box -- larger than the box of the transformed geometry under rotation or shear; an instance whose matrix is
 // bit for bit the identity reports the local box.  Local box: triangles by their corners, curves by the hull of their
 // control points widened by the largest control radius.  (The tree is built over the transformed primitives.)
+// (the LOCAL box of instance i into ll / lh; false: it has no primitive)
+static bool instance_local_box(const pbrhip_scene* s, uint32_t i, float ll[3], float lh[3]) {
+  const float inf = std::numeric_limits<float>::infinity();
+  const HostInstance& inst = s->instances[i];
+  for (int k = 0; k < 3; k++) ll[k] = inf, lh[k] = -inf;
+  bool any = false;
+  for (uint32_t g = 0; g < inst.material_ids.size(); g++) {
+    const HostMesh& m = *inst_mesh(s, i, g);
+    for (uint32_t p = 0; p < m.num_prims(); p++) {
+      any = true;
+      if (m.kind == 0) {
+        for (int c = 0; c < 3; c++) {
+          const V3 v = mesh_vertex(m, p, c);
+          const float a[3] = {v.x, v.y, v.z};
+          for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], a[k]), lh[k] = fmaxf(lh[k], a[k]);
+        }
+      } else {
+        float r = 0.f, cl[3] = {inf, inf, inf}, ch[3] = {-inf, -inf, -inf};
+        for (int c = 0; c < 4; c++) {
+          const float* cp = m.cverts.data() + ((size_t)m.cidx[p] + c) * 4;
+          r = fmaxf(r, fabsf(cp[3]));
+          for (int k = 0; k < 3; k++) cl[k] = fminf(cl[k], cp[k]), ch[k] = fmaxf(ch[k], cp[k]);
+        }
+        for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], cl[k] - r), lh[k] = fmaxf(lh[k], ch[k] + r);
+      }
+    }
+  }
+  return any;
+}
+// (what an instance with local box ll / lh adds to the scene's box)
+static void unite_instance_box(const HostInstance& inst, const float ll[3], const float lh[3], float bmin[3], float bmax[3]) {
+  if (inst.identity) {
+    for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], ll[k]), bmax[k] = fmaxf(bmax[k], lh[k]);
+  } else {
+    for (int c = 0; c < 8; c++) {
+      const V3 v = xf_point(inst.xf, V3((c & 1) ? lh[0] : ll[0], (c & 2) ? lh[1] : ll[1], (c & 4) ? lh[2] : ll[2]));
+      const float a[3] = {v.x, v.y, v.z};
+      for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], a[k]), bmax[k] = fmaxf(bmax[k], a[k]);
+    }
+  }
+}
 static void scene_bounds(pbrhip_scene* s) {
   const float inf = std::numeric_limits<float>::infinity();
   float bmin[3] = {inf, inf, inf}, bmax[3] = {-inf, -inf, -inf};
   for (uint32_t i = 0; i < s->instances.size(); i++) {
-    const HostInstance& inst = s->instances[i];
-    float ll[3] = {inf, inf, inf}, lh[3] = {-inf, -inf, -inf};
-    bool any = false;
-    for (uint32_t g = 0; g < inst.material_ids.size(); g++) {
-      const HostMesh& m = *inst_mesh(s, i, g);
-      for (uint32_t p = 0; p < m.num_prims(); p++) {
-        any = true;
-        if (m.kind == 0) {
-          for (int c = 0; c < 3; c++) {
-            const V3 v = mesh_vertex(m, p, c);
-            const float a[3] = {v.x, v.y, v.z};
-            for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], a[k]), lh[k] = fmaxf(lh[k], a[k]);
-          }
-        } else {
-          float r = 0.f, cl[3] = {inf, inf, inf}, ch[3] = {-inf, -inf, -inf};
-          for (int c = 0; c < 4; c++) {
-            const float* cp = m.cverts.data() + ((size_t)m.cidx[p] + c) * 4;
-            r = fmaxf(r, fabsf(cp[3]));
-            for (int k = 0; k < 3; k++) cl[k] = fminf(cl[k], cp[k]), ch[k] = fmaxf(ch[k], cp[k]);
-          }
-          for (int k = 0; k < 3; k++) ll[k] = fminf(ll[k], cl[k] - r), lh[k] = fmaxf(lh[k], ch[k] + r);
-        }
-      }
-    }
-    if (!any) continue;
-    if (inst.identity) {
-      for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], ll[k]), bmax[k] = fmaxf(bmax[k], lh[k]);
-    } else {
-      for (int c = 0; c < 8; c++) {
-        const V3 v = xf_point(inst.xf, V3((c & 1) ? lh[0] : ll[0], (c & 2) ? lh[1] : ll[1], (c & 4) ? lh[2] : ll[2]));
-        const float a[3] = {v.x, v.y, v.z};
-        for (int k = 0; k < 3; k++) bmin[k] = fminf(bmin[k], a[k]), bmax[k] = fmaxf(bmax[k], a[k]);
-      }
-    }
+    float ll[3], lh[3];
+    if (instance_local_box(s, i, ll, lh)) unite_instance_box(s->instances[i], ll, lh, bmin, bmax);
   }
   memcpy(s->bmin, bmin, sizeof(bmin));
   memcpy(s->bmax, bmax, sizeof(bmax));
@@ -528,6 +522,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   // the steps rewrite what the scene records and reallocate its device buffers: one that fails leaves the scene uncommitted, not
   // bound to tables that were never uploaded or to freed memory
   s->committed = false;
+  s->dg.drop();  // (device geometry mode ends with the commit it belonged to)
   stage_lights(s, &cs);
   if (int rc = flatten_prims(s, &cs.prims)) return rc;
   const uint32_t np = (uint32_t)cs.prims.size();
@@ -585,6 +580,233 @@ int pb::update_material(pbrhip_scene* s, uint32_t id, const HostMaterial& hm) {
   return PBRHIP_OK;
 }
 
+// ------------------------------------------------------------------ device geometry mode (geom_gpu.h; DESIGN.md section 8, "Staging on the device")
+static const std::vector<float>& mesh_positions(const HostMesh& m) { return m.kind == 0 ? m.vertices : m.cverts; }
+static const std::vector<uint32_t>& mesh_indices(const HostMesh& m) { return m.kind == 0 ? m.vid : m.cidx; }
+
+// The one-off cost of the mode: every mesh's arrays, the (instance, geom) -> mesh table and the instances' slot lists go to the device;
+// the instances' local boxes are cached for scene_bounds' last step.  The model is read as it stands.
+static int switch_on_device_geometry(pbrhip_scene* s) {
+  DevGeom& g = s->dg;
+  hipStream_t st = s->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t ninst = s->instances.size();
+  const uint32_t ns = s->tree.num_slots;
+  std::vector<PrimRef> prims;
+  if (int rc = flatten_prims(s, &prims)) return rc;
+  if (s->slot_gid.size() != ns || prims.size() != ns) return fail(PBRHIP_ESTATE, "the model no longer has the committed topology");
+  std::vector<float> verts, normals;
+  std::vector<uint32_t> vidx, nidx, geom_mesh, ig_off(ninst), slot_list(ns);
+  g.h_recs.clear();
+  for (const HostMesh& m : s->meshes) {
+    const std::vector<float>& pos = mesh_positions(m);
+    const std::vector<uint32_t>& idx = mesh_indices(m);
+    DgMeshRec r = {};
+    r.vert_off = (uint32_t)(verts.size() / 4), r.nverts = (uint32_t)(pos.size() / 4);
+    r.idx_off = (uint32_t)vidx.size(), r.nidx = (uint32_t)idx.size();
+    verts.insert(verts.end(), pos.begin(), pos.end());
+    vidx.insert(vidx.end(), idx.begin(), idx.end());
+    if (m.kind == 0) {
+      r.norm_off = (uint32_t)(normals.size() / 4), r.nnorm = (uint32_t)(m.normals.size() / 4), r.nid_off = (uint32_t)nidx.size();
+      normals.insert(normals.end(), m.normals.begin(), m.normals.end());
+      nidx.insert(nidx.end(), m.nid.begin(), m.nid.end());
+    }
+    g.h_recs.push_back(r);
+  }
+  if (std::max({verts.size() / 4, normals.size() / 4, vidx.size(), nidx.size()}) >= (size_t(1) << 31))
+    return fail(PBRHIP_EUNSUPPORTED, "device geometry: the meshes' arrays are too large for 32-bit offsets");
+  for (size_t i = 0; i < ninst; i++) {
+    ig_off[i] = (uint32_t)geom_mesh.size();
+    for (uint32_t m : s->locals[s->instances[i].local_scene]) geom_mesh.push_back(m);
+  }
+  // the slots grouped by instance, in slot order within one
+  g.inst_first.assign(ninst + 1, 0);
+  for (uint32_t k = 0; k < ns; k++) g.inst_first[prims[s->slot_gid[k]].instance_id + 1]++;
+  for (size_t i = 0; i < ninst; i++) g.inst_first[i + 1] += g.inst_first[i];
+  std::vector<uint32_t> at(g.inst_first.begin(), g.inst_first.end() - 1);
+  for (uint32_t k = 0; k < ns; k++) slot_list[at[prims[s->slot_gid[k]].instance_id]++] = k;
+  g.local_lo.assign(3 * ninst, INFINITY), g.local_hi.assign(3 * ninst, -INFINITY);
+  for (size_t i = 0; i < ninst; i++) instance_local_box(s, (uint32_t)i, &g.local_lo[3 * i], &g.local_hi[3 * i]);
+  g.ngeoms = (uint32_t)geom_mesh.size();
+  auto upload4 = [&](DevBuf<float4>& b, const std::vector<float>& h) {  // (xyzw per element)
+    hipError_t e4 = b.reserve(h.size() / 4);
+    if (e4 == hipSuccess && !h.empty()) e4 = hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, st);
+    return e4;
+  };
+  hipError_t e = upload4(g.verts, verts);
+  if (e == hipSuccess) e = upload4(g.normals, normals);
+  if (e == hipSuccess) e = g.vidx.upload(vidx, st);
+  if (e == hipSuccess) e = g.nidx.upload(nidx, st);
+  if (e == hipSuccess) e = g.recs.upload(g.h_recs, st);
+  if (e == hipSuccess) e = g.geom_mesh.upload(geom_mesh, st);
+  if (e == hipSuccess) e = g.ig_off.upload(ig_off, st);
+  if (e == hipSuccess) e = g.slot_list.upload(slot_list, st);
+  if (e == hipSuccess) e = g.xf.reserve(ninst);
+  if (e == hipSuccess) e = g.bounds.reserve(ninst * kDgBoundWords);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the staged arrays die here)
+  if (e != hipSuccess) {
+    const double keep = g.download_ms;
+    g.drop();
+    g.download_ms = keep;
+    return fail(PBRHIP_EHIP, "device geometry: the upload of the meshes failed: %s", hipGetErrorString(e));
+  }
+  g.on = true;
+  g.switch_ms += ms_since(t0);
+  return PBRHIP_OK;
+}
+
+int pb::update_mesh_device(pbrhip_scene* s, uint32_t mesh_id, const void* d_verts, const void* d_normals, void* stream, const char* who) {
+  DevGeom& g = s->dg;
+  HostMesh& m = s->meshes[mesh_id];
+  std::vector<float>& pos = m.kind == 0 ? m.vertices : m.cverts;
+  const size_t nv = pos.size() / 4, nn = d_normals ? m.normals.size() / 4 : 0;
+  if (g.on && mesh_id >= g.h_recs.size()) return fail(PBRHIP_ESTATE, "%s: mesh %u was added after the commit (pbrhip_scene_commit takes it in)", who, mesh_id);
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  {  // the arrays are read only after what the caller's stream already holds: an event there, and this scene's stream waits for it
+    hipEvent_t ev;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+    (void)hipEventDestroy(ev);
+    HIPCHK(e);
+  }
+  // checked on the device; on a committed scene copied beside the device copy meanwhile, so that a refused array never reaches it and an
+  // accepted one needs no second read of the caller's buffer
+  float4* inc = nullptr;
+  if (s->committed) {
+    HIPCHK(g.incoming.reserve(nv + nn));
+    inc = g.incoming.p;
+  }
+  HIPCHK(g.flag.reserve(1));
+  HIPCHK(hipMemsetAsync(g.flag.p, 0, sizeof(uint32_t), st));
+  HIPCHK(dg_check_gpu(st, d_verts, nv, inc, g.flag.p));
+  if (nn) HIPCHK(dg_check_gpu(st, d_normals, nn, inc ? inc + nv : nullptr, g.flag.p));
+  std::vector<float> hv(4 * nv), hn(4 * nn);
+  uint32_t flag = 0;
+  if (nv) HIPCHK(hipMemcpyAsync(hv.data(), inc ? (const void*)inc : d_verts, nv * 16, hipMemcpyDeviceToHost, st));
+  if (nn) HIPCHK(hipMemcpyAsync(hn.data(), inc ? (const void*)(inc + nv) : d_normals, nn * 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&flag, g.flag.p, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // (the one synchronise of the call: the caller may overwrite its buffer from here on)
+  if (flag) return fail(PBRHIP_EINVAL, "%s: a value is not finite", who);
+  g.download_ms += ms_since(t0);
+  if (s->committed && !g.on)
+    if (int rc = switch_on_device_geometry(s)) return rc;  // (before the model changes: a failure leaves everything as it was)
+  pos.swap(hv);
+  if (nn) m.normals.swap(hn);
+  if (g.on) {
+    const DgMeshRec& r = g.h_recs[mesh_id];
+    if (nv) HIPCHK(hipMemcpyAsync(g.verts.p + r.vert_off, inc, nv * 16, hipMemcpyDeviceToDevice, st));
+    if (nn) HIPCHK(hipMemcpyAsync(g.normals.p + r.norm_off, inc + nv, nn * 16, hipMemcpyDeviceToDevice, st));
+  }
+  return PBRHIP_OK;
+}
+
+int pb::refresh_mesh_device(pbrhip_scene* s, uint32_t mesh_id) {
+  DevGeom& g = s->dg;
+  if (!g.on || mesh_id >= g.h_recs.size()) return PBRHIP_OK;  // (a mesh added after the commit is in no committed instance)
+  const HostMesh& m = s->meshes[mesh_id];
+  const DgMeshRec& r = g.h_recs[mesh_id];
+  const std::vector<float>& pos = mesh_positions(m);
+  HIPCHK(hipSetDevice(s->device));
+  if (r.nverts) HIPCHK(hipMemcpyAsync(g.verts.p + r.vert_off, pos.data(), (size_t)r.nverts * 16, hipMemcpyHostToDevice, s->stream));
+  if (r.nnorm) HIPCHK(hipMemcpyAsync(g.normals.p + r.norm_off, m.normals.data(), (size_t)r.nnorm * 16, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return PBRHIP_OK;
+}
+
+// What refit stages for the dirty instances, one of two ways.  Both leave the new slots and ShadeRecs on the device, the dirty instances'
+// world bounds in ilo / ihi, the scene's box in s->bmin / bmax and the number of dirty slots in *m.
+// On the host: flatten_prims, slot_and_shade per dirty slot, scene_bounds over the whole model, one packed upload and k_rf_scatter.
+// (`packed` is handed to hipMemcpyAsync from pageable memory: the caller owns it until its final synchronise)
+static int stage_refit_host(pbrhip_scene* s, std::chrono::steady_clock::time_point t_host, std::vector<float>& ilo, std::vector<float>& ihi, std::vector<float4>& packed,
+                            uint32_t* m_out, double* ms_host, double* ms_upload) {
+  hipStream_t st = s->stream;
+  const TreeBufs& t = s->tree;
+  std::vector<PrimRef> prims;
+  if (int rc = flatten_prims(s, &prims)) return rc;
+  const uint32_t ns = t.num_slots;
+  if (s->slot_gid.size() != ns || prims.size() != ns) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
+  std::vector<uint32_t> dirty;
+  for (uint32_t slot = 0; slot < ns; slot++)
+    if (s->dirty_inst[prims[s->slot_gid[slot]].instance_id]) dirty.push_back(slot);
+  const uint32_t m = (uint32_t)dirty.size();
+  const size_t idx_words = ((size_t)m + 3) / 4;
+  packed.assign(idx_words + 12 * (size_t)m, make_float4(0, 0, 0, 0));
+  for (uint32_t e = 0; e < m; e++) {
+    const uint32_t g = s->slot_gid[dirty[e]];
+    float4* sl = &packed[idx_words + 4 * (size_t)e];
+    ShadeRec sr;
+    if (int rc = slot_and_shade(s, prims[g], g, s->light_heads, sl, sr)) return rc;
+    reinterpret_cast<uint32_t*>(packed.data())[e] = dirty[e];
+    memcpy(&packed[idx_words + 4 * (size_t)m + 8 * (size_t)e], &sr, sizeof(sr));
+    float lo[3], hi[3];
+    slot_tight_box(sl, prims[g].kind != 0, lo, hi);
+    accumulate_instance_bounds(ilo, ihi, prims[g].instance_id, lo, hi);
+  }
+  scene_bounds(s);
+  *ms_host = ms_since(t_host);
+  const auto t_up = std::chrono::steady_clock::now();
+  HIPCHK(s->rf_packed.upload(packed, st));
+  HIPCHK(scatter_slots_gpu(st, s->rf_packed.p, m, ns, t.slots(), reinterpret_cast<float4*>(s->d_shade.p)));
+  *ms_upload = ms_since(t_up);
+  *m_out = m;
+  return PBRHIP_OK;
+}
+// On the device (device geometry mode): the instances' transforms as a small table, k_dg_stage per dirty instance, the bounds back.  The
+// scene's box is finished here as scene_bounds finishes it -- instances in ascending order -- from the dirty instances' new local boxes
+// (llo / lhi: every instance's, the clean ones' as cached) .
+static int stage_refit_device(pbrhip_scene* s, std::vector<float>& ilo, std::vector<float>& ihi, std::vector<float>& llo, std::vector<float>& lhi, uint32_t* m_out) {
+  DevGeom& g = s->dg;
+  hipStream_t st = s->stream;
+  const TreeBufs& t = s->tree;
+  const size_t ninst = s->instances.size();
+  if (g.inst_first.size() != ninst + 1 || g.inst_first[ninst] != t.num_slots) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
+  g.h_xf.resize(ninst);
+  for (size_t i = 0; i < ninst; i++) {
+    memcpy(g.h_xf[i].m, s->instances[i].xf, sizeof(g.h_xf[i].m));
+    g.h_xf[i].identity = s->instances[i].identity ? 1u : 0u;
+  }
+  HIPCHK(g.xf.upload(g.h_xf, st));
+  HIPCHK(hipMemsetAsync(g.flag.p, 0, sizeof(uint32_t), st));
+  HIPCHK(dg_init_bounds_gpu(st, g.bounds.p, (uint32_t)ninst));
+  DgScene d;
+  d.slots = t.slots(), d.shade = reinterpret_cast<float4*>(s->d_shade.p), d.ns = t.num_slots;
+  d.verts = g.verts.p, d.normals = g.normals.p, d.vidx = g.vidx.p, d.nidx = g.nidx.p, d.recs = g.recs.p;
+  d.geom_mesh = g.geom_mesh.p, d.ig_off = g.ig_off.p, d.ngeoms = g.ngeoms, d.slot_list = g.slot_list.p, d.xf = g.xf.p;
+  d.bounds = g.bounds.p, d.flag = g.flag.p;
+  uint32_t m = 0;
+  for (size_t i = 0; i < ninst; i++)
+    if (s->dirty_inst[i]) {
+      const uint32_t count = g.inst_first[i + 1] - g.inst_first[i];
+      HIPCHK(dg_stage_gpu(st, d, (uint32_t)i, g.inst_first[i], count));
+      m += count;
+    }
+  g.h_bounds.assign(ninst * kDgBoundWords, 0u);
+  uint32_t flag = 0;
+  if (ninst) HIPCHK(hipMemcpyAsync(g.h_bounds.data(), g.bounds.p, g.h_bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&flag, g.flag.p, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (flag) return fail(PBRHIP_ESTATE, "scene_refit: the device geometry tables hold an index out of range; the scene stays stale (pbrhip_scene_commit rebuilds it)");
+  const float inf = std::numeric_limits<float>::infinity();
+  float bmin[3] = {inf, inf, inf}, bmax[3] = {-inf, -inf, -inf};
+  for (size_t i = 0; i < ninst; i++) {
+    if (g.inst_first[i + 1] == g.inst_first[i]) continue;  // (no primitive: no box)
+    if (s->dirty_inst[i]) {
+      const uint32_t* b = &g.h_bounds[i * kDgBoundWords];
+      for (int a = 0; a < 3; a++) {
+        llo[3 * i + a] = dg_decode(b[a]), lhi[3 * i + a] = dg_decode(b[3 + a]);
+        ilo[3 * i + a] = dg_decode(b[6 + a]), ihi[3 * i + a] = dg_decode(b[9 + a]);
+      }
+    }
+    unite_instance_box(s->instances[i], &llo[3 * i], &lhi[3 * i], bmin, bmax);
+  }
+  memcpy(s->bmin, bmin, sizeof(bmin)), memcpy(s->bmax, bmax, sizeof(bmax));
+  *m_out = m;
+  return PBRHIP_OK;
+}
+
 extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
   return guarded([&]() -> int {
   if (!s) return fail(PBRHIP_EINVAL, "scene is NULL");
@@ -595,7 +817,7 @@ extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
   HIPCHK(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const TreeBufs& t = s->tree;
-  const auto t_host = std::chrono::steady_clock::now();
+  const auto t_stage = std::chrono::steady_clock::now();
   const size_t ninst = s->instances.size();
   s->dirty_inst.resize(ninst, 0);
   CommitStage cs;  // (outlives the last synchronise)
@@ -605,43 +827,36 @@ extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
     if (s->dirty_inst[i])
       for (int has : s->instances[i].has_area_light) lights_dirty = lights_dirty || has != 0;
   if (lights_dirty) stage_lights(s, &cs);
-  // the dirty slots and their ShadeRecs, packed for one upload: index | 64 B | 128 B; the dirty instances' bounds from their new boxes
-  if (int rc = flatten_prims(s, &cs.prims)) return rc;
+  // the dirty slots and their ShadeRecs; the dirty instances' bounds from their new boxes
   const uint32_t ns = t.num_slots;
-  if (s->slot_gid.size() != ns || cs.prims.size() != ns) return fail(PBRHIP_ESTATE, "scene_refit: the model no longer has the committed topology");
-  std::vector<uint32_t> dirty;
-  for (uint32_t slot = 0; slot < ns; slot++)
-    if (s->dirty_inst[cs.prims[s->slot_gid[slot]].instance_id]) dirty.push_back(slot);
-  const uint32_t m = (uint32_t)dirty.size();
-  const size_t idx_words = ((size_t)m + 3) / 4;
-  std::vector<float4> packed(idx_words + 12 * (size_t)m, make_float4(0, 0, 0, 0));
   std::vector<float> ilo = s->inst_lo, ihi = s->inst_hi;
   for (size_t i = 0; i < ninst; i++)
     if (s->dirty_inst[i])
       for (int a = 0; a < 3; a++) ilo[3 * i + a] = INFINITY, ihi[3 * i + a] = -INFINITY;
-  for (uint32_t e = 0; e < m; e++) {
-    const uint32_t g = s->slot_gid[dirty[e]];
-    float4* sl = &packed[idx_words + 4 * (size_t)e];
-    ShadeRec sr;
-    if (int rc = slot_and_shade(s, cs.prims[g], g, s->light_heads, sl, sr)) return rc;
-    reinterpret_cast<uint32_t*>(packed.data())[e] = dirty[e];
-    memcpy(&packed[idx_words + 4 * (size_t)m + 8 * (size_t)e], &sr, sizeof(sr));
-    float lo[3], hi[3];
-    slot_tight_box(sl, cs.prims[g].kind != 0, lo, hi);
-    accumulate_instance_bounds(ilo, ihi, cs.prims[g].instance_id, lo, hi);
-  }
   float keep_min[3], keep_max[3];  // (a failed refit leaves the scene as stale as it was)
   memcpy(keep_min, s->bmin, 12), memcpy(keep_max, s->bmax, 12);
-  scene_bounds(s);
-  const double ms_host = ms_since(t_host);
-
-  const auto t_up = std::chrono::steady_clock::now();
-  HIPCHK(s->rf_packed.upload(packed, st));
-  HIPCHK(scatter_slots_gpu(st, s->rf_packed.p, m, ns, t.slots(), reinterpret_cast<float4*>(s->d_shade.p)));
+  const bool on_device = s->dg.on;
+  std::vector<float> llo, lhi;
+  std::vector<float4> packed;
+  uint32_t m = 0;
+  double ms_host = 0.0, ms_upload = 0.0;
+  int rc;
+  if (on_device) {
+    llo = s->dg.local_lo, lhi = s->dg.local_hi;
+    rc = stage_refit_device(s, ilo, ihi, llo, lhi, &m);
+  } else {
+    rc = stage_refit_host(s, t_stage, ilo, ihi, packed, &m, &ms_host, &ms_upload);
+  }
+  if (rc) {
+    memcpy(s->bmin, keep_min, 12), memcpy(s->bmax, keep_max, 12);
+    return rc;
+  }
+  const double ms_stage = ms_since(t_stage);
+  const auto t_lights = std::chrono::steady_clock::now();
   if (lights_dirty)
-    if (int rc = upload_lights(s, cs)) return rc;
+    if (int rc2 = upload_lights(s, cs)) return rc2;
   if (k.debug) HIPCHK(hipStreamSynchronize(st));
-  const double ms_upload = ms_since(t_up);
+  ms_upload += ms_since(t_lights);
 
   RefitTimes rt;
   HIPCHK(refit_tree_gpu(st, t.refit_tree(s->num_curves == 0), k.debug, &s->rf_plan, &rt));
@@ -655,14 +870,18 @@ extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
     cs.q.nodes.resize(t.wide_nodes);
     HIPCHK(hipMemcpyAsync(cs.q.nodes.data(), t.d_wide.p, cs.q.nodes.size() * sizeof(QNode), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (int rc = update_walk_entries(s, k, true, ilo, ihi, &cs, nullptr)) return rc;
+    if (int rc2 = update_walk_entries(s, k, true, ilo, ihi, &cs, nullptr)) return rc2;
   }
   HIPCHK(hipStreamSynchronize(st));
-  if (k.debug)
+  if (k.debug && !on_device)
     fprintf(stderr, "pbrhip: refit: %u of %u slots dirty: host staging %.2f ms, upload + scatter %.2f ms, plan %.2f ms, pack + trees %.2f ms (%u + %u levels), Q-node download + walk entries %.2f ms\n",
             m, ns, ms_host, ms_upload, rt.plan_ms, rt.trees_ms, rt.bin_levels, rt.q_levels, ms_since(t_entries));
+  if (k.debug && on_device)
+    fprintf(stderr, "pbrhip: refit (device geometry): %u of %u slots dirty: switch-on %.2f ms, updates' check + download to the model %.2f ms, staging + bounds kernels %.2f ms, light tables %.2f ms, plan %.2f ms, pack + trees %.2f ms (%u + %u levels), Q-node download + walk entries %.2f ms\n",
+            m, ns, s->dg.switch_ms, s->dg.download_ms, ms_stage, ms_upload, rt.plan_ms, rt.trees_ms, rt.bin_levels, rt.q_levels, ms_since(t_entries));
   bind_dscene(s);
   s->inst_lo = std::move(ilo), s->inst_hi = std::move(ihi);
+  if (on_device) s->dg.local_lo = std::move(llo), s->dg.local_hi = std::move(lhi), s->dg.switch_ms = s->dg.download_ms = 0.0;
   s->dirty_inst.assign(ninst, 0), s->stale = false;
   return PBRHIP_OK;
   });

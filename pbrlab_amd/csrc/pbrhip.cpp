@@ -438,7 +438,7 @@ extern "C" int pbrhip_scene_update_triangle_mesh(pbrhip_scene* s, uint32_t mesh_
   m.vertices.assign(vertices_xyzw, vertices_xyzw + (size_t)num_vertices * 4);
   if (normals_xyzw) m.normals.assign(normals_xyzw, normals_xyzw + (size_t)num_normals * 4);
   mark_dirty(s, mesh_id, kNone);
-  return PBRHIP_OK;
+  return refresh_mesh_device(s, mesh_id);  // (device geometry mode: the device copy follows the model)
   });
 }
 extern "C" int pbrhip_scene_update_curve_mesh(pbrhip_scene* s, uint32_t mesh_id, const float* vertices_xyzr, uint32_t num_vertices) {
@@ -450,6 +450,79 @@ extern "C" int pbrhip_scene_update_curve_mesh(pbrhip_scene* s, uint32_t mesh_id,
   if (!all_finite(vertices_xyzr, (size_t)num_vertices * 4)) return fail(PBRHIP_EINVAL, "update_curve_mesh: a value is not finite");
   m.cverts.assign(vertices_xyzr, vertices_xyzr + (size_t)num_vertices * 4);
   mark_dirty(s, mesh_id, kNone);
+  return refresh_mesh_device(s, mesh_id);
+  });
+}
+// `bytes` at p: device memory of the scene's device (hipPointerGetAttributes; a host pointer has no attributes or is "unregistered") and,
+// where the runtime knows the allocation's range, all of it inside that allocation
+static int check_device_array(const pbrhip_scene* s, const void* p, size_t bytes, const char* who) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PBRHIP_EINVAL, "%s: the array is not device memory", who);
+  }
+  if (at.type != hipMemoryTypeDevice) return fail(PBRHIP_EINVAL, "%s: the array is not device memory", who);
+  if (at.device != s->device) return fail(PBRHIP_EINVAL, "%s: the array is on device %d, the scene on device %d", who, at.device, s->device);
+  void* base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<void*>(p)) == hipSuccess) {
+    const size_t at_byte = (size_t)((const char*)p - (const char*)base);
+    if (at_byte > size || bytes > size - at_byte) return fail(PBRHIP_ESIZE, "%s: the array ends %zu bytes past its device allocation", who, at_byte + bytes - size);
+  } else {
+    (void)hipGetLastError();  // (memory mapped through the virtual-memory calls has no such range: its attributes are what is known of it)
+  }
+  if ((uintptr_t)p % 16) return fail(PBRHIP_EINVAL, "%s: the array is not 16-byte aligned", who);
+  return PBRHIP_OK;
+}
+extern "C" int pbrhip_scene_update_triangle_mesh_device(pbrhip_scene* s, uint32_t mesh_id, const void* d_vertices_xyzw, uint32_t num_vertices,
+                                                        const void* d_normals_xyzw, uint32_t num_normals, void* stream) {
+  return guarded([&]() -> int {
+  const char* who = "update_triangle_mesh_device";
+  if (!s || (!d_vertices_xyzw && num_vertices)) return fail(PBRHIP_EINVAL, "%s: NULL argument", who);
+  if (int rc = check_mesh_update(s, mesh_id, 0, who)) return rc;
+  const HostMesh& m = s->meshes[mesh_id];
+  if ((size_t)num_vertices * 4 != m.vertices.size()) return fail(PBRHIP_ESIZE, "%s: %u vertices, the mesh has %zu", who, num_vertices, m.vertices.size() / 4);
+  if (d_normals_xyzw && (size_t)num_normals * 4 != m.normals.size()) return fail(PBRHIP_ESIZE, "%s: %u normals, the mesh has %zu", who, num_normals, m.normals.size() / 4);
+  HIPCHK(hipSetDevice(s->device));
+  if (num_vertices)
+    if (int rc = check_device_array(s, d_vertices_xyzw, (size_t)num_vertices * 16, who)) return rc;
+  if (d_normals_xyzw && num_normals)
+    if (int rc = check_device_array(s, d_normals_xyzw, (size_t)num_normals * 16, who)) return rc;
+  if (int rc = update_mesh_device(s, mesh_id, d_vertices_xyzw, num_normals ? d_normals_xyzw : nullptr, stream, who)) return rc;
+  mark_dirty(s, mesh_id, kNone);
+  return PBRHIP_OK;
+  });
+}
+extern "C" int pbrhip_scene_update_curve_mesh_device(pbrhip_scene* s, uint32_t mesh_id, const void* d_vertices_xyzr, uint32_t num_vertices, void* stream) {
+  return guarded([&]() -> int {
+  const char* who = "update_curve_mesh_device";
+  if (!s || (!d_vertices_xyzr && num_vertices)) return fail(PBRHIP_EINVAL, "%s: NULL argument", who);
+  if (int rc = check_mesh_update(s, mesh_id, 1, who)) return rc;
+  const HostMesh& m = s->meshes[mesh_id];
+  if ((size_t)num_vertices * 4 != m.cverts.size()) return fail(PBRHIP_ESIZE, "%s: %u vertices, the mesh has %zu", who, num_vertices, m.cverts.size() / 4);
+  HIPCHK(hipSetDevice(s->device));
+  if (num_vertices)
+    if (int rc = check_device_array(s, d_vertices_xyzr, (size_t)num_vertices * 16, who)) return rc;
+  if (int rc = update_mesh_device(s, mesh_id, d_vertices_xyzr, nullptr, stream, who)) return rc;
+  mark_dirty(s, mesh_id, kNone);
+  return PBRHIP_OK;
+  });
+}
+// test hook: the committed scene's slots (64 B each, leaf order) and ShadeRecs (128 B each) as the device holds them
+extern "C" int pbrhip_scene_read_slots(pbrhip_scene* s, void* slots_out, void* shade_out, uint32_t* num_slots) {
+  return guarded([&]() -> int {
+  if (!s) return fail(PBRHIP_EINVAL, "scene_read_slots: scene is NULL");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
+  const uint32_t ns = s->tree.num_slots;
+  if (num_slots) *num_slots = ns;
+  if ((slots_out || shade_out) && ns) {
+    HIPCHK(hipSetDevice(s->device));
+    if (slots_out) HIPCHK(hipMemcpyAsync(slots_out, s->dscene.slots, (size_t)ns * 64, hipMemcpyDeviceToHost, s->stream));
+    if (shade_out) HIPCHK(hipMemcpyAsync(shade_out, s->dscene.shade, (size_t)ns * sizeof(ShadeRec), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+  }
   return PBRHIP_OK;
   });
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/pbrhip.h"
+#include "geom_gpu.h"
 #include "host_scene.h"
 #include "kernels.h"
 
@@ -130,6 +131,32 @@ struct TreeBufs {
     return r;
   }
 };
+// Device geometry mode (geom_gpu.h): on from the first successful pbrhip_scene_update_*_mesh_device call on a committed scene until the
+// next commit.  A scene that never makes such a call holds empty buffers here and nothing else.
+struct DevGeom {
+  bool on = false;
+  DevBuf<float4> verts, normals;           // every mesh's vertices / control points, and normals, concatenated (DgMeshRec says where)
+  DevBuf<uint32_t> vidx, nidx;             // vid / cidx, and nid
+  DevBuf<DgMeshRec> recs;
+  DevBuf<uint32_t> geom_mesh, ig_off, slot_list;
+  DevBuf<DgXf> xf;                         // per refit
+  DevBuf<uint32_t> bounds, flag;
+  DevBuf<float4> incoming;                 // a device update's array while it is checked: copied on only once it is accepted
+  std::vector<DgMeshRec> h_recs;
+  std::vector<uint32_t> inst_first;        // instance i's slots are slot_list[inst_first[i] .. inst_first[i + 1])
+  std::vector<float> local_lo, local_hi;   // per instance: scene_bounds' local box, as of the last refit (the clean instances keep theirs)
+  std::vector<DgXf> h_xf;                  // (staged here: outlives the copy)
+  std::vector<uint32_t> h_bounds;
+  uint32_t ngeoms = 0;
+  double switch_ms = 0.0, download_ms = 0.0;  // since the last refit: the switch-on; the device updates' check + download to the model
+  void drop() {
+    on = false;
+    verts.release(), normals.release(), vidx.release(), nidx.release(), recs.release(), geom_mesh.release(), ig_off.release();
+    slot_list.release(), xf.release(), bounds.release(), incoming.release();
+    h_recs.clear(), inst_first.clear(), local_lo.clear(), local_hi.clear(), h_xf.clear(), h_bounds.clear();
+    ngeoms = 0, switch_ms = download_ms = 0.0;
+  }
+};
 inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
   return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
 }
@@ -169,6 +196,7 @@ struct pbrhip_scene {
   bool lights_transformed = false;  // DScene::lights_transformed
   pb::RefitPlan rf_plan;            // built at the first refit of a committed tree, dropped by the next commit
   pb::DevBuf<float4> rf_packed;     // the dirty slots' upload: index | 64 B | 128 B (refit_gpu.hip::k_rf_scatter)
+  pb::DevGeom dg;                   // device geometry mode (off, and empty, unless a *_mesh_device update switched it on)
   // device scene
   pb::TreeBufs tree;
   pb::DevBuf<pb::ShadeRec> d_shade;
@@ -253,6 +281,11 @@ inline const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, ui
   return &s->meshes[s->locals[in.local_scene][geom_id]];
 }
 int update_material(pbrhip_scene* s, uint32_t id, const HostMaterial& hm);  // pbrhip_scene_update_*_material's body (commit.cpp)
+// pbrhip_scene_update_triangle_mesh_device / _curve_mesh_device after their argument checks (commit.cpp): the arrays checked on the
+// device, downloaded into the model and, on a committed scene, taken into the device copy (switching device geometry mode on)
+int update_mesh_device(pbrhip_scene* s, uint32_t mesh_id, const void* d_verts, const void* d_normals, void* stream, const char* who);
+// device geometry mode on: the device copy of a mesh the host update calls just edited, refreshed from the model
+int refresh_mesh_device(pbrhip_scene* s, uint32_t mesh_id);
 // the scene's cameras for a width x height image (pbrhip.cpp; pbrhip_camera_rays launches them too)
 UserCamera make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
 Camera make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
