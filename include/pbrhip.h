@@ -342,6 +342,53 @@ int pbrhip_denoise_device(int device, uint32_t width, uint32_t height, const flo
                           const float* d_albedo_hits, const float* d_normal_depth, const uint32_t* d_feature_count, uint32_t iterations,
                           float sigma_color, float sigma_depth, uint32_t normal_squarings, uint32_t flags, float* d_out_rgba);
 
+/* ---- adaptive sampling ----
+ * pbrhip_render with a sample count per 8x8 TILE: tiles whose error estimate has fallen to `threshold` stop, the rest render on, up to
+ * desc->num_sample passes (the maximum level).  The contract: pixel p of the layer holds, bit for bit, what pbrhip_render with
+ * num_sample = count[p] (same descriptor otherwise) holds at p -- a pixel's value is a function of (pixel, pass) and its float sums run in
+ * ascending pass order, however the passes were grouped.  Which count a pixel gets is defined exactly:
+ *   tiles   8x8 pixels aligned to the image origin, clipped at the right and bottom edges; id = ty * ceil(W / 8) + tx.  shard_block must be
+ *           a multiple of 8 (0 = 64), so that every tile belongs to one rank.
+ *   levels  n_0 = first_level (0 = PBRHIP_ADAPTIVE_FIRST_LEVEL), n_k = min(2 n_(k-1), num_sample).  Round 0 renders the passes [first_pass,
+ *           first_pass + n_0) of every pixel of the rank, round k >= 1 the passes [first_pass + n_(k-1), first_pass + n_k) of the pixels of
+ *           the tiles still active.  A decision follows every round k >= 1 (so every pixel holds at least min(2 first_level, num_sample)
+ *           passes); a stopped tile never restarts.  first_level >= num_sample: one plain round of num_sample, no decision.
+ *   error   with A the layer at level n_(k-1) and I the layer at level n_k, per pixel in float32, every operation rounded once:
+ *           a = A.rgb / (float)n_(k-1), b = (I.rgb - A.rgb) / (float)(n_k - n_(k-1)), m = I.rgb / (float)n_k,
+ *           d = |a.r - b.r| + |a.g - b.g| + |a.b - b.b|, s = m.r + m.g + m.b (both left to right), e = d / sqrtf(s + 1e-3f)
+ *           (the 1e-3f keeps black pixels finite: a design constant).  E = the float64 sum of the tile's e, lane (y & 7) * 8 + (x & 7),
+ *           absent lanes of a clipped tile 0, as a butterfly over the xor distances 1, 2, 4, 8, 16, 32, divided by the tile's pixel count.
+ *   stop    when E <= (double)threshold; a NaN E compares false and the tile stays active.
+ * tile_error: ceil(W / 8) * ceil(H / 8) floats, a tile's last (float)E (a NaN as 0x7FC00000); 0 for tiles of other ranks and for tiles no
+ * decision reached.  *finish_pass is stored after every round with the level every pixel of the rank holds; *samples = the sum of count
+ * over the rank's pixels; *rounds = the rounds rendered.  tile_error, finish_pass, samples and rounds may be NULL.
+ * max_paths_in_flight, num_streams, tail_paths, seed_seq, tile_rank / tile_world / shard_block act as in pbrhip_render and do not change
+ * the result; PBRHIP_RENDER_NO_CLEAR is refused (an adaptive layer cannot be resumed), other flags are ignored.
+ * PBRHIP_EINVAL: a NULL scene, descriptor or layer, PBRHIP_RENDER_NO_CLEAR, a negative or NaN threshold, shard_block % 8 != 0,
+ * num_sample == 0; an uncommitted or stale scene: PBRHIP_ESTATE.  cancel: the round in flight ends as pbrhip_render's does (the active
+ * pixels hold n_(k-1) + the passes that were complete), no decision follows, the call returns PBRHIP_OK and the contract above holds.
+ * BIAS: stopping on an estimate made from the samples themselves is biased, as in every such scheme (a tile that looks converged by
+ * chance stops early and keeps its luck).  The guards are the two-level minimum and the tile mean: 64 pixels decide together.
+ * Not provided: dilation of the active set into neighbouring tiles, lists finer than a tile, a pbrhip_render_multi twin (render the
+ * shards with tile_rank / tile_world and add them), resuming an adaptive layer.
+ * PBRHIP_ADAPTIVE_THRESHOLD: see profiles/README.md ("Adaptive sampling") for the sweep behind the value. */
+#define PBRHIP_ADAPTIVE_FIRST_LEVEL 8u
+#define PBRHIP_ADAPTIVE_THRESHOLD 0.07f
+int pbrhip_render_adaptive(pbrhip_scene*, const pbrhip_render_desc*, float threshold, uint32_t first_level,
+                           const volatile unsigned char* cancel, float* rgba, uint32_t* count, float* tile_error, size_t* finish_pass,
+                           uint64_t* samples, uint32_t* rounds);
+/* Same, into DEVICE buffers on the scene's device (d_tile_error may be NULL). */
+int pbrhip_render_adaptive_device(pbrhip_scene*, const pbrhip_render_desc*, float threshold, uint32_t first_level,
+                                  const volatile unsigned char* cancel, float* d_rgba, uint32_t* d_count, float* d_tile_error,
+                                  size_t* finish_pass, uint64_t* samples, uint32_t* rounds);
+/* One decision step without a scene (host pointers): a test hook.  rgba = I at level n_now, snapshot_inout = A at level n_prev (on
+ * return: I for the pixels of the tiles of tiles_in), tiles_in = num_tiles_in distinct tile ids.  tiles_out / pixels_out (room for
+ * num_tiles_in ids / width * height pixels) receive the tiles that stay active, in the order they had, and their pixels, tile after
+ * tile and row-major inside a tile; tile_error_inout (ceil(W / 8) * ceil(H / 8)) receives the E of the tiles of tiles_in. */
+int pbrhip_adaptive_step(int device, uint32_t width, uint32_t height, const float* rgba, float* snapshot_inout, uint32_t n_prev,
+                         uint32_t n_now, float threshold, const uint32_t* tiles_in, uint32_t num_tiles_in, uint32_t* tiles_out,
+                         uint32_t* num_tiles_out, uint32_t* pixels_out, uint32_t* num_pixels_out, float* tile_error_inout);
+
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks
  * with index % world == r (pbrhip_render_desc.tile_rank / tile_world / shard_block) into a zeroed full-size layer, then the

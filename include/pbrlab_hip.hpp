@@ -610,5 +610,39 @@ inline std::vector<float> Denoise(const RenderLayer& layer, const FeatureLayer* 
   return out;
 }
 
+// ---- adaptive sampling (not in the reference) ----
+struct AdaptiveOptions {
+  float threshold = PBRHIP_ADAPTIVE_THRESHOLD;  // a tile stops when its error estimate E <= threshold
+  uint32_t first_level = 0;                     // 0: PBRHIP_ADAPTIVE_FIRST_LEVEL
+};
+struct AdaptiveResult {
+  std::vector<float> tile_error;  // ceil(width / 8) * ceil(height / 8): every tile's last E
+  uint64_t samples = 0;           // the sum of layer->count
+  uint32_t rounds = 0;
+};
+// pbrhip_render_adaptive: Render() with a sample count per 8x8 tile, at most max_sample.  Pixel p of *layer holds, bit for bit, what
+// Render() with num_sample = layer->count[p] holds at p.  Clears and resizes *layer; cancel_render_flag and finish_pass as for Render()
+// (*finish_pass: the level every pixel holds).  Throws with pbrhip_last_error() on a library error.
+inline AdaptiveResult RenderAdaptive(const Scene& scene, const uint32_t width, const uint32_t height, const uint32_t max_sample,
+                                     const std::atomic_bool& cancel_render_flag, RenderLayer* layer, std::atomic_size_t* finish_pass = nullptr,
+                                     const AdaptiveOptions& o = AdaptiveOptions()) {
+  layer->Resize(width, height);
+  scene.PushMaterialEdits();
+  pbrhip_render_desc d = {};
+  d.width = width, d.height = height, d.num_sample = max_sample;
+  d.seed_seq = 1234567890;  // Render()'s
+  d.tile_world = 1;
+  AdaptiveResult r;
+  r.tile_error.resize(size_t((width + 7) / 8) * ((height + 7) / 8));
+  std::atomic_size_t local_fin(0);
+  std::atomic_size_t* fin = finish_pass ? finish_pass : &local_fin;
+  fin->store(0);
+  if (pbrhip_render_adaptive(scene.handle(), &d, o.threshold, o.first_level, reinterpret_cast<const volatile unsigned char*>(&cancel_render_flag),
+                             layer->rgba.data(), layer->count.data(), r.tile_error.data(), reinterpret_cast<size_t*>(fin), &r.samples,
+                             &r.rounds) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderAdaptive: ") + pbrhip_last_error());
+  return r;
+}
+
 }  // namespace pbrlab
 #endif  // PBRLAB_HIP_HPP_

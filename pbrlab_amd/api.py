@@ -627,6 +627,58 @@ def DenoiseDevice(device, width, height, rgba_ptr, count_ptr, out_ptr, features=
                                           *_denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo), out_ptr))
 
 
+# pbrhip_render_adaptive's defaults (include/pbrhip.h PBRHIP_ADAPTIVE_*)
+ADAPTIVE_FIRST_LEVEL, ADAPTIVE_THRESHOLD, ADAPTIVE_TILE = 8, 0.07, 8
+
+
+def RenderAdaptive(scene, width, height, max_sample, threshold=ADAPTIVE_THRESHOLD, first_level=0, layer=None, cancel_render_flag=None,
+                   finish_pass=None, device_out=None, **desc_kw):
+    """pbrhip_render_adaptive: Render with a sample count per 8x8 tile -- tiles whose error estimate has fallen to
+    `threshold` stop, the rest render on up to `max_sample` passes.  Pixel p of the layer holds, bit for bit, what Render with
+    num_sample = layer.count[p] holds at p.  first_level 0 = 8; desc_kw: Render's keywords (first_pass, seed_seq, tile_rank, tile_world,
+    max_paths_in_flight, num_streams, tail_paths, shard_block -- a multiple of 8 --, flags).  Returns the layer (resized and cleared)
+    with .tile_error (ceil(H / 8), ceil(W / 8)) float32, .samples and .rounds attached.
+    device_out: optional (rgba_ptr, count_ptr, tile_error_ptr or None) DEVICE pointers (ints) instead of a layer; returns
+    (samples, rounds)."""
+    L = _lib.lib()
+    desc = _desc(width, height, max_sample, **desc_kw)
+    fin = finish_pass if finish_pass is not None else C.c_size_t(0)
+    cancel = C.byref(cancel_render_flag) if cancel_render_flag is not None else None
+    samples, rounds = C.c_uint64(0), C.c_uint32(0)
+    if device_out is not None:
+        _chk(L.pbrhip_render_adaptive_device(scene.h if scene is not None else None, C.byref(desc), float(threshold), int(first_level), cancel,
+                                             *[C.c_void_p(p or None) for p in device_out], C.byref(fin), C.byref(samples), C.byref(rounds)))
+        return samples.value, rounds.value
+    if layer is None:
+        layer = RenderLayer()
+    layer.Resize(width, height)
+    tile_error = np.zeros((-(-int(height) // ADAPTIVE_TILE), -(-int(width) // ADAPTIVE_TILE)), np.float32)
+    _chk(L.pbrhip_render_adaptive(scene.h if scene is not None else None, C.byref(desc), float(threshold), int(first_level), cancel,
+                                  layer.rgba.ctypes.data, layer.count.ctypes.data, tile_error.ctypes.data, C.byref(fin), C.byref(samples),
+                                  C.byref(rounds)))
+    layer.tile_error, layer.samples, layer.rounds = tile_error, samples.value, rounds.value
+    return layer
+
+
+def adaptive_step(rgba, snapshot, n_prev, n_now, threshold, tiles_in, tile_error=None, device=None):
+    """pbrhip_adaptive_step, a test hook: one decision step of RenderAdaptive on given layers.  rgba (H, W, 4) = the layer at level n_now,
+    snapshot (H, W, 4) = the layer at level n_prev, tiles_in = the active tile ids.  Returns (tiles_out, pixels_out, tile_error,
+    new_snapshot): the tiles that stay active in the order they had, their pixels, the tiles' error (entries of other tiles as given,
+    0 without tile_error) and the snapshot after the step."""
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    h, w = rgba.shape[:2]
+    snap = np.array(snapshot, np.float32, order="C", copy=True).reshape(h, w, 4)
+    tiles_in = np.ascontiguousarray(tiles_in, np.uint32).reshape(-1)
+    th, tw = -(-h // ADAPTIVE_TILE), -(-w // ADAPTIVE_TILE)
+    err = np.zeros((th, tw), np.float32) if tile_error is None else np.array(tile_error, np.float32, order="C", copy=True).reshape(th, tw)
+    tiles_out, pixels_out = np.zeros(max(len(tiles_in), 1), np.uint32), np.zeros(h * w, np.uint32)
+    nt, npx = C.c_uint32(0), C.c_uint32(0)
+    _chk(_lib.lib().pbrhip_adaptive_step(_device if device is None else int(device), w, h, rgba.ctypes.data, snap.ctypes.data, int(n_prev),
+                                         int(n_now), float(threshold), tiles_in.ctypes.data, len(tiles_in), tiles_out.ctypes.data,
+                                         C.byref(nt), pixels_out.ctypes.data, C.byref(npx), err.ctypes.data))
+    return tiles_out[:nt.value].copy(), pixels_out[:npx.value].copy(), err, snap
+
+
 def _desc(width, height, num_sample, first_pass=0, seed_seq=1234567890, tile_rank=0, tile_world=1,
           max_paths_in_flight=0, flags=0, num_streams=0, tail_paths=0, shard_block=0):
     return RenderDesc(width, height, num_sample, first_pass, seed_seq, tile_rank, tile_world, max_paths_in_flight,

@@ -3,7 +3,7 @@
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
 //                  [--gpus N] [--bvh host|gpu|gpu-wide] [--env FILE [--env-scale S]]
 //                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
-//                  [--aov PREFIX] [--denoise] [--feature-spp N]
+//                  [--aov PREFIX] [--denoise] [--feature-spp N] [--adaptive THRESHOLD [--min-spp N]]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
@@ -18,6 +18,9 @@
 // (0.5 N + 0.5, linear) and PREFIX.depth.png ((z - z_min) / (z_max - z_min) over the covered pixels, background 1).  --denoise filters the
 // frame with the edge-avoiding A-trous filter before it is written.  Both use the features of the first --feature-spp passes (default:
 // min(spp, 16)), rendered on the first GPU.
+// --adaptive THRESHOLD renders with adaptive sampling: --spp is then the MAXIMUM per pixel, 8 x 8 tiles whose error
+// estimate has fallen to THRESHOLD stop early (0 = the library's default), and --min-spp N is the first level (default 8; every pixel
+// holds at least twice that, or --spp).  The image is rgba / count with each pixel's own count; --denoise works on the result.  One GPU.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
@@ -44,7 +47,9 @@ int main(int argc, char** argv) {
   float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, 0}, up[3] = {0, 1, 0}, fov = 30.0f, lens_radius = 0.0f, focus = 0.0f;
   const char* aov = nullptr;
   bool denoise = false;
-  size_t feature_spp = 0;
+  size_t feature_spp = 0, min_spp = 0;
+  bool adaptive = false;
+  float adaptive_threshold = PBRHIP_ADAPTIVE_THRESHOLD;
   std::vector<const char*> files;
   files.push_back(argv[0]);
   for (int i = 1; i < argc; ++i) {
@@ -81,6 +86,18 @@ int main(int argc, char** argv) {
     else if (a == "--aov") aov = value("--aov");
     else if (a == "--denoise") denoise = true;
     else if (a == "--feature-spp") feature_spp = number("--feature-spp", 0xFFFFFFFFul);
+    else if (a == "--min-spp") min_spp = number("--min-spp", 0xFFFFFFFFul);
+    else if (a == "--adaptive") {
+      const char* v = value("--adaptive");
+      char* end = nullptr;
+      const float x = strtof(v, &end);
+      if (end == v || *end || !(x >= 0.0f) || x > 3.0e38f) {
+        std::cerr << "--adaptive needs a finite threshold >= 0 (0: the default), got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
+      adaptive = true;
+      if (x > 0.0f) adaptive_threshold = x;
+    }
     else if (a == "--env-scale") {
       const char* v = value("--env-scale");
       char* end = nullptr;
@@ -128,6 +145,14 @@ int main(int argc, char** argv) {
   }
   if (feature_spp && !aov && !denoise) {
     std::cerr << "--feature-spp needs --aov or --denoise" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (min_spp && !adaptive) {
+    std::cerr << "--min-spp needs --adaptive" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (adaptive && gpus != 1) {
+    std::cerr << "--adaptive renders on one GPU (--gpus 1)" << std::endl;
     return EXIT_FAILURE;
   }
   if (files.size() < 2) {
@@ -184,7 +209,18 @@ int main(int argc, char** argv) {
   }
   std::atomic_bool cancel_render_flag(false);
   std::atomic_size_t finish_pass(0);
-  if (gpus == 1) {
+  if (adaptive) {
+    try {
+      pbrlab::AdaptiveOptions o;
+      o.threshold = adaptive_threshold, o.first_level = uint32_t(min_spp);
+      const pbrlab::AdaptiveResult r = pbrlab::RenderAdaptive(scene, uint32_t(width), uint32_t(height), uint32_t(samples), cancel_render_flag, &layer, &finish_pass, o);
+      std::cerr << "adaptive: " << r.samples << " samples (" << double(r.samples) / double(width * height) << " per pixel, at most " << samples << ") in "
+                << r.rounds << " rounds" << std::endl;
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return EXIT_FAILURE;
+    }
+  } else if (gpus == 1) {
     if (!pbrlab::Render(scene, uint32_t(width), uint32_t(height), uint32_t(samples), cancel_render_flag, &layer, &finish_pass))
       return EXIT_FAILURE;
   } else {

@@ -1003,8 +1003,9 @@ struct ChunkRun {
   float* d_rgba;
   uint32_t* d_count;
   std::chrono::steady_clock::time_point t_begin;
+  const uint32_t* pix;  // the pixels the paths of a pass are laid out over: ensure_pixels' list, or the caller's (render_impl)
+  uint32_t npix;
   const DScene& sc = s->dscene;
-  const uint32_t npix = s->pk_npix;
   const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;
   const bool trace_timing_only = (d->flags & PBRHIP_RENDER_TIMING) == 0 && (d->flags & PBRHIP_RENDER_TIMING_TRACE) != 0;
   const bool want_timing = (d->flags & (PBRHIP_RENDER_TIMING | PBRHIP_RENDER_TIMING_TRACE)) != 0;
@@ -1074,7 +1075,7 @@ struct ChunkRun {
     const size_t off = gr.slot0;
     gr.P.q_in += off, gr.P.q_out += off, gr.P.q_principled += off, gr.P.q_hair += off, gr.P.q_sss += off, gr.P.q_shadow += off, gr.P.q_shadow_in += off;
     for (int a = 0; a < 3; a++) gr.P.cam_org[a] = cam.org[a];
-    gr.P.cam = cam, gr.P.pix_index = s->path_pix.p, gr.P.npix = npix, gr.P.width = d->width, gr.P.first_pass = gr.first_pass;
+    gr.P.cam = cam, gr.P.pix_index = pix, gr.P.npix = npix, gr.P.width = d->width, gr.P.first_pass = gr.first_pass;
     gr.P.slot0 = gr.slot0, gr.P.seed_seq = d->seed_seq;
     gr.P.pass_run = pass_run_for(k, gr.npass, sc.num_curves != 0);
     gr.P.shadow_first = k.shadow_first, gr.P.susp_turns = 0u;
@@ -1240,7 +1241,7 @@ struct ChunkRun {
       Timer tm{s, want_timing, st};
       tm.only = trace_timing_only ? &S.ms_trace_closest : nullptr;
       HIPCHK(tm.begin(&S.ms_accumulate));
-      launch_accumulate(st, PA, s->path_pix.p, npix, gr.npass, d_rgba, d_count);
+      launch_accumulate(st, PA, pix, npix, gr.npass, d_rgba, d_count);
       HIPCHK(tm.end());
       HIPCHK(hipGetLastError());
       if (want_timing && !trace_timing_only) {  // (trace-only timing has nothing to collect here and must not stall the host)
@@ -1313,7 +1314,7 @@ static int read_render_stats(const pbrhip_scene* s, const Knobs& k, pbrhip_rende
 }
 
 int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
-                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats) {
+                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels, uint32_t num_pixels) {
   const auto t_begin = std::chrono::steady_clock::now();
   if (int rc = check_render_desc(s, d)) return rc;
   const Knobs k = read_knobs();
@@ -1328,7 +1329,8 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
   pbrhip_render_stats S;
   memset(&S, 0, sizeof(S));
   if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
-  const uint32_t npix = s->pk_npix;
+  const uint32_t* const pix = d_pixels ? d_pixels : s->path_pix.p;
+  const uint32_t npix = d_pixels ? num_pixels : s->pk_npix;
   const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;
   uint32_t done = 0;  // passes accumulated into the layer
   if (npix > 0 && d->num_sample > 0) {
@@ -1346,7 +1348,7 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
     // the environment's share of NEE events: the light count is known once the scene is committed
     s->dscene.env_p = s->dscene.num_lights ? 0.5f : 1.0f;
     s->dscene.env_area_scale = 1.0f - s->dscene.env_p;
-    ChunkRun run{s, d, k, P, S, cancel, finish_pass, d_rgba, d_count, t_begin};
+    ChunkRun run{s, d, k, P, S, cancel, finish_pass, d_rgba, d_count, t_begin, pix, npix};
     if (int rc = run.reserve_lanes(chunk_passes)) return rc;
     while (done < d->num_sample && !run.stop && !run.cancelled()) {  // render.cc:217
       uint32_t passes = 0;

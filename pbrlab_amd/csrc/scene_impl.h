@@ -157,6 +157,16 @@ struct DevGeom {
     ngeoms = 0, switch_ms = download_ms = 0.0;
   }
 };
+// What pbrhip_render_adaptive keeps between its rounds and calls (render_adaptive.cpp): lists of its own, so that path_pix,
+// pix_index and the pk_* key stay what ensure_pixels made them.
+struct AdaptiveBufs {
+  DevBuf<uint32_t> tiles[2], pixels;       // the active tiles (in / out of a decision step) and the next round's pixel list
+  DevBuf<uint32_t> keep, tile_off, pix_off, totals;
+  DevBuf<float4> snapshot;                 // A: W x H
+  DevBuf<float> tile_error;                // ceil(W / 8) x ceil(H / 8)
+  std::vector<uint32_t> tiles0;            // the rank's tiles in the order of ensure_pixels' list: round 0's
+  uint32_t key[7] = {0, 0, 0, 0, 0, 0, 0}; // the pk_* key tiles0 was derived under
+};
 inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
   return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
 }
@@ -248,6 +258,7 @@ struct pbrhip_scene {
   std::vector<size_t> xk_off, xk_cnt;             // per rank: first entry in xchg_pix / number of pixels
   uint32_t xk_key[7] = {0, 0, 0, 0, 0, 0, 0};     // w, h, world, block, first rank, end rank, skipped rank
   pb::DevBuf<float4> feat_albedo;                 // pbrhip_render_features: per material, albedo rgb | base-colour texture id (feature_kernels.h)
+  pb::AdaptiveBufs as;                            // pbrhip_render_adaptive's lists and snapshot (empty unless it was called)
 
   // The buffers of the device scene, each named once.  `s.member...` expands over the scenes given: f(counted, buffer) for one scene,
   // f(counted, buffer, its counterpart) for two.  `counted`: in pbrhip_scene_info's device bytes.  (Not the environment's tables.)
@@ -272,9 +283,11 @@ int ensure_pixels(pbrhip_scene* s, const Knobs& k, uint32_t w, uint32_t h, uint3
 int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t height, float scale, const float* world_to_env);
 // pbrhip_scene_set_camera's body (eye null: the reference's camera); also what pbrhip_scene_replicate calls to carry it over
 int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const float* up, float vfov, float lens_radius, float focus_distance);
-// the body of pbrhip_render_device (device pointers on the scene's device)
+// the body of pbrhip_render_device (device pointers on the scene's device).  d_pixels: null, or a device list of num_pixels of the
+// rank's pixels (y * width + x, distinct) to render in place of ensure_pixels' list (render_adaptive.cpp); the cached list stays as it is
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
-                uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats);
+                uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels = nullptr,
+                uint32_t num_pixels = 0);
 void bind_dscene(pbrhip_scene* s);  // points every DScene member that comes from a scene buffer at it, with its count (commit.cpp)
 inline const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id) {  // (per primitive in commit's loops: inline)
   const HostInstance& in = s->instances[instance_id];
