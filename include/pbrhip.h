@@ -389,6 +389,55 @@ int pbrhip_adaptive_step(int device, uint32_t width, uint32_t height, const floa
                          uint32_t n_now, float threshold, const uint32_t* tiles_in, uint32_t num_tiles_in, uint32_t* tiles_out,
                          uint32_t* num_tiles_out, uint32_t* pixels_out, uint32_t* num_pixels_out, float* tile_error_inout);
 
+/* ---- rendering along caller-supplied rays ----
+ * pbrhip_render with the first ray of every sample read from a buffer instead of computed by the scene's camera: a sensor model of the
+ * caller's own (a distorted lens, a lidar pattern, a stereo pair, a ring of probes), or one of the projections below.
+ *   rays        desc->width x desc->height is the shape of the ray grid; the ray of (pixel y * width + x, pass) is
+ *               rays[(ray_passes == 1 ? 0 : pass - desc->first_pass) * width * height + y * width + x].  ray_passes: 1 (one ray per pixel,
+ *               reused by every pass) or desc->num_sample; anything else is PBRHIP_EINVAL.
+ *   a ray       is traced as given: org, dir, and the interval [tmin, tmax] for the first segment.  dir must be of unit length; it is
+ *               NOT renormalised (that would change its bits).
+ *   generator   the path of (pixel, pass) draws from the generator every sample of this renderer owns, seeded with (pass << 32) + pixel
+ *               and desc->seed_seq, advanced by camera_draws draws (0 .. 16) first: a caller who builds its rays from the first draws of
+ *               that generator passes how many it took and gets path draws that do not repeat them.  With the rays of pbrhip_camera_rays
+ *               for every (pixel, pass) and camera_draws = 2 (the reference's camera, a pinhole) or 4 (a thin lens) the frame equals
+ *               pbrhip_render's bit for bit; so it does under any max_paths_in_flight, num_streams, tail_paths, tile_rank / tile_world /
+ *               shard_block, first_pass with PBRHIP_RENDER_NO_CLEAR (with per-pass rays the call's buffer starts at ITS first pass) and
+ *               tree builder, which all act as in pbrhip_render.
+ *   inactive    a ray with a NaN among its eight numbers, an infinite origin or direction component, a zero direction, tmin < 0 or
+ *               !(tmax >= tmin) is inactive: its sample adds exactly (0, 0, 0, 1) to rgba and 1 to count -- no fault, no environment.
+ * pbrhip_render_rays takes host rays; pbrhip_render_rays_device takes rays in device memory of the scene's device and `stream`, the
+ * stream they are produced on: they are read only after the work already enqueued there (pbrhip_scene_update_triangle_mesh_device's
+ * rule; the call itself is synchronous like pbrhip_render_device).  cancel, finish_pass, stats: as pbrhip_render's.
+ * PBRHIP_EINVAL ("NULL" in pbrhip_last_error) for a NULL scene, descriptor, rays or layer; PBRHIP_EINVAL for a bad ray_passes or
+ * camera_draws > 16, before any device work; then pbrhip_render's errors.
+ * Not provided: a ray source for pbrhip_render_multi, pbrhip_render_adaptive and the RCCL gather (render the shards with tile_rank /
+ * tile_world, which work here, and add them). */
+int pbrhip_render_rays(pbrhip_scene*, const pbrhip_render_desc*, const pbrhip_ray* rays, uint32_t ray_passes, uint32_t camera_draws,
+                       const volatile unsigned char* cancel, float* rgba, uint32_t* count, size_t* finish_pass, pbrhip_render_stats*);
+int pbrhip_render_rays_device(pbrhip_scene*, const pbrhip_render_desc*, const void* d_rays, uint32_t ray_passes, uint32_t camera_draws,
+                              void* stream, const volatile unsigned char* cancel, float* d_rgba, uint32_t* d_count, size_t* finish_pass,
+                              pbrhip_render_stats*);
+/* pbrhip_render_features_device over the same rays (layout, ray_passes, stream, inactive rays -- a miss -- as above): with the rays of
+ * pbrhip_camera_rays the buffers equal pbrhip_render_features' bit for bit.  The traversal starts from each ray's tmin and tmax. */
+int pbrhip_render_features_rays_device(pbrhip_scene*, const pbrhip_render_desc*, const void* d_rays, uint32_t ray_passes, void* stream,
+                                       float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count);
+/* The rays of three projections, written on the device into d_rays (num_pass x width x height pbrhip_ray, pass-major: the layout
+ * pbrhip_render_rays_device takes with ray_passes = num_pass, first_pass = desc->first_pass, camera_draws = 2), asynchronously on `stream`.
+ * The frame is the scene's pbrhip_scene_set_camera one (eye; f towards lookat, r = f x up, u = r x f, normalised); PBRHIP_ESTATE when the
+ * scene has none.  With jx, jy the first two draws of the sample's generator, sx = 2 (x + jx) / W - 1, sy = 1 - 2 (y + jy) / H and
+ * aspect = W / H, in float32:
+ *   LATLONG  phi = 2 pi (x + jx) / W - pi, theta = pi (y + jy) / H, dir = sin theta sin phi r + cos theta u + sin theta cos phi f: a 360 degree
+ *            panorama, the inverse of the environment light's texel mapping with the image centre along f.  param is ignored.
+ *   FISHEYE  equidistant: rho = sqrt((sx aspect)^2 + sy^2), angle = rho fov / 2, dir = sin(angle) (sx aspect r + sy u) / rho + cos(angle) f;
+ *            rho = 0: f; rho > 1: an inactive ray (the corners of the frame are black).  param: fov in degrees, up to 360; 0 = the
+ *            camera's vertical field of view.
+ *   ORTHO    org = eye + sx aspect param r + sy param u, dir = f; param: half the height of the view in world units, > 0.
+ * tmin = 0, tmax as the cameras'.  The scene need not be committed. */
+enum { PBRHIP_PROJECTION_LATLONG = 0, PBRHIP_PROJECTION_FISHEYE = 1, PBRHIP_PROJECTION_ORTHO = 2 };
+int pbrhip_projection_rays_device(pbrhip_scene*, uint32_t projection, float param, uint32_t width, uint32_t height, uint32_t first_pass,
+                                  uint32_t num_pass, uint64_t seed_seq, void* d_rays, void* stream);
+
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks
  * with index % world == r (pbrhip_render_desc.tile_rank / tile_world / shard_block) into a zeroed full-size layer, then the

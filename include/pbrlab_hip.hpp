@@ -29,6 +29,8 @@
 #include <variant>
 #include <vector>
 
+#include <dlfcn.h>
+
 #include "pbrhip.h"
 
 #ifndef PBRLAB_HIP_NO_MPARK_ALIAS
@@ -642,6 +644,142 @@ inline AdaptiveResult RenderAdaptive(const Scene& scene, const uint32_t width, c
                              &r.rounds) != PBRHIP_OK)
     throw std::runtime_error(std::string("pbrlab::RenderAdaptive: ") + pbrhip_last_error());
   return r;
+}
+
+// ---- rendering along caller-supplied rays and the projections (not in the reference) ----
+namespace detail {
+// Device memory for the calls below that take device pointers: the HIP runtime libpbrhip.so is linked with is in the process with it,
+// so its hipMalloc / hipFree / hipMemcpy are found by name and a caller of this header needs no HIP headers.
+class DeviceMem {
+public:
+  explicit DeviceMem(size_t bytes) {
+    if (!Fn().malloc_ || !Fn().free_ || !Fn().memcpy_) throw std::runtime_error("the HIP runtime of libpbrhip.so was not found in the process");
+    if (Fn().malloc_(&p_, bytes ? bytes : 1) != 0) throw std::runtime_error("hipMalloc failed");
+  }
+  ~DeviceMem() {
+    if (p_) Fn().free_(p_);
+  }
+  DeviceMem(const DeviceMem&) = delete;
+  DeviceMem& operator=(const DeviceMem&) = delete;
+  void* get() const { return p_; }
+  void Upload(const void* src, size_t bytes, size_t offset = 0) { Copy(static_cast<char*>(p_) + offset, src, bytes, 1); }
+  void Download(void* dst, size_t bytes, size_t offset = 0) const { Copy(dst, static_cast<const char*>(p_) + offset, bytes, 2); }
+
+private:
+  struct Fns {
+    int (*malloc_)(void**, size_t) = reinterpret_cast<int (*)(void**, size_t)>(dlsym(RTLD_DEFAULT, "hipMalloc"));
+    int (*free_)(void*) = reinterpret_cast<int (*)(void*)>(dlsym(RTLD_DEFAULT, "hipFree"));
+    int (*memcpy_)(void*, const void*, size_t, int) = reinterpret_cast<int (*)(void*, const void*, size_t, int)>(dlsym(RTLD_DEFAULT, "hipMemcpy"));
+  };
+  static const Fns& Fn() {
+    static const Fns f;
+    return f;
+  }
+  static void Copy(void* dst, const void* src, size_t bytes, int kind) {  // (hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2)
+    if (bytes && Fn().memcpy_(dst, src, bytes, kind) != 0) throw std::runtime_error("hipMemcpy failed");
+  }
+  void* p_ = nullptr;
+};
+inline pbrhip_render_desc RayDesc(uint32_t width, uint32_t height, uint32_t num_sample, uint32_t first_pass, bool no_clear) {
+  pbrhip_render_desc d = {};
+  d.width = width, d.height = height, d.num_sample = num_sample, d.first_pass = first_pass;
+  d.seed_seq = 1234567890;  // Render()'s
+  d.tile_world = 1;
+  d.flags = no_clear ? PBRHIP_RENDER_NO_CLEAR : 0u;
+  return d;
+}
+}  // namespace detail
+
+struct RayOptions {
+  uint32_t camera_draws = 2;  // draws of the sample's generator the rays' maker consumed (0 .. 16)
+  uint32_t first_pass = 0;
+  bool no_clear = false;      // accumulate on top of *layer
+};
+// pbrhip_render_rays: Render() with the first ray of every sample taken from `rays`: width x height of them (one per pixel, reused by
+// every pass) or num_sample x width x height (pass-major).  A ray is traced as given, tmin and tmax included; an inactive one adds
+// (0, 0, 0, 1).  Throws with pbrhip_last_error() on a library error.
+inline void RenderRays(const Scene& scene, const uint32_t width, const uint32_t height, const uint32_t num_sample, const std::vector<pbrhip_ray>& rays,
+                       const std::atomic_bool& cancel_render_flag, RenderLayer* layer, std::atomic_size_t* finish_pass = nullptr,
+                       const RayOptions& o = RayOptions()) {
+  const size_t npx = size_t(width) * height;
+  if (rays.size() != npx && rays.size() != npx * num_sample) throw std::runtime_error("pbrlab::RenderRays: width x height rays, or num_sample times as many");
+  if (!o.no_clear || layer->width != width || layer->height != height) layer->Resize(width, height);
+  scene.PushMaterialEdits();
+  const pbrhip_render_desc d = detail::RayDesc(width, height, num_sample, o.first_pass, o.no_clear);
+  std::atomic_size_t local_fin(0);
+  std::atomic_size_t* fin = finish_pass ? finish_pass : &local_fin;
+  fin->store(0);
+  if (pbrhip_render_rays(scene.handle(), &d, rays.data(), rays.size() == npx ? 1u : num_sample, o.camera_draws,
+                         reinterpret_cast<const volatile unsigned char*>(&cancel_render_flag), layer->rgba.data(), layer->count.data(),
+                         reinterpret_cast<size_t*>(fin), nullptr) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderRays: ") + pbrhip_last_error());
+}
+
+// pbrhip_render_features_rays_device: RenderFeatures() over the same rays (uploaded, and the buffers downloaded, by this call)
+inline void RenderFeaturesRays(const Scene& scene, const uint32_t width, const uint32_t height, const uint32_t num_sample,
+                               const std::vector<pbrhip_ray>& rays, FeatureLayer* features, const uint32_t first_pass = 0) {
+  const size_t npx = size_t(width) * height;
+  if (rays.size() != npx && rays.size() != npx * num_sample) throw std::runtime_error("pbrlab::RenderFeaturesRays: width x height rays, or num_sample times as many");
+  features->Resize(width, height);
+  scene.PushMaterialEdits();
+  const pbrhip_render_desc d = detail::RayDesc(width, height, num_sample, first_pass, false);
+  detail::DeviceMem d_rays(rays.size() * sizeof(pbrhip_ray)), d_out(npx * 36);  // albedo | normal_depth | count
+  d_rays.Upload(rays.data(), rays.size() * sizeof(pbrhip_ray));
+  char* const out = static_cast<char*>(d_out.get());
+  if (pbrhip_render_features_rays_device(scene.handle(), &d, d_rays.get(), rays.size() == npx ? 1u : num_sample, nullptr,
+                                         reinterpret_cast<float*>(out), reinterpret_cast<float*>(out + npx * 16),
+                                         reinterpret_cast<uint32_t*>(out + npx * 32)) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderFeaturesRays: ") + pbrhip_last_error());
+  d_out.Download(features->albedo.data(), npx * 16), d_out.Download(features->normal_depth.data(), npx * 16, npx * 16);
+  d_out.Download(features->count.data(), npx * 4, npx * 32);
+}
+
+enum Projection { kProjectionLatLong = PBRHIP_PROJECTION_LATLONG, kProjectionFisheye = PBRHIP_PROJECTION_FISHEYE, kProjectionOrtho = PBRHIP_PROJECTION_ORTHO };
+// pbrhip_projection_rays_device: the rays of passes [first_pass, first_pass + num_pass) of a width x height frame through `projection`
+// about the SetCamera() frame, as host rays.  param: fisheye -- the field of view in degrees (0: the camera's); ortho -- half the height.
+inline std::vector<pbrhip_ray> ProjectionRays(const Scene& scene, const Projection projection, const float param, const uint32_t width,
+                                              const uint32_t height, const uint32_t first_pass, const uint32_t num_pass) {
+  std::vector<pbrhip_ray> rays(size_t(width) * height * num_pass);
+  detail::DeviceMem d_rays(rays.size() * sizeof(pbrhip_ray));
+  if (pbrhip_projection_rays_device(scene.handle(), uint32_t(projection), param, width, height, first_pass, num_pass, 1234567890, d_rays.get(), nullptr) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::ProjectionRays: ") + pbrhip_last_error());
+  d_rays.Download(rays.data(), rays.size() * sizeof(pbrhip_ray));  // (a copy on the null stream: behind the kernel)
+  return rays;
+}
+
+constexpr size_t kRayBufferBytes = size_t(256) << 20;  // RenderProjection's cap on its ray buffer
+// A frame through a projection: in chunks of passes whose rays fit kRayBufferBytes (at least one pass), pbrhip_projection_rays_device
+// then pbrhip_render_rays_device with first_pass and PBRHIP_RENDER_NO_CLEAR per chunk, all in device memory of this call's own; the frame
+// does not depend on the chunking.  Clears and resizes *layer; cancel_render_flag as for Render(), *finish_pass counts the frame's passes.
+// Throws with pbrhip_last_error() on a library error.
+inline void RenderProjection(const Scene& scene, const Projection projection, const float param, const uint32_t width, const uint32_t height,
+                             const uint32_t num_sample, const std::atomic_bool& cancel_render_flag, RenderLayer* layer,
+                             std::atomic_size_t* finish_pass = nullptr) {
+  layer->Resize(width, height);
+  layer->Clear();
+  scene.PushMaterialEdits();
+  const size_t npx = size_t(width) * height;
+  if (npx == 0) throw std::runtime_error("pbrlab::RenderProjection: empty image");
+  const uint32_t chunk = uint32_t(std::max<size_t>(1, std::min<size_t>(std::max<uint32_t>(num_sample, 1u), kRayBufferBytes / (npx * sizeof(pbrhip_ray)))));
+  detail::DeviceMem d_rays(size_t(chunk) * npx * sizeof(pbrhip_ray)), d_layer(npx * 20);  // rgba | count
+  float* const d_rgba = static_cast<float*>(d_layer.get());
+  uint32_t* const d_count = reinterpret_cast<uint32_t*>(static_cast<char*>(d_layer.get()) + npx * 16);
+  if (finish_pass) finish_pass->store(0);
+  bool rendered = false;  // (the first chunk's call clears the device layer)
+  for (uint32_t done = 0; done < num_sample && !cancel_render_flag.load();) {
+    const uint32_t n = std::min(chunk, num_sample - done);
+    if (pbrhip_projection_rays_device(scene.handle(), uint32_t(projection), param, width, height, done, n, 1234567890, d_rays.get(), nullptr) != PBRHIP_OK)
+      throw std::runtime_error(std::string("pbrlab::RenderProjection: ") + pbrhip_last_error());
+    const pbrhip_render_desc d = detail::RayDesc(width, height, n, done, done != 0);
+    size_t fin = 0;
+    if (pbrhip_render_rays_device(scene.handle(), &d, d_rays.get(), n, 2u, nullptr, reinterpret_cast<const volatile unsigned char*>(&cancel_render_flag),
+                                  d_rgba, d_count, &fin, nullptr) != PBRHIP_OK)
+      throw std::runtime_error(std::string("pbrlab::RenderProjection: ") + pbrhip_last_error());
+    done += n, rendered = true;
+    if (finish_pass) finish_pass->store(done - n + fin);
+    if (fin < n) break;  // cancelled inside the chunk
+  }
+  if (rendered) d_layer.Download(layer->rgba.data(), npx * 16), d_layer.Download(layer->count.data(), npx * 4, npx * 16);
 }
 
 }  // namespace pbrlab

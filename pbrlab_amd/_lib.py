@@ -29,6 +29,7 @@ EXPORTS = [
     "pbrhip_tree_refit",
     "pbrhip_scene_update_triangle_mesh_device", "pbrhip_scene_update_curve_mesh_device", "pbrhip_scene_read_slots",
     "pbrhip_render_adaptive", "pbrhip_render_adaptive_device", "pbrhip_adaptive_step",
+    "pbrhip_render_rays", "pbrhip_render_rays_device", "pbrhip_render_features_rays_device", "pbrhip_projection_rays_device",
 ]
 
 
@@ -71,6 +72,10 @@ def lib():
         _lib.pbrhip_tree_refit.argtypes = [C.c_int, u32, vp, vp, vp, u32, vp, u32, C.c_int, vp, vp, u32]
         _lib.pbrhip_render_adaptive.argtypes = _lib.pbrhip_render_adaptive_device.argtypes = [vp, vp, f32, u32, vp, vp, vp, vp, vp, vp, vp]
         _lib.pbrhip_adaptive_step.argtypes = [C.c_int, u32, u32, vp, vp, u32, u32, f32, vp, u32, vp, vp, vp, vp, vp]
+        _lib.pbrhip_render_rays.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+        _lib.pbrhip_render_rays_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        _lib.pbrhip_render_features_rays_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
+        _lib.pbrhip_projection_rays_device.argtypes = [vp, u32, f32, u32, u32, u32, u32, C.c_uint64, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

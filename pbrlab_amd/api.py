@@ -426,6 +426,31 @@ class Scene:
                                        C.c_size_t(len(xyp)), C.c_void_p(rays.ctypes.data)))
         return rays
 
+    def ProjectionRays(self, projection, width, height, first_pass, num_pass, param=0.0, out=None, *, seed_seq=1234567890, stream=None):
+        """pbrhip_projection_rays_device: the rays of passes [first_pass, first_pass + num_pass) of a width x height frame through
+        `projection` -- "latlong" (a 360 degree panorama, param ignored), "fisheye" (equidistant; param = field of view in degrees up to
+        360, 0 = the camera's fov) or "ortho" (param = half the height in world units) -- about SetCamera's frame, written on the
+        device.  out: None (a new DeviceRays), a DeviceRays of that shape, or a float32 (num_pass, H, W, 8) tensor on the scene's
+        device.  Returns out; RenderRays takes it with camera_draws = 2 and first_pass."""
+        if isinstance(projection, str):
+            if projection not in _PROJECTIONS:
+                raise ValueError(f"unknown projection {projection!r}: one of {sorted(_PROJECTIONS)}")
+            projection = _PROJECTIONS[projection]
+        shape = (int(num_pass), int(height), int(width))
+        if out is None:
+            out = DeviceRays(shape, self.device)
+        if isinstance(out, DeviceRays):
+            if out.shape != shape:
+                raise ValueError(f"out has the shape {out.shape}, the rays {shape}")
+            ptr = out.ptr
+        else:
+            where, ptr, grid, _ = _ray_source(out, self, num_pass)
+            if where != "device" or grid != shape:
+                raise ValueError(f"out: a float32 tensor of shape {shape + (8,)} on the scene's device")
+        _chk(self.L.pbrhip_projection_rays_device(self.h, int(projection), float(param), int(width), int(height), int(first_pass), int(num_pass),
+                                                  C.c_uint64(seed_seq), C.c_void_p(ptr), _device_stream(stream, out)))
+        return out
+
     def AddLightParam(self, emission):
         e = np.ascontiguousarray(emission, np.float32).reshape(3)
         out = C.c_uint32()
@@ -593,6 +618,255 @@ def RenderFeatures(scene, width, height, num_sample, layer=None, *, first_pass=0
         layer.Resize(width, height)
     _chk(L.pbrhip_render_features(scene.h, C.byref(desc), layer.albedo.ctypes.data, layer.normal_depth.ctypes.data, layer.count.ctypes.data))
     return layer
+
+
+# pbrhip_projection_rays_device's projections (include/pbrhip.h PBRHIP_PROJECTION_*)
+PROJECTION_LATLONG, PROJECTION_FISHEYE, PROJECTION_ORTHO = 0, 1, 2
+_PROJECTIONS = {"latlong": PROJECTION_LATLONG, "fisheye": PROJECTION_FISHEYE, "ortho": PROJECTION_ORTHO}
+RAY_BUFFER_BYTES = 256 << 20  # RenderProjection's cap on its ray buffer: it renders in chunks of passes that fit
+
+
+class DeviceRays:
+    """A buffer of rays in device memory, allocated through the library (the HIP runtime it is linked with): .ptr, .shape = (P, H, W),
+    .device.  numpy() downloads it as a RAY_DT array; close() (or the collector) frees it."""
+
+    def __init__(self, shape, device):
+        self.shape, self.device = tuple(int(n) for n in (shape if isinstance(shape, (tuple, list)) else (shape,))), int(device)
+        self.L = _lib.lib()
+        self.nbytes = int(np.prod(self.shape)) * RAY_DT.itemsize
+        _chk(self.L.pbrhip_set_device(self.device))
+        p = C.c_void_p()
+        self._hip(self.L.hipMalloc(C.byref(p), C.c_size_t(max(self.nbytes, 1))), "hipMalloc")
+        self.ptr = p.value
+
+    @staticmethod
+    def _hip(rc, what):
+        if rc != 0:
+            raise PbrHipError(-4, f"{what} failed with HIP error {rc}")
+
+    def upload(self, rays):
+        a = np.ascontiguousarray(rays)
+        if a.nbytes != self.nbytes:
+            raise ValueError("upload: the array does not have the buffer's size")
+        self._hip(self.L.hipMemcpy(C.c_void_p(self.ptr), C.c_void_p(a.ctypes.data), C.c_size_t(self.nbytes), 1), "hipMemcpy")
+        return self
+
+    def numpy(self):
+        out = np.zeros(self.shape, RAY_DT)
+        if self.nbytes:
+            self._hip(self.L.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(self.ptr), C.c_size_t(self.nbytes), 2), "hipMemcpy")
+        return out
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self.L.hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _ray_grid(shape, last, what):
+    """(P, H, W) of a ray array's shape: (H, W) or (P, H, W), followed by `last` when it is not None"""
+    shape = tuple(int(n) for n in shape)
+    if last is not None:
+        if len(shape) not in (3, 4) or shape[-1] != last:
+            raise ValueError(f"{what} must have the shape (H, W, {last}) or (P, H, W, {last}), not {shape}")
+        shape = shape[:-1]
+    elif len(shape) not in (2, 3):
+        raise ValueError(f"{what} must have the shape (H, W) or (P, H, W), not {shape}")
+    p, h, w = ((1,) + shape)[-3:]
+    if h <= 0 or w <= 0 or p <= 0:
+        raise ValueError(f"{what} is empty: {shape}")
+    return p, h, w
+
+
+def _ray_source(rays, scene, num_sample):
+    """The rays argument of RenderRays / RenderFeaturesRays -> (where, pointer, (P, H, W), keep-alive): a numpy RAY_DT array (H, W) or
+    (P, H, W), a numpy float32 array (H, W, 8) or (P, H, W, 8) (org, tmin, dir, tmax), a DeviceRays, a (pointer, shape) pair of device
+    memory, or a float32 tensor on the scene's device with data_ptr() and the float shapes.  P is 1 or num_sample.  TypeError /
+    ValueError here, before any C call."""
+    keep = rays
+    if isinstance(rays, np.ndarray):
+        if rays.dtype == RAY_DT:
+            grid = _ray_grid(rays.shape, None, "a RAY_DT array")
+        elif rays.dtype == np.float32:
+            grid = _ray_grid(rays.shape, 8, "a float32 ray array")
+        else:
+            raise TypeError(f"a ray array must be RAY_DT or float32, not {rays.dtype}")
+        keep = np.ascontiguousarray(rays)
+        where, ptr = "host", keep.ctypes.data
+    elif isinstance(rays, DeviceRays):
+        where, ptr, grid = "device", rays.ptr, _ray_grid(rays.shape, None, "a DeviceRays buffer")
+    elif isinstance(rays, (tuple, list)):
+        if len(rays) != 2 or not isinstance(rays[1], (tuple, list)):
+            raise TypeError("device rays are a tensor, a DeviceRays or a (pointer, (P, H, W)) pair")
+        if not rays[0]:
+            raise ValueError("the ray pointer is NULL")
+        where, ptr, grid = "device", int(rays[0]), _ray_grid(rays[1], None, "a device ray buffer")
+    elif hasattr(rays, "data_ptr"):
+        if not str(getattr(rays, "dtype", "")).endswith("float32"):
+            raise TypeError(f"a ray tensor must be float32, not {getattr(rays, 'dtype', None)}")
+        grid = _ray_grid(getattr(rays, "shape", ()), 8, "a ray tensor")
+        if not rays.is_contiguous():
+            raise ValueError("a ray tensor must be contiguous")
+        dev = getattr(rays, "device", None)
+        if getattr(dev, "type", None) != "cuda":
+            raise ValueError(f"a ray tensor must be in GPU memory, not on {dev}")
+        want = getattr(scene, "device", None)
+        if want is not None and dev.index is not None and dev.index != want:
+            raise ValueError(f"the rays are on device {dev.index}, the scene on device {want}")
+        where, ptr = "device", int(rays.data_ptr())
+    else:
+        raise TypeError(f"{type(rays).__name__} is no ray array")
+    if grid[0] not in (1, int(num_sample)):
+        raise ValueError(f"{grid[0]} planes of rays: one (reused by every pass) or num_sample = {num_sample}")
+    return where, ptr, grid, keep
+
+
+def RenderRays(scene, rays, num_sample, layer=None, *, camera_draws=2, device_out=None, stream=None, cancel_render_flag=None,
+               finish_pass=None, **desc_kw):
+    """pbrhip_render_rays: Render with the first ray of every sample taken from `rays` (see _ray_source for what it may
+    be: host or device, (H, W) = one ray per pixel reused by every pass, or (num_sample, H, W)); the image is W x H.  A ray is traced as
+    given, tmin and tmax included; its direction must be of unit length.  camera_draws (0 .. 16): how many draws of the sample's
+    generator the rays' maker consumed -- 2 replays the reference's camera and a pinhole from Scene.CameraRays bit for bit, 4 a thin
+    lens.  An inactive ray (NaN, infinite, zero direction, tmin < 0, tmax < tmin) adds (0, 0, 0, 1).  desc_kw: Render's keywords
+    (first_pass, seed_seq, tile_rank, tile_world, max_paths_in_flight, flags, num_streams, tail_paths, shard_block); with per-pass rays
+    and first_pass the buffer starts at first_pass.  stream: the hipStream_t device rays are produced on (None: torch's current stream
+    for a tensor, else the null stream).  Returns the layer (made when None; resized and cleared unless RENDER_NO_CLEAR) with .stats
+    attached; with device_out = (rgba_ptr, count_ptr) DEVICE pointers no layer is touched and the stats are returned."""
+    if not 0 <= int(camera_draws) <= 16:
+        raise ValueError(f"camera_draws {camera_draws} is not in 0 .. 16")
+    where, ptr, (planes, height, width), keep = _ray_source(rays, scene, num_sample)
+    if where == "host" and device_out is not None:
+        raise ValueError("device_out needs rays in device memory")
+    L = _lib.lib()
+    desc = _desc(width, height, num_sample, **desc_kw)
+    st = RenderStats()
+    fin = finish_pass if finish_pass is not None else C.c_size_t(0)
+    cancel = C.byref(cancel_render_flag) if cancel_render_flag is not None else None
+    h = scene.h if scene is not None else None
+    if device_out is not None:
+        _chk(L.pbrhip_render_rays_device(h, C.byref(desc), ptr, planes, int(camera_draws), _device_stream(stream, rays), cancel,
+                                         C.c_void_p(device_out[0]), C.c_void_p(device_out[1]), C.byref(fin), C.byref(st)))
+        return st.as_dict()
+    if layer is None:
+        layer = RenderLayer()
+    if not (desc.flags & RENDER_NO_CLEAR) or (layer.width, layer.height) != (width, height):
+        layer.Resize(width, height)
+    if where == "host":
+        _chk(L.pbrhip_render_rays(h, C.byref(desc), ptr, planes, int(camera_draws), cancel, layer.rgba.ctypes.data, layer.count.ctypes.data,
+                                  C.byref(fin), C.byref(st)))
+    elif h is None:
+        _chk(L.pbrhip_render_rays_device(None, C.byref(desc), ptr, planes, int(camera_draws), None, cancel, None, None, None, None))
+    else:  # device rays into a host layer: through a device layer of the call's own
+        out = DeviceRays((5 * height * width + 7) // 8, scene.device)  # rgba (16 B) + count (4 B) per pixel, in units of 32 bytes
+        try:
+            d_rgba, d_count = out.ptr, out.ptr + 16 * height * width
+            if desc.flags & RENDER_NO_CLEAR:
+                DeviceRays._hip(L.hipMemcpy(C.c_void_p(d_rgba), C.c_void_p(layer.rgba.ctypes.data), C.c_size_t(layer.rgba.nbytes), 1), "hipMemcpy")
+                DeviceRays._hip(L.hipMemcpy(C.c_void_p(d_count), C.c_void_p(layer.count.ctypes.data), C.c_size_t(layer.count.nbytes), 1), "hipMemcpy")
+            _chk(L.pbrhip_render_rays_device(h, C.byref(desc), ptr, planes, int(camera_draws), _device_stream(stream, rays), cancel,
+                                             C.c_void_p(d_rgba), C.c_void_p(d_count), C.byref(fin), C.byref(st)))
+            DeviceRays._hip(L.hipMemcpy(C.c_void_p(layer.rgba.ctypes.data), C.c_void_p(d_rgba), C.c_size_t(layer.rgba.nbytes), 2), "hipMemcpy")
+            DeviceRays._hip(L.hipMemcpy(C.c_void_p(layer.count.ctypes.data), C.c_void_p(d_count), C.c_size_t(layer.count.nbytes), 2), "hipMemcpy")
+        finally:
+            out.close()
+    layer.stats = st.as_dict()
+    return layer
+
+
+def RenderFeaturesRays(scene, rays, num_sample, layer=None, *, device_out=None, stream=None, first_pass=0, seed_seq=1234567890,
+                       tile_rank=0, tile_world=1, max_paths_in_flight=0, shard_block=0, no_clear=False):
+    """pbrhip_render_features_rays_device: RenderFeatures over the rays RenderRays takes (the first hit of each ray inside its tmin and
+    tmax; an inactive ray is a miss).  Host rays are uploaded and the FeatureLayer downloaded through buffers of the call's own.
+    device_out: (albedo_ptr, normal_depth_ptr, count_ptr) DEVICE pointers (0 / None = not wanted) instead of a layer, with device rays."""
+    where, ptr, (planes, height, width), keep = _ray_source(rays, scene, num_sample)
+    if where == "host" and device_out is not None:
+        raise ValueError("device_out needs rays in device memory")
+    L = _lib.lib()
+    desc = RenderDesc(width, height, num_sample, first_pass, seed_seq, tile_rank, tile_world, max_paths_in_flight,
+                      RENDER_NO_CLEAR if no_clear else 0, 0, 0, shard_block)
+    h = scene.h if scene is not None else None
+    if device_out is not None:
+        _chk(L.pbrhip_render_features_rays_device(h, C.byref(desc), ptr, planes, _device_stream(stream, rays),
+                                                  *[C.c_void_p(p or None) for p in device_out]))
+        return None
+    if h is None:
+        _chk(L.pbrhip_render_features_rays_device(None, C.byref(desc), ptr, planes, None, None, None, None))
+    if layer is None:
+        layer = FeatureLayer()
+    if not no_clear or (layer.width, layer.height) != (width, height):
+        layer.Resize(width, height)
+    npx = height * width
+    own = DeviceRays((planes, height, width), scene.device).upload(keep) if where == "host" else None
+    out = DeviceRays((9 * npx + 7) // 8, scene.device)  # albedo, normal_depth (16 B each) + count (4 B) per pixel, in units of 32 bytes
+    try:
+        ptrs = (out.ptr, out.ptr + 16 * npx, out.ptr + 32 * npx)
+        arrays = (layer.albedo, layer.normal_depth, layer.count)
+        if no_clear:
+            for p, a in zip(ptrs, arrays):
+                DeviceRays._hip(L.hipMemcpy(C.c_void_p(p), C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), 1), "hipMemcpy")
+        _chk(L.pbrhip_render_features_rays_device(h, C.byref(desc), own.ptr if own else ptr, planes, None if own else _device_stream(stream, rays),
+                                                  *[C.c_void_p(p) for p in ptrs]))
+        for p, a in zip(ptrs, arrays):
+            DeviceRays._hip(L.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(p), C.c_size_t(a.nbytes), 2), "hipMemcpy")
+    finally:
+        out.close()
+        if own:
+            own.close()
+    return layer
+
+
+def RenderProjection(scene, projection, width, height, num_sample, layer=None, param=0.0, *, rays=None, **kw):
+    """A frame through one of Scene.ProjectionRays' projections ("latlong", "fisheye", "ortho"; the frame is SetCamera's): in chunks of
+    passes whose rays fit RAY_BUFFER_BYTES (256 MiB; at least one pass), ProjectionRays then RenderRays(first_pass=..., flags |=
+    RENDER_NO_CLEAR) per chunk -- the result does not depend on the chunking.  The ray buffer is a DeviceRays of the call's own, or
+    `rays`: a float32 tensor of at least chunk x H x W x 8 elements on the scene's device (torch is not imported otherwise).  kw:
+    RenderRays' keywords.  Returns the layer (or the last chunk's stats with device_out)."""
+    width, height, num_sample = int(width), int(height), int(num_sample)
+    if width <= 0 or height <= 0:
+        raise ValueError("empty image")
+    first_pass, flags = int(kw.pop("first_pass", 0)), int(kw.pop("flags", 0))
+    seed_seq = kw.get("seed_seq", 1234567890)
+    chunk = max(1, min(max(num_sample, 1), RAY_BUFFER_BYTES // (RAY_DT.itemsize * width * height)))
+    if rays is not None:
+        if not hasattr(rays, "data_ptr") or not str(getattr(rays, "dtype", "")).endswith("float32") or not rays.is_contiguous():
+            raise TypeError("rays: a contiguous float32 tensor on the scene's device")
+        chunk = min(chunk, int(rays.numel()) // (8 * width * height))
+        if chunk < 1:
+            raise ValueError("rays: room for at least one pass of H x W x 8 floats")
+    if kw.get("device_out") is None:
+        if layer is None:
+            layer = RenderLayer()
+        if not (flags & RENDER_NO_CLEAR) or (layer.width, layer.height) != (width, height):
+            layer.Resize(width, height)
+    own = None
+    out = None
+    try:
+        done = 0
+        while done < num_sample:
+            n = min(chunk, num_sample - done)
+            if rays is not None:
+                buf = rays.view(-1)[:n * height * width * 8].view(n, height, width, 8)
+                scene.ProjectionRays(projection, width, height, first_pass + done, n, param, out=buf, seed_seq=seed_seq, stream=kw.get("stream"))
+            else:
+                if own is None or own.shape[0] != n:
+                    if own is not None:
+                        own.close()
+                    own = DeviceRays((n, height, width), scene.device)
+                buf = scene.ProjectionRays(projection, width, height, first_pass + done, n, param, out=own, seed_seq=seed_seq, stream=kw.get("stream"))
+            # (every chunk but a clearing call's first accumulates on top)
+            out = RenderRays(scene, buf, n, layer, camera_draws=2, first_pass=first_pass + done,
+                             flags=flags | (RENDER_NO_CLEAR if done else 0), **kw)
+            done += n
+    finally:
+        if own is not None:
+            own.close()
+    return out if out is not None else layer
 
 
 def _denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo):

@@ -4,6 +4,7 @@
 //                  [--gpus N] [--bvh host|gpu|gpu-wide] [--env FILE [--env-scale S]]
 //                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
 //                  [--aov PREFIX] [--denoise] [--feature-spp N] [--adaptive THRESHOLD [--min-spp N]]
+//                  [--projection latlong|fisheye|ortho [--ortho-height H]]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
 // directory = sRGB(rgba / count) quantised as byte(x * 256).  --gpus N deals 16 x 16 pixel blocks to N ranks, rank g on
@@ -21,6 +22,9 @@
 // --adaptive THRESHOLD renders with adaptive sampling: --spp is then the MAXIMUM per pixel, 8 x 8 tiles whose error
 // estimate has fallen to THRESHOLD stop early (0 = the library's default), and --min-spp N is the first level (default 8; every pixel
 // holds at least twice that, or --spp).  The image is rgba / count with each pixel's own count; --denoise works on the result.  One GPU.
+// --projection replaces the --eye / --lookat camera's perspective projection: latlong = a 360 degree panorama with the
+// image centre along the view direction, fisheye = equidistant with --fov (up to 360) across the image height and black corners, ortho =
+// parallel rays over a view --ortho-height world units high.  One GPU; not with --adaptive, --aov or --denoise.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
@@ -50,6 +54,8 @@ int main(int argc, char** argv) {
   size_t feature_spp = 0, min_spp = 0;
   bool adaptive = false;
   float adaptive_threshold = PBRHIP_ADAPTIVE_THRESHOLD;
+  int projection = -1;  // pbrlab::Projection, or none
+  float ortho_height = 0.0f;
   std::vector<const char*> files;
   files.push_back(argv[0]);
   for (int i = 1; i < argc; ++i) {
@@ -97,6 +103,23 @@ int main(int argc, char** argv) {
       }
       adaptive = true;
       if (x > 0.0f) adaptive_threshold = x;
+    }
+    else if (a == "--projection") {
+      const std::string v = value("--projection");
+      projection = v == "latlong" ? int(pbrlab::kProjectionLatLong) : v == "fisheye" ? int(pbrlab::kProjectionFisheye) : v == "ortho" ? int(pbrlab::kProjectionOrtho) : -1;
+      if (projection < 0) {
+        std::cerr << "--projection needs latlong, fisheye or ortho, got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
+    }
+    else if (a == "--ortho-height") {
+      const char* v = value("--ortho-height");
+      char* end = nullptr;
+      ortho_height = strtof(v, &end);
+      if (end == v || *end || !(ortho_height > 0.0f) || ortho_height > 3.0e38f) {
+        std::cerr << "--ortho-height needs a finite number > 0, got '" << v << "'" << std::endl;
+        exit(EXIT_FAILURE);
+      }
     }
     else if (a == "--env-scale") {
       const char* v = value("--env-scale");
@@ -155,6 +178,22 @@ int main(int argc, char** argv) {
     std::cerr << "--adaptive renders on one GPU (--gpus 1)" << std::endl;
     return EXIT_FAILURE;
   }
+  if (projection >= 0 && !have_eye) {
+    std::cerr << "--projection needs --eye and --lookat" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (projection >= 0 && (adaptive || aov || denoise || gpus != 1)) {
+    std::cerr << "--projection renders on one GPU, without --adaptive, --aov or --denoise" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if ((projection == int(pbrlab::kProjectionOrtho)) != (ortho_height > 0.0f)) {
+    std::cerr << (ortho_height > 0.0f ? "--ortho-height needs --projection ortho" : "--projection ortho needs --ortho-height") << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (projection == int(pbrlab::kProjectionFisheye) && !(fov > 0.0f && fov <= 360.0f)) {
+    std::cerr << "--projection fisheye needs --fov in (0, 360]" << std::endl;
+    return EXIT_FAILURE;
+  }
   if (files.size() < 2) {
     std::cerr << "not specified obj filename" << std::endl;
     return EXIT_FAILURE;
@@ -201,7 +240,8 @@ int main(int argc, char** argv) {
   }
   if (have_eye) {
     try {
-      scene.SetCamera(eye, lookat, up, fov, lens_radius, focus);
+      // (a projection takes the frame alone: a fisheye's field of view goes to it, beyond what a perspective camera accepts)
+      scene.SetCamera(eye, lookat, up, projection >= 0 ? 30.0f : fov, lens_radius, focus);
     } catch (const std::exception& e) {
       std::cerr << "camera: " << e.what() << std::endl;
       return EXIT_FAILURE;
@@ -216,6 +256,15 @@ int main(int argc, char** argv) {
       const pbrlab::AdaptiveResult r = pbrlab::RenderAdaptive(scene, uint32_t(width), uint32_t(height), uint32_t(samples), cancel_render_flag, &layer, &finish_pass, o);
       std::cerr << "adaptive: " << r.samples << " samples (" << double(r.samples) / double(width * height) << " per pixel, at most " << samples << ") in "
                 << r.rounds << " rounds" << std::endl;
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return EXIT_FAILURE;
+    }
+  } else if (projection >= 0) {
+    try {
+      const float param = projection == int(pbrlab::kProjectionOrtho) ? 0.5f * ortho_height : projection == int(pbrlab::kProjectionFisheye) ? fov : 0.0f;
+      pbrlab::RenderProjection(scene, pbrlab::Projection(projection), param, uint32_t(width), uint32_t(height), uint32_t(samples), cancel_render_flag, &layer,
+                               &finish_pass);
     } catch (const std::exception& e) {
       std::cerr << e.what() << std::endl;
       return EXIT_FAILURE;

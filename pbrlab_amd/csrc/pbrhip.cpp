@@ -1005,13 +1005,15 @@ struct ChunkRun {
   std::chrono::steady_clock::time_point t_begin;
   const uint32_t* pix;  // the pixels the paths of a pass are laid out over: ensure_pixels' list, or the caller's (render_impl)
   uint32_t npix;
+  const RaySource* rays;  // the caller's first rays, or null: the scene's camera
   const DScene& sc = s->dscene;
   const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;
   const bool trace_timing_only = (d->flags & PBRHIP_RENDER_TIMING) == 0 && (d->flags & PBRHIP_RENDER_TIMING_TRACE) != 0;
   const bool want_timing = (d->flags & (PBRHIP_RENDER_TIMING | PBRHIP_RENDER_TIMING_TRACE)) != 0;
   const Camera cam = make_camera(s, d->width, d->height);
   // a user camera: k_generate_camera stores each path's first ray and the first bounce is an ordinary one (PathState::first = 0)
-  const bool user_cam = s->cam_set;
+  // ... and so does a ray source: k_generate_rays stores the caller's rays in the same places
+  const bool user_cam = s->cam_set && !rays;
   const UserCamera ucam = user_cam ? make_user_camera(s, d->width, d->height) : UserCamera{};
   const uint64_t rng_inc = (d->seed_seq << 1u) | 1u;  // pcg32_srandom (rng.h:30-36)
   const uint32_t tail_paths = k.tail_paths.value_or(d->tail_paths == 0xFFFFFFFFu ? 0u : (d->tail_paths ? d->tail_paths : 262144u));
@@ -1110,7 +1112,8 @@ struct ChunkRun {
     hc[kCntIn] = gr.n0;
     HIPCHK(hipMemcpyAsync(gr.P.counts, hc, sizeof(uint32_t) * kCntNum, hipMemcpyHostToDevice, gst));
     HIPCHK(gr.tm.begin(&S.ms_generate));
-    if (user_cam) launch_generate_camera(gst, gr.P, ucam, d->height, gr.n0);
+    if (rays) launch_generate_rays(gst, gr.P, *rays, gr.n0);
+    else if (user_cam) launch_generate_camera(gst, gr.P, ucam, d->height, gr.n0);
     else launch_generate(gst, gr.P, gr.n0);
     HIPCHK(gr.tm.end());
     return feed(gr);
@@ -1137,7 +1140,7 @@ struct ChunkRun {
   int enqueue_iteration(Group& gr, uint32_t n_upper, bool to_tail) {
     hipStream_t gst = lane_stream(gr.lane);
     const uint32_t n = std::max(n_upper, 1u);
-    gr.P.first = gr.iters++ == 0 && !user_cam ? 1u : 0u;
+    gr.P.first = gr.iters++ == 0 && !user_cam && !rays ? 1u : 0u;
     // the launch's suspend records: written by this k_trace, read by the next (alternating halves of the lane's area)
     uint32_t* const susp_lane = s->susp.p + (size_t)gr.lane * 2u * kSuspRecords * kSuspWords;
     gr.P.susp_out = susp_lane + (size_t)(gr.iters & 1u) * kSuspRecords * kSuspWords;
@@ -1314,7 +1317,8 @@ static int read_render_stats(const pbrhip_scene* s, const Knobs& k, pbrhip_rende
 }
 
 int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
-                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels, uint32_t num_pixels) {
+                    uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels, uint32_t num_pixels,
+                    const RaySource* rays) {
   const auto t_begin = std::chrono::steady_clock::now();
   if (int rc = check_render_desc(s, d)) return rc;
   const Knobs k = read_knobs();
@@ -1348,7 +1352,9 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
     // the environment's share of NEE events: the light count is known once the scene is committed
     s->dscene.env_p = s->dscene.num_lights ? 0.5f : 1.0f;
     s->dscene.env_area_scale = 1.0f - s->dscene.env_p;
-    ChunkRun run{s, d, k, P, S, cancel, finish_pass, d_rgba, d_count, t_begin, pix, npix};
+    RaySource src{};
+    if (rays) src = *rays, src.base_pass = d->first_pass, src.height = d->height;
+    ChunkRun run{s, d, k, P, S, cancel, finish_pass, d_rgba, d_count, t_begin, pix, npix, rays ? &src : nullptr};
     if (int rc = run.reserve_lanes(chunk_passes)) return rc;
     while (done < d->num_sample && !run.stop && !run.cancelled()) {  // render.cc:217
       uint32_t passes = 0;
@@ -1420,7 +1426,9 @@ static float4 feature_albedo(const HostMaterial& hm) {
 }
 
 // the body of pbrhip_render_features_device: device pointers on the scene's device, each may be null
-static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count) {
+// rays: null, or the caller's rays in place of the scene's camera (k_features_rays)
+static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count,
+                         const RaySource* rays = nullptr) {
   if (int rc = check_render_desc(s, d)) return rc;
   if (d->num_sample == 0) return fail(PBRHIP_EINVAL, "render_features: no samples");
   if ((uint64_t)d->first_pass + d->num_sample > (1ull << 32)) return fail(PBRHIP_EINVAL, "render_features: the passes do not fit 32 bits");
@@ -1458,9 +1466,16 @@ static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_
   // chunk to chunk in pass order, so the split is invisible in the result
   uint32_t chunk = d->num_sample;
   if (d->max_paths_in_flight) chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(d->num_sample, d->max_paths_in_flight / npix));
+  FeatureRayArgs ra{};
+  if (rays) {
+    ra.src = *rays, ra.src.base_pass = d->first_pass, ra.src.height = d->height;
+    ra.width = d->width, ra.pix = a.pix, ra.npix = npix, ra.mat_albedo = a.mat_albedo;
+    ra.albedo_hits = a.albedo_hits, ra.normal_depth = a.normal_depth, ra.count = a.count, ra.overflow = a.overflow, ra.spill = a.spill;
+  }
   for (uint32_t done = 0; done < d->num_sample; done += chunk) {
-    a.first_pass = d->first_pass + done, a.npass = std::min(chunk, d->num_sample - done);
-    launch_features(st, s->dscene, a, k);
+    a.first_pass = ra.first_pass = d->first_pass + done, a.npass = ra.npass = std::min(chunk, d->num_sample - done);
+    if (rays) launch_features_rays(st, s->dscene, ra, k);
+    else launch_features(st, s->dscene, a, k);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, st));
@@ -1498,6 +1513,114 @@ extern "C" int pbrhip_render_features(pbrhip_scene* s, const pbrhip_render_desc*
     if (normal_depth) HIPCHK(hipMemcpyAsync(normal_depth, d_n.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     if (count) HIPCHK(hipMemcpyAsync(count, d_c.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+// ------------------------------------------------------------------ rendering along caller-supplied rays
+// what the ray-list entry points check before anything touches a device: pointers, then the shape of the ray buffer, then the scene
+static int check_ray_args(const char* who, const pbrhip_scene* s, const pbrhip_render_desc* d, const void* rays, uint32_t ray_passes,
+                          uint32_t camera_draws) {
+  if (!d || !rays) return fail(PBRHIP_EINVAL, "%s: NULL descriptor or rays", who);
+  if (ray_passes != 1u && ray_passes != d->num_sample)
+    return fail(PBRHIP_EINVAL, "%s: ray_passes %u is neither 1 nor num_sample %u", who, ray_passes, d->num_sample);
+  if (camera_draws > kMaxCameraDraws) return fail(PBRHIP_EINVAL, "%s: camera_draws %u (at most %u)", who, camera_draws, kMaxCameraDraws);
+  if (!s) return fail(PBRHIP_EINVAL, "%s: NULL scene", who);
+  return PBRHIP_OK;
+}
+// the caller's rays are read only after what its stream already holds (pbrhip_scene_update_triangle_mesh_device's rule): an event there,
+// and the scene's stream -- behind which every path group starts -- waits for it
+static int wait_for_caller_stream(pbrhip_scene* s, void* stream) {
+  hipEvent_t ev;
+  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
+  (void)hipEventDestroy(ev);
+  HIPCHK(e);
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_render_rays_device(pbrhip_scene* s, const pbrhip_render_desc* d, const void* d_rays, uint32_t ray_passes,
+                                         uint32_t camera_draws, void* stream, const volatile unsigned char* cancel, float* d_rgba,
+                                         uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats) {
+  return guarded([&]() -> int {
+    if (!d_rgba || !d_count) return fail(PBRHIP_EINVAL, "render_rays: NULL layer");
+    if (int rc = check_ray_args("render_rays", s, d, d_rays, ray_passes, camera_draws)) return rc;
+    if (int rc = check_render_desc(s, d)) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = wait_for_caller_stream(s, stream)) return rc;
+    RaySource src{};
+    src.rays = static_cast<const float4*>(d_rays), src.ray_passes = ray_passes, src.camera_draws = camera_draws;
+    return render_impl(s, d, cancel, d_rgba, d_count, finish_pass, stats, nullptr, 0, &src);
+  });
+}
+
+extern "C" int pbrhip_render_rays(pbrhip_scene* s, const pbrhip_render_desc* d, const pbrhip_ray* rays, uint32_t ray_passes,
+                                  uint32_t camera_draws, const volatile unsigned char* cancel, float* rgba, uint32_t* count,
+                                  size_t* finish_pass, pbrhip_render_stats* stats) {
+  return guarded([&]() -> int {
+    if (!rgba || !count) return fail(PBRHIP_EINVAL, "render_rays: NULL layer");
+    if (int rc = check_ray_args("render_rays", s, d, rays, ray_passes, camera_draws)) return rc;
+    if (int rc = check_render_desc(s, d)) return rc;
+    auto t_begin = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(s->device));
+    const size_t npx = (size_t)d->width * d->height, nrays = npx * ray_passes;
+    HIPCHK(s->own_rgba.reserve(npx * 4));
+    HIPCHK(s->own_count.reserve(npx));
+    HIPCHK(s->own_rays.reserve(2 * nrays));
+    if (nrays) HIPCHK(hipMemcpyAsync(s->own_rays.p, rays, nrays * sizeof(pbrhip_ray), hipMemcpyHostToDevice, s->stream));
+    if (d->flags & PBRHIP_RENDER_NO_CLEAR) {
+      HIPCHK(hipMemcpyAsync(s->own_rgba.p, rgba, npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+      HIPCHK(hipMemcpyAsync(s->own_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    }
+    RaySource src{};
+    src.rays = s->own_rays.p, src.ray_passes = ray_passes, src.camera_draws = camera_draws;
+    if (int rc = render_impl(s, d, cancel, s->own_rgba.p, s->own_count.p, finish_pass, stats, nullptr, 0, &src)) return rc;
+    HIPCHK(hipMemcpyAsync(rgba, s->own_rgba.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(count, s->own_count.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return PBRHIP_OK;
+  });
+}
+
+extern "C" int pbrhip_render_features_rays_device(pbrhip_scene* s, const pbrhip_render_desc* d, const void* d_rays, uint32_t ray_passes,
+                                                  void* stream, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count) {
+  return guarded([&]() -> int {
+    if (int rc = check_ray_args("render_features_rays", s, d, d_rays, ray_passes, 0)) return rc;
+    if (int rc = check_render_desc(s, d)) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = wait_for_caller_stream(s, stream)) return rc;
+    RaySource src{};
+    src.rays = static_cast<const float4*>(d_rays), src.ray_passes = ray_passes;
+    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count, &src);
+  });
+}
+
+extern "C" int pbrhip_projection_rays_device(pbrhip_scene* s, uint32_t projection, float param, uint32_t width, uint32_t height,
+                                             uint32_t first_pass, uint32_t num_pass, uint64_t seed_seq, void* d_rays, void* stream) {
+  return guarded([&]() -> int {
+    if (!s || !d_rays) return fail(PBRHIP_EINVAL, "projection_rays: NULL scene or rays");
+    if (projection > PBRHIP_PROJECTION_ORTHO) return fail(PBRHIP_EINVAL, "projection_rays: unknown projection %u", projection);
+    if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "projection_rays: zero image size");
+    if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "projection_rays: image too large");
+    if ((uint64_t)first_pass + num_pass > (1ull << 32)) return fail(PBRHIP_EINVAL, "projection_rays: the passes do not fit 32 bits");
+    if (!isfinite(param) || param < 0.0f) return fail(PBRHIP_EINVAL, "projection_rays: param %g is not a finite number >= 0", (double)param);
+    if (projection == PBRHIP_PROJECTION_FISHEYE && param > 360.0f) return fail(PBRHIP_EINVAL, "projection_rays: a fisheye of %g degrees (at most 360)", (double)param);
+    if (projection == PBRHIP_PROJECTION_ORTHO && !(param > 0.0f)) return fail(PBRHIP_EINVAL, "projection_rays: an orthographic view needs its half height > 0");
+    if (!s->cam_set) return fail(PBRHIP_ESTATE, "projection_rays: the scene has no camera (pbrhip_scene_set_camera gives the frame)");
+    if (num_pass == 0) return PBRHIP_OK;
+    HIPCHK(hipSetDevice(s->device));
+    ProjectArgs a{};
+    a.cam = make_user_camera(s, width, height);
+    a.projection = projection;
+    // fisheye: the field of view in degrees, 0 = the camera's vertical one; the kernel takes half of it in radians, rounded once
+    if (projection == PBRHIP_PROJECTION_FISHEYE) a.param = (float)((double)(param > 0.0f ? param : s->cam_vfov) * M_PI / 360.0);
+    else a.param = param;
+    a.width = width, a.height = height, a.first_pass = first_pass, a.npass = num_pass, a.seed_seq = seed_seq;
+    a.rays = static_cast<float4*>(d_rays);
+    launch_project_rays(static_cast<hipStream_t>(stream), a);
+    HIPCHK(hipGetLastError());
     return PBRHIP_OK;
   });
 }

@@ -17,6 +17,7 @@
 #include "geom_gpu.h"
 #include "host_scene.h"
 #include "kernels.h"
+#include "rays_kernels.h"
 
 namespace pb {
 
@@ -228,6 +229,7 @@ struct pbrhip_scene {
   float cam_eye[3] = {0, 0, 0}, cam_lookat[3] = {0, 0, -1}, cam_up[3] = {0, 1, 0};
   float cam_vfov = 30.0f, cam_lens = 0.0f, cam_focus = 0.0f;
   pb::DevBuf<uint32_t> hook_xyp;  // pbrhip_camera_rays' (x, y, pass) triples
+  pb::DevBuf<float4> own_rays;    // pbrhip_render_rays' device copy of the caller's host rays
   pb::DScene dscene;
   // render working set (grown on demand, reused across calls)
   pb::DevBuf<float4> rec, srec, ssrec, L, hit, sss_A, sh_e;  // path state (kernels.h::PathState): rec = 4 words of 16 B per path, srec = 2
@@ -284,10 +286,11 @@ int set_environment(pbrhip_scene* s, const float* rgb, uint32_t width, uint32_t 
 // pbrhip_scene_set_camera's body (eye null: the reference's camera); also what pbrhip_scene_replicate calls to carry it over
 int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const float* up, float vfov, float lens_radius, float focus_distance);
 // the body of pbrhip_render_device (device pointers on the scene's device).  d_pixels: null, or a device list of num_pixels of the
-// rank's pixels (y * width + x, distinct) to render in place of ensure_pixels' list (render_adaptive.cpp); the cached list stays as it is
+// rank's pixels (y * width + x, distinct) to render in place of ensure_pixels' list (render_adaptive.cpp); the cached list stays as it is.
+// rays: null, or the caller's first rays in place of the scene's camera (base_pass and height are filled in here)
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
                 uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels = nullptr,
-                uint32_t num_pixels = 0);
+                uint32_t num_pixels = 0, const RaySource* rays = nullptr);
 void bind_dscene(pbrhip_scene* s);  // points every DScene member that comes from a scene buffer at it, with its count (commit.cpp)
 inline const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id) {  // (per primitive in commit's loops: inline)
   const HostInstance& in = s->instances[instance_id];
