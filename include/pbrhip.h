@@ -526,8 +526,18 @@ int pbrhip_camera_rays(pbrhip_scene*, uint32_t width, uint32_t height, uint64_t 
  *   LAMBERT      in: u0, u1 -> wi[3], f, pdf     SPHERE: u1, u2 -> v[3]     TRIANGLE: u1, u2 -> a, b
  *   GGX_EVAL     in: wi[3], wo[3], ax, ay, distrib -> f, pdf        GGX_SAMPLE: wo[3], ax, ay, u0, u1, distrib -> wi[3], f, pdf
  *   HAIR_EVAL    in: wi[3], wo[3], params[23] -> f[3], pdf           HAIR_SAMPLE: wo[3], params[23], us[4] -> wi[3], f[3], pdf
- *   (params: h, v[4], s, sigma_a[3], eta, alpha, tints[4][3], transparent_scale) */
+ *   (params: h, v[4], s, sigma_a[3], eta, alpha, tints[4][3], transparent_scale)
+ * and the random walk's leaves (src/shader/random-walk-sss.h, cycles-principled-shader.cc:326-365), held to a float64 model of the text:
+ *   SSS_MEDIUM   in: the 25 words of a pbrhip_principled_param -> enable_diffuse, enable_subsurface, subsurface weight[3], albedo[3], radius[3],
+ *                diffuse weight[3], sigma_t[3], sigma_s[3], first walk throughput[3]: ParamToBsdf, then the medium as commit hoists it
+ *   SSS_DISTANCE in: throughput[3], sigma_s[3], sigma_t[3], u0, u1 -> t, channel pdf[3] (albedo computed inside) | t, channel pdf[3] (albedo
+ *                handed in): SampleScatterDistance
+ *   SSS_SCATTER  in: org[3], dir[3], sigma_t[3], sigma_s[3], throughput[3], t_scatter, step, generator state lo, hi, increment lo, hi
+ *                -> alive, org[3], dir[3], throughput[3], t_scatter, step, state lo, hi, 1 when the step kernel's and the walk kernel's way
+ *                of calling it agree in every bit: one scattering event of the walk (random-walk-sss.h:343-361, :287-314); a walk that
+ *                ends leaves its state as it came */
 enum {
+  PBRHIP_LEAF_SSS_MEDIUM = 11, PBRHIP_LEAF_SSS_DISTANCE = 12, PBRHIP_LEAF_SSS_SCATTER = 13,
   PBRHIP_LEAF_RNG = 0, PBRHIP_LEAF_FASTMATH = 1, PBRHIP_LEAF_FRESNEL = 2, PBRHIP_LEAF_MIS = 3, PBRHIP_LEAF_LAMBERT = 4, PBRHIP_LEAF_SPHERE = 5,
   PBRHIP_LEAF_TRIANGLE = 6, PBRHIP_LEAF_GGX_EVAL = 7, PBRHIP_LEAF_GGX_SAMPLE = 8, PBRHIP_LEAF_HAIR_EVAL = 9, PBRHIP_LEAF_HAIR_SAMPLE = 10
 };

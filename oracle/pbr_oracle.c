@@ -2392,6 +2392,33 @@ void orc_kat_param_to_bsdf(const orc_principled_param* p, float out[34]) {
   out[28] = b.clearcoat_alpha_x, out[29] = b.clearcoat_alpha_y, out[30] = b.clearcoat_ior;
   out[31] = b.clearcoat_color.x, out[32] = b.clearcoat_color.y, out[33] = b.clearcoat_color.z;
 }
+/* ParamToBsdf's subsurface branch, BssrdfSetup and ComputeScatteringCoefficient as random_walk_subsurface runs them.
+ * out: [0] en_diffuse [1] en_sss [2..4] sss_w [5..7] albedo [8..10] radius [11..13] diffuse_w [14..16] sigma_t [17..19] sigma_s [20..22] thr0 */
+void orc_kat_sss_medium(const orc_principled_param* p, float out[23]) {
+  orc_bsdf b;
+  param_to_bsdf(NULL, NULL, p, &b);
+  f3 sigma_t, sigma_s;
+  scattering_from_albedo(b.subsurface_albedo.x, b.subsurface_radius.x, &sigma_t.x, &sigma_s.x);
+  scattering_from_albedo(b.subsurface_albedo.y, b.subsurface_radius.y, &sigma_t.y, &sigma_s.y);
+  scattering_from_albedo(b.subsurface_albedo.z, b.subsurface_radius.z, &sigma_t.z, &sigma_s.z);
+  f3 thr = orc_safe_divide_spectrum(b.subsurface_weight, b.subsurface_albedo);
+  out[0] = (float)b.enable_diffuse, out[1] = (float)b.enable_subsurface;
+  out[2] = b.subsurface_weight.x, out[3] = b.subsurface_weight.y, out[4] = b.subsurface_weight.z;
+  out[5] = b.subsurface_albedo.x, out[6] = b.subsurface_albedo.y, out[7] = b.subsurface_albedo.z;
+  out[8] = b.subsurface_radius.x, out[9] = b.subsurface_radius.y, out[10] = b.subsurface_radius.z;
+  out[11] = b.diffuse_weight.x, out[12] = b.diffuse_weight.y, out[13] = b.diffuse_weight.z;
+  out[14] = sigma_t.x, out[15] = sigma_t.y, out[16] = sigma_t.z;
+  out[17] = sigma_s.x, out[18] = sigma_s.y, out[19] = sigma_s.z;
+  out[20] = thr.x, out[21] = thr.y, out[22] = thr.z;
+}
+/* SampleScatterDistance.  in: throughput[3], sigma_s[3], sigma_t[3], u0, u1; out: t, channel pdf[3], the channel picked */
+void orc_kat_scatter_distance(const float in[11], float out[5]) {
+  f3 thr = f3_make(in[0], in[1], in[2]), sigma_s = f3_make(in[3], in[4], in[5]), sigma_t = f3_make(in[6], in[7], in[8]), pdf;
+  f3 albedo = orc_safe_divide_spectrum(sigma_s, sigma_t);
+  out[4] = (float)sample_channel(albedo, thr, in[9], &pdf);
+  out[0] = sample_scatter_distance(thr, sigma_s, sigma_t, in[9], in[10], &pdf);
+  out[1] = pdf.x, out[2] = pdf.y, out[3] = pdf.z;
+}
 void orc_kat_hair_param_to_bsdf(const orc_hair_param* p, float h, float out[23]) {
   orc_hair_bsdf b;
   hair_param_to_bsdf(p, h, &b);

@@ -160,6 +160,11 @@ void orc_kat_uniform_sphere(float u1, float u2, float out[3]);
 void orc_kat_triangle_sampler(float u1, float u2, float out[2]);
 /* ParamToBsdf (cycles-principled-shader.cc:244-412) dump: 34 floats, see pbr_oracle.c */
 void orc_kat_param_to_bsdf(const orc_principled_param*, float out[34]);
+/* the random walk's medium (cycles-principled-shader.cc:326-365, random-walk-sss.h:71-136): en_diffuse, en_sss, sss weight[3], albedo[3],
+ * radius[3], diffuse weight[3], sigma_t[3], sigma_s[3], first throughput[3] */
+void orc_kat_sss_medium(const orc_principled_param*, float out[23]);
+/* SampleScatterDistance (random-walk-sss.h:141-187).  in: throughput[3], sigma_s[3], sigma_t[3], u0, u1 -> t, channel pdf[3], channel */
+void orc_kat_scatter_distance(const float in[11], float out[5]);
 /* hair ParamToBsdf (hair-shader.cc:100-151) with h: 23 floats in the orc_kat_hair_eval order */
 void orc_kat_hair_param_to_bsdf(const orc_hair_param*, float h, float out[23]);
 /* light tables: returns number of lights; per light (instance, geom, nprim, p_light, cdf_light) */

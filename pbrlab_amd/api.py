@@ -143,6 +143,7 @@ def make_hair(d):
 
 
 LEAF_RNG, LEAF_FASTMATH, LEAF_FRESNEL, LEAF_MIS, LEAF_LAMBERT, LEAF_SPHERE, LEAF_TRIANGLE, LEAF_GGX_EVAL, LEAF_GGX_SAMPLE, LEAF_HAIR_EVAL, LEAF_HAIR_SAMPLE = range(11)
+LEAF_SSS_MEDIUM, LEAF_SSS_DISTANCE, LEAF_SSS_SCATTER = 11, 12, 13
 
 
 def leaf_eval(op, inputs, out_words):

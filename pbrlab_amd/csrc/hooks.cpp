@@ -148,8 +148,8 @@ extern "C" int pbrhip_tree_refit(int device, uint32_t n, const void* slots, void
 extern "C" int pbrhip_leaf_eval(uint32_t op, const float* in, size_t n, uint32_t in_words, float* out, uint32_t out_words) {
   return guarded([&]() -> int {
     if ((!in || !out) && n) return fail(PBRHIP_EINVAL, "leaf_eval: NULL argument");
-    if (op > 10u || in_words == 0 || out_words == 0 || n > (1u << 24)) return fail(PBRHIP_EINVAL, "leaf_eval: bad operation or sizes");
-    static const uint32_t need_in[11] = {4, 3, 2, 2, 2, 2, 2, 9, 8, 29, 30}, need_out[11] = {1, 1, 1, 1, 5, 3, 2, 2, 5, 4, 7};
+    if (op > 13u || in_words == 0 || out_words == 0 || n > (1u << 24)) return fail(PBRHIP_EINVAL, "leaf_eval: bad operation or sizes");
+    static const uint32_t need_in[14] = {4, 3, 2, 2, 2, 2, 2, 9, 8, 29, 30, 25, 11, 21}, need_out[14] = {1, 1, 1, 1, 5, 3, 2, 2, 5, 4, 7, 23, 8, 15};
     if (in_words < need_in[op] || out_words < need_out[op]) return fail(PBRHIP_EINVAL, "leaf_eval: operation %u needs %u words in, %u out", op, need_in[op], need_out[op]);
     if (!n) return PBRHIP_OK;
     DevBuf<float> d_in, d_out;

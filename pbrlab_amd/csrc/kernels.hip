@@ -1724,9 +1724,67 @@ void launch_texture_fetch(hipStream_t s, const DScene& sc, uint32_t tex_id, cons
   const uint32_t blocks = (n + kBlock - 1u) / kBlock;
   hipLaunchKernelGGL(k_texture_fetch, dim3(blocks < 1u ? 1u : (blocks > 1024u ? 1024u : blocks)), dim3(kBlock), 0, s, sc, tex_id, uv, n, rgb);
 }
+// The random walk's leaves (ops 11-13 of pbrhip_leaf_eval), in a kernel of their own so that k_leaf_eval keeps its code: the closure
+// set and the medium of a material as commit.cpp hoists them, the distance sampler with its channel pdf computed both ways, and one
+// scattering event through sss_scatter -- the function k_sss_step and k_sss_walk run -- in both of the forms they call it in.
+__device__ __forceinline__ void st3(float* o, V3 v) { o[0] = v.x, o[1] = v.y, o[2] = v.z; }
+__device__ __forceinline__ bool same_bits(V3 a, V3 b) {
+  return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) && __float_as_uint(a.z) == __float_as_uint(b.z);
+}
+__global__ __launch_bounds__(kBlock) void k_leaf_eval_sss(uint32_t op, const float* __restrict__ in, uint32_t n, uint32_t in_words, float* __restrict__ out,
+                                                          uint32_t out_words) {
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const float* a = in + (size_t)i * in_words;
+    float* o = out + (size_t)i * out_words;
+    switch (op) {
+      case 11: {  // (PrincipledParam, 25 words) -> en_diffuse, en_sss, sss_w, albedo, radius, diffuse_w, sigma_t, sigma_s, thr0
+        PrincipledParam m;
+        uint32_t* mw = reinterpret_cast<uint32_t*>(&m);
+        for (uint32_t k = 0; k < sizeof(PrincipledParam) / 4; k++) mw[k] = __float_as_uint(a[k]);
+        const PrincipledBsdf b = param_to_bsdf(m);
+        V3 sigt, sigs, wthr;
+        medium_coefficients(b, sigt, sigs, wthr);
+        o[0] = (float)b.enable_diffuse, o[1] = (float)b.enable_subsurface;
+        st3(o + 2, b.subsurface_weight), st3(o + 5, b.subsurface_albedo), st3(o + 8, b.subsurface_radius), st3(o + 11, b.diffuse_weight);
+        st3(o + 14, sigt), st3(o + 17, sigs), st3(o + 20, wthr);
+      } break;
+      case 12: {  // (thr, sigma_s, sigma_t, u0, u1) -> t, channel pdf (albedo_in null) | t, channel pdf (albedo_in precomputed)
+        const V3 thr(a[0], a[1], a[2]), sigs(a[3], a[4], a[5]), sigt(a[6], a[7], a[8]);
+        V3 pdf0, pdf1;
+        o[0] = sample_scatter_distance(thr, sigs, sigt, a[9], a[10], pdf0);
+        const V3 albedo = safe_divide_spectrum(sigs, sigt);
+        o[4] = sample_scatter_distance(thr, sigs, sigt, a[9], a[10], pdf1, &albedo);
+        st3(o + 1, pdf0), st3(o + 5, pdf1);
+      } break;
+      case 13: {  // (org, dir, sigma_t, sigma_s, thr, t_scatter, step, generator state lo hi, inc lo hi) -> alive, org, dir, thr, t_scatter, step, state lo hi, forms agree
+        const uint64_t state = (uint64_t)__float_as_uint(a[17]) | ((uint64_t)__float_as_uint(a[18]) << 32);
+        const uint64_t inc = (uint64_t)__float_as_uint(a[19]) | ((uint64_t)__float_as_uint(a[20]) << 32);
+        const WalkState w0 = {V3(a[0], a[1], a[2]), V3(a[3], a[4], a[5]), V3(a[6], a[7], a[8]), V3(a[9], a[10], a[11]), V3(a[12], a[13], a[14]),
+                              a[15], __float_as_uint(a[16]), state};
+        WalkState w = w0, v = w0;
+        const bool alive = sss_scatter(w, inc);  // k_sss_step's form
+        const V3 albedo = safe_divide_spectrum(v.sigs, v.sigt);
+        V3 chpdf(0.f);
+        const bool alive2 = sss_scatter(v, inc, &chpdf, false, &albedo);  // k_sss_walk's form, nothing carried yet
+        const bool agree = alive == alive2 && same_bits(w.wthr, v.wthr) && same_bits(w.dir, v.dir) && same_bits(w.org, v.org) &&
+                           __float_as_uint(w.t_scatter) == __float_as_uint(v.t_scatter) && w.bounce == v.bounce && w.rng_state == v.rng_state;
+        o[0] = alive ? 1.f : 0.f;
+        st3(o + 1, w.org), st3(o + 4, w.dir), st3(o + 7, w.wthr);
+        o[10] = w.t_scatter, o[11] = __uint_as_float(w.bounce);
+        o[12] = __uint_as_float((uint32_t)w.rng_state), o[13] = __uint_as_float((uint32_t)(w.rng_state >> 32));
+        o[14] = agree ? 1.f : 0.f;
+      } break;
+      default: break;
+    }
+  }
+}
 void launch_leaf_eval(hipStream_t s, uint32_t op, const float* in, uint32_t n, uint32_t in_words, float* out, uint32_t out_words) {
   const uint32_t blocks = (n + kBlock - 1u) / kBlock;
-  hipLaunchKernelGGL(k_leaf_eval, dim3(blocks < 1u ? 1u : (blocks > 1024u ? 1024u : blocks)), dim3(kBlock), 0, s, op, in, n, in_words, out, out_words);
+  if (op >= 11u) {
+    hipLaunchKernelGGL(k_leaf_eval_sss, dim3(blocks < 1u ? 1u : (blocks > 1024u ? 1024u : blocks)), dim3(kBlock), 0, s, op, in, n, in_words, out, out_words);
+    return;
+  }
+  hipLaunchKernelGGL(k_leaf_eval,dim3(blocks < 1u ? 1u : (blocks > 1024u ? 1024u : blocks)), dim3(kBlock), 0, s, op, in, n, in_words, out, out_words);
 }
 
 // ------------------------------------------------------------------ RenderLayer shards (multi-GPU exchange, multi.cpp)

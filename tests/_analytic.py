@@ -221,7 +221,7 @@ def closure_set(mat):
     sat = lambda v: min(max(float(v), 0.0), 1.0)  # noqa: E731
     base = np.asarray(mat["base_color"], np.float64)
     metallic, spec, transmission = float(mat["metallic"]), float(mat["specular"]), float(mat["transmission"])
-    assert float(mat["subsurface"]) == 0, "the random-walk closure is not modelled"
+    assert float(mat["subsurface"]) == 0, "the random-walk closure is modelled by tests/_sss_analytic.py, not here"
     diffuse_w = (1 - sat(metallic)) * (1 - sat(transmission))                       # :326-327
     final_transmission = sat(transmission) * (1 - sat(metallic))                    # :328-329
     specular_w = 1 - final_transmission                                             # :330

@@ -159,6 +159,8 @@ def lib():
         L.orc_kat_uniform_sphere.argtypes = [C.c_float, C.c_float, fp]
         L.orc_kat_triangle_sampler.argtypes = [C.c_float, C.c_float, fp]
         L.orc_kat_param_to_bsdf.argtypes = [C.POINTER(PrincipledParam), fp]
+        L.orc_kat_sss_medium.argtypes = [C.POINTER(PrincipledParam), fp]
+        L.orc_kat_scatter_distance.argtypes = [fp, fp]
         L.orc_kat_hair_param_to_bsdf.argtypes = [C.POINTER(HairParam), C.c_float, fp]
         L.orc_light_table.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, fp, fp, u32p]
         L.orc_light_table.restype = C.c_uint32
