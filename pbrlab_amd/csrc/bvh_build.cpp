@@ -2,7 +2,8 @@
 // src/raytracer/raytracer_impl.cc:136-147,181-192).  Binned SAH (48 bins), leaves of <= kMaxLeaf
 // primitives of a single kind, 64-byte nodes that carry both children's boxes so that one node fetch
 // decides both descents.  Large subtrees are built on worker threads.  Optionally (BvhBuildOptions) the largest subtrees of a
-// triangle-only tree are re-inserted where the tree grows least before it is flattened; the Q collapse's own cost decides whether a pass is kept.
+// triangle-only tree are re-inserted before it is flattened: the best few positions by area growth are priced by the Q collapse's own
+// cost -- loop turns of the traversal, host_scene.h::BvhBuildOptions -- and the subtree goes where that is lowest.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -209,7 +210,36 @@ struct QV {
   int32_t l = -1, r = -1;  // children, or -1: leaf
   uint32_t ref = 0;        // leaf: the Q tree's reference
   uint32_t prims = 0;      // leaf: primitives behind the reference
+  uint8_t curve = 0;       // leaf: a curve leaf
 };
+
+// What a vertex of the collapse's programme is charged (host_scene.h::BvhBuildOptions): a node turn, a leaf turn (per primitive: the
+// pricing of before and of trees with curve leaves), and per unit of a leaf's primitive area the rays that start on it (0: not priced).
+struct QCost {
+  double node = 1.0, leaf = 1.0;
+  bool per_prim = true;
+  double surface = 0.0;  // area of the root's box / primitive area of the scene: the share of surface-origin rays, in the units of qarea
+};
+// The area of the primitives behind a leaf, from its box alone (the builder never sees corners): a triangle is half a parallelogram
+// whose projections fill its box's faces at most, so 1/2 |(dy dz, dz dx, dx dy)| bounds it from above and is exact for the axis-aligned
+// right triangles that walls and floors are made of; a leaf of two is priced as the whole parallelogram.
+double leaf_prim_area(const float* lo, const float* hi, uint32_t prims) {
+  const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
+  const double a = sqrt(dx * dy * dx * dy + dy * dz * dy * dz + dz * dx * dz * dx);
+  return std::isfinite(a) ? (prims >= 2 ? a : 0.5 * a) : 0.0;
+}
+double half_area(const float* lo, const float* hi) {
+  const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
+  const double a = dx * dy + dy * dz + dz * dx;
+  return a >= 0.0 && std::isfinite(a) ? a : 0.0;
+}
+QCost make_qcost(const BvhBuildOptions& opt, bool curves, double root_area, double prim_area) {
+  QCost C;
+  if (opt.cost == kBvhCostPrims || curves) return C;
+  C.node = kCostNode, C.leaf = opt.cost_leaf, C.per_prim = false;
+  if (opt.surface_term && prim_area > 0.0 && std::isfinite(root_area / prim_area)) C.surface = root_area / prim_area;
+  return C;
+}
 
 // ... of a flattened tree.  Children follow their parent.
 void qv_of_nodes(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QV>* out) {
@@ -236,7 +266,7 @@ void qv_of_nodes(const std::vector<BvhNode>& N2, const std::function<uint32_t(ui
       T.emplace_back();
       for (int a = 0; a < 3; a++) T[v].lo[a] = b.lo[a][k], T[v].hi[a] = b.hi[a][k];
       kids[nk++] = v;
-      if (ref & kLeafBit) T[v].ref = map_leaf(ref), T[v].prims = (ref & 7u) + 1u;
+      if (ref & kLeafBit) T[v].ref = map_leaf(ref), T[v].prims = (ref & 7u) + 1u, T[v].curve = (ref & kCurveBit) ? 1 : 0;
       else todo.push_back({ref, v});
     }
     // vertex t.v takes the node's children; a node with one child (a scene of one leaf) passes it through
@@ -251,23 +281,37 @@ void qv_of_nodes(const std::vector<BvhNode>& N2, const std::function<uint32_t(ui
   }
 }
 
+// The cost of a flattened tree's programme: curve leaves anywhere mean the pricing per primitive.
+QCost qcost_of_tree(const std::vector<QV>& T, const BvhBuildOptions& opt) {
+  bool curves = false;
+  double prim_area = 0.0;
+  for (const QV& v : T)
+    if (v.l < 0 && v.prims) curves = curves || (v.curve != 0), prim_area += leaf_prim_area(v.lo, v.hi, v.prims);
+  return make_qcost(opt, curves, T.empty() ? 0.0 : half_area(T[0].lo, T[0].hi), prim_area);
+}
+
 // Which descendants become the (up to four) children of the Q node of a vertex v is chosen bottom-up over the surface-area
 // cost, with the box a child really presents to a ray: its box rounded outwards on the 8-bit grid of v (step = extent of v /
 // 253 ).  That looseness is what matters for thin primitives in big nodes -- a wall triangle of
 // the Cornell box as a child of a node two units wide is a slab 0.016 thick, and every ray that starts on the wall tests it:
 // with plain areas the collapse put such leaves high up and a shadow ray tested 2.7 triangles instead of 0.9.
-//   below[v] = min over the frontiers F below v, |F| <= 4, of  sum_{u in F} qarea(u | v) * (u leaf ? prims : 1) + below[u]
+//   below[v] = min over the frontiers F below v, |F| <= 4, of  sum_{u in F} term(u | v) + below[u]
+//   term(u | v) = qarea(u | v) * kCostNode                                                   u inner: one node turn
+//               = (qarea(u | v) + [slab] * C.surface * prim_area(u)) * kCostLeaf             u a triangle leaf: one TriPair, one turn
+//   [slab]: the box of u on v's grid is thicker than u's own along u's thinnest axis by more than kSurfaceEps -- the rays that start
+//   on u's primitives (tmin = kSurfaceEps) then pass the slab test and take the leaf's turn, whatever their direction; C.surface puts
+//   their share (area of u's primitives / the scene's) into the units of qarea (probability of crossing * area of the root's box).
+//   (QCost::per_prim -- the pricing of before, and of trees with curve leaves -- : a leaf is qarea * prims, a node qarea, nothing else.)
 // A vertex has at most a dozen frontiers (each inner member may be replaced by its two children while there is room).
 // One vertex of that programme: below[vi] and the chosen frontier choice[4 vi ..], from the values of the vertices under it.
-void qdp_vertex(const std::vector<QV>& T, size_t vi, std::vector<double>& below, std::vector<int32_t>& choice) {
+void qdp_vertex(const std::vector<QV>& T, size_t vi, const QCost& C, std::vector<double>& below, std::vector<int32_t>& choice) {
   using V = QV;
   auto area = [](const V& v) {
     const float dx = v.hi[0] - v.lo[0], dy = v.hi[1] - v.lo[1], dz = v.hi[2] - v.lo[2];
     const float a = dx * dy + dy * dz + dz * dx;
     return a >= 0.f && std::isfinite(a) ? (double)a : 0.0;
   };
-  constexpr double kCostNode = 1.0, kCostPrim = 1.0;
-  auto qarea = [&](const V& u, const V& v) {
+  auto qarea = [&](const V& u, const V& v, bool* slab) {
     double e[3];
     for (int a = 0; a < 3; a++) {
       const double ext = (double)v.hi[a] - (double)v.lo[a];
@@ -275,8 +319,18 @@ void qdp_vertex(const std::vector<QV>& T, size_t vi, std::vector<double>& below,
       const double ql = floor(((double)u.lo[a] - (double)v.lo[a]) / st), qh = ceil(((double)u.hi[a] - (double)v.lo[a]) / st);
       e[a] = std::max(qh - ql, 0.0) * st;
     }
+    if (slab) {
+      int thin = 0;
+      for (int a = 1; a < 3; a++)
+        if (u.hi[a] - u.lo[a] < u.hi[thin] - u.lo[thin]) thin = a;
+      *slab = e[thin] - ((double)u.hi[thin] - (double)u.lo[thin]) > kSurfaceEps;
+    }
     const double a = e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
     return std::isfinite(a) ? a : 0.0;
+  };
+  auto leaf_term = [&](const V& u, double qa, bool slab) {
+    if (C.per_prim) return qa * C.leaf * u.prims;
+    return (qa + (slab ? C.surface * leaf_prim_area(u.lo, u.hi, u.prims) : 0.0)) * C.leaf;
   };
   const V& v = T[vi];
   for (int m = 0; m < 4; m++) choice[vi * 4 + m] = -1;
@@ -284,7 +338,7 @@ void qdp_vertex(const std::vector<QV>& T, size_t vi, std::vector<double>& below,
   if (v.l < 0) return;  // leaf: nothing below
   if (v.r < 0) {        // pass-through (the root of a scene with one leaf or one subtree)
     choice[vi * 4] = v.l;
-    below[vi] = T[v.l].l < 0 ? area(T[v.l]) * kCostPrim * T[v.l].prims : area(T[v.l]) * kCostNode + below[v.l];
+    below[vi] = T[v.l].l < 0 ? leaf_term(T[v.l], area(T[v.l]), false) : area(T[v.l]) * C.node + below[v.l];
     return;
   }
   // enumerate the frontiers: start from {l, r}; replace inner members by their children while the size stays <= 4
@@ -317,7 +371,14 @@ void qdp_vertex(const std::vector<QV>& T, size_t vi, std::vector<double>& below,
     for (int k = 0; k < nt; k++)
       if (term_of[k] == ui) return term[k];
     const V& u = T[ui];
-    term_of[nt] = ui, term[nt] = u.l < 0 ? qarea(u, v) * kCostPrim * u.prims : qarea(u, v) * kCostNode + below[ui];
+    if (u.l < 0) {
+      bool slab = false;
+      const double qa = qarea(u, v, C.surface > 0.0 ? &slab : nullptr);
+      term[nt] = leaf_term(u, qa, slab);
+    } else {
+      term[nt] = qarea(u, v, nullptr) * C.node + below[ui];
+    }
+    term_of[nt] = ui;
     return term[nt++];
   };
   double best = 1e300;
@@ -347,8 +408,11 @@ uint32_t qdp_need(const std::vector<QV>& T, size_t vi, const std::vector<int32_t
 // Subtree re-insertion on the build-time tree.  A top-down split decides near the root with the least knowledge:
 // a dozen wall triangles among half a million small ones end up in nodes that span the room.  A pass takes the largest nodes, one
 // after the other, out of the tree and puts each back where the tree grows least; leaves move as they are (ranges, kinds and the
-// order array never change).  Whether a pass is kept is decided by what the Q collapse would pay for the tree, not by the binary
-// surface-area sum: that one keeps falling while the collapsed tree gets worse.
+// order array never change).  What decides is what the Q collapse would pay for the tree, not the binary surface-area sum: that one
+// keeps falling while the collapsed tree gets worse.  With the turn cost (host_scene.h::BvhBuildOptions) every move is decided on its
+// own: the area growth only ranks the positions, the best few are priced by below[root] and the subtree goes where that is lowest, or
+// back (place_by_cost).  With the pricing of before, or where the rays walk the binary tree, a pass is placed by area growth alone and
+// kept or undone as a whole.  The pass-level guards -- binary depth and Q stack need within kStackDepth -- hold either way.
 struct Reinserter {
   std::vector<TNode>& T;
   int32_t root;
@@ -364,6 +428,9 @@ struct Reinserter {
     int32_t n, sibling;  // n was taken from beside `sibling`
   };
   std::vector<Move> log;  // the moves of the running pass, for undoing it
+  QCost C;                // what the programme charges
+  uint32_t ntry = 0;      // positions priced per candidate; 0: a pass is placed by area growth alone and kept or undone as a whole
+  double cur = 0.0;       // below[root] of the tree as it stands (ntry > 0)
 
   static Box unite(const Box& a, const Box& b) {
     Box u = a;
@@ -401,6 +468,62 @@ struct Reinserter {
     else replace_child(g, x, p), refit_up(g);
   }
 
+  using Entry = std::pair<double, int32_t>;  // (area growth of the ancestors, node): the least first, ties to the lower index
+
+  // n, unlinked from beside s with its parent p, goes where the collapse pays least: the (up to) ntry positions whose area growth is
+  // the smallest and below `here`, that of where it was, are linked one after the other and priced by below[root] -- an evaluation
+  // walks the two paths a link dirties -- and n ends at the cheapest, or back beside s when none is cheaper than `cur` (ties: where
+  // it was, then the smaller growth, then the lower index).  A position that takes the Q stack need beyond the stack is no position.
+  // Returns 1 when n has moved.
+  uint32_t place_by_cost(int32_t p, int32_t n, int32_t s, const Box& nb, double an, double here, std::vector<Entry>& heap) {
+    Entry top[kMaxReinsertTry];  // (total growth, position), ascending
+    uint32_t nt = 0;
+    double bound = here;
+    heap.clear();
+    heap.push_back({0.0, root});
+    while (!heap.empty()) {
+      std::pop_heap(heap.begin(), heap.end(), std::greater<Entry>());
+      const Entry e = heap.back();
+      heap.pop_back();
+      if (!(e.first + an < bound)) break;
+      const int32_t x = e.second;
+      const double total = e.first + (double)unite(T[x].box, nb).area();
+      if (total < bound && x != s) {
+        if (nt < ntry) nt++;
+        uint32_t k = nt - 1;
+        for (; k > 0 && Entry(total, x) < top[k - 1]; k--) top[k] = top[k - 1];
+        top[k] = {total, x};
+        if (nt == ntry) bound = top[nt - 1].first;
+      }
+      const double grown = total - (double)T[x].box.area();
+      if (T[x].left >= 0 && grown + an < bound) {
+        heap.push_back({grown, T[x].left}), std::push_heap(heap.begin(), heap.end(), std::greater<Entry>());
+        heap.push_back({grown, T[x].right}), std::push_heap(heap.begin(), heap.end(), std::greater<Entry>());
+      }
+    }
+    if (nt == 0) {
+      link(p, n, s);  // (back where it was: the boxes are the same unions again, nothing is dirty)
+      return 0;
+    }
+    mark_up(parent[s]);
+    double best_c = cur;
+    int32_t bx = s;
+    for (uint32_t k = 0; k < nt; k++) {
+      link(p, n, top[k].second);
+      mark_up(p);
+      const double c = evaluate();
+      if (c < best_c && need[root] <= (uint32_t)kStackDepth) best_c = c, bx = top[k].second;
+      unlink(n);
+      mark_up(parent[top[k].second]);
+    }
+    link(p, n, bx);
+    mark_up(p);
+    cur = evaluate();
+    if (bx == s) return 0;
+    log.push_back({n, s});
+    return 1;
+  }
+
   // One pass over the opt.reinsert_top largest nodes, in descending order of area (ties: the lower index).  Returns the moves made.
   uint32_t pass() {
     std::vector<std::pair<float, int32_t>> cand;
@@ -413,7 +536,6 @@ struct Reinserter {
     };
     if (K < cand.size()) std::nth_element(cand.begin(), cand.begin() + (ptrdiff_t)K, cand.end(), larger);
     std::sort(cand.begin(), cand.begin() + (ptrdiff_t)K, larger);
-    using Entry = std::pair<double, int32_t>;  // (area growth of the ancestors, node): the least first, ties to the lower index
     std::vector<Entry> heap;
     uint32_t moves = 0;
     for (size_t c = 0; c < K; c++) {
@@ -426,6 +548,10 @@ struct Reinserter {
       // where it was: the position to beat
       double best = unite(T[s].box, nb).area();
       for (int32_t a = parent[s]; a >= 0; a = parent[a]) best += (double)unite(T[a].box, nb).area() - (double)T[a].box.area();
+      if (ntry > 0) {
+        moves += place_by_cost(p, n, s, nb, an, best, heap);
+        continue;
+      }
       int32_t bx = s;
       // best first from the root; a subtree whose ancestors alone grow by as much as the best position costs is left out
       heap.clear();
@@ -474,7 +600,7 @@ struct Reinserter {
       QV& q = qv[i];
       for (int a = 0; a < 3; a++) q.lo[a] = BvhNode::widen_lo(t.box.lo[a]), q.hi[a] = BvhNode::widen_hi(t.box.hi[a]);  // (the boxes the flattened tree stores)
       q.l = t.left, q.r = t.right, q.prims = t.left < 0 ? t.count : 0u;
-      qdp_vertex(qv, (size_t)i, below, choice);
+      qdp_vertex(qv, (size_t)i, C, below, choice);
       need[i] = qdp_need(qv, (size_t)i, choice, need);
       dirty[i] = 0;
     }
@@ -510,17 +636,30 @@ struct Reinserter {
     bool by_q = opt.for_qtree;
     double cost = 0.0;
     if (by_q) {
+      // (the root's box and the leaves never change: the surface term's scale is the one qtree_cost and build_qtree work out)
+      float rlo[3], rhi[3];
+      for (int a = 0; a < 3; a++) rlo[a] = BvhNode::widen_lo(T[root].box.lo[a]), rhi[a] = BvhNode::widen_hi(T[root].box.hi[a]);
+      double prim_area = 0.0;
+      for (const TNode& t : T)
+        if (t.left < 0) {
+          float lo[3], hi[3];
+          for (int a = 0; a < 3; a++) lo[a] = BvhNode::widen_lo(t.box.lo[a]), hi[a] = BvhNode::widen_hi(t.box.hi[a]);
+          prim_area += leaf_prim_area(lo, hi, t.count);
+        }
+      C = make_qcost(opt, false, half_area(rlo, rhi), prim_area);
       qv.resize(T.size()), below.assign(T.size(), 0.0), choice.assign(T.size() * 4, -1), need.assign(T.size(), 0u), dirty.assign(T.size(), 1);
       cost = evaluate();
       by_q = need[root] <= (uint32_t)kStackDepth;  // (a Q tree that is dropped anyway: the binary tree is what gets walked)
       if (!by_q) dirty.clear();
+      else if (opt.cost != kBvhCostPrims) ntry = std::min(opt.reinsert_try, kMaxReinsertTry);
+      cur = cost;
     }
     if (!by_q) cost = inner_area();
     out->reinsert_cost0 = out->reinsert_cost = cost;
     for (uint32_t k = 0; k < opt.reinsert_passes; k++) {
       const uint32_t moves = pass();
       if (moves == 0) break;
-      const double c = by_q ? evaluate() : inner_area();
+      const double c = by_q ? evaluate() : inner_area();  // (moves priced one by one: nothing is dirty, this is `cur`)
       const bool fits = set_depths() <= (uint32_t)kStackDepth && (!by_q || need[root] <= (uint32_t)kStackDepth);
       if (!(c < cost) || !fits) {  // the first pass that does not pay, or that the traversal stack cannot hold, is taken back
         undo_pass();
@@ -652,17 +791,18 @@ uint32_t qtree_stack_need(const std::vector<QNode>& N) {
   return need[0];
 }
 
-double qtree_cost(const std::vector<BvhNode>& N2, uint32_t* stack_need) {
+double qtree_cost(const std::vector<BvhNode>& N2, uint32_t* stack_need, const BvhBuildOptions& opt) {
   if (stack_need) *stack_need = 0;
   if (N2.empty()) return 0.0;
   std::vector<QV> T;
   qv_of_nodes(N2, [](uint32_t ref) { return ref; }, &T);
+  const QCost C = qcost_of_tree(T, opt);
   const size_t nv = T.size();
   std::vector<double> below(nv, 0.0);
   std::vector<int32_t> choice(nv * 4, -1);
   std::vector<uint32_t> need(nv, 0u);
   for (size_t vi = nv; vi-- > 0;) {  // (children follow their parent)
-    qdp_vertex(T, vi, below, choice);
+    qdp_vertex(T, vi, C, below, choice);
     need[vi] = qdp_need(T, vi, choice, need);
   }
   // (a pass-through root whose only child is inner gets a node of its own under the root's: one child, nothing left behind)
@@ -670,16 +810,18 @@ double qtree_cost(const std::vector<BvhNode>& N2, uint32_t* stack_need) {
   return below[0];
 }
 
-uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out) {
+uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out,
+                     const BvhBuildOptions& opt) {
   out->clear();
   if (N2.empty()) return 0;
   using V = QV;
   std::vector<V> T;
   qv_of_nodes(N2, map_leaf, &T);
+  const QCost C = qcost_of_tree(T, opt);
   const size_t nv = T.size();
   std::vector<double> below(nv, 0.0);
   std::vector<int32_t> choice(nv * 4, -1);  // the chosen frontier of v
-  for (size_t vi = nv; vi-- > 0;) qdp_vertex(T, vi, below, choice);
+  for (size_t vi = nv; vi-- > 0;) qdp_vertex(T, vi, C, below, choice);
   // emit: the Q node of vertex v has its chosen frontier as children
   struct Item {
     int32_t v;
@@ -729,7 +871,8 @@ uint32_t build_qtree(const std::vector<BvhNode>& N2, const std::function<uint32_
   return qtree_stack_need(*out);
 }
 
-void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out) {
+void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out,
+                   const BvhBuildOptions& opt) {
   static_assert(kMaxLeaf <= 2, "a leaf of the binary tree becomes one TriPair / one curve record");
   *out = QLayout();
   std::vector<float4>&qtri = out->tri, &qpts = out->pts;
@@ -784,7 +927,7 @@ void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const s
     return kLeafBit | (tri_leaf(first, count) << 3) | (count - 1u);
   };
   // (a tree the traversal stack cannot hold, or with point indices beyond the reference's 27 bits, is dropped: no Q tree)
-  out->stack_need = build_qtree(bvh.nodes, map_leaf, &out->nodes);
+  out->stack_need = build_qtree(bvh.nodes, map_leaf, &out->nodes, opt);
   if (out->stack_need > (uint32_t)kStackDepth || qpts.size() >= (1u << 27)) out->nodes.clear();
   while (qtri.size() % 4) qtri.push_back(zero);    // (q_pt0 a multiple of 4: the low bits of a curve record's address are free)
   for (int k = 0; k < 4; k++) qpts.push_back(zero);  // (the load site reads four words of a leaf)

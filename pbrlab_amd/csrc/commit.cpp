@@ -348,6 +348,7 @@ struct CommitStage {
   std::vector<float> lo, hi, lprim_cdf;  // (lo, hi, kinds: what the tree is built over)
   std::vector<uint8_t> kinds;
   FlatBvh bvh;  // (built on the GPU: no nodes here, they are on the device)
+  BvhBuildOptions bvh_opt;  // what the host tree was built with: its collapse prices the same cost
   std::vector<float4> slots;
   std::vector<ShadeRec> shade;
   std::vector<Material> mats;
@@ -392,9 +393,10 @@ static int build_binary_tree(pbrhip_scene* s, const Knobs& k, int builder, Commi
     }
   }
   if (!s->bvh_built_on_gpu) {
-    BvhBuildOptions opt;
+    BvhBuildOptions& opt = cs->bvh_opt;
     opt.reinsert_passes = k.bvh_reinsert ? kReinsertPasses : 0u, opt.reinsert_top = k.bvh_reinsert_top;
     opt.for_qtree = k.wide;  // (no Q tree at this commit: the binary tree is what the rays walk)
+    opt.cost = k.bvh_cost ? kBvhCostTurns : kBvhCostPrims;
     build_bvh(cs->lo, cs->hi, cs->kinds, &bvh, opt);
     if (k.debug)
       fprintf(stderr, "pbrhip: commit: host BVH: top-down build %.2f ms; re-insertion %.2f ms: %u passes kept, %u subtrees moved, %s %.6g -> %.6g\n", bvh.build_ms,
@@ -441,7 +443,7 @@ static int build_wide_tree(pbrhip_scene* s, const Knobs& k, int builder, CommitS
   QLayout& q = cs->q;
   s->wide_built_on_gpu = false;
   if (!s->bvh_built_on_gpu && t.num_nodes && k.wide) {
-    build_qlayout(cs->bvh, cs->slots, cs->kinds, &q);
+    build_qlayout(cs->bvh, cs->slots, cs->kinds, &q, cs->bvh_opt);
     if (k.debug) fprintf(stderr, "pbrhip: commit: curve leaves of the Q tree (counted over the collapse's visits): %zu of one piece, %zu of two pieces\n", q.leaves_one, q.leaves_pair);
   }
   if (s->bvh_built_on_gpu && builder == PBRHIP_BVH_GPU_LBVH_WIDE && k.wide) {

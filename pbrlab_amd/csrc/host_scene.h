@@ -77,11 +77,38 @@ struct FlatBvh {
 // traversal stack.  0 passes: the builder's tree, byte for byte.  Sets with curves get no pass whatever the options say: the passes
 // gained 3 % on the hair scene, but a frame of a small hair scene with nearly every ray suspended did not end once on such a tree and
 // the reason is not known; triangle-only trees are what the flagship scenes have.
-constexpr uint32_t kReinsertPasses = 4, kReinsertTop = 20000;
+//
+// What the collapse and the passes minimise (`cost`; DESIGN.md section 8, "The cost").  kBvhCostTurns prices what a ray's traversal pays
+// in loop turns: a Q node visit is one turn of weight kCostNode, a triangle leaf of a triangle-only tree is one TriPair and one turn of
+// weight kCostLeaf whether it holds one triangle or two, and (`surface_term`) a leaf whose box on its Q node's 8-bit grid is thicker than
+// the primitives behind it by more than the rays' tmin is also charged for the rays that START on those primitives -- every bounce and
+// shadow ray starts on a surface and passes such a slab.  With this cost a pass decides every move on its own (`reinsert_try`): the
+// best few positions by area growth are priced by the collapse's below[root] and the node goes where that is lowest, or back.
+// kBvhCostPrims is the pricing of before: a leaf costs its primitives, a node 1, no surface term, a pass placed by area growth and kept
+// or undone as a whole.  Trees with curve leaves are priced that way whatever `cost` says (a curve leaf's pieces ARE tested one after
+// the other) and get no passes (above).
+// Like the passes, the turn cost is something the caller asks for: a default-constructed BvhBuildOptions, and build_qtree / qtree_cost /
+// build_qlayout called without options, build and collapse as they always did (tests/golden/qlayout_hashes.txt records exactly that);
+// the scene commit fills the options from the knobs, where both are on by default.
+constexpr uint32_t kReinsertPasses = 4, kReinsertTop = 20000, kReinsertTry = 4, kMaxReinsertTry = 8;
+constexpr uint32_t kBvhCostPrims = 0, kBvhCostTurns = 1;
+// The weights of a node turn and of a leaf turn.  Derivation (the re-insertion's A/B on C2, which runs about 6
+// closest-hit rays per 4 shadow rays): per mixed ray 0.6 * 6.28 + 0.4 * 7.54 = 6.78 node visits and 2.84 triangle tests before,
+// 0.6 * 5.40 + 0.4 * 6.03 = 5.65 and 0.6 * 3.01 + 0.4 * 4.78 = 3.72 after, k_trace 29.3 -> 27.7 ms.  With time ~ n + r * l:
+// 29.3 / 27.7 = (6.78 + 2.84 r) / (5.65 + 3.72 r) gives r = 0.74.  Cross-check on the loop's two blocks: the leaf turn is 168
+// instructions (136 VALU) against the node turn's 198 (157 VALU), 0.85-0.87 -- an upper bound, the node turn also pays the stack
+// traffic and the sort.  On walked rays (tests/cpp/bvh_rays_check.cc --explore, the flagship's scene) 0.60, 0.75 and 0.85 build trees
+// within 0.4 % of each other in turns per bounce and per shadow ray, and 1.00 costs camera rays 2 % more: 0.75 stays.
+constexpr double kCostNode = 1.0, kCostLeaf = 0.75;
+constexpr double kSurfaceEps = 1e-3;  // the tmin of bounce and shadow rays (dshade.h): a slab thinner than this lets a ray that starts on it out
 struct BvhBuildOptions {
   uint32_t reinsert_passes = 0;
   uint32_t reinsert_top = kReinsertTop;
   bool for_qtree = true;
+  uint32_t cost = kBvhCostPrims;        // kBvhCostTurns: what commit asks for unless PBRHIP_BVH_COST=0; kBvhCostPrims: the tree of before, byte for byte
+  bool surface_term = true;             // (kBvhCostTurns only)
+  uint32_t reinsert_try = kReinsertTry; // positions priced per candidate, at most kMaxReinsertTry; 0: passes placed by area growth and kept as a whole (kBvhCostTurns only)
+  double cost_leaf = kCostLeaf;         // (kBvhCostTurns only; the harness varies it)
 };
 
 // Binned-SAH BVH2 over primitive boxes; leaves hold <= kMaxLeaf primitives of ONE kind.
@@ -91,7 +118,7 @@ void build_bvh(const std::vector<float>& lo, const std::vector<float>& hi, const
 
 // What the collapse below pays for a binary tree -- below[root] of its dynamic programme -- without emitting a node, and the exact
 // stack need of the Q tree it would emit.
-double qtree_cost(const std::vector<BvhNode>& nodes, uint32_t* stack_need);
+double qtree_cost(const std::vector<BvhNode>& nodes, uint32_t* stack_need, const BvhBuildOptions& opt = BvhBuildOptions());
 
 // The binary tree collapsed to four children per node with quantised boxes (dscene.h::QNode).  Which descendants of a
 // binary node become the children of its Q node -- a frontier of at most four subtrees below it -- is chosen bottom-up by
@@ -102,7 +129,9 @@ double qtree_cost(const std::vector<BvhNode>& nodes, uint32_t* stack_need);
 // rounds outwards from there, as the traversal's exactness argument needs.
 // Returns the EXACT stack need of a near-first traversal of the Q tree: the maximum over root-to-leaf paths of the sum of
 // (children - 1) of the nodes on the path (a node pushes all hit children but the nearest).
-uint32_t build_qtree(const std::vector<BvhNode>& nodes, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out);
+// opt: the cost (`cost`, `surface_term`, `cost_leaf`) -- the one the tree was built for.
+uint32_t build_qtree(const std::vector<BvhNode>& nodes, const std::function<uint32_t(uint32_t)>& map_leaf, std::vector<QNode>* out,
+                     const BvhBuildOptions& opt = BvhBuildOptions());
 
 // The Q tree as the traversal kernels read it (DScene::wide: nodes, then `tri` from q_tri0, then `pts` from q_pt0; dscene.h::QNode).
 struct QLayout {
@@ -113,7 +142,8 @@ struct QLayout {
   size_t leaves_one = 0, leaves_pair = 0;  // curve leaves of one / two pieces (counted over the collapse's visits)
 };
 // slots: the binary tree's slots as dscene.h lays them out (routing bits in slots[4k + 2].w); kinds: per primitive, 0 triangle / 1 curve.
-void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out);
+void build_qlayout(const FlatBvh& bvh, const std::vector<float4>& slots, const std::vector<uint8_t>& kinds, QLayout* out,
+                   const BvhBuildOptions& opt = BvhBuildOptions());
 
 // Where the random walks' rays start (dscene.h::SssEntry), per instance: the cut of the Q tree around the instance's primitive
 // bounds ilo / ihi (3 floats per instance) with at most max_foreign foreign references.  entry 0: start at the root.

@@ -18,6 +18,7 @@ struct Knobs {
   bool wide = true;             // PBRHIP_WIDE: a value that atoi reads as 0 (any non-number too) = no Q tree: none is built at commit, none is walked at render
   bool bvh_reinsert = true;     // PBRHIP_BVH_REINSERT (1): 0 = the host builder's tree as its top-down splits leave it, no subtree re-insertion (host_scene.h::BvhBuildOptions; triangle-only scenes, the others never get it)
   uint32_t bvh_reinsert_top = 20000;  // PBRHIP_BVH_REINSERT_TOP (kReinsertTop): the largest nodes by box area that a re-insertion pass takes out and puts back; 0 = none
+  bool bvh_cost = true;         // PBRHIP_BVH_COST (1): 0 = the host builder and its Q collapse price a leaf per primitive and place re-insertion passes by area growth alone, as before the traversal's turns were priced (host_scene.h::BvhBuildOptions::cost; for A/Bs)
   bool sss_entry = true;        // PBRHIP_SSS_ENTRY (1): 0 = random walks start at the root, not at the cut of the Q tree around their instance
   uint32_t sss_foreign = 3;     // PBRHIP_SSS_FOREIGN (3): foreign references allowed in a walk's entry cut (at most kSssMaxForeign)
   bool debug = false;           // PBRHIP_DEBUG: set = commit and render print sizes and free memory on stderr

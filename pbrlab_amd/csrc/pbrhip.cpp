@@ -73,6 +73,7 @@ Knobs pb::read_knobs() {
   k.wide = not_zero("PBRHIP_WIDE");
   k.bvh_reinsert = u32("PBRHIP_BVH_REINSERT", 1u) != 0u;
   k.bvh_reinsert_top = u32("PBRHIP_BVH_REINSERT_TOP", kReinsertTop);
+  k.bvh_cost = u32("PBRHIP_BVH_COST", 1u) != 0u;
   k.sss_entry = u32("PBRHIP_SSS_ENTRY", 1u) != 0u;
   k.sss_foreign = u32("PBRHIP_SSS_FOREIGN", 3u);
   k.debug = env("PBRHIP_DEBUG") != nullptr;
