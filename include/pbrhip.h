@@ -438,6 +438,68 @@ enum { PBRHIP_PROJECTION_LATLONG = 0, PBRHIP_PROJECTION_FISHEYE = 1, PBRHIP_PROJ
 int pbrhip_projection_rays_device(pbrhip_scene*, uint32_t projection, float param, uint32_t width, uint32_t height, uint32_t first_pass,
                                   uint32_t num_pass, uint64_t seed_seq, void* d_rays, void* stream);
 
+/* ---- motion vectors and temporal accumulation across refits ----
+ * For a sequence rendered at a few samples per pixel per frame: where the surface point seen in each pixel was one frame ago, and an
+ * accumulation that re-uses the previous frames' samples there and rejects history where the point was hidden.  Per frame:
+ *   pbrhip_scene_snapshot_pose -> pbrhip_scene_update_* / pbrhip_scene_set_camera -> pbrhip_scene_refit -> pbrhip_render ->
+ *   pbrhip_render_motion -> pbrhip_temporal_accumulate (-> pbrhip_denoise of the accumulated mean).
+ *
+ * pbrhip_scene_snapshot_pose keeps a device-to-device copy of what defines the pose of a committed scene: its slots (64 bytes each,
+ * world space: a triangle's corners, a curve piece's two end points) and the camera state in effect -- pbrhip_scene_set_camera's
+ * arguments, or without a user camera the scene's bounds, which the reference's camera is derived from (it moves when they do).  The copy
+ * is ordered on the scene's stream.  A second call replaces the first.  The snapshot survives pbrhip_scene_update_*, pbrhip_scene_refit
+ * (host path and device geometry mode), material updates, pbrhip_scene_set_camera and pbrhip_scene_set_environment; pbrhip_scene_commit
+ * drops it (slot order changes); pbrhip_scene_replicate does not carry it.  An uncommitted or stale scene: PBRHIP_ESTATE.  A scene that
+ * never calls it allocates nothing. */
+int pbrhip_scene_snapshot_pose(pbrhip_scene*);
+/* Per pixel (x, y) of the rank's pixels (tile_rank / tile_world / shard_block select them as in pbrhip_render_features; the other
+ * pixels of the buffers are zeroed): the pixel-CENTRE ray of the scene's current camera -- jitter jx = jy = 0.5, the lens point at the lens
+ * centre, so a pinhole even when a thin lens is set; the cameras' own arithmetic -- and its closest hit.  No generator is involved:
+ * num_sample, first_pass, seed_seq, flags, max_paths_in_flight, num_streams and tail_paths are ignored.  Each output may be NULL.
+ *   ident   W*H*4 uint32: slot (the hit's index into pbrhip_scene_read_slots' arrays), then the bits of u, v, t: what
+ *           pbrhip_trace_closest reports for that ray, bit for bit; a miss: (PBRHIP_NONE, 0, 0, 0).  Also a picking buffer.
+ *   guide   W*H*4 float: the shading normal (Surface::n_s) turned towards the viewer -- a curve's tangent as it is -- | t; a miss: zeros.
+ *   motion  W*H*4 float: (mx, my, z_prev, valid).  X_prev = the hit's point on the snapshot's pose: (1 - u - v) v0 + u v1 + v v2 of the
+ *           snapshot's slot for a triangle; for a curve the point a + (4 u - sub) (b - a) on the axis of the snapshot's piece (u is the
+ *           cubic's parameter, the piece covers [sub / 4, (sub + 1) / 4]: the centre line the traversal tests; the ribbon's width is
+ *           ignored).  (px, py) = the continuous pixel coordinates at which the snapshot's pinhole camera -- the one pbrhip_render would
+ *           have derived from the snapshot's state for desc->width x desc->height -- sees X_prev; mx = px - (x + 0.5),
+ *           my = py - (y + 0.5), z_prev = |X_prev - eye_prev|.  valid = 1 (a triangle) or 2 (a curve: the accumulation's normal test
+ *           takes |N . N| for it, a tangent has no facing -- guide has no component to spare for that mark, its .w is t bit for bit)
+ *           when the ray hit and X_prev lies in front of the snapshot's camera, else the whole value is (0, 0, 0, 0).  A point outside
+ *           the frame keeps its valid: the accumulation decides.
+ * The results do not depend on the tree builder, shard_block or PBRHIP_WIDE.  No snapshot: PBRHIP_ESTATE; the other errors are
+ * pbrhip_render_features'.  Not provided: caller-supplied ray lists and the lat-long / fisheye / ortho projections, motion through the
+ * thin lens, motion of the environment background. */
+int pbrhip_render_motion(pbrhip_scene*, const pbrhip_render_desc*, float* motion, float* guide, uint32_t* ident);
+/* Same, into DEVICE buffers on the scene's device. */
+int pbrhip_render_motion_device(pbrhip_scene*, const pbrhip_render_desc*, float* d_motion, float* d_guide, uint32_t* d_ident);
+/* The reprojecting accumulation; needs no scene.  rgba / count: the current frame's RenderLayer; motion / guide: the current frame's
+ * pbrhip_render_motion buffers; hist_rgba: W*H*4, the accumulated mean | history length (a previous call's out_rgba); hist_guide: the
+ * guide of the frame hist_rgba was made for; both NULL: no history.  out_rgba: W*H*4, the new mean | the new history length (it must not
+ * be hist_rgba; the guide to hand in with the next frame is this frame's guide).  Per pixel (x, y), float32, every operation rounded
+ * once: c = rgb / count; count == 0: out = (0, 0, 0, 0); valid == 0 or no history: out = (c, 1).  Otherwise q = (x + mx, y + my),
+ * x0 = floor(q.x), y0 = floor(q.y), f = q - (x0, y0); the taps (x0 + i, y0 + j), i, j in {0, 1}, in the order (0, 0) (1, 0) (0, 1) (1, 1),
+ * with the weights w = (i ? f.x : 1 - f.x) (j ? f.y : 1 - f.y).  A tap is accepted when it is inside the image, its history length is > 0,
+ * hist_guide.w > 0, |hist_guide.w - z_prev| <= sigma_depth z_prev and N_hist . N_now >= normal_cos_min (|N_hist . N_now| when valid == 2).
+ * S = the sum of the accepted weights; S == 0: out = (c, 1).  Otherwise h = sum(w hist.rgb) / S, n = sum(w hist.len) / S,
+ * len = min(n + 1, max_history), a = max(1 / len, alpha_min), out = (h + a (c - h), len).
+ * PBRHIP_EINVAL, before any device work: a NULL rgba, count, motion, guide or out_rgba, one of hist_rgba / hist_guide without the other,
+ * out_rgba == hist_rgba, a NaN parameter, max_history outside [1, 2^24], a zero size.  The parameters are never read as "default": pass
+ * the macros (profiles/README.md "Temporal accumulation" has the sweep behind them).
+ * Not provided: variance-guided filtering, reprojection of the background by direction, a multi-GPU twin. */
+#define PBRHIP_TEMPORAL_ALPHA_MIN 0.2f
+#define PBRHIP_TEMPORAL_SIGMA_DEPTH 0.05f
+#define PBRHIP_TEMPORAL_NORMAL_COS_MIN 0.9f
+#define PBRHIP_TEMPORAL_MAX_HISTORY 32u
+int pbrhip_temporal_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* motion,
+                               const float* guide, const float* hist_rgba, const float* hist_guide, float alpha_min, float sigma_depth,
+                               float normal_cos_min, uint32_t max_history, float* out_rgba);
+/* Same with DEVICE pointers on `device`. */
+int pbrhip_temporal_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                      const float* d_motion, const float* d_guide, const float* d_hist_rgba, const float* d_hist_guide,
+                                      float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* d_out_rgba);
+
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks
  * with index % world == r (pbrhip_render_desc.tile_rank / tile_world / shard_block) into a zeroed full-size layer, then the

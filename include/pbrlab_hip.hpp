@@ -381,6 +381,9 @@ public:
     Check(pbrhip_scene_update_curve_mesh_device(h_, LibraryMeshId(mesh_ptr), d_vertices_xyzr, num_vertices, stream));
   }
   void RefitScene() { Check(pbrhip_scene_refit(h_)); }
+  // pbrhip_scene_snapshot_pose: keeps the committed scene's slots and camera state as the pose RenderMotion() measures from; before the
+  // frame's edits.  A second call replaces the first, CommitScene() drops it.
+  void SnapshotPose() { Check(pbrhip_scene_snapshot_pose(h_)); }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
   void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }
@@ -609,6 +612,62 @@ inline std::vector<float> Denoise(const RenderLayer& layer, const FeatureLayer* 
                                 features ? features->count.data() : nullptr, o.iterations, o.sigma_color, o.sigma_depth, o.normal_squarings,
                                 o.albedo ? 0u : PBRHIP_DENOISE_NO_ALBEDO, out.data());
   if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::Denoise: ") + pbrhip_last_error());
+  return out;
+}
+
+// ---- motion vectors and temporal accumulation (not in the reference) ----
+// motion: mx, my, z_prev, valid (0 none, 1 triangle, 2 curve); guide: viewer-facing shading normal | t; ident: slot (PBRHIP_NONE: a miss),
+// the bits of u, v, t -- width x height x 4 each
+struct MotionLayer {
+  size_t width = 0, height = 0;
+  std::vector<float> motion, guide;
+  std::vector<uint32_t> ident;
+};
+// pbrhip_render_motion: where the point the current camera's centre ray sees in each pixel was at scene.SnapshotPose().  Throws with
+// pbrhip_last_error() on a library error (no snapshot among them).
+inline void RenderMotion(const Scene& scene, const uint32_t width, const uint32_t height, MotionLayer* out) {
+  out->width = width, out->height = height;
+  out->motion.assign(size_t(width) * height * 4, 0.0f), out->guide.assign(size_t(width) * height * 4, 0.0f), out->ident.assign(size_t(width) * height * 4, 0u);
+  pbrhip_render_desc d = {};
+  d.width = width, d.height = height, d.num_sample = 1, d.tile_world = 1;
+  if (pbrhip_render_motion(scene.handle(), &d, out->motion.data(), out->guide.data(), out->ident.data()) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderMotion: ") + pbrhip_last_error());
+}
+// the accumulated mean | history length, and the guide of the frame it was made for: what TemporalAccumulate returns and takes back
+struct TemporalHistory {
+  size_t width = 0, height = 0;
+  std::vector<float> rgba, guide;
+  // the RenderLayer Denoise() takes for the accumulated frame: mean | 1, count 1 (0 where the history holds nothing)
+  void Layer(RenderLayer* l) const {
+    l->Resize(width, height);
+    for (size_t i = 0; i < width * height; ++i) {
+      const bool any = rgba[4 * i + 3] > 0.0f;
+      l->count[i] = any ? 1u : 0u;
+      for (int c = 0; c < 3; ++c) l->rgba[4 * i + c] = rgba[4 * i + c];
+      l->rgba[4 * i + 3] = any ? 1.0f : 0.0f;
+    }
+  }
+};
+struct TemporalOptions {
+  float alpha_min = PBRHIP_TEMPORAL_ALPHA_MIN, sigma_depth = PBRHIP_TEMPORAL_SIGMA_DEPTH, normal_cos_min = PBRHIP_TEMPORAL_NORMAL_COS_MIN;
+  uint32_t max_history = PBRHIP_TEMPORAL_MAX_HISTORY;
+  int device = 0;
+};
+// pbrhip_temporal_accumulate: the current frame's layer blended into `history` (nullptr: none) where `motion` says it shows the same
+// surface -> the new history.  Throws with pbrhip_last_error() on a library error.
+inline TemporalHistory TemporalAccumulate(const RenderLayer& layer, const MotionLayer& motion, const TemporalHistory* history,
+                                          const TemporalOptions& o = TemporalOptions()) {
+  if (motion.width != layer.width || motion.height != layer.height || (history && (history->width != layer.width || history->height != layer.height)))
+    throw std::runtime_error("pbrlab::TemporalAccumulate: layer, motion and history differ in size");
+  TemporalHistory out;
+  out.width = layer.width, out.height = layer.height;
+  out.rgba.resize(layer.width * layer.height * 4);
+  out.guide = motion.guide;
+  const int rc = pbrhip_temporal_accumulate(o.device, uint32_t(layer.width), uint32_t(layer.height), layer.rgba.data(), layer.count.data(),
+                                            motion.motion.data(), motion.guide.data(), history ? history->rgba.data() : nullptr,
+                                            history ? history->guide.data() : nullptr, o.alpha_min, o.sigma_depth, o.normal_cos_min,
+                                            o.max_history, out.rgba.data());
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::TemporalAccumulate: ") + pbrhip_last_error());
   return out;
 }
 

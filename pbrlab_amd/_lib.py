@@ -30,6 +30,7 @@ EXPORTS = [
     "pbrhip_scene_update_triangle_mesh_device", "pbrhip_scene_update_curve_mesh_device", "pbrhip_scene_read_slots",
     "pbrhip_render_adaptive", "pbrhip_render_adaptive_device", "pbrhip_adaptive_step",
     "pbrhip_render_rays", "pbrhip_render_rays_device", "pbrhip_render_features_rays_device", "pbrhip_projection_rays_device",
+    "pbrhip_scene_snapshot_pose", "pbrhip_render_motion", "pbrhip_render_motion_device", "pbrhip_temporal_accumulate", "pbrhip_temporal_accumulate_device",
 ]
 
 
@@ -76,6 +77,9 @@ def lib():
         _lib.pbrhip_render_rays_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         _lib.pbrhip_render_features_rays_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
         _lib.pbrhip_projection_rays_device.argtypes = [vp, u32, f32, u32, u32, u32, u32, C.c_uint64, vp, vp]
+        _lib.pbrhip_scene_snapshot_pose.argtypes = [vp]
+        _lib.pbrhip_render_motion.argtypes = _lib.pbrhip_render_motion_device.argtypes = [vp, vp, vp, vp, vp]
+        _lib.pbrhip_temporal_accumulate.argtypes = _lib.pbrhip_temporal_accumulate_device.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, vp, f32, f32, f32, u32, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -384,6 +384,11 @@ class Scene:
         a fresh scene built from the edited model and committed with the same builder"""
         _chk(self.L.pbrhip_scene_refit(self.h))
 
+    def SnapshotPose(self):
+        """pbrhip_scene_snapshot_pose: keeps the committed scene's slots and camera state on the device as the pose
+        RenderMotion measures from.  Call it before the frame's edits; a second call replaces the first, CommitScene drops it."""
+        _chk(self.L.pbrhip_scene_snapshot_pose(self.h))
+
     def AddTexture(self, pixels):
         """Scene::AddTexture: pixels (H, W, C) float32."""
         px = np.ascontiguousarray(pixels, np.float32)
@@ -900,6 +905,115 @@ def DenoiseDevice(device, width, height, rgba_ptr, count_ptr, out_ptr, features=
     f = (None, None, None) if features is None else tuple(features)
     _chk(_lib.lib().pbrhip_denoise_device(int(device), width, height, rgba_ptr, count_ptr, *f,
                                           *_denoise_args(iterations, sigma_color, sigma_depth, normal_squarings, albedo), out_ptr))
+
+
+# pbrhip_temporal_accumulate's defaults (include/pbrhip.h PBRHIP_TEMPORAL_*)
+TEMPORAL_ALPHA_MIN, TEMPORAL_SIGMA_DEPTH, TEMPORAL_NORMAL_COS_MIN, TEMPORAL_MAX_HISTORY = 0.2, 0.05, 0.9, 32
+NONE = 0xFFFFFFFF  # PBRHIP_NONE: MotionLayer.ident's slot of a miss
+
+
+class MotionLayer:
+    """pbrhip_render_motion's buffers: motion (H, W, 4) float32 = mx, my, z_prev, valid (0 none, 1 triangle, 2 curve),
+    guide (H, W, 4) float32 = viewer-facing shading normal (a curve's tangent as it is) | t, ident (H, W, 4) uint32 = slot (NONE: a
+    miss), bits of u, v, t.  Each is a numpy array, or a tensor on the scene's GPU when RenderMotion wrote into the caller's."""
+
+    def __init__(self, motion, guide, ident):
+        self.motion, self.guide, self.ident = motion, guide, ident
+
+
+class TemporalHistory:
+    """What TemporalAccumulate returns and takes back with the next frame: rgba (H, W, 4) = the accumulated mean | the history length,
+    guide = the guide of the frame it was made for (numpy arrays, or tensors on one GPU)."""
+
+    def __init__(self, rgba, guide):
+        self.rgba, self.guide = rgba, guide
+
+    def layer(self):
+        """The RenderLayer Denoise takes for the accumulated frame: rgba = mean | 1, count = 1 (0 where the history holds nothing);
+        Accumulate -> Denoise is the chain.  Downloads a tensor history."""
+        rgba = np.array(self.rgba.cpu().numpy() if hasattr(self.rgba, "data_ptr") else self.rgba, np.float32)
+        out = RenderLayer(rgba.shape[1], rgba.shape[0])
+        out.count[...] = rgba[..., 3] > 0
+        out.rgba[...] = rgba
+        out.rgba[..., 3] = out.count
+        return out
+
+
+def _image_arg(a, shape, dtype, what, device=None):
+    """An image argument of the temporal calls -> (pointer, is_device, keep-alive): None, a numpy array, or a contiguous tensor of that
+    shape and dtype in GPU memory (on `device` when that is known).  TypeError / ValueError here, before any C call."""
+    if a is None:
+        return None, False, None
+    if hasattr(a, "data_ptr"):
+        if not str(getattr(a, "dtype", "")).endswith(dtype):
+            raise TypeError(f"{what} must be {dtype}, not {getattr(a, 'dtype', None)}")
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{what} must have the shape {tuple(shape)}, not {tuple(a.shape)}")
+        if not a.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        dev = getattr(a, "device", None)
+        if getattr(dev, "type", None) != "cuda":
+            raise ValueError(f"{what} must be in GPU memory, not on {dev}")
+        if device is not None and dev.index is not None and dev.index != device:
+            raise ValueError(f"{what} is on device {dev.index}, not on device {device}")
+        return int(a.data_ptr()), True, a
+    keep = np.ascontiguousarray(a, dtype)
+    if keep.shape != tuple(shape):
+        raise ValueError(f"{what} must have the shape {tuple(shape)}, not {keep.shape}")
+    return keep.ctypes.data, False, keep
+
+
+def RenderMotion(scene, width, height, *, tile_rank=0, tile_world=1, shard_block=0, device_out=None):
+    """pbrhip_render_motion: per pixel where the point the current camera's centre ray sees was at Scene.SnapshotPose()
+    -> MotionLayer of numpy arrays.  device_out: optional (motion, guide, ident) -- float32, float32, int32 / uint32 (H, W, 4) tensors on
+    the scene's GPU, or DEVICE pointers (ints); None / 0 = not wanted -- written in place; the MotionLayer then holds them as given."""
+    L = _lib.lib()
+    desc = RenderDesc(width, height, 1, 0, 0, tile_rank, tile_world, 0, 0, 0, 0, shard_block)
+    shape = (int(height), int(width), 4)
+    if device_out is not None:
+        if len(device_out) != 3:
+            raise TypeError("device_out: (motion, guide, ident)")
+        ptrs = []
+        for a, dt, what in zip(device_out, ("float32", "float32", "int32"), ("motion", "guide", "ident")):
+            if a is None or isinstance(a, int):
+                ptrs.append(a or None)
+            else:
+                ptrs.append(_image_arg(a, shape, dt, f"device_out's {what}", getattr(scene, "device", None))[0])
+        _chk(L.pbrhip_render_motion_device(scene.h, C.byref(desc), *[C.c_void_p(p) for p in ptrs]))
+        return MotionLayer(*device_out)
+    out = MotionLayer(np.zeros(shape, np.float32), np.zeros(shape, np.float32), np.zeros(shape, np.uint32))
+    _chk(L.pbrhip_render_motion(scene.h, C.byref(desc), out.motion.ctypes.data, out.guide.ctypes.data, out.ident.ctypes.data))
+    return out
+
+
+def TemporalAccumulate(layer, motion_layer, history=None, *, alpha_min=TEMPORAL_ALPHA_MIN, sigma_depth=TEMPORAL_SIGMA_DEPTH,
+                       normal_cos_min=TEMPORAL_NORMAL_COS_MIN, max_history=TEMPORAL_MAX_HISTORY, device=None):
+    """pbrhip_temporal_accumulate: the RenderLayer of the current frame (anything with .rgba sums and .count) blended into
+    `history` (a TemporalHistory of the previous frame; None: none) where its MotionLayer says the history shows the same surface ->
+    the new TemporalHistory.  With numpy arrays everything travels through the host; when layer.rgba is a tensor, every buffer has to be
+    a tensor on that GPU (layer.count int32 / uint32) and the result is made of tensors too (torch is then the caller's)."""
+    on_gpu = hasattr(layer.rgba, "data_ptr")
+    h, w = (int(n) for n in tuple(layer.count.shape))
+    dev = (layer.rgba.device.index or 0) if on_gpu else (_device if device is None else int(device))
+    img, cnt = (h, w, 4), (h, w)
+    args = [_image_arg(layer.rgba, img, "float32", "layer.rgba", dev if on_gpu else None),
+            _image_arg(layer.count, cnt, "int32" if on_gpu else "uint32", "layer.count", dev if on_gpu else None),
+            _image_arg(motion_layer.motion, img, "float32", "motion", dev if on_gpu else None),
+            _image_arg(motion_layer.guide, img, "float32", "guide", dev if on_gpu else None),
+            _image_arg(None if history is None else history.rgba, img, "float32", "history.rgba", dev if on_gpu else None),
+            _image_arg(None if history is None else history.guide, img, "float32", "history.guide", dev if on_gpu else None)]
+    if any(d != on_gpu for p, d, _ in args if p is not None):
+        raise TypeError("TemporalAccumulate: the buffers are either all numpy arrays or all tensors on one GPU")
+    params = (C.c_float(alpha_min), C.c_float(sigma_depth), C.c_float(normal_cos_min), C.c_uint32(int(max_history)))
+    if on_gpu:
+        import torch
+        out = torch.empty_like(layer.rgba)
+        torch.cuda.current_stream(layer.rgba.device).synchronize()  # (the library works on the device's null stream)
+        _chk(_lib.lib().pbrhip_temporal_accumulate_device(dev, w, h, *[p for p, _, _ in args], *params, int(out.data_ptr())))
+    else:
+        out = np.zeros(img, np.float32)
+        _chk(_lib.lib().pbrhip_temporal_accumulate(dev, w, h, *[p for p, _, _ in args], *params, out.ctypes.data))
+    return TemporalHistory(out, motion_layer.guide)
 
 
 # pbrhip_render_adaptive's defaults (include/pbrhip.h PBRHIP_ADAPTIVE_*)

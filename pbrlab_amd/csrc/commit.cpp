@@ -525,6 +525,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   // bound to tables that were never uploaded or to freed memory
   s->committed = false;
   s->dg.drop();  // (device geometry mode ends with the commit it belonged to)
+  s->pose_set = false, s->pose_slots.release();  // (a pose snapshot is in the old tree's slot order: DESIGN.md §16)
   stage_lights(s, &cs);
   if (int rc = flatten_prims(s, &cs.prims)) return rc;
   const uint32_t np = (uint32_t)cs.prims.size();

@@ -17,6 +17,7 @@
 #include "env_tables.h"
 #include "feature_kernels.h"
 #include "scene_impl.h"
+#include "temporal_kernels.h"
 
 using namespace pb;
 
@@ -633,9 +634,18 @@ extern "C" int pbrhip_scene_set_camera(pbrhip_scene* s, const float eye[3], cons
   });
 }
 // the frame of the scene's user camera for a width x height image, in double, rounded once (dscene.h::UserCamera)
-UserCamera pb::make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
+PoseCamera pb::pose_camera(const pbrhip_scene* s) {
+  PoseCamera c;
+  c.set = s->cam_set;
+  memcpy(c.eye, s->cam_eye, sizeof(c.eye)), memcpy(c.lookat, s->cam_lookat, sizeof(c.lookat)), memcpy(c.up, s->cam_up, sizeof(c.up));
+  c.vfov = s->cam_vfov, c.lens = s->cam_lens, c.focus = s->cam_focus;
+  memcpy(c.bmin, s->bmin, sizeof(c.bmin)), memcpy(c.bmax, s->bmax, sizeof(c.bmax));
+  return c;
+}
+UserCamera pb::make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) { return make_user_camera(pose_camera(s), width, height); }
+UserCamera pb::make_user_camera(const PoseCamera& pc, uint32_t width, uint32_t height) {
   double f[3], r[3], u[3], up[3];
-  for (int k = 0; k < 3; k++) f[k] = (double)s->cam_lookat[k] - s->cam_eye[k], up[k] = s->cam_up[k];
+  for (int k = 0; k < 3; k++) f[k] = (double)pc.lookat[k] - pc.eye[k], up[k] = pc.up[k];
   const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
   for (int k = 0; k < 3; k++) f[k] /= fl;
   r[0] = f[1] * up[2] - f[2] * up[1], r[1] = f[2] * up[0] - f[0] * up[2], r[2] = f[0] * up[1] - f[1] * up[0];
@@ -643,10 +653,10 @@ UserCamera pb::make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t 
   for (int k = 0; k < 3; k++) r[k] /= rl;
   u[0] = r[1] * f[2] - r[2] * f[1], u[1] = r[2] * f[0] - r[0] * f[2], u[2] = r[0] * f[1] - r[1] * f[0];
   UserCamera c;
-  for (int k = 0; k < 3; k++) c.eye[k] = s->cam_eye[k], c.f[k] = (float)f[k], c.r[k] = (float)r[k], c.u[k] = (float)u[k];
-  const double h = tan((double)s->cam_vfov * M_PI / 360.0);
+  for (int k = 0; k < 3; k++) c.eye[k] = pc.eye[k], c.f[k] = (float)f[k], c.r[k] = (float)r[k], c.u[k] = (float)u[k];
+  const double h = tan((double)pc.vfov * M_PI / 360.0);
   c.h = (float)h, c.ha = (float)(h * width / height);
-  c.lens = s->cam_lens, c.focus = s->cam_focus > 0.0f ? s->cam_focus : (float)fl;
+  c.lens = pc.lens, c.focus = pc.focus > 0.0f ? pc.focus : (float)fl;
   return c;
 }
 
@@ -670,8 +680,9 @@ extern "C" int pbrhip_create_tiles(uint32_t width, uint32_t height, uint32_t* ou
 }
 
 // camera of RenderingTile (render.cc:132-158)
-Camera pb::make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) {
-  const float *bmin = s->bmin, *bmax = s->bmax;
+Camera pb::make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height) { return make_camera(pose_camera(s), width, height); }
+Camera pb::make_camera(const PoseCamera& pc, uint32_t width, uint32_t height) {
+  const float *bmin = pc.bmin, *bmax = pc.bmax;
   float hs, vs;
   if (bmax[0] - bmin[0] > bmax[1] - bmin[1]) {
     hs = bmax[0] - bmin[0];
@@ -1715,6 +1726,167 @@ extern "C" int pbrhip_denoise(int device, uint32_t width, uint32_t height, const
     }
     if (int rc = denoise_impl(device, width, height, d_rgba.p, d_count.p, d_a.p, d_n.p, d_fc.p, iterations, sigma_color, sigma_depth,
                               normal_squarings, flags, d_out.p))
+      return rc;
+    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    return PBRHIP_OK;
+  });
+}
+
+// ------------------------------------------------------------------ motion vectors and temporal accumulation
+extern "C" int pbrhip_scene_snapshot_pose(pbrhip_scene* s) {
+  return guarded([&]() -> int {
+    if (!s) return fail(PBRHIP_EINVAL, "scene_snapshot_pose: scene is NULL");
+    if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+    PB_NOT_STALE(s);
+    HIPCHK(hipSetDevice(s->device));
+    const size_t words = (size_t)s->tree.num_slots * 4;
+    s->pose_set = false;
+    HIPCHK(s->pose_slots.reserve(words));
+    // on the scene's stream: behind the render that still reads the slots, in front of the refit that rewrites them
+    if (words) HIPCHK(hipMemcpyAsync(s->pose_slots.p, s->dscene.slots, words * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    s->pose_cam = pose_camera(s);
+    s->pose_set = true;
+    return PBRHIP_OK;
+  });
+}
+
+// the body of pbrhip_render_motion_device: device pointers on the scene's device, each may be null
+static int motion_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_motion, float* d_guide, uint32_t* d_ident) {
+  if (int rc = check_render_desc(s, d)) return rc;
+  if (!s->pose_set) return fail(PBRHIP_ESTATE, "render_motion: the scene has no pose snapshot (pbrhip_scene_snapshot_pose)");
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const size_t npx_img = (size_t)d->width * d->height;
+  if (d_motion) HIPCHK(hipMemsetAsync(d_motion, 0, npx_img * 4 * sizeof(float), st));
+  if (d_guide) HIPCHK(hipMemsetAsync(d_guide, 0, npx_img * 4 * sizeof(float), st));
+  if (d_ident) HIPCHK(hipMemsetAsync(d_ident, 0, npx_img * 4 * sizeof(uint32_t), st));
+  if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
+  const uint32_t npix = s->pk_npix;
+  if (npix == 0 || (!d_motion && !d_guide && !d_ident)) {
+    HIPCHK(hipStreamSynchronize(st));
+    return PBRHIP_OK;
+  }
+  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
+  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, st));
+  HIPCHK(s->spill.reserve(kSpillWords));
+  MotionArgs a{};
+  a.user = s->cam_set ? 1u : 0u, a.user_prev = s->pose_cam.set ? 1u : 0u;
+  if (a.user) a.ucam = make_user_camera(s, d->width, d->height);
+  else a.cam = make_camera(s, d->width, d->height);
+  if (a.user_prev) a.ucam_prev = make_user_camera(s->pose_cam, d->width, d->height);
+  else a.cam_prev = make_camera(s->pose_cam, d->width, d->height);
+  a.width = d->width, a.height = d->height;
+  a.pix = s->path_pix.p, a.npix = npix;
+  a.prev_slots = s->pose_slots.p;
+  a.motion = reinterpret_cast<float4*>(d_motion), a.guide = reinterpret_cast<float4*>(d_guide), a.ident = reinterpret_cast<uint4*>(d_ident);
+  a.overflow = s->counts.p + kCntOverflow, a.spill = s->spill.p;
+  launch_motion(st, s->dscene, a, k);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_render_motion_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_motion, float* d_guide, uint32_t* d_ident) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_motion: NULL argument");
+    return motion_impl(s, d, d_motion, d_guide, d_ident);
+  });
+}
+
+extern "C" int pbrhip_render_motion(pbrhip_scene* s, const pbrhip_render_desc* d, float* motion, float* guide, uint32_t* ident) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_motion: NULL argument");
+    if (int rc = check_render_desc(s, d)) return rc;
+    if (!s->pose_set) return fail(PBRHIP_ESTATE, "render_motion: the scene has no pose snapshot (pbrhip_scene_snapshot_pose)");
+    HIPCHK(hipSetDevice(s->device));
+    const size_t npx = (size_t)d->width * d->height;
+    DevBuf<float> d_m, d_g;
+    DevBuf<uint32_t> d_i;
+    if (motion) HIPCHK(d_m.reserve(npx * 4));
+    if (guide) HIPCHK(d_g.reserve(npx * 4));
+    if (ident) HIPCHK(d_i.reserve(npx * 4));
+    if (int rc = motion_impl(s, d, d_m.p, d_g.p, d_i.p)) return rc;
+    if (motion) HIPCHK(hipMemcpyAsync(motion, d_m.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (guide) HIPCHK(hipMemcpyAsync(guide, d_g.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (ident) HIPCHK(hipMemcpyAsync(ident, d_i.p, npx * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+// the checks both accumulation entry points share, before any device work
+static int check_temporal(int device, uint32_t width, uint32_t height, const void* rgba, const void* count, const void* motion, const void* guide,
+                          const void* hist_rgba, const void* hist_guide, float alpha_min, float sigma_depth, float normal_cos_min,
+                          uint32_t max_history, const void* out_rgba) {
+  if (!rgba || !count || !motion || !guide || !out_rgba) return fail(PBRHIP_EINVAL, "temporal_accumulate: NULL rgba, count, motion, guide or out_rgba");
+  if ((hist_rgba != nullptr) != (hist_guide != nullptr)) return fail(PBRHIP_EINVAL, "temporal_accumulate: hist_rgba and hist_guide come together or not at all");
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "temporal_accumulate: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "temporal_accumulate: image too large");
+  if (alpha_min != alpha_min || sigma_depth != sigma_depth || normal_cos_min != normal_cos_min) return fail(PBRHIP_EINVAL, "temporal_accumulate: a parameter is NaN");
+  if (max_history == 0 || max_history > (1u << 24)) return fail(PBRHIP_EINVAL, "temporal_accumulate: max_history %u is not in [1, 2^24]", max_history);
+  if (out_rgba == hist_rgba) return fail(PBRHIP_EINVAL, "temporal_accumulate: out_rgba is hist_rgba (the taps of one pixel read what another wrote)");
+  int n = 0;
+  if (int rc = pbrhip_device_count(&n)) return rc;
+  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "temporal_accumulate: device %d out of range (%d devices)", device, n);
+  return PBRHIP_OK;
+}
+
+// one launch on the device's null stream
+static int temporal_impl(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* motion, const float* guide,
+                         const float* hist_rgba, const float* hist_guide, float alpha_min, float sigma_depth, float normal_cos_min,
+                         uint32_t max_history, float* out_rgba) {
+  HIPCHK(hipSetDevice(device));
+  TemporalArgs a{};
+  a.width = width, a.height = height;
+  a.rgba = reinterpret_cast<const float4*>(rgba), a.count = count;
+  a.motion = reinterpret_cast<const float4*>(motion), a.guide = reinterpret_cast<const float4*>(guide);
+  a.hist_rgba = reinterpret_cast<const float4*>(hist_rgba), a.hist_guide = reinterpret_cast<const float4*>(hist_guide);
+  a.alpha_min = alpha_min, a.sigma_depth = sigma_depth, a.normal_cos_min = normal_cos_min, a.max_history = (float)max_history;
+  a.out = reinterpret_cast<float4*>(out_rgba);
+  launch_temporal(nullptr, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_temporal_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                                 const float* d_motion, const float* d_guide, const float* d_hist_rgba, const float* d_hist_guide,
+                                                 float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* d_out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_temporal(device, width, height, d_rgba, d_count, d_motion, d_guide, d_hist_rgba, d_hist_guide, alpha_min, sigma_depth,
+                                normal_cos_min, max_history, d_out_rgba))
+      return rc;
+    return temporal_impl(device, width, height, d_rgba, d_count, d_motion, d_guide, d_hist_rgba, d_hist_guide, alpha_min, sigma_depth,
+                         normal_cos_min, max_history, d_out_rgba);
+  });
+}
+
+extern "C" int pbrhip_temporal_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* motion,
+                                          const float* guide, const float* hist_rgba, const float* hist_guide, float alpha_min, float sigma_depth,
+                                          float normal_cos_min, uint32_t max_history, float* out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_temporal(device, width, height, rgba, count, motion, guide, hist_rgba, hist_guide, alpha_min, sigma_depth, normal_cos_min,
+                                max_history, out_rgba))
+      return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_img[5], d_out;  // rgba, motion, guide, hist_rgba, hist_guide
+    DevBuf<uint32_t> d_count;
+    const float* src[5] = {rgba, motion, guide, hist_rgba, hist_guide};
+    for (int i = 0; i < 5; i++) {
+      if (!src[i]) continue;
+      HIPCHK(d_img[i].reserve(npx * 4));
+      HIPCHK(hipMemcpy(d_img[i].p, src[i], npx * 4 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIPCHK(d_count.reserve(npx));
+    HIPCHK(d_out.reserve(npx * 4));
+    HIPCHK(hipMemcpy(d_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = temporal_impl(device, width, height, d_img[0].p, d_count.p, d_img[1].p, d_img[2].p, d_img[3].p, d_img[4].p, alpha_min, sigma_depth,
+                               normal_cos_min, max_history, d_out.p))
       return rc;
     HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;

@@ -168,6 +168,13 @@ struct AdaptiveBufs {
   std::vector<uint32_t> tiles0;            // the rank's tiles in the order of ensure_pixels' list: round 0's
   uint32_t key[7] = {0, 0, 0, 0, 0, 0, 0}; // the pk_* key tiles0 was derived under
 };
+// What defines the camera pbrhip_render derives for an image size: the caller's look-at camera (set), else the scene's bounds
+struct PoseCamera {
+  bool set = false;
+  float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, -1}, up[3] = {0, 1, 0};
+  float vfov = 30.0f, lens = 0.0f, focus = 0.0f;
+  float bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
+};
 inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
   return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
 }
@@ -230,6 +237,11 @@ struct pbrhip_scene {
   float cam_vfov = 30.0f, cam_lens = 0.0f, cam_focus = 0.0f;
   pb::DevBuf<uint32_t> hook_xyp;  // pbrhip_camera_rays' (x, y, pass) triples
   pb::DevBuf<float4> own_rays;    // pbrhip_render_rays' device copy of the caller's host rays
+  // pbrhip_scene_snapshot_pose: the slots and the camera state of the pose it was taken at; dropped by the next commit
+  // (slot order changes), not carried by pbrhip_scene_replicate.  A scene that never takes one holds an empty buffer and nothing else.
+  bool pose_set = false;
+  pb::DevBuf<float4> pose_slots;  // tree.num_slots x 4 words, DScene::slots' layout
+  pb::PoseCamera pose_cam;
   pb::DScene dscene;
   // render working set (grown on demand, reused across calls)
   pb::DevBuf<float4> rec, srec, ssrec, L, hit, sss_A, sh_e;  // path state (kernels.h::PathState): rec = 4 words of 16 B per path, srec = 2
@@ -305,4 +317,8 @@ int refresh_mesh_device(pbrhip_scene* s, uint32_t mesh_id);
 // the scene's cameras for a width x height image (pbrhip.cpp; pbrhip_camera_rays launches them too)
 UserCamera make_user_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
 Camera make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
+// the same two from a recorded state (pose_camera: the scene's current one)
+PoseCamera pose_camera(const pbrhip_scene* s);
+UserCamera make_user_camera(const PoseCamera& c, uint32_t width, uint32_t height);
+Camera make_camera(const PoseCamera& c, uint32_t width, uint32_t height);
 }  // namespace pb
