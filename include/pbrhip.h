@@ -487,7 +487,8 @@ int pbrhip_render_motion_device(pbrhip_scene*, const pbrhip_render_desc*, float*
  * PBRHIP_EINVAL, before any device work: a NULL rgba, count, motion, guide or out_rgba, one of hist_rgba / hist_guide without the other,
  * out_rgba == hist_rgba, a NaN parameter, max_history outside [1, 2^24], a zero size.  The parameters are never read as "default": pass
  * the macros (profiles/README.md "Temporal accumulation" has the sweep behind them).
- * Not provided: variance-guided filtering, reprojection of the background by direction, a multi-GPU twin. */
+ * Variance-guided filtering and an identity test of the history: the block below (pbrhip_svgf_accumulate, pbrhip_svgf_filter).
+ * Not provided: reprojection of the background by direction, a multi-GPU twin. */
 #define PBRHIP_TEMPORAL_ALPHA_MIN 0.2f
 #define PBRHIP_TEMPORAL_SIGMA_DEPTH 0.05f
 #define PBRHIP_TEMPORAL_NORMAL_COS_MIN 0.9f
@@ -499,6 +500,99 @@ int pbrhip_temporal_accumulate(int device, uint32_t width, uint32_t height, cons
 int pbrhip_temporal_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
                                       const float* d_motion, const float* d_guide, const float* d_hist_rgba, const float* d_hist_guide,
                                       float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* d_out_rgba);
+
+/* ---- variance-guided filtering and identity-tested history (SVGF, Schied et al. 2017) ----
+ * A second pipeline beside pbrhip_temporal_accumulate -> pbrhip_denoise, for the same sequences:
+ *   pbrhip_render -> pbrhip_render_features -> pbrhip_render_motion -> pbrhip_scene_object_ids -> pbrhip_svgf_accumulate -> pbrhip_svgf_filter.
+ * The accumulation also rejects history that belongs to another object and carries a per-pixel variance of what is filtered; the filter's
+ * luminance weight is scaled by that variance, so a pixel with a long history is filtered narrowly and a disoccluded one widely.
+ * Notation: u = 2^-24; "live" = history length > 0; lum(e) = (0.2126f e.r + 0.7152f e.g) + 0.0722f e.b.  All arithmetic is float32, every
+ * operation rounded once, in the order written here; exp is the library's; square root and division are correctly rounded.
+ *
+ * Object ids.  ident: pbrhip_render_motion's W*H*4 buffer.  ids[p] = word 24 + what of the ShadeRec (pbrhip_scene_read_slots) of slot
+ * ident[4 p]; PBRHIP_NONE for a miss and for any slot >= the scene's slot count (the kernel checks: the buffer is the caller's).  One
+ * gather, a lane per pixel.  The three words do not depend on the tree builder (the slot order does).  The buffer doubles as an object
+ * matte.  The device variant is ordered behind the caller's `stream` as pbrhip_render_rays_device is, and returns when the ids are
+ * written.  PBRHIP_ESTATE: an uncommitted or stale scene.  PBRHIP_EINVAL: a NULL scene, a NULL buffer with num_pixels > 0, what > 2. */
+#define PBRHIP_ID_PRIMITIVE 0u /* ShadeRec word 24: the canonical primitive id (gid) */
+#define PBRHIP_ID_INSTANCE 1u  /* word 25 */
+#define PBRHIP_ID_GEOM 2u      /* word 26 */
+int pbrhip_scene_object_ids(pbrhip_scene*, const uint32_t* ident, size_t num_pixels, uint32_t what, uint32_t* ids);
+int pbrhip_scene_object_ids_device(pbrhip_scene*, const void* d_ident, size_t num_pixels, uint32_t what, void* d_ids, void* stream);
+
+/* The accumulation; needs no scene.  rgba / count, motion / guide: as pbrhip_temporal_accumulate's.  albedo_hits + feature_count
+ * (pbrhip_render_features; both or neither): the albedo a = (albedo_hits.rgb + misses) / feature_count with misses = feature_count -
+ * albedo_hits.w, exactly pbrhip_denoise's (a miss counts as white; 1 where feature_count == 0 or without the buffers).  ids: this frame's
+ * object ids (W*H) or NULL.  History, all three or none: hist_illum W*H*4 (e.rgb | history length: a previous call's out_illum, or a
+ * filter's out_feedback), hist_var W*H (that call's out_var), hist_guide W*H*4 (that frame's guide); hist_ids W*H (that frame's ids) is
+ * given exactly when ids is given and the history is present.  Outputs: out_illum W*H*4 and out_var W*H; neither may be a history buffer.
+ * Per pixel p: count == 0: out_illum = (0, 0, 0, 0), out_var = 0.  Otherwise c = rgb / count, e = c / max(a, 1e-3) per channel,
+ * l = lum(e).  The taps, their weights and their acceptance are pbrhip_temporal_accumulate's, in its order and with its comparisons,
+ * hist_illum.w in the place of the history length; with ids one more condition: hist_ids[q] == ids[p].  valid == 0, no history, or
+ * S == 0: out_illum = (e, 1), out_var = 0.  Otherwise with the accepted taps' w: h = sum(w hist_illum.rgb) / S, n = sum(w hist_illum.w) / S,
+ * v = sum(w hist_var) / S (each sum in tap order), len = min(n + 1, max_history), al = max(1 / len, alpha_min), d = l - lum(h),
+ *   out_illum = (h + al (e - h), len),   out_var = (1 - al) (v + (al d) d).
+ * Without ids and albedo out_illum is pbrhip_temporal_accumulate's out_rgba bit for bit.  The variance is the exponentially weighted
+ * central form: it subtracts no large equals (mu2 - mu1^2 cancels where the variance is small against the mean, which is where the filter
+ * should be wide), it is never negative, with alpha_min = 0 it is the population variance of the pixel's l so far (Welford), and the
+ * mean it refers to is lum of the accumulated illumination: no moment image is carried.
+ * PBRHIP_EINVAL, before any device work: pbrhip_temporal_accumulate's refusals (out_var among the outputs), alpha_min outside [0, 1],
+ * one of albedo_hits / feature_count without the other, a history of one or two of its three buffers, hist_ids against the rule above,
+ * an output that is a history buffer or the other output.  The parameters are never read as "default": pass the macros. */
+#define PBRHIP_SVGF_ALPHA_MIN 0.2f
+int pbrhip_svgf_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
+                           const uint32_t* feature_count, const float* motion, const float* guide, const uint32_t* ids,
+                           const float* hist_illum, const float* hist_var, const float* hist_guide, const uint32_t* hist_ids,
+                           float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* out_illum,
+                           float* out_var);
+/* Same with DEVICE pointers on `device`. */
+int pbrhip_svgf_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                  const float* d_albedo_hits, const uint32_t* d_feature_count, const float* d_motion, const float* d_guide,
+                                  const uint32_t* d_ids, const float* d_hist_illum, const float* d_hist_var, const float* d_hist_guide,
+                                  const uint32_t* d_hist_ids, float alpha_min, float sigma_depth, float normal_cos_min,
+                                  uint32_t max_history, float* d_out_illum, float* d_out_var);
+
+/* The filter; needs no scene.  illum / var: an accumulation's outputs (a negative var reads as 0); guide: that frame's guide, N = guide.xyz
+ * as it is, z = guide.w, a pixel with guide.w == 0 is background; ids, albedo_hits + feature_count: as above, optional.  out_rgba: W*H*4,
+ * colour | 1, zeros where the pixel is not live.  out_feedback (may be NULL): W*H*4, the illumination after the FIRST iteration | the
+ * pixel's length (zeros where not live); handed in as the next frame's hist_illum it is the paper's feedback loop.
+ * Per pair (p, q) of live pixels inside the image, q = p + (dx, dy) s: w_n = max(0, N_p . N_q)^(2^normal_squarings) and the depth term
+ * x_z = |z_p - z_q| / ((sigma_depth z_p s) sqrt(dx dx + dy dy)) (0 when sigma_depth <= 0 or z_p == z_q) are pbrhip_denoise's; between two
+ * background pixels w_n = 1, x_z = 0; a background pixel and a surface weigh 0; w_id = 1 when ids is NULL or ids[p] == ids[q], else 0.
+ * Variance in, per live p with len_p = illum.w: len_p >= 4: v(0)_p = var_p.  Otherwise over the 7 x 7 window (s = 1, rows top to bottom,
+ * each left to right, p itself with g = 1 first) with g = w_id w_n exp(-x_z):
+ *   m = l_p + sum g (l_q - l_p) / sum g,   sigma2 = sum g ((l_q - m)(l_q - m)) / sum g,   v(0)_p = (sigma2 * 4) / len_p
+ * with l = lum(illum.rgb): two passes over the window, not a difference of moments.
+ * Iteration i = 0 .. iterations - 1, step s = 2^i, e(0) = illum.rgb: gv_p = sum k v(i)_q / sum k over the live pixels of the 3 x 3
+ * window at distance 1 (whatever s; rows top to bottom), k = [1 2 1] x [1 2 1]; S_p = sigma_lum sqrt(gv_p) + PBRHIP_SVGF_LUM_EPS.  Over
+ * pbrhip_denoise's 25 taps with its B3 weights h: w(p, p) = 1, else w = w_id w_n exp(-(x_z + x_l)), x_l = |lum(e_p) - lum(e_q)| / S_p
+ * (0 when sigma_lum <= 0 or the two are equal), and with hw = (w_n exp(..)) h:
+ *   e(i+1)_p = e_p + sum hw (e_q - e_p) / sum hw,   v(i+1)_p = sum (hw hw) v_q / (sum hw)(sum hw)
+ * -- the denoiser's form: a constant neighbourhood returns to the bit.  out.rgb = e(iterations) max(a, 1e-3): the clamped value the
+ * accumulation divided by -- deliberately not pbrhip_denoise's unclamped product, so that a surface of black albedo keeps its radiance.
+ * iterations: 1 .. 8, 0 = PBRHIP_SVGF_ITERATIONS.  PBRHIP_SVGF_LUM_EPS is fixed: far above the rounding noise 2^-23 l of a constant region
+ * for any l up to about 100 (such a region keeps weight 1), far below any real luminance step.  PBRHIP_SVGF_SIGMA_LUM is not the paper's
+ * 4 but the optimum of the sweep over (1, 2, 4, 8, 16) on the orbiting Cornell sequence (profiles/README.md "SVGF": the error rises
+ * with sigma_lum from 1 on; smaller values were not swept); sigma_depth and normal_squarings default to
+ * PBRHIP_DENOISE_SIGMA_DEPTH and PBRHIP_DENOISE_NORMAL_SQUARINGS.  The sigmas are never read as "default": pass the macros.
+ * PBRHIP_EINVAL: a NULL illum / var / guide / out_rgba, a NaN sigma, iterations > 8, normal_squarings > 16, a zero size, one of
+ * albedo_hits / feature_count without the other, an output that is illum, guide or the other output.
+ * Where the albedo hurts: a is estimated from each frame's own few samples, so at a pixel that an emitter of BLACK albedo covers partly
+ * it changes from frame to frame between about 1e-3 and the neighbour's albedo, and a history e = c / 1e-3 multiplied by this frame's a
+ * is wrong by orders of magnitude.  With such an emitter in view pass no albedo_hits / feature_count to either call (the colour itself
+ * is then accumulated and filtered): DESIGN.md §17 has the figures of both on the Cornell box, whose light is one.
+ * Not provided: a colour clamp against the current neighbourhood; |N . N| for hair tangents in the spatial weights (the filter has no
+ * valid mark: two hairs of opposite tangent weigh 0); a multi-GPU twin. */
+#define PBRHIP_SVGF_ITERATIONS 5
+#define PBRHIP_SVGF_LUM_EPS 1e-4f
+#define PBRHIP_SVGF_SIGMA_LUM 1.0f
+int pbrhip_svgf_filter(int device, uint32_t width, uint32_t height, const float* illum, const float* var, const float* guide,
+                       const uint32_t* ids, const float* albedo_hits, const uint32_t* feature_count, uint32_t iterations, float sigma_lum,
+                       float sigma_depth, uint32_t normal_squarings, float* out_rgba, float* out_feedback);
+/* Same with DEVICE pointers on `device`. */
+int pbrhip_svgf_filter_device(int device, uint32_t width, uint32_t height, const float* d_illum, const float* d_var, const float* d_guide,
+                              const uint32_t* d_ids, const float* d_albedo_hits, const uint32_t* d_feature_count, uint32_t iterations,
+                              float sigma_lum, float sigma_depth, uint32_t normal_squarings, float* d_out_rgba, float* d_out_feedback);
 
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks

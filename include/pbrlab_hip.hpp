@@ -384,6 +384,13 @@ public:
   // pbrhip_scene_snapshot_pose: keeps the committed scene's slots and camera state as the pose RenderMotion() measures from; before the
   // frame's edits.  A second call replaces the first, CommitScene() drops it.
   void SnapshotPose() { Check(pbrhip_scene_snapshot_pose(h_)); }
+  // pbrhip_scene_object_ids: per pixel of RenderMotion()'s ident buffer the primitive, instance or geometry id (PBRHIP_ID_*) of the slot seen
+  // there, PBRHIP_NONE for a miss: what SvgfAccumulate() tests the history's identity with, and an object matte
+  std::vector<uint32_t> ObjectIds(const std::vector<uint32_t>& ident, const uint32_t what = PBRHIP_ID_INSTANCE) const {
+    std::vector<uint32_t> ids(ident.size() / 4);
+    Check(pbrhip_scene_object_ids(h_, ident.data(), ids.size(), what, ids.data()));
+    return ids;
+  }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
   void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }
@@ -668,6 +675,69 @@ inline TemporalHistory TemporalAccumulate(const RenderLayer& layer, const Motion
                                             history ? history->guide.data() : nullptr, o.alpha_min, o.sigma_depth, o.normal_cos_min,
                                             o.max_history, out.rgba.data());
   if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::TemporalAccumulate: ") + pbrhip_last_error());
+  return out;
+}
+
+// ---- variance-guided filtering and identity-tested history (not in the reference) ----
+// the accumulated albedo-free illumination | history length, the variance of its luminance, and the guide and object ids (empty: none) of
+// the frame it was made for: what SvgfAccumulate returns and takes back, and what SvgfFilter filters
+struct SvgfHistory {
+  size_t width = 0, height = 0;
+  std::vector<float> illum, var, guide;
+  std::vector<uint32_t> ids;
+};
+struct SvgfAccumulateOptions {
+  float alpha_min = PBRHIP_SVGF_ALPHA_MIN, sigma_depth = PBRHIP_TEMPORAL_SIGMA_DEPTH, normal_cos_min = PBRHIP_TEMPORAL_NORMAL_COS_MIN;
+  uint32_t max_history = PBRHIP_TEMPORAL_MAX_HISTORY;
+  int device = 0;
+};
+// pbrhip_svgf_accumulate: TemporalAccumulate on colour / albedo (`features`; nullptr: albedo 1) that also rejects history of another
+// object (`ids`: scene.ObjectIds() of the frame; nullptr: no such test, as with a history made without ids) and carries the variance
+// of the luminance -> the new history.  Throws with pbrhip_last_error() on a library error.
+inline SvgfHistory SvgfAccumulate(const RenderLayer& layer, const MotionLayer& motion, const SvgfHistory* history, const FeatureLayer* features,
+                                  const std::vector<uint32_t>* ids, const SvgfAccumulateOptions& o = SvgfAccumulateOptions()) {
+  const size_t npx = layer.width * layer.height;
+  if (motion.width != layer.width || motion.height != layer.height || (history && (history->width != layer.width || history->height != layer.height)) ||
+      (features && (features->width != layer.width || features->height != layer.height)) || (ids && ids->size() != npx))
+    throw std::runtime_error("pbrlab::SvgfAccumulate: layer, motion, history, features and ids differ in size");
+  const bool with_ids = ids && (!history || !history->ids.empty());
+  SvgfHistory out;
+  out.width = layer.width, out.height = layer.height;
+  out.illum.resize(npx * 4), out.var.resize(npx);
+  out.guide = motion.guide;
+  if (ids) out.ids = *ids;
+  const int rc = pbrhip_svgf_accumulate(o.device, uint32_t(layer.width), uint32_t(layer.height), layer.rgba.data(), layer.count.data(),
+                                        features ? features->albedo.data() : nullptr, features ? features->count.data() : nullptr,
+                                        motion.motion.data(), motion.guide.data(), with_ids ? ids->data() : nullptr,
+                                        history ? history->illum.data() : nullptr, history ? history->var.data() : nullptr,
+                                        history ? history->guide.data() : nullptr, with_ids && history ? history->ids.data() : nullptr, o.alpha_min,
+                                        o.sigma_depth, o.normal_cos_min, o.max_history, out.illum.data(), out.var.data());
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::SvgfAccumulate: ") + pbrhip_last_error());
+  return out;
+}
+struct SvgfFilterOptions {
+  uint32_t iterations = 0;  // 0: PBRHIP_SVGF_ITERATIONS
+  float sigma_lum = PBRHIP_SVGF_SIGMA_LUM, sigma_depth = PBRHIP_DENOISE_SIGMA_DEPTH;  // <= 0: that weight off
+  uint32_t normal_squarings = PBRHIP_DENOISE_NORMAL_SQUARINGS;
+  int device = 0;
+};
+// pbrhip_svgf_filter: the variance-guided A-trous filter of `history`, the albedo of `features` multiplied back -> width x height x 4
+// floats, colour | 1.  feedback (may be nullptr) receives the history whose illumination is the one after the first iteration: hand it
+// to the next SvgfAccumulate() in the place of `history`.  Throws with pbrhip_last_error() on a library error.
+inline std::vector<float> SvgfFilter(const SvgfHistory& history, const FeatureLayer* features, SvgfHistory* feedback = nullptr,
+                                     const SvgfFilterOptions& o = SvgfFilterOptions()) {
+  if (features && (features->width != history.width || features->height != history.height))
+    throw std::runtime_error("pbrlab::SvgfFilter: features and history differ in size");
+  std::vector<float> out(history.width * history.height * 4), fb(feedback ? out.size() : 0);
+  const int rc = pbrhip_svgf_filter(o.device, uint32_t(history.width), uint32_t(history.height), history.illum.data(), history.var.data(),
+                                    history.guide.data(), history.ids.empty() ? nullptr : history.ids.data(),
+                                    features ? features->albedo.data() : nullptr, features ? features->count.data() : nullptr, o.iterations,
+                                    o.sigma_lum, o.sigma_depth, o.normal_squarings, out.data(), feedback ? fb.data() : nullptr);
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::SvgfFilter: ") + pbrhip_last_error());
+  if (feedback) {
+    if (feedback != &history) *feedback = history;
+    feedback->illum = fb;
+  }
   return out;
 }
 

@@ -31,6 +31,8 @@ EXPORTS = [
     "pbrhip_render_adaptive", "pbrhip_render_adaptive_device", "pbrhip_adaptive_step",
     "pbrhip_render_rays", "pbrhip_render_rays_device", "pbrhip_render_features_rays_device", "pbrhip_projection_rays_device",
     "pbrhip_scene_snapshot_pose", "pbrhip_render_motion", "pbrhip_render_motion_device", "pbrhip_temporal_accumulate", "pbrhip_temporal_accumulate_device",
+    "pbrhip_scene_object_ids", "pbrhip_scene_object_ids_device", "pbrhip_svgf_accumulate", "pbrhip_svgf_accumulate_device", "pbrhip_svgf_filter",
+    "pbrhip_svgf_filter_device",
 ]
 
 
@@ -80,6 +82,10 @@ def lib():
         _lib.pbrhip_scene_snapshot_pose.argtypes = [vp]
         _lib.pbrhip_render_motion.argtypes = _lib.pbrhip_render_motion_device.argtypes = [vp, vp, vp, vp, vp]
         _lib.pbrhip_temporal_accumulate.argtypes = _lib.pbrhip_temporal_accumulate_device.argtypes = [C.c_int, u32, u32, vp, vp, vp, vp, vp, vp, f32, f32, f32, u32, vp]
+        _lib.pbrhip_scene_object_ids.argtypes = [vp, vp, C.c_size_t, u32, vp]
+        _lib.pbrhip_scene_object_ids_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp]
+        _lib.pbrhip_svgf_accumulate.argtypes = _lib.pbrhip_svgf_accumulate_device.argtypes = [C.c_int, u32, u32] + [vp] * 11 + [f32, f32, f32, u32, vp, vp]
+        _lib.pbrhip_svgf_filter.argtypes = _lib.pbrhip_svgf_filter_device.argtypes = [C.c_int, u32, u32] + [vp] * 6 + [u32, f32, f32, u32, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -276,6 +276,9 @@ class RenderLayer:
         self.count[...] = 0
 
 
+ID_PRIMITIVE, ID_INSTANCE, ID_GEOM = 0, 1, 2  # PBRHIP_ID_*: which ShadeRec word Scene.ObjectIds gathers
+
+
 class Scene:
     """pbrlab::Scene (src/scene.h:14-111) over libpbrhip."""
 
@@ -388,6 +391,29 @@ class Scene:
         """pbrhip_scene_snapshot_pose: keeps the committed scene's slots and camera state on the device as the pose
         RenderMotion measures from.  Call it before the frame's edits; a second call replaces the first, CommitScene drops it."""
         _chk(self.L.pbrhip_scene_snapshot_pose(self.h))
+
+    def ObjectIds(self, motion_layer, what=ID_INSTANCE, device_out=None, stream=None):
+        """pbrhip_scene_object_ids: per pixel of RenderMotion's ident buffer (a MotionLayer, or the (H, W, 4) buffer itself)
+        the primitive, instance or geometry id of the slot seen there, NONE for a miss -> (H, W) uint32.  A numpy ident travels through
+        the host; an int32 tensor on the scene's GPU is read in place behind `stream` (None: torch's current one) and the result is an
+        int32 tensor: device_out when given, else a new one."""
+        ident = getattr(motion_layer, "ident", motion_layer)
+        if what not in (ID_PRIMITIVE, ID_INSTANCE, ID_GEOM):
+            raise ValueError(f"ObjectIds: what = {what} is none of ID_PRIMITIVE, ID_INSTANCE, ID_GEOM")
+        h, w = (int(n) for n in tuple(ident.shape)[:2])
+        if hasattr(ident, "data_ptr"):
+            import torch
+            src = _image_arg(ident, (h, w, 4), "int32", "ident", getattr(self, "device", None))[0]
+            out = torch.empty((h, w), dtype=torch.int32, device=ident.device) if device_out is None else device_out
+            dst = _image_arg(out, (h, w), "int32", "device_out", getattr(self, "device", None))[0]
+            _chk(self.L.pbrhip_scene_object_ids_device(self.h, src, h * w, int(what), dst, _device_stream(stream, ident)))
+            return out
+        if device_out is not None:
+            raise TypeError("ObjectIds: device_out goes with an ident tensor")
+        src = _image_arg(ident, (h, w, 4), "uint32", "ident")[2]
+        out = np.zeros((h, w), np.uint32)
+        _chk(self.L.pbrhip_scene_object_ids(self.h, src.ctypes.data, h * w, int(what), out.ctypes.data))
+        return out
 
     def AddTexture(self, pixels):
         """Scene::AddTexture: pixels (H, W, C) float32."""
@@ -1014,6 +1040,92 @@ def TemporalAccumulate(layer, motion_layer, history=None, *, alpha_min=TEMPORAL_
         out = np.zeros(img, np.float32)
         _chk(_lib.lib().pbrhip_temporal_accumulate(dev, w, h, *[p for p, _, _ in args], *params, out.ctypes.data))
     return TemporalHistory(out, motion_layer.guide)
+
+
+# pbrhip_svgf_*'s defaults (include/pbrhip.h PBRHIP_SVGF_*)
+SVGF_ALPHA_MIN, SVGF_ITERATIONS, SVGF_SIGMA_LUM, SVGF_LUM_EPS = 0.2, 5, 1.0, 1e-4
+
+
+class SvgfHistory:
+    """What SvgfAccumulate returns and takes back with the next frame: illum (H, W, 4) = the accumulated albedo-free
+    illumination | the history length, var (H, W) = the variance of its luminance, guide = the guide and ids = the object ids (or None)
+    of the frame it was made for.  Numpy arrays, or tensors on one GPU."""
+
+    def __init__(self, illum, var, guide, ids=None):
+        self.illum, self.var, self.guide, self.ids = illum, var, guide, ids
+
+
+def _svgf_features(features, img, cnt, on_gpu, dev):
+    """(albedo_hits, feature_count) of a FeatureLayer (anything with .albedo and .count), or two Nones"""
+    if features is None:
+        return [_image_arg(None, img, "float32", ""), _image_arg(None, cnt, "uint32", "")]
+    return [_image_arg(features.albedo, img, "float32", "features.albedo", dev if on_gpu else None),
+            _image_arg(features.count, cnt, "int32" if on_gpu else "uint32", "features.count", dev if on_gpu else None)]
+
+
+def SvgfAccumulate(layer, motion_layer, history=None, features=None, ids=None, *, alpha_min=SVGF_ALPHA_MIN, sigma_depth=TEMPORAL_SIGMA_DEPTH,
+                   normal_cos_min=TEMPORAL_NORMAL_COS_MIN, max_history=TEMPORAL_MAX_HISTORY, device=None):
+    """pbrhip_svgf_accumulate: TemporalAccumulate on colour / albedo (`features`: a FeatureLayer of the frame, None: albedo
+    1) that also rejects history of another object (`ids`: Scene.ObjectIds of the frame, None: no such test; a history made without ids
+    is then taken without the test) and carries the variance of the luminance -> the new SvgfHistory.  With an emitter of black albedo in
+    view pass no features, here and to SvgfFilter (include/pbrhip.h says why).  Numpy arrays or tensors exactly
+    as TemporalAccumulate takes them (ids, counts: int32 tensors)."""
+    on_gpu = hasattr(layer.rgba, "data_ptr")
+    h, w = (int(n) for n in tuple(layer.count.shape))
+    dev = (layer.rgba.device.index or 0) if on_gpu else (_device if device is None else int(device))
+    img, cnt, gd, it = (h, w, 4), (h, w), dev if on_gpu else None, "int32" if on_gpu else "uint32"
+    with_ids = ids is not None and (history is None or history.ids is not None)
+    args = ([_image_arg(layer.rgba, img, "float32", "layer.rgba", gd), _image_arg(layer.count, cnt, it, "layer.count", gd)]
+            + _svgf_features(features, img, cnt, on_gpu, dev)
+            + [_image_arg(motion_layer.motion, img, "float32", "motion", gd), _image_arg(motion_layer.guide, img, "float32", "guide", gd),
+               _image_arg(ids if with_ids else None, cnt, it, "ids", gd),
+               _image_arg(None if history is None else history.illum, img, "float32", "history.illum", gd),
+               _image_arg(None if history is None else history.var, cnt, "float32", "history.var", gd),
+               _image_arg(None if history is None else history.guide, img, "float32", "history.guide", gd),
+               _image_arg(history.ids if with_ids and history is not None else None, cnt, it, "history.ids", gd)])
+    if any(d != on_gpu for p, d, _ in args if p is not None):
+        raise TypeError("SvgfAccumulate: the buffers are either all numpy arrays or all tensors on one GPU")
+    params = (C.c_float(alpha_min), C.c_float(sigma_depth), C.c_float(normal_cos_min), C.c_uint32(int(max_history)))
+    if on_gpu:
+        import torch
+        out, var = torch.empty_like(layer.rgba), torch.empty((h, w), dtype=torch.float32, device=layer.rgba.device)
+        torch.cuda.current_stream(layer.rgba.device).synchronize()  # (the library works on the device's null stream)
+        _chk(_lib.lib().pbrhip_svgf_accumulate_device(dev, w, h, *[p for p, _, _ in args], *params, int(out.data_ptr()), int(var.data_ptr())))
+    else:
+        out, var = np.zeros(img, np.float32), np.zeros(cnt, np.float32)
+        _chk(_lib.lib().pbrhip_svgf_accumulate(dev, w, h, *[p for p, _, _ in args], *params, out.ctypes.data, var.ctypes.data))
+    return SvgfHistory(out, var, motion_layer.guide, ids)
+
+
+def SvgfFilter(history, features=None, *, iterations=0, sigma_lum=None, sigma_depth=None, normal_squarings=DENOISE_NORMAL_SQUARINGS,
+               use_ids=True, feedback=False, device=None):
+    """pbrhip_svgf_filter: the variance-guided A-trous filter of an SvgfHistory, the albedo of `features` multiplied back
+    -> (H, W, 4) float32, colour | 1; with feedback=True -> (image, SvgfHistory) where the history's illum is the illumination after the
+    first iteration: hand it to the next SvgfAccumulate in the place of `history`.  iterations 0 = 5; a sigma of None = the library's
+    default, <= 0 = that weight off; use_ids=False filters across objects although the history has ids."""
+    on_gpu = hasattr(history.illum, "data_ptr")
+    h, w = (int(n) for n in tuple(history.illum.shape)[:2])
+    dev = (history.illum.device.index or 0) if on_gpu else (_device if device is None else int(device))
+    img, cnt, gd, it = (h, w, 4), (h, w), dev if on_gpu else None, "int32" if on_gpu else "uint32"
+    args = ([_image_arg(history.illum, img, "float32", "history.illum", gd), _image_arg(history.var, cnt, "float32", "history.var", gd),
+             _image_arg(history.guide, img, "float32", "history.guide", gd), _image_arg(history.ids if use_ids else None, cnt, it, "history.ids", gd)]
+            + _svgf_features(features, img, cnt, on_gpu, dev))
+    if any(d != on_gpu for p, d, _ in args if p is not None):
+        raise TypeError("SvgfFilter: the buffers are either all numpy arrays or all tensors on one GPU")
+    params = (int(iterations), C.c_float(SVGF_SIGMA_LUM if sigma_lum is None else sigma_lum),
+              C.c_float(DENOISE_SIGMA_DEPTH if sigma_depth is None else sigma_depth), int(normal_squarings))
+    if on_gpu:
+        import torch
+        out = torch.empty_like(history.illum)
+        fb = torch.empty_like(history.illum) if feedback else None
+        torch.cuda.current_stream(history.illum.device).synchronize()  # (the library works on the device's null stream)
+        _chk(_lib.lib().pbrhip_svgf_filter_device(dev, w, h, *[p for p, _, _ in args], *params, int(out.data_ptr()),
+                                                  None if fb is None else int(fb.data_ptr())))
+    else:
+        out = np.zeros(img, np.float32)
+        fb = np.zeros(img, np.float32) if feedback else None
+        _chk(_lib.lib().pbrhip_svgf_filter(dev, w, h, *[p for p, _, _ in args], *params, out.ctypes.data, None if fb is None else fb.ctypes.data))
+    return (out, SvgfHistory(fb, history.var, history.guide, history.ids)) if feedback else out
 
 
 # pbrhip_render_adaptive's defaults (include/pbrhip.h PBRHIP_ADAPTIVE_*)

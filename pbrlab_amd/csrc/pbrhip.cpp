@@ -17,6 +17,7 @@
 #include "env_tables.h"
 #include "feature_kernels.h"
 #include "scene_impl.h"
+#include "svgf_kernels.h"
 #include "temporal_kernels.h"
 
 using namespace pb;
@@ -1889,6 +1890,245 @@ extern "C" int pbrhip_temporal_accumulate(int device, uint32_t width, uint32_t h
                                normal_cos_min, max_history, d_out.p))
       return rc;
     HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    return PBRHIP_OK;
+  });
+}
+
+// ------------------------------------------------------------------ variance-guided filtering
+static int check_object_ids(pbrhip_scene* s, const void* ident, size_t num_pixels, uint32_t what, const void* ids) {
+  if (!s) return fail(PBRHIP_EINVAL, "scene_object_ids: scene is NULL");
+  if (what > PBRHIP_ID_GEOM) return fail(PBRHIP_EINVAL, "scene_object_ids: unknown id %u", what);
+  if (num_pixels && (!ident || !ids)) return fail(PBRHIP_EINVAL, "scene_object_ids: NULL ident or ids");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_scene_object_ids_device(pbrhip_scene* s, const void* d_ident, size_t num_pixels, uint32_t what, void* d_ids, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = check_object_ids(s, d_ident, num_pixels, what, d_ids)) return rc;
+    if (!num_pixels) return PBRHIP_OK;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = wait_for_caller_stream(s, stream)) return rc;
+    launch_object_ids(s->stream, s->dscene.shade, s->tree.num_slots, static_cast<const uint4*>(d_ident), num_pixels, what, static_cast<uint32_t*>(d_ids));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+extern "C" int pbrhip_scene_object_ids(pbrhip_scene* s, const uint32_t* ident, size_t num_pixels, uint32_t what, uint32_t* ids) {
+  return guarded([&]() -> int {
+    if (int rc = check_object_ids(s, ident, num_pixels, what, ids)) return rc;
+    if (!num_pixels) return PBRHIP_OK;
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf<uint32_t> d_ident, d_ids;
+    HIPCHK(d_ident.reserve(num_pixels * 4));
+    HIPCHK(d_ids.reserve(num_pixels));
+    HIPCHK(hipMemcpyAsync(d_ident.p, ident, num_pixels * 4 * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    launch_object_ids(s->stream, s->dscene.shade, s->tree.num_slots, reinterpret_cast<const uint4*>(d_ident.p), num_pixels, what, d_ids.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ids, d_ids.p, num_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+// what every svgf entry point checks last: a device to work on
+static int check_svgf_device(const char* who, int device) {
+  int n = 0;
+  if (int rc = pbrhip_device_count(&n)) return rc;
+  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
+  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "%s: device %d out of range (%d devices)", who, device, n);
+  return PBRHIP_OK;
+}
+
+// the accumulation's pointers, host or device: the checks and both entry points pass them as one
+struct SvgfAccumPtrs {
+  const float* rgba;
+  const uint32_t* count;
+  const float* albedo_hits;
+  const uint32_t* feature_count;
+  const float *motion, *guide;
+  const uint32_t* ids;
+  const float *hist_illum, *hist_var, *hist_guide;
+  const uint32_t* hist_ids;
+  float *out_illum, *out_var;
+};
+
+// the checks both accumulation entry points share, before any device work
+static int check_svgf_accumulate(int device, uint32_t width, uint32_t height, const SvgfAccumPtrs& p, float alpha_min, float sigma_depth,
+                                 float normal_cos_min, uint32_t max_history) {
+  if (!p.rgba || !p.count || !p.motion || !p.guide || !p.out_illum || !p.out_var)
+    return fail(PBRHIP_EINVAL, "svgf_accumulate: NULL rgba, count, motion, guide, out_illum or out_var");
+  if ((p.albedo_hits != nullptr) != (p.feature_count != nullptr)) return fail(PBRHIP_EINVAL, "svgf_accumulate: albedo_hits and feature_count come together or not at all");
+  const int nhist = (p.hist_illum ? 1 : 0) + (p.hist_var ? 1 : 0) + (p.hist_guide ? 1 : 0);
+  if (nhist != 0 && nhist != 3) return fail(PBRHIP_EINVAL, "svgf_accumulate: hist_illum, hist_var and hist_guide come together or not at all");
+  if ((p.hist_ids != nullptr) != (p.ids != nullptr && nhist == 3))
+    return fail(PBRHIP_EINVAL, "svgf_accumulate: hist_ids is given exactly when ids is given and a history is present");
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "svgf_accumulate: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "svgf_accumulate: image too large");
+  if (alpha_min != alpha_min || sigma_depth != sigma_depth || normal_cos_min != normal_cos_min) return fail(PBRHIP_EINVAL, "svgf_accumulate: a parameter is NaN");
+  if (alpha_min < 0.0f || alpha_min > 1.0f) return fail(PBRHIP_EINVAL, "svgf_accumulate: alpha_min %g is not in [0, 1]", (double)alpha_min);
+  if (max_history == 0 || max_history > (1u << 24)) return fail(PBRHIP_EINVAL, "svgf_accumulate: max_history %u is not in [1, 2^24]", max_history);
+  const void* outs[2] = {p.out_illum, p.out_var};
+  const void* hists[4] = {p.hist_illum, p.hist_var, p.hist_guide, p.hist_ids};
+  for (const void* o : outs)
+    for (const void* h : hists)
+      if (h && o == h) return fail(PBRHIP_EINVAL, "svgf_accumulate: an output is a history buffer (the taps of one pixel read what another wrote)");
+  if ((const void*)p.out_illum == (const void*)p.out_var) return fail(PBRHIP_EINVAL, "svgf_accumulate: out_illum is out_var");
+  return check_svgf_device("svgf_accumulate", device);
+}
+
+// one launch on the device's null stream; device pointers
+static int svgf_accumulate_impl(int device, uint32_t width, uint32_t height, const SvgfAccumPtrs& p, float alpha_min, float sigma_depth,
+                                float normal_cos_min, uint32_t max_history) {
+  HIPCHK(hipSetDevice(device));
+  SvgfAccumArgs a{};
+  a.width = width, a.height = height;
+  a.rgba = reinterpret_cast<const float4*>(p.rgba), a.count = p.count;
+  a.albedo_hits = reinterpret_cast<const float4*>(p.albedo_hits), a.feature_count = p.feature_count;
+  a.motion = reinterpret_cast<const float4*>(p.motion), a.guide = reinterpret_cast<const float4*>(p.guide), a.ids = p.ids;
+  a.hist_illum = reinterpret_cast<const float4*>(p.hist_illum), a.hist_var = p.hist_var;
+  a.hist_guide = reinterpret_cast<const float4*>(p.hist_guide), a.hist_ids = p.hist_ids;
+  a.alpha_min = alpha_min, a.sigma_depth = sigma_depth, a.normal_cos_min = normal_cos_min, a.max_history = (float)max_history;
+  a.out_illum = reinterpret_cast<float4*>(p.out_illum), a.out_var = p.out_var;
+  launch_svgf_accumulate(nullptr, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_svgf_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                             const float* d_albedo_hits, const uint32_t* d_feature_count, const float* d_motion,
+                                             const float* d_guide, const uint32_t* d_ids, const float* d_hist_illum, const float* d_hist_var,
+                                             const float* d_hist_guide, const uint32_t* d_hist_ids, float alpha_min, float sigma_depth,
+                                             float normal_cos_min, uint32_t max_history, float* d_out_illum, float* d_out_var) {
+  return guarded([&]() -> int {
+    const SvgfAccumPtrs p{d_rgba, d_count, d_albedo_hits, d_feature_count, d_motion, d_guide, d_ids, d_hist_illum, d_hist_var, d_hist_guide,
+                          d_hist_ids, d_out_illum, d_out_var};
+    if (int rc = check_svgf_accumulate(device, width, height, p, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
+    return svgf_accumulate_impl(device, width, height, p, alpha_min, sigma_depth, normal_cos_min, max_history);
+  });
+}
+
+// a host image's copy on the device (null stays null): `words` 4-byte words per pixel
+template <typename T>
+static int svgf_upload(DevBuf<T>& d, const T* src, size_t npx, size_t words) {
+  if (!src) return PBRHIP_OK;
+  HIPCHK(d.reserve(npx * words));
+  HIPCHK(hipMemcpy(d.p, src, npx * words * sizeof(T), hipMemcpyHostToDevice));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_svgf_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
+                                      const uint32_t* feature_count, const float* motion, const float* guide, const uint32_t* ids,
+                                      const float* hist_illum, const float* hist_var, const float* hist_guide, const uint32_t* hist_ids,
+                                      float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* out_illum,
+                                      float* out_var) {
+  return guarded([&]() -> int {
+    const SvgfAccumPtrs h{rgba, count, albedo_hits, feature_count, motion, guide, ids, hist_illum, hist_var, hist_guide, hist_ids, out_illum, out_var};
+    if (int rc = check_svgf_accumulate(device, width, height, h, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_f[7], d_oi, d_ov;  // rgba, albedo_hits, motion, guide, hist_illum, hist_var, hist_guide
+    DevBuf<uint32_t> d_u[4];           // count, feature_count, ids, hist_ids
+    const float* fs[7] = {rgba, albedo_hits, motion, guide, hist_illum, hist_var, hist_guide};
+    const uint32_t* us[4] = {count, feature_count, ids, hist_ids};
+    for (int i = 0; i < 7; i++)
+      if (int rc = svgf_upload(d_f[i], fs[i], npx, i == 5 ? 1 : 4)) return rc;
+    for (int i = 0; i < 4; i++)
+      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
+    HIPCHK(d_oi.reserve(npx * 4));
+    HIPCHK(d_ov.reserve(npx));
+    const SvgfAccumPtrs d{d_f[0].p, d_u[0].p, d_f[1].p, d_u[1].p, d_f[2].p, d_f[3].p, d_u[2].p, d_f[4].p, d_f[5].p, d_f[6].p, d_u[3].p, d_oi.p, d_ov.p};
+    if (int rc = svgf_accumulate_impl(device, width, height, d, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
+    HIPCHK(hipMemcpy(out_illum, d_oi.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_var, d_ov.p, npx * sizeof(float), hipMemcpyDeviceToHost));
+    return PBRHIP_OK;
+  });
+}
+
+// the checks both filter entry points share; resolves the iteration default
+static int check_svgf_filter(int device, uint32_t width, uint32_t height, const void* illum, const void* var, const void* guide,
+                             const void* albedo_hits, const void* feature_count, uint32_t* iterations, float sigma_lum, float sigma_depth,
+                             uint32_t normal_squarings, const void* out_rgba, const void* out_feedback) {
+  if (!illum || !var || !guide || !out_rgba) return fail(PBRHIP_EINVAL, "svgf_filter: NULL illum, var, guide or out_rgba");
+  if ((albedo_hits != nullptr) != (feature_count != nullptr)) return fail(PBRHIP_EINVAL, "svgf_filter: albedo_hits and feature_count come together or not at all");
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "svgf_filter: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "svgf_filter: image too large");
+  if (sigma_lum != sigma_lum || sigma_depth != sigma_depth) return fail(PBRHIP_EINVAL, "svgf_filter: a sigma is NaN");
+  if (*iterations > 8) return fail(PBRHIP_EINVAL, "svgf_filter: %u iterations (at most 8)", *iterations);
+  if (normal_squarings > 16) return fail(PBRHIP_EINVAL, "svgf_filter: %u normal squarings (at most 16)", normal_squarings);
+  if (out_rgba == illum || out_rgba == guide || out_feedback == illum || out_feedback == guide || out_feedback == out_rgba)
+    return fail(PBRHIP_EINVAL, "svgf_filter: an output is an input or the other output (the taps of one pixel read what another wrote)");
+  if (*iterations == 0) *iterations = PBRHIP_SVGF_ITERATIONS;
+  return check_svgf_device("svgf_filter", device);
+}
+
+// prepare + one launch per iteration on the device's null stream; the two temporaries (e | v, twice) live for the call
+static int svgf_filter_impl(int device, uint32_t width, uint32_t height, const float* illum, const float* var, const float* guide, const uint32_t* ids,
+                            const float* albedo_hits, const uint32_t* feature_count, uint32_t iterations, float sigma_lum, float sigma_depth,
+                            uint32_t normal_squarings, float* out_rgba, float* out_feedback) {
+  HIPCHK(hipSetDevice(device));
+  const size_t npx = (size_t)width * height;
+  DevBuf<float4> e0, e1;
+  HIPCHK(e0.reserve(npx));
+  if (iterations > 1) HIPCHK(e1.reserve(npx));
+  SvgfFilterArgs a{};
+  a.width = width, a.height = height;
+  a.illum = reinterpret_cast<const float4*>(illum), a.var = var, a.guide = reinterpret_cast<const float4*>(guide), a.ids = ids;
+  a.albedo_hits = reinterpret_cast<const float4*>(albedo_hits), a.feature_count = feature_count;
+  a.sigma_lum = sigma_lum, a.sigma_depth = sigma_depth, a.normal_squarings = normal_squarings;
+  launch_svgf_prepare(nullptr, a, e0.p);
+  HIPCHK(hipGetLastError());
+  for (uint32_t i = 0; i < iterations; i++) {
+    const bool last = i + 1 == iterations;
+    float4* const src = (i & 1u) ? e1.p : e0.p;
+    float4* const dst = last ? reinterpret_cast<float4*>(out_rgba) : ((i & 1u) ? e0.p : e1.p);
+    launch_svgf_iteration(nullptr, a, i, last, src, dst, i == 0 ? reinterpret_cast<float4*>(out_feedback) : nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_svgf_filter_device(int device, uint32_t width, uint32_t height, const float* d_illum, const float* d_var, const float* d_guide,
+                                         const uint32_t* d_ids, const float* d_albedo_hits, const uint32_t* d_feature_count, uint32_t iterations,
+                                         float sigma_lum, float sigma_depth, uint32_t normal_squarings, float* d_out_rgba, float* d_out_feedback) {
+  return guarded([&]() -> int {
+    if (int rc = check_svgf_filter(device, width, height, d_illum, d_var, d_guide, d_albedo_hits, d_feature_count, &iterations, sigma_lum, sigma_depth,
+                                   normal_squarings, d_out_rgba, d_out_feedback))
+      return rc;
+    return svgf_filter_impl(device, width, height, d_illum, d_var, d_guide, d_ids, d_albedo_hits, d_feature_count, iterations, sigma_lum, sigma_depth,
+                            normal_squarings, d_out_rgba, d_out_feedback);
+  });
+}
+
+extern "C" int pbrhip_svgf_filter(int device, uint32_t width, uint32_t height, const float* illum, const float* var, const float* guide,
+                                  const uint32_t* ids, const float* albedo_hits, const uint32_t* feature_count, uint32_t iterations, float sigma_lum,
+                                  float sigma_depth, uint32_t normal_squarings, float* out_rgba, float* out_feedback) {
+  return guarded([&]() -> int {
+    if (int rc = check_svgf_filter(device, width, height, illum, var, guide, albedo_hits, feature_count, &iterations, sigma_lum, sigma_depth,
+                                   normal_squarings, out_rgba, out_feedback))
+      return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_f[4], d_out, d_fb;  // illum, var, guide, albedo_hits
+    DevBuf<uint32_t> d_u[2];            // ids, feature_count
+    const float* fs[4] = {illum, var, guide, albedo_hits};
+    const uint32_t* us[2] = {ids, feature_count};
+    for (int i = 0; i < 4; i++)
+      if (int rc = svgf_upload(d_f[i], fs[i], npx, i == 1 ? 1 : 4)) return rc;
+    for (int i = 0; i < 2; i++)
+      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
+    HIPCHK(d_out.reserve(npx * 4));
+    if (out_feedback) HIPCHK(d_fb.reserve(npx * 4));
+    if (int rc = svgf_filter_impl(device, width, height, d_f[0].p, d_f[1].p, d_f[2].p, d_u[0].p, d_f[3].p, d_u[1].p, iterations, sigma_lum, sigma_depth,
+                                  normal_squarings, d_out.p, d_fb.p))
+      return rc;
+    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_feedback) HIPCHK(hipMemcpy(out_feedback, d_fb.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;
   });
 }
