@@ -580,7 +580,8 @@ int pbrhip_svgf_accumulate_device(int device, uint32_t width, uint32_t height, c
  * Where the albedo hurts: a is estimated from each frame's own few samples, so at a pixel that an emitter of BLACK albedo covers partly
  * it changes from frame to frame between about 1e-3 and the neighbour's albedo, and a history e = c / 1e-3 multiplied by this frame's a
  * is wrong by orders of magnitude.  With such an emitter in view pass no albedo_hits / feature_count to either call (the colour itself
- * is then accumulated and filtered): DESIGN.md §17 has the figures of both on the Cornell box, whose light is one.
+ * is then accumulated and filtered): DESIGN.md §17 has the figures of both on the Cornell box, whose light is one.  Or keep the albedo
+ * and take the emitter's own radiance out of what is divided by it: pbrhip_emission_split below.
  * Not provided: a colour clamp against the current neighbourhood; |N . N| for hair tangents in the spatial weights (the filter has no
  * valid mark: two hairs of opposite tangent weigh 0); a multi-GPU twin. */
 #define PBRHIP_SVGF_ITERATIONS 5
@@ -593,6 +594,53 @@ int pbrhip_svgf_filter(int device, uint32_t width, uint32_t height, const float*
 int pbrhip_svgf_filter_device(int device, uint32_t width, uint32_t height, const float* d_illum, const float* d_var, const float* d_guide,
                               const uint32_t* d_ids, const float* d_albedo_hits, const uint32_t* d_feature_count, uint32_t iterations,
                               float sigma_lum, float sigma_depth, uint32_t normal_squarings, float* d_out_rgba, float* d_out_feedback);
+
+/* ---- the first-hit emission layer: demodulate only the reflected light ----
+ * The radiance the camera sees directly never touched an albedo, so it must not be divided by one.  The pipelines above become
+ *   pbrhip_render -> pbrhip_render_features_emission -> pbrhip_render_motion -> pbrhip_scene_object_ids -> pbrhip_emission_split ->
+ *   pbrhip_svgf_accumulate -> pbrhip_svgf_filter -> pbrhip_emission_merge,   or   pbrhip_emission_split -> pbrhip_denoise -> pbrhip_emission_merge,
+ * the accumulation, the filter and the denoiser being the functions above, unchanged.
+ *
+ * The feature pass with one more buffer, in one trace.  albedo_hits, normal_depth and count are pbrhip_render_features' bit for bit, from
+ * the same descriptor fields, with the same PBRHIP_RENDER_NO_CLEAR continuation, refusals and error codes; any of the four may be NULL.
+ *   emission  W*H*4: sum of Le_first rgb | number of samples that added one
+ * Le_first of a sample is what the renderer adds to its radiance at depth 0, with weight 1 and throughput 1 and no draw beyond the
+ * camera's: on a hit that faces the ray (geometric and shading normal both against the direction) on a primitive of an area light, the
+ * light's emission; on a miss in a scene with an environment, the environment's stored (scaled) texel in the ray's direction; otherwise
+ * nothing.  Both are float32 sums in ascending pass order per pixel.  The layer does not depend on the materials: emission.rgb equals
+ * the rgb sums pbrhip_render makes of the same scene with every material id PBRHIP_NONE, bit for bit.  It is also the emission AOV.
+ * Not provided: an emission output for pbrhip_render_features_rays_device; the emission of deeper bounces. */
+int pbrhip_render_features_emission(pbrhip_scene*, const pbrhip_render_desc*, float* albedo_hits, float* normal_depth, uint32_t* count,
+                                    float* emission);
+/* Same, into DEVICE buffers on the scene's device. */
+int pbrhip_render_features_emission_device(pbrhip_scene*, const pbrhip_render_desc*, float* d_albedo_hits, float* d_normal_depth,
+                                           uint32_t* d_count, float* d_emission);
+
+/* Split and merge; they need no scene.  All arithmetic is float32, every operation rounded once.
+ * Split, per pixel p (rgba / count: the RenderLayer's sums; emission: the layer above over the same passes):
+ *   count == 0: out_rgba = (0, 0, 0, 0); otherwise d = rgba.rgb - emission.rgb per channel, out_rgba = (d > 0 ? d : +0, rgba.a)
+ *   out_albedo_hits = (albedo_hits.rgb, (float)feature_count)
+ * The subtraction is done on the sums, so what follows still divides by count.  With hits == feature_count the albedo of
+ * pbrhip_denoise, pbrhip_svgf_accumulate and pbrhip_svgf_filter, a = (albedo.rgb + misses) / feature_count, becomes albedo.rgb /
+ * feature_count: a miss (and an emitter) counts as BLACK, because its radiance is in the emission layer.  A pixel an emitter covers
+ * with a fraction f of its samples has c = f Le + (1 - f) a_c e_c and a = (1 - f) a_c: (c - f Le) / a = e_c whatever f is.
+ * albedo_hits, feature_count and out_albedo_hits are given all three or none.  out_rgba may be rgba, out_albedo_hits may be albedo_hits.
+ * Merge, per pixel p (filtered_rgba: a filter's out_rgba of the split buffers; count: the RenderLayer's):
+ *   count == 0: out_rgba = filtered_rgba; otherwise out.rgb = filtered.rgb + emission.rgb / (float)count, out.a = filtered.a
+ * out_rgba may be filtered_rgba.
+ * PBRHIP_EINVAL, before any device work: a zero size, a NULL required buffer, one or two of the albedo triple, out_albedo_hits being an
+ * input other than albedo_hits (or out_rgba), an out_rgba that is an input other than rgba / filtered_rgba. */
+int pbrhip_emission_split(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* emission,
+                          const float* albedo_hits, const uint32_t* feature_count, float* out_rgba, float* out_albedo_hits);
+/* Same with DEVICE pointers on `device`. */
+int pbrhip_emission_split_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                 const float* d_emission, const float* d_albedo_hits, const uint32_t* d_feature_count, float* d_out_rgba,
+                                 float* d_out_albedo_hits);
+int pbrhip_emission_merge(int device, uint32_t width, uint32_t height, const float* filtered_rgba, const float* emission,
+                          const uint32_t* count, float* out_rgba);
+/* Same with DEVICE pointers on `device`. */
+int pbrhip_emission_merge_device(int device, uint32_t width, uint32_t height, const float* d_filtered_rgba, const float* d_emission,
+                                 const uint32_t* d_count, float* d_out_rgba);
 
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks

@@ -741,6 +741,72 @@ inline std::vector<float> SvgfFilter(const SvgfHistory& history, const FeatureLa
   return out;
 }
 
+// ---- the first-hit emission layer (not in the reference) ----
+// emission: sum of what the renderer adds to a sample's radiance at depth 0 (an area light seen from its front, the environment behind a
+// miss) | the number of samples that added one -- width x height x 4
+struct EmissionLayer {
+  EmissionLayer() = default;
+  EmissionLayer(size_t w, size_t h) { Resize(w, h), Clear(); }
+  void Clear() { std::fill(emission.begin(), emission.end(), 0.0f); }
+  void Resize(size_t w, size_t h) {
+    width = w, height = h;
+    emission.resize(w * h * 4);
+  }
+  size_t width = 0, height = 0;
+  std::vector<float> emission;
+};
+// pbrhip_render_features_emission: RenderFeatures() -- the same buffers, bit for bit -- and the emission layer of the same samples, in one
+// trace.  Resizes both unless no_clear, which accumulates on top of them.  Throws with pbrhip_last_error() on a library error.
+inline void RenderFeaturesEmission(const Scene& scene, const uint32_t width, const uint32_t height, const uint32_t num_sample,
+                                   FeatureLayer* features, EmissionLayer* emission, const uint32_t first_pass = 0, const bool no_clear = false) {
+  if (!no_clear || features->width != width || features->height != height) features->Resize(width, height);
+  if (!no_clear || emission->width != width || emission->height != height) emission->Resize(width, height);
+  scene.PushMaterialEdits();
+  pbrhip_render_desc d = {};
+  d.width = width, d.height = height, d.num_sample = num_sample, d.first_pass = first_pass;
+  d.seed_seq = 1234567890;  // Render()'s
+  d.tile_world = 1;
+  d.flags = no_clear ? PBRHIP_RENDER_NO_CLEAR : 0u;
+  if (pbrhip_render_features_emission(scene.handle(), &d, features->albedo.data(), features->normal_depth.data(), features->count.data(),
+                                      emission->emission.data()) != PBRHIP_OK)
+    throw std::runtime_error(std::string("pbrlab::RenderFeaturesEmission: ") + pbrhip_last_error());
+}
+// pbrhip_emission_split: *out_layer = `layer` without the directly seen emission, *out_features (with `features`; both or neither) =
+// `features` with a miss counted as black albedo: what SvgfAccumulate(), SvgfFilter() and Denoise() take in the place of the originals.
+// out_layer may be &layer, out_features may be features.  Throws with pbrhip_last_error() on a library error.
+inline void SplitEmission(const RenderLayer& layer, const EmissionLayer& emission, const FeatureLayer* features, RenderLayer* out_layer,
+                          FeatureLayer* out_features = nullptr, const int device = 0) {
+  if (emission.width != layer.width || emission.height != layer.height || (features && (features->width != layer.width || features->height != layer.height)))
+    throw std::runtime_error("pbrlab::SplitEmission: layer, emission and features differ in size");
+  if ((features != nullptr) != (out_features != nullptr)) throw std::runtime_error("pbrlab::SplitEmission: features and out_features come together");
+  if (out_layer != &layer) {
+    out_layer->Resize(layer.width, layer.height);
+    out_layer->count = layer.count;
+  }
+  if (features && out_features != features) {
+    out_features->Resize(features->width, features->height);
+    out_features->normal_depth = features->normal_depth;
+    out_features->count = features->count;
+  }
+  const int rc = pbrhip_emission_split(device, uint32_t(layer.width), uint32_t(layer.height), layer.rgba.data(), layer.count.data(),
+                                       emission.emission.data(), features ? features->albedo.data() : nullptr,
+                                       features ? features->count.data() : nullptr, out_layer->rgba.data(),
+                                       features ? out_features->albedo.data() : nullptr);
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::SplitEmission: ") + pbrhip_last_error());
+}
+// pbrhip_emission_merge: a filtered image of the split layer + the mean of the emission layer over `count` samples (the RenderLayer's)
+// -> width x height x 4 floats.  Throws with pbrhip_last_error() on a library error.
+inline std::vector<float> MergeEmission(const std::vector<float>& rgba, const EmissionLayer& emission, const std::vector<uint32_t>& count,
+                                        const int device = 0) {
+  if (rgba.size() != emission.emission.size() || count.size() * 4 != rgba.size())
+    throw std::runtime_error("pbrlab::MergeEmission: rgba, emission and count differ in size");
+  std::vector<float> out(rgba.size());
+  const int rc = pbrhip_emission_merge(device, uint32_t(emission.width), uint32_t(emission.height), rgba.data(), emission.emission.data(),
+                                       count.data(), out.data());
+  if (rc != PBRHIP_OK) throw std::runtime_error(std::string("pbrlab::MergeEmission: ") + pbrhip_last_error());
+  return out;
+}
+
 // ---- adaptive sampling (not in the reference) ----
 struct AdaptiveOptions {
   float threshold = PBRHIP_ADAPTIVE_THRESHOLD;  // a tile stops when its error estimate E <= threshold

@@ -33,6 +33,8 @@ EXPORTS = [
     "pbrhip_scene_snapshot_pose", "pbrhip_render_motion", "pbrhip_render_motion_device", "pbrhip_temporal_accumulate", "pbrhip_temporal_accumulate_device",
     "pbrhip_scene_object_ids", "pbrhip_scene_object_ids_device", "pbrhip_svgf_accumulate", "pbrhip_svgf_accumulate_device", "pbrhip_svgf_filter",
     "pbrhip_svgf_filter_device",
+    "pbrhip_render_features_emission", "pbrhip_render_features_emission_device", "pbrhip_emission_split", "pbrhip_emission_split_device",
+    "pbrhip_emission_merge", "pbrhip_emission_merge_device",
 ]
 
 
@@ -86,6 +88,9 @@ def lib():
         _lib.pbrhip_scene_object_ids_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp]
         _lib.pbrhip_svgf_accumulate.argtypes = _lib.pbrhip_svgf_accumulate_device.argtypes = [C.c_int, u32, u32] + [vp] * 11 + [f32, f32, f32, u32, vp, vp]
         _lib.pbrhip_svgf_filter.argtypes = _lib.pbrhip_svgf_filter_device.argtypes = [C.c_int, u32, u32] + [vp] * 6 + [u32, f32, f32, u32, vp, vp]
+        _lib.pbrhip_render_features_emission.argtypes = _lib.pbrhip_render_features_emission_device.argtypes = [vp] * 6
+        _lib.pbrhip_emission_split.argtypes = _lib.pbrhip_emission_split_device.argtypes = [C.c_int, u32, u32] + [vp] * 7
+        _lib.pbrhip_emission_merge.argtypes = _lib.pbrhip_emission_merge_device.argtypes = [C.c_int, u32, u32] + [vp] * 4
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

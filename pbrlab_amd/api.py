@@ -1068,7 +1068,8 @@ def SvgfAccumulate(layer, motion_layer, history=None, features=None, ids=None, *
     """pbrhip_svgf_accumulate: TemporalAccumulate on colour / albedo (`features`: a FeatureLayer of the frame, None: albedo
     1) that also rejects history of another object (`ids`: Scene.ObjectIds of the frame, None: no such test; a history made without ids
     is then taken without the test) and carries the variance of the luminance -> the new SvgfHistory.  With an emitter of black albedo in
-    view pass no features, here and to SvgfFilter (include/pbrhip.h says why).  Numpy arrays or tensors exactly
+    view pass no features, here and to SvgfFilter (include/pbrhip.h says why) -- or what SplitEmission makes of the layer and the features.
+    Numpy arrays or tensors exactly
     as TemporalAccumulate takes them (ids, counts: int32 tensors)."""
     on_gpu = hasattr(layer.rgba, "data_ptr")
     h, w = (int(n) for n in tuple(layer.count.shape))
@@ -1126,6 +1127,110 @@ def SvgfFilter(history, features=None, *, iterations=0, sigma_lum=None, sigma_de
         fb = np.zeros(img, np.float32) if feedback else None
         _chk(_lib.lib().pbrhip_svgf_filter(dev, w, h, *[p for p, _, _ in args], *params, out.ctypes.data, None if fb is None else fb.ctypes.data))
     return (out, SvgfHistory(fb, history.var, history.guide, history.ids)) if feedback else out
+
+
+class EmissionLayer:
+    """The first-hit emission layer (pbrhip_render_features_emission): emission (H, W, 4) float32 = the sum of what the
+    renderer adds to a sample's radiance at depth 0 (an area light seen from its front, or the environment behind a miss) | the number
+    of samples that added one.  A numpy array, or a tensor on one GPU when the caller made it."""
+
+    def __init__(self, w=0, h=0):
+        self.Resize(w, h)
+
+    def Resize(self, w, h):
+        self.width, self.height = int(w), int(h)
+        self.emission = np.zeros((self.height, self.width, 4), np.float32)
+
+    def Clear(self):
+        self.emission[...] = 0
+
+
+def RenderFeaturesEmission(scene, width, height, num_sample, layer=None, emission=None, *, first_pass=0, seed_seq=1234567890, tile_rank=0,
+                           tile_world=1, max_paths_in_flight=0, shard_block=0, no_clear=False, device_out=None):
+    """pbrhip_render_features_emission: RenderFeatures -- the same buffers, bit for bit, from the same keywords -- and the
+    EmissionLayer of the same samples, in one trace -> (FeatureLayer, EmissionLayer).  device_out: optional (albedo_ptr,
+    normal_depth_ptr, count_ptr, emission_ptr) DEVICE pointers (ints, 0 / None = not wanted) instead of the layers."""
+    L = _lib.lib()
+    desc = RenderDesc(width, height, num_sample, first_pass, seed_seq, tile_rank, tile_world, max_paths_in_flight,
+                      RENDER_NO_CLEAR if no_clear else 0, 0, 0, shard_block)
+    if device_out is not None:
+        if len(device_out) != 4:
+            raise TypeError("device_out: (albedo, normal_depth, count, emission)")
+        _chk(L.pbrhip_render_features_emission_device(scene.h, C.byref(desc), *[C.c_void_p(p or None) for p in device_out]))
+        return None
+    if layer is None:
+        layer = FeatureLayer()
+    if emission is None:
+        emission = EmissionLayer()
+    if not no_clear or (layer.width, layer.height) != (width, height):
+        layer.Resize(width, height)
+    if not no_clear or (emission.width, emission.height) != (width, height):
+        emission.Resize(width, height)
+    _chk(L.pbrhip_render_features_emission(scene.h, C.byref(desc), layer.albedo.ctypes.data, layer.normal_depth.ctypes.data,
+                                           layer.count.ctypes.data, emission.emission.ctypes.data))
+    return layer, emission
+
+
+def _bare(cls, **fields):
+    """an instance of a layer class around buffers that exist already (numpy arrays or tensors)"""
+    out = cls.__new__(cls)
+    out.__dict__.update(fields)
+    return out
+
+
+def SplitEmission(layer, emission, features=None, *, device=None):
+    """pbrhip_emission_split: the RenderLayer's sums without the directly seen emission (clamped at 0), and the
+    FeatureLayer with a miss counted as black albedo (hits := samples) -> (RenderLayer, FeatureLayer or None): what SvgfAccumulate,
+    SvgfFilter and Denoise take in the place of the originals; MergeEmission adds the emission back to their result.  `emission`: an
+    EmissionLayer or its array.  Numpy arrays or tensors exactly as SvgfAccumulate takes them; the inputs are left as they are."""
+    em = getattr(emission, "emission", emission)
+    on_gpu = hasattr(layer.rgba, "data_ptr")
+    h, w = (int(n) for n in tuple(layer.count.shape))
+    dev = (layer.rgba.device.index or 0) if on_gpu else (_device if device is None else int(device))
+    img, cnt, gd, it = (h, w, 4), (h, w), dev if on_gpu else None, "int32" if on_gpu else "uint32"
+    args = ([_image_arg(layer.rgba, img, "float32", "layer.rgba", gd), _image_arg(layer.count, cnt, it, "layer.count", gd),
+             _image_arg(em, img, "float32", "emission", gd)] + _svgf_features(features, img, cnt, on_gpu, dev))
+    if any(d != on_gpu for p, d, _ in args if p is not None):
+        raise TypeError("SplitEmission: the buffers are either all numpy arrays or all tensors on one GPU")
+    ptrs = [p for p, _, _ in args]
+    if on_gpu:
+        import torch
+        out = torch.empty_like(layer.rgba)
+        alb = None if features is None else torch.empty_like(features.albedo)
+        torch.cuda.current_stream(layer.rgba.device).synchronize()  # (the library works on the device's null stream)
+        _chk(_lib.lib().pbrhip_emission_split_device(dev, w, h, *ptrs, int(out.data_ptr()), None if alb is None else int(alb.data_ptr())))
+    else:
+        out = np.zeros(img, np.float32)
+        alb = None if features is None else np.zeros(img, np.float32)
+        _chk(_lib.lib().pbrhip_emission_split(dev, w, h, *ptrs, out.ctypes.data, None if alb is None else alb.ctypes.data))
+    split = _bare(RenderLayer, width=w, height=h, rgba=out, count=layer.count)
+    if features is None:
+        return split, None
+    return split, _bare(FeatureLayer, width=w, height=h, albedo=alb, normal_depth=features.normal_depth, count=features.count)
+
+
+def MergeEmission(rgba, emission, count, *, device=None):
+    """pbrhip_emission_merge: a filtered image of the split layer (H, W, 4) + the mean of the emission layer over `count`
+    samples (the RenderLayer's count) -> (H, W, 4) float32, the alpha as it came.  Numpy arrays, or tensors on one GPU."""
+    em = getattr(emission, "emission", emission)
+    on_gpu = hasattr(rgba, "data_ptr")
+    h, w = (int(n) for n in tuple(rgba.shape)[:2])
+    dev = (rgba.device.index or 0) if on_gpu else (_device if device is None else int(device))
+    img, cnt, gd = (h, w, 4), (h, w), dev if on_gpu else None
+    args = [_image_arg(rgba, img, "float32", "rgba", gd), _image_arg(em, img, "float32", "emission", gd),
+            _image_arg(count, cnt, "int32" if on_gpu else "uint32", "count", gd)]
+    if any(d != on_gpu for p, d, _ in args):
+        raise TypeError("MergeEmission: the buffers are either all numpy arrays or all tensors on one GPU")
+    ptrs = [p for p, _, _ in args]
+    if on_gpu:
+        import torch
+        out = torch.empty_like(rgba)
+        torch.cuda.current_stream(rgba.device).synchronize()  # (the library works on the device's null stream)
+        _chk(_lib.lib().pbrhip_emission_merge_device(dev, w, h, *ptrs, int(out.data_ptr())))
+    else:
+        out = np.zeros(img, np.float32)
+        _chk(_lib.lib().pbrhip_emission_merge(dev, w, h, *ptrs, out.ctypes.data))
+    return out
 
 
 # pbrhip_render_adaptive's defaults (include/pbrhip.h PBRHIP_ADAPTIVE_*)

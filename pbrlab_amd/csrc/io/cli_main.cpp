@@ -3,7 +3,7 @@
 //   pbrlab-hip-cli scene.obj [more.obj ...] [strands.hair ...] [--width W] [--height H] [--spp N] [--out FILE.png]
 //                  [--gpus N] [--bvh host|gpu|gpu-wide] [--env FILE [--env-scale S]]
 //                  [--eye X,Y,Z --lookat X,Y,Z [--up X,Y,Z] [--fov DEG] [--lens-radius R] [--focus D]]
-//                  [--aov PREFIX] [--denoise] [--feature-spp N] [--adaptive THRESHOLD [--min-spp N]]
+//                  [--aov PREFIX] [--denoise] [--feature-spp N] [--split-emission] [--adaptive THRESHOLD [--min-spp N]]
 //                  [--projection latlong|fisheye|ortho [--ortho-height H]]
 //
 // Without options it does what the reference binary does: 512 x 512, 32 samples per pixel, "rgba.png" in the current
@@ -18,7 +18,10 @@
 // --aov PREFIX writes the first-hit features: PREFIX.albedo.png (mean albedo, sRGB like the image), PREFIX.normal.png
 // (0.5 N + 0.5, linear) and PREFIX.depth.png ((z - z_min) / (z_max - z_min) over the covered pixels, background 1).  --denoise filters the
 // frame with the edge-avoiding A-trous filter before it is written.  Both use the features of the first --feature-spp passes (default:
-// min(spp, 16)), rendered on the first GPU.
+// min(spp, 16)), rendered on the first GPU.  --split-emission (with --aov or --denoise) renders the first-hit emission
+// layer of all --spp passes beside the features: --denoise then filters only the reflected light (the albedo counts a miss and an
+// emitter as black) and adds the emission back, and --aov also writes PREFIX.emission.png (the mean emission, sRGB like the image).
+// Not with --adaptive.  Without the flag every command line writes what it wrote before.
 // --adaptive THRESHOLD renders with adaptive sampling: --spp is then the MAXIMUM per pixel, 8 x 8 tiles whose error
 // estimate has fallen to THRESHOLD stop early (0 = the library's default), and --min-spp N is the first level (default 8; every pixel
 // holds at least twice that, or --spp).  The image is rgba / count with each pixel's own count; --denoise works on the result.  One GPU.
@@ -50,7 +53,7 @@ int main(int argc, char** argv) {
   bool have_eye = false, have_lookat = false;
   float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, 0}, up[3] = {0, 1, 0}, fov = 30.0f, lens_radius = 0.0f, focus = 0.0f;
   const char* aov = nullptr;
-  bool denoise = false;
+  bool denoise = false, split_emission = false;
   size_t feature_spp = 0, min_spp = 0;
   bool adaptive = false;
   float adaptive_threshold = PBRHIP_ADAPTIVE_THRESHOLD;
@@ -91,6 +94,7 @@ int main(int argc, char** argv) {
     else if (a == "--env") env = value("--env");
     else if (a == "--aov") aov = value("--aov");
     else if (a == "--denoise") denoise = true;
+    else if (a == "--split-emission") split_emission = true;
     else if (a == "--feature-spp") feature_spp = number("--feature-spp", 0xFFFFFFFFul);
     else if (a == "--min-spp") min_spp = number("--min-spp", 0xFFFFFFFFul);
     else if (a == "--adaptive") {
@@ -168,6 +172,10 @@ int main(int argc, char** argv) {
   }
   if (feature_spp && !aov && !denoise) {
     std::cerr << "--feature-spp needs --aov or --denoise" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (split_emission && ((!aov && !denoise) || adaptive)) {
+    std::cerr << "--split-emission needs --aov or --denoise, and a fixed sample count (no --adaptive)" << std::endl;
     return EXIT_FAILURE;
   }
   if (min_spp && !adaptive) {
@@ -298,10 +306,29 @@ int main(int argc, char** argv) {
   const size_t npx = width * height;
   if (aov || denoise) {
     pbrlab::FeatureLayer feat;
-    const std::vector<uint32_t> ones(npx, 1u);
+    pbrlab::EmissionLayer emission;
+    const std::vector<uint32_t> ones(npx, 1u), samples_taken = layer.count;
+    const uint32_t fspp = uint32_t(std::min<size_t>(samples, feature_spp ? feature_spp : 16));
     try {
-      pbrlab::RenderFeatures(scene, uint32_t(width), uint32_t(height), uint32_t(feature_spp ? feature_spp : std::min<size_t>(samples, 16)), &feat);
-      if (denoise) {  // the mean colour takes the layer's place: sum = mean, count = 1
+      if (split_emission) {
+        // the features of the first passes, the emission of all of them: the rest of the passes continues the emission sums alone
+        pbrlab::RenderFeaturesEmission(scene, uint32_t(width), uint32_t(height), fspp, &feat, &emission);
+        if (fspp < samples) {
+          pbrhip_render_desc d = {};
+          d.width = uint32_t(width), d.height = uint32_t(height), d.num_sample = uint32_t(samples) - fspp, d.first_pass = fspp;
+          d.seed_seq = 1234567890, d.tile_world = 1, d.flags = PBRHIP_RENDER_NO_CLEAR;
+          if (pbrhip_render_features_emission(scene.handle(), &d, nullptr, nullptr, nullptr, emission.emission.data()) != PBRHIP_OK)
+            throw std::runtime_error(std::string("--split-emission: ") + pbrhip_last_error());
+        }
+      } else {
+        pbrlab::RenderFeatures(scene, uint32_t(width), uint32_t(height), uint32_t(feature_spp ? feature_spp : std::min<size_t>(samples, 16)), &feat);
+      }
+      if (denoise && split_emission) {  // filter the reflected light, add the emission back
+        pbrlab::FeatureLayer black;
+        pbrlab::SplitEmission(layer, emission, &feat, &layer, &black);
+        layer.rgba = pbrlab::MergeEmission(pbrlab::Denoise(layer, &black), emission, samples_taken);
+        layer.count = ones;
+      } else if (denoise) {  // the mean colour takes the layer's place: sum = mean, count = 1
         layer.rgba = pbrlab::Denoise(layer, &feat);
         layer.count = ones;
       }
@@ -335,6 +362,10 @@ int main(int argc, char** argv) {
       if (rc == PBRHIP_OK) rc = pbrio_write_png_u8(name.c_str(), dir.c_str(), normal.data(), width, height, 3);
       split(std::string(aov) + ".depth.png", &dir, &name);
       if (rc == PBRHIP_OK) rc = pbrio_write_png_u8(name.c_str(), dir.c_str(), depth.data(), width, height, 3);
+      if (split_emission) {  // the emission sums over the samples taken
+        split(std::string(aov) + ".emission.png", &dir, &name);
+        if (rc == PBRHIP_OK) rc = pbrio_write_layer_png(name.c_str(), dir.c_str(), emission.emission.data(), samples_taken.data(), width, height);
+      }
       if (rc != PBRHIP_OK) {
         std::cerr << "--aov: " << pbrio_last_error() << std::endl;
         return EXIT_FAILURE;

@@ -18,6 +18,7 @@
 #include "feature_kernels.h"
 #include "scene_impl.h"
 #include "svgf_kernels.h"
+#include "emission_kernels.h"
 #include "temporal_kernels.h"
 
 using namespace pb;
@@ -1440,8 +1441,9 @@ static float4 feature_albedo(const HostMaterial& hm) {
 
 // the body of pbrhip_render_features_device: device pointers on the scene's device, each may be null
 // rays: null, or the caller's rays in place of the scene's camera (k_features_rays)
+// with_emission: the pass of pbrhip_render_features_emission (k_features_emission; not with rays); d_emission may be null
 static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count,
-                         const RaySource* rays = nullptr) {
+                         const RaySource* rays = nullptr, bool with_emission = false, float* d_emission = nullptr) {
   if (int rc = check_render_desc(s, d)) return rc;
   if (d->num_sample == 0) return fail(PBRHIP_EINVAL, "render_features: no samples");
   if ((uint64_t)d->first_pass + d->num_sample > (1ull << 32)) return fail(PBRHIP_EINVAL, "render_features: the passes do not fit 32 bits");
@@ -1453,10 +1455,11 @@ static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_
     if (d_albedo_hits) HIPCHK(hipMemsetAsync(d_albedo_hits, 0, npx_img * 4 * sizeof(float), st));
     if (d_normal_depth) HIPCHK(hipMemsetAsync(d_normal_depth, 0, npx_img * 4 * sizeof(float), st));
     if (d_count) HIPCHK(hipMemsetAsync(d_count, 0, npx_img * sizeof(uint32_t), st));
+    if (d_emission) HIPCHK(hipMemsetAsync(d_emission, 0, npx_img * 4 * sizeof(float), st));
   }
   if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
   const uint32_t npix = s->pk_npix;
-  if (npix == 0 || (!d_albedo_hits && !d_normal_depth && !d_count)) {
+  if (npix == 0 || (!d_albedo_hits && !d_normal_depth && !d_count && !d_emission)) {
     HIPCHK(hipStreamSynchronize(st));
     return PBRHIP_OK;
   }
@@ -1488,6 +1491,7 @@ static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_
   for (uint32_t done = 0; done < d->num_sample; done += chunk) {
     a.first_pass = ra.first_pass = d->first_pass + done, a.npass = ra.npass = std::min(chunk, d->num_sample - done);
     if (rays) launch_features_rays(st, s->dscene, ra, k);
+    else if (with_emission) launch_features_emission(st, s->dscene, a, reinterpret_cast<float4*>(d_emission), k);
     else launch_features(st, s->dscene, a, k);
     HIPCHK(hipGetLastError());
   }
@@ -2129,6 +2133,167 @@ extern "C" int pbrhip_svgf_filter(int device, uint32_t width, uint32_t height, c
       return rc;
     HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_feedback) HIPCHK(hipMemcpy(out_feedback, d_fb.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    return PBRHIP_OK;
+  });
+}
+
+// ------------------------------------------------------------------ the first-hit emission layer
+extern "C" int pbrhip_render_features_emission_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth,
+                                                      uint32_t* d_count, float* d_emission) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
+    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count, nullptr, true, d_emission);
+  });
+}
+
+extern "C" int pbrhip_render_features_emission(pbrhip_scene* s, const pbrhip_render_desc* d, float* albedo_hits, float* normal_depth,
+                                               uint32_t* count, float* emission) {
+  return guarded([&]() -> int {
+    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
+    if (int rc = check_render_desc(s, d)) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t npx = (size_t)d->width * d->height;
+    DevBuf<float> d_f[3];  // albedo_hits, normal_depth, emission
+    DevBuf<uint32_t> d_c;
+    float* const host[3] = {albedo_hits, normal_depth, emission};
+    for (int i = 0; i < 3; i++)
+      if (host[i]) HIPCHK(d_f[i].reserve(npx * 4));
+    if (count) HIPCHK(d_c.reserve(npx));
+    if (d->flags & PBRHIP_RENDER_NO_CLEAR) {
+      for (int i = 0; i < 3; i++)
+        if (host[i]) HIPCHK(hipMemcpyAsync(d_f[i].p, host[i], npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+      if (count) HIPCHK(hipMemcpyAsync(d_c.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    }
+    if (int rc = features_impl(s, d, d_f[0].p, d_f[1].p, d_c.p, nullptr, true, d_f[2].p)) return rc;
+    for (int i = 0; i < 3; i++)
+      if (host[i]) HIPCHK(hipMemcpyAsync(host[i], d_f[i].p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (count) HIPCHK(hipMemcpyAsync(count, d_c.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
+
+// the pointers of pbrhip_emission_split, host or device
+struct EmissionSplitPtrs {
+  const float* rgba;
+  const uint32_t* count;
+  const float *emission, *albedo_hits;
+  const uint32_t* feature_count;
+  float *out_rgba, *out_albedo_hits;
+};
+
+// the checks both split entry points share, before any device work
+static int check_emission_split(int device, uint32_t width, uint32_t height, const EmissionSplitPtrs& p) {
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "emission_split: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "emission_split: image too large");
+  if (!p.rgba || !p.count || !p.emission || !p.out_rgba) return fail(PBRHIP_EINVAL, "emission_split: NULL rgba, count, emission or out_rgba");
+  const int nal = (p.albedo_hits ? 1 : 0) + (p.feature_count ? 1 : 0) + (p.out_albedo_hits ? 1 : 0);
+  if (nal != 0 && nal != 3) return fail(PBRHIP_EINVAL, "emission_split: albedo_hits, feature_count and out_albedo_hits come together or not at all");
+  const void* ins[4] = {p.rgba, p.count, p.emission, p.feature_count};
+  for (const void* in : ins)
+    if (p.out_albedo_hits && (const void*)p.out_albedo_hits == in)
+      return fail(PBRHIP_EINVAL, "emission_split: out_albedo_hits is an input other than albedo_hits");
+  if (p.out_albedo_hits && (const void*)p.out_albedo_hits == (const void*)p.out_rgba) return fail(PBRHIP_EINVAL, "emission_split: out_albedo_hits is out_rgba");
+  const void* others[4] = {p.count, p.emission, p.albedo_hits, p.feature_count};
+  for (const void* in : others)
+    if (in && (const void*)p.out_rgba == in) return fail(PBRHIP_EINVAL, "emission_split: out_rgba is an input other than rgba");
+  return check_svgf_device("emission_split", device);
+}
+
+// one launch on the device's null stream; device pointers
+static int emission_split_impl(int device, uint32_t width, uint32_t height, const EmissionSplitPtrs& p) {
+  HIPCHK(hipSetDevice(device));
+  EmissionSplitArgs a{};
+  a.npx = (size_t)width * height;
+  a.rgba = reinterpret_cast<const float4*>(p.rgba), a.count = p.count, a.emission = reinterpret_cast<const float4*>(p.emission);
+  a.albedo_hits = reinterpret_cast<const float4*>(p.albedo_hits), a.feature_count = p.feature_count;
+  a.out_rgba = reinterpret_cast<float4*>(p.out_rgba), a.out_albedo_hits = reinterpret_cast<float4*>(p.out_albedo_hits);
+  launch_emission_split(nullptr, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_emission_split_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
+                                            const float* d_emission, const float* d_albedo_hits, const uint32_t* d_feature_count,
+                                            float* d_out_rgba, float* d_out_albedo_hits) {
+  return guarded([&]() -> int {
+    const EmissionSplitPtrs p{d_rgba, d_count, d_emission, d_albedo_hits, d_feature_count, d_out_rgba, d_out_albedo_hits};
+    if (int rc = check_emission_split(device, width, height, p)) return rc;
+    return emission_split_impl(device, width, height, p);
+  });
+}
+
+extern "C" int pbrhip_emission_split(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* emission,
+                                     const float* albedo_hits, const uint32_t* feature_count, float* out_rgba, float* out_albedo_hits) {
+  return guarded([&]() -> int {
+    const EmissionSplitPtrs h{rgba, count, emission, albedo_hits, feature_count, out_rgba, out_albedo_hits};
+    if (int rc = check_emission_split(device, width, height, h)) return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_f[3], d_or, d_oa;  // rgba, emission, albedo_hits
+    DevBuf<uint32_t> d_u[2];           // count, feature_count
+    const float* fs[3] = {rgba, emission, albedo_hits};
+    const uint32_t* us[2] = {count, feature_count};
+    for (int i = 0; i < 3; i++)
+      if (int rc = svgf_upload(d_f[i], fs[i], npx, 4)) return rc;
+    for (int i = 0; i < 2; i++)
+      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
+    HIPCHK(d_or.reserve(npx * 4));
+    if (out_albedo_hits) HIPCHK(d_oa.reserve(npx * 4));
+    const EmissionSplitPtrs d{d_f[0].p, d_u[0].p, d_f[1].p, d_f[2].p, d_u[1].p, d_or.p, d_oa.p};
+    if (int rc = emission_split_impl(device, width, height, d)) return rc;
+    HIPCHK(hipMemcpy(out_rgba, d_or.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_albedo_hits) HIPCHK(hipMemcpy(out_albedo_hits, d_oa.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    return PBRHIP_OK;
+  });
+}
+
+static int check_emission_merge(int device, uint32_t width, uint32_t height, const void* filtered, const void* emission, const void* count,
+                                const void* out_rgba) {
+  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "emission_merge: empty image");
+  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "emission_merge: image too large");
+  if (!filtered || !emission || !count || !out_rgba) return fail(PBRHIP_EINVAL, "emission_merge: NULL filtered_rgba, emission, count or out_rgba");
+  if (out_rgba == emission || out_rgba == count) return fail(PBRHIP_EINVAL, "emission_merge: out_rgba is an input other than filtered_rgba");
+  return check_svgf_device("emission_merge", device);
+}
+
+static int emission_merge_impl(int device, uint32_t width, uint32_t height, const float* filtered, const float* emission, const uint32_t* count,
+                               float* out_rgba) {
+  HIPCHK(hipSetDevice(device));
+  EmissionMergeArgs a{};
+  a.npx = (size_t)width * height;
+  a.filtered = reinterpret_cast<const float4*>(filtered), a.emission = reinterpret_cast<const float4*>(emission), a.count = count;
+  a.out = reinterpret_cast<float4*>(out_rgba);
+  launch_emission_merge(nullptr, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return PBRHIP_OK;
+}
+
+extern "C" int pbrhip_emission_merge_device(int device, uint32_t width, uint32_t height, const float* d_filtered_rgba, const float* d_emission,
+                                            const uint32_t* d_count, float* d_out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_emission_merge(device, width, height, d_filtered_rgba, d_emission, d_count, d_out_rgba)) return rc;
+    return emission_merge_impl(device, width, height, d_filtered_rgba, d_emission, d_count, d_out_rgba);
+  });
+}
+
+extern "C" int pbrhip_emission_merge(int device, uint32_t width, uint32_t height, const float* filtered_rgba, const float* emission,
+                                     const uint32_t* count, float* out_rgba) {
+  return guarded([&]() -> int {
+    if (int rc = check_emission_merge(device, width, height, filtered_rgba, emission, count, out_rgba)) return rc;
+    HIPCHK(hipSetDevice(device));
+    const size_t npx = (size_t)width * height;
+    DevBuf<float> d_f[2], d_out;  // filtered_rgba, emission
+    DevBuf<uint32_t> d_c;
+    const float* fs[2] = {filtered_rgba, emission};
+    for (int i = 0; i < 2; i++)
+      if (int rc = svgf_upload(d_f[i], fs[i], npx, 4)) return rc;
+    if (int rc = svgf_upload(d_c, count, npx, 1)) return rc;
+    HIPCHK(d_out.reserve(npx * 4));
+    if (int rc = emission_merge_impl(device, width, height, d_f[0].p, d_f[1].p, d_c.p, d_out.p)) return rc;
+    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;
   });
 }
