@@ -642,6 +642,54 @@ int pbrhip_emission_merge(int device, uint32_t width, uint32_t height, const flo
 int pbrhip_emission_merge_device(int device, uint32_t width, uint32_t height, const float* d_filtered_rgba, const float* d_emission,
                                  const uint32_t* d_count, float* d_out_rgba);
 
+/* ---- ray and nearest-point queries from device memory ----
+ * What a simulation on the scene's GPU asks of a committed scene between its pbrhip_scene_update_*_device calls and refits, without a
+ * round trip through the host: "what does this ray hit", "is this segment blocked", "which primitive is nearest to this point".
+ *
+ * Alignment: the kernels read and write 16 bytes at a time, so d_rays, d_points, d_ident and d_closest must be 16-byte aligned device
+ * pointers (what hipMalloc returns, and any float32 tensor of shape (n, 8) or (n, 4) that starts its allocation, is); d_hits needs
+ * 4 bytes, d_occluded none.  A pointer that is not is refused with PBRHIP_EINVAL before any device work.
+ *
+ * Ray queries.  d_rays: n pbrhip_ray in device memory of the scene's device; `stream`: the stream they are produced on -- they are read
+ * only after the work already enqueued there, and the call returns when the outputs are written (pbrhip_scene_object_ids_device's rule).
+ *   d_ident  4 words per ray: slot, then the bits of u, v, t; a miss: (PBRHIP_NONE, 0, 0, 0).  pbrhip_render_motion's identity format:
+ *            pbrhip_scene_object_ids_device takes it as it is.
+ *   d_hits   bit for bit what pbrhip_trace_closest writes for the same ray.
+ *   d_occluded  one byte per ray, what pbrhip_trace_any writes.
+ * Either of d_ident and d_hits may be NULL.  A ray is traced as given: tmin and tmax are honoured, dir is not renormalised.  An inactive
+ * ray (pbrhip_render_rays' rule: a NaN among its eight numbers, an infinite origin or direction component, a zero direction, tmin < 0 or
+ * !(tmax >= tmin)) is a miss / not occluded, with no fault.  The kernels run the production traversal on the tree the scene's render
+ * walks (PBRHIP_WIDE=0 selects the binary tree); the results do not depend on the tree.
+ * PBRHIP_EINVAL ("NULL" in pbrhip_last_error): a NULL scene, or with n > 0 NULL rays or no output; PBRHIP_EINVAL: n >= 2^31 -- both before
+ * any device work; PBRHIP_ESTATE: an uncommitted or stale scene; PBRHIP_EOVERFLOW: a traversal stack overflow; n == 0: PBRHIP_OK. */
+int pbrhip_trace_closest_device(pbrhip_scene*, const void* d_rays, size_t n, void* stream, uint32_t* d_ident, pbrhip_hit* d_hits);
+int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* stream, uint8_t* d_occluded);
+
+/* Nearest-point queries.  Per query (p, max_dist): the primitive of smallest distance D2 among those with D2 <= max_dist * max_dist
+ * (rounded once; max_dist = +inf: no bound); equal D2 goes to the smaller canonical primitive id (the ray contract's tie rule).
+ *   ident    4 words per query: slot, then the bits of u, v, sqrtf(D2); a miss: (PBRHIP_NONE, 0, 0, 0)
+ *   closest  4 floats per query: the closest point q, then D2; a miss: zeros
+ * Either may be NULL.  A query with a NaN or infinite coordinate, or max_dist NaN or below 0, is inactive: a miss.
+ * D2 is defined exactly, in float32 with every operation rounded once (DESIGN.md §19 has it operation by operation):
+ *   segment (x, y): e = y - x, t = clamp(dot(p - x, e) / dot(e, e), 0, 1) (0 when dot(e, e) is not > 0), q = x + t e, |p - q|^2
+ *   triangle (a, b, c): d2_raw = the minimum of the segments ab, bc, ca in that order (a strict < replaces) and, last and again by strict <,
+ *     of the plane term (h h) / nn, n = cross(b - a, c - a), nn = dot(n, n), h = dot(p - a, n), which applies when nn > 0 and
+ *     dot(cross(y - x, p - x), n) >= 0 for the three edges; q = the closest point of the winning feature (the plane's: p - (h / nn) n);
+ *     (u, v) = its barycentrics of b and c (ab: (t, 0); bc: (1 - t, t); ca: (0, 1 - t); plane: the ca and ab sign terms over nn)
+ *   curve piece: the segment between its end points -- the centre line; the radius is ignored --, u = (sub + t) / 4, v = 0
+ *   D2 = max(d2_raw, L) with L the squared distance from p to the primitive's own box (the one the intersection contract validates
+ *     with, widened the same way): every stored box of either tree contains that box, so a traversal that skips a box only when its own
+ *     squared distance exceeds the best D2 cannot skip the answer, and the result is a property of (point, primitive set) alone: it does
+ *     not depend on builder, tree, refit or visiting order.
+ * The device variant orders the read of d_points behind `stream` as above.  Errors as the ray queries'.
+ * Not provided: signed distance, the ribbon's radius, k-nearest and all-hits queries, a multi-GPU twin, asynchronous return. */
+typedef struct {
+  float p[3];
+  float max_dist;
+} pbrhip_point; /* 16 bytes */
+int pbrhip_nearest_point(pbrhip_scene*, const pbrhip_point* points, size_t n, uint32_t* ident, float* closest);
+int pbrhip_nearest_point_device(pbrhip_scene*, const void* d_points, size_t n, void* stream, uint32_t* d_ident, float* d_closest);
+
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks
  * with index % world == r (pbrhip_render_desc.tile_rank / tile_world / shard_block) into a zeroed full-size layer, then the

@@ -391,6 +391,25 @@ public:
     Check(pbrhip_scene_object_ids(h_, ident.data(), ids.size(), what, ids.data()));
     return ids;
   }
+  // Ray and nearest-point queries (include/pbrhip.h, "ray and nearest-point queries from device memory").  The *Device calls take
+  // DEVICE pointers on the scene's GPU: n pbrhip_ray / pbrhip_point, read after the work already enqueued on `stream` (a hipStream_t;
+  // null: the null stream); d_ident: 4 words per query (slot, bits of u, v, t or the distance; a miss: PBRHIP_NONE, 0, 0, 0), d_hits:
+  // pbrhip_trace_closest's records, d_closest: the closest point | its squared distance; of the two outputs either may be null.  The
+  // outputs are written when the call returns.  NearestPoint is the same query on host arrays: ident and closest are resized to 4 n.
+  void TraceClosestDevice(const void* d_rays, size_t n, uint32_t* d_ident, pbrhip_hit* d_hits, void* stream = nullptr) const {
+    Check(pbrhip_trace_closest_device(h_, d_rays, n, stream, d_ident, d_hits));
+  }
+  void TraceAnyDevice(const void* d_rays, size_t n, uint8_t* d_occluded, void* stream = nullptr) const {
+    Check(pbrhip_trace_any_device(h_, d_rays, n, stream, d_occluded));
+  }
+  void NearestPoint(const std::vector<pbrhip_point>& points, std::vector<uint32_t>* ident, std::vector<float>* closest) const {
+    if (ident) ident->assign(4 * points.size(), 0u);
+    if (closest) closest->assign(4 * points.size(), 0.0f);
+    Check(pbrhip_nearest_point(h_, points.data(), points.size(), ident ? ident->data() : nullptr, closest ? closest->data() : nullptr));
+  }
+  void NearestPointDevice(const void* d_points, size_t n, uint32_t* d_ident, float* d_closest, void* stream = nullptr) const {
+    Check(pbrhip_nearest_point_device(h_, d_points, n, stream, d_ident, d_closest));
+  }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
   void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }

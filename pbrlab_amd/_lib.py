@@ -35,6 +35,7 @@ EXPORTS = [
     "pbrhip_svgf_filter_device",
     "pbrhip_render_features_emission", "pbrhip_render_features_emission_device", "pbrhip_emission_split", "pbrhip_emission_split_device",
     "pbrhip_emission_merge", "pbrhip_emission_merge_device",
+    "pbrhip_trace_closest_device", "pbrhip_trace_any_device", "pbrhip_nearest_point", "pbrhip_nearest_point_device",
 ]
 
 
@@ -91,6 +92,8 @@ def lib():
         _lib.pbrhip_render_features_emission.argtypes = _lib.pbrhip_render_features_emission_device.argtypes = [vp] * 6
         _lib.pbrhip_emission_split.argtypes = _lib.pbrhip_emission_split_device.argtypes = [C.c_int, u32, u32] + [vp] * 7
         _lib.pbrhip_emission_merge.argtypes = _lib.pbrhip_emission_merge_device.argtypes = [C.c_int, u32, u32] + [vp] * 4
+        _lib.pbrhip_trace_closest_device.argtypes = _lib.pbrhip_nearest_point_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        _lib.pbrhip_trace_any_device.argtypes = _lib.pbrhip_nearest_point.argtypes = [vp, vp, C.c_size_t, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

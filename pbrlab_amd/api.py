@@ -67,6 +67,7 @@ class RenderStats(C.Structure):
 RAY_DT = np.dtype([("org", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])
 HIT_DT = np.dtype([("normal_g", "<f4", 3), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
                    ("instance_id", "<u4"), ("geom_id", "<u4"), ("prim_id", "<u4")])
+POINT_DT = np.dtype([("p", "<f4", 3), ("max_dist", "<f4")])  # pbrhip_point: a nearest-point query (max_dist inf: no bound)
 
 
 class PbrHipError(RuntimeError):
@@ -110,6 +111,30 @@ def _device_array(a, scene):
     if want is not None and dev.index is not None and dev.index != want:
         raise ValueError(f"the array is on device {dev.index}, the scene on device {want}")
     return C.c_void_p(int(a.data_ptr())), int(shape[0])
+
+
+def _query_array(a, scene, words, what):
+    """The input of a *Device query -> (pointer, n): a (pointer, n) pair, or a float32, contiguous (n, words) tensor on the scene's
+    device.  TypeError / ValueError here, before any C call."""
+    if isinstance(a, (tuple, list)):
+        if len(a) != 2:
+            raise TypeError(f"{what}: a tensor or a (pointer, n) pair")
+        return C.c_void_p(None if a[0] is None else int(a[0])), int(a[1])
+    if not hasattr(a, "data_ptr"):
+        raise TypeError(f"{what}: {type(a).__name__} is no device array: pass a tensor on the scene's device or a (pointer, n) pair")
+    shape = tuple(getattr(a, "shape", ()))
+    n = int(shape[0]) if shape else 0
+    return C.c_void_p(_image_arg(a, (n, words), "float32", what, getattr(scene, "device", None))[0]), n
+
+
+def _query_out(a, scene, shape, dtype, what):
+    """An output of a *Device query -> pointer: None (not wanted), a device pointer (an int), or a contiguous tensor of that shape and
+    dtype on the scene's device"""
+    if a is None or isinstance(a, int):
+        return C.c_void_p(a or None)
+    if not hasattr(a, "data_ptr"):
+        raise TypeError(f"{what}: {type(a).__name__} is no device array: pass a tensor on the scene's device or a device pointer")
+    return C.c_void_p(_image_arg(a, shape, dtype, what, getattr(scene, "device", None))[0])
 
 
 def _device_stream(stream, *arrays):
@@ -560,6 +585,63 @@ class Scene:
         _chk(self.L.pbrhip_trace_any(self.h, C.c_void_p(rays.ctypes.data), C.c_size_t(len(rays)),
                                      C.c_void_p(occ.ctypes.data)))
         return occ
+
+    # ray and nearest-point queries from device memory
+    def TraceClosestDevice(self, rays, ident=None, hits=None, stream=None):
+        """pbrhip_trace_closest_device: the closest hit of n rays held in memory of the scene's GPU -> (ident, hits).  rays: a float32,
+        contiguous (n, 8) tensor (org, tmin, dir, tmax per row: RAY_DT) or a (pointer, n) pair.  ident: (n, 4) int32 = slot (NONE: a miss),
+        bits of u, v, t -- RenderMotion's identity format, ObjectIds takes it; hits: (n, 9) int32 holding trace_closest's HIT_DT records
+        bit for bit.  Each is a tensor or a device pointer (an int) and is written in place; with tensor rays and neither given both are
+        allocated; one that is not given otherwise is not computed (None).  stream: the stream the rays are produced on (None: with
+        tensors torch's current one): they are read after the work already enqueued there; the outputs are written when the call returns.
+        Device pointers of rays and ident must be 16-byte aligned (the library refuses others); a tensor that starts its allocation is."""
+        ptr, n = _query_array(rays, self, 8, "rays")
+        if ident is None and hits is None and hasattr(rays, "data_ptr"):
+            import torch
+            ident, hits = (torch.empty((n, w), dtype=torch.int32, device=rays.device) for w in (4, 9))
+        pi, ph = _query_out(ident, self, (n, 4), "int32", "ident"), _query_out(hits, self, (n, 9), "int32", "hits")
+        _chk(self.L.pbrhip_trace_closest_device(self.h, ptr, n, _device_stream(stream, rays), pi, ph))
+        return ident, hits
+
+    def TraceAnyDevice(self, rays, out=None, stream=None):
+        """pbrhip_trace_any_device: whether each of n rays in memory of the scene's GPU is blocked -> out, (n,) uint8 (a tensor or a device
+        pointer; allocated when rays is a tensor and none is given).  rays and stream as TraceClosestDevice's."""
+        ptr, n = _query_array(rays, self, 8, "rays")
+        if out is None and hasattr(rays, "data_ptr"):
+            import torch
+            out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        _chk(self.L.pbrhip_trace_any_device(self.h, ptr, n, _device_stream(stream, rays), _query_out(out, self, (n,), "uint8", "out")))
+        return out
+
+    def NearestPoint(self, points):
+        """pbrhip_nearest_point: per query point the nearest primitive within max_dist -> (ident, closest).  points: POINT_DT records,
+        or (n, 4) float32 rows x, y, z, max_dist (inf: no bound).  ident: (n, 4) uint32 = slot (NONE: a miss), bits of u, v,
+        sqrt(D2); closest: (n, 4) float32 = the closest point | D2 (zeros for a miss).  The definition of D2 is exact.
+        Anything else than records or (n, 4) rows: ValueError, before any C call."""
+        points = np.asarray(points)
+        if points.dtype.names:
+            pts = np.ascontiguousarray(points, POINT_DT).reshape(-1)
+        elif points.ndim == 2 and points.shape[1] == 4:
+            pts = np.ascontiguousarray(points, np.float32)
+        else:
+            raise ValueError(f"points must be POINT_DT records or have the shape (n, 4), not {points.shape}")
+        n = len(pts)
+        ident, closest = np.zeros((n, 4), np.uint32), np.zeros((n, 4), np.float32)
+        _chk(self.L.pbrhip_nearest_point(self.h, C.c_void_p(pts.ctypes.data), n, C.c_void_p(ident.ctypes.data), C.c_void_p(closest.ctypes.data)))
+        return ident, closest
+
+    def NearestPointDevice(self, points, ident=None, closest=None, stream=None):
+        """pbrhip_nearest_point_device: NearestPoint for n points in memory of the scene's GPU -> (ident, closest).  points: a float32,
+        contiguous (n, 4) tensor or a (pointer, n) pair; ident: (n, 4) int32, closest: (n, 4) float32, tensors or device pointers written
+        in place; outputs and stream as TraceClosestDevice's.  Device pointers must be 16-byte aligned (the library refuses others)."""
+        ptr, n = _query_array(points, self, 4, "points")
+        if ident is None and closest is None and hasattr(points, "data_ptr"):
+            import torch
+            ident = torch.empty((n, 4), dtype=torch.int32, device=points.device)
+            closest = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+        pi, pc = _query_out(ident, self, (n, 4), "int32", "ident"), _query_out(closest, self, (n, 4), "float32", "closest")
+        _chk(self.L.pbrhip_nearest_point_device(self.h, ptr, n, _device_stream(stream, points), pi, pc))
+        return ident, closest
 
 
 def Render(scene, width, height, num_sample, cancel_render_flag=None, layer=None, finish_pass=None, *,

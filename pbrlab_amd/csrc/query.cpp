@@ -1,0 +1,127 @@
+// query.cpp -- the query entry points of the C ABI: ray queries on device memory and nearest-point queries, host and
+// device variants.  Host C++ only; the kernels are query.hip's.
+#include "query_kernels.h"
+#include "scene_impl.h"
+
+using namespace pb;
+
+static_assert(sizeof(pbrhip_hit) == sizeof(HookHit), "hit layout");
+static_assert(sizeof(pbrhip_ray) == 32, "ray layout");
+static_assert(sizeof(pbrhip_point) == 16, "point layout");
+
+// what every query checks before anything touches a device or the scene: pointers, then the count
+static int check_query(const char* who, const pbrhip_scene* s, const void* in, size_t n, const void* out_a, const void* out_b) {
+  if (!s) return fail(PBRHIP_EINVAL, "%s: NULL scene", who);
+  if (n && !in) return fail(PBRHIP_EINVAL, "%s: NULL input array", who);
+  if (n && !out_a && !out_b) return fail(PBRHIP_EINVAL, "%s: NULL output", who);
+  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "%s: too many queries (%zu; fewer than 2^31)", who, n);
+  return PBRHIP_OK;
+}
+// the kernels move 16 bytes at a time: a device pointer that is not 16-byte aligned is refused (null: not wanted)
+static int check_aligned(const char* who, const void* a, const void* b, const void* c) {
+  for (const void* p : {a, b, c})
+    if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(PBRHIP_EINVAL, "%s: a device pointer is not 16-byte aligned", who);
+  return PBRHIP_OK;
+}
+// ... then the scene's state.  Returns 1 for "nothing to do" (n == 0 on a scene that could answer).
+static int check_state(const pbrhip_scene* s, size_t n) {
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
+  return n ? PBRHIP_OK : 1;
+}
+// the caller's array is read only after what its stream already holds (pbrhip_scene_object_ids_device's rule): an event there, and the
+// scene's stream waits for it
+static int wait_for_caller_stream(pbrhip_scene* s, void* stream) {
+  hipEvent_t ev;
+  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
+  (void)hipEventDestroy(ev);
+  HIPCHK(e);
+  return PBRHIP_OK;
+}
+// zeroed counters (queue head, overflow flag) and the spill area, on the scene's stream
+static int prepare_traversal(pbrhip_scene* s) {
+  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
+  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
+  HIPCHK(s->spill.reserve(kSpillWords));
+  return PBRHIP_OK;
+}
+// the end of every query: the counters come back, the stream drains, an overflow is reported
+static int finish_traversal(pbrhip_scene* s) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
+  return PBRHIP_OK;
+}
+
+// ------------------------------------------------------------------ ray queries on device memory
+static int ray_query_device(const char* who, pbrhip_scene* s, const void* d_rays, size_t n, void* stream, uint32_t* d_ident, pbrhip_hit* d_hits,
+                            uint8_t* d_occ) {
+  if (int rc = check_query(who, s, d_rays, n, d_occ ? static_cast<void*>(d_occ) : static_cast<void*>(d_ident), d_occ ? nullptr : d_hits)) return rc;
+  if (int rc = check_aligned(who, d_rays, d_ident, nullptr)) return rc;
+  if (reinterpret_cast<uintptr_t>(d_hits) & 3u) return fail(PBRHIP_EINVAL, "%s: d_hits is not 4-byte aligned", who);
+  if (int rc = check_state(s, n)) return rc < 0 ? rc : PBRHIP_OK;
+  const Knobs k = read_knobs();
+  HIPCHK(hipSetDevice(s->device));
+  if (int rc = wait_for_caller_stream(s, stream)) return rc;
+  if (int rc = prepare_traversal(s)) return rc;
+  RayQueryArgs a{};
+  a.rays = static_cast<const float4*>(d_rays), a.n = (uint32_t)n;
+  a.ident = reinterpret_cast<uint4*>(d_ident), a.hits = reinterpret_cast<HookHit*>(d_hits), a.occ = d_occ;
+  a.counts = s->counts.p, a.spill = s->spill.p;
+  launch_ray_query(s->stream, s->dscene, a, k);
+  return finish_traversal(s);
+}
+
+extern "C" int pbrhip_trace_closest_device(pbrhip_scene* s, const void* d_rays, size_t n, void* stream, uint32_t* d_ident, pbrhip_hit* d_hits) {
+  return guarded([&]() -> int { return ray_query_device("trace_closest_device", s, d_rays, n, stream, d_ident, d_hits, nullptr); });
+}
+
+extern "C" int pbrhip_trace_any_device(pbrhip_scene* s, const void* d_rays, size_t n, void* stream, uint8_t* d_occluded) {
+  return guarded([&]() -> int { return ray_query_device("trace_any_device", s, d_rays, n, stream, nullptr, nullptr, d_occluded); });
+}
+
+// ------------------------------------------------------------------ nearest-point queries
+// the launch on the scene's stream; device pointers on the scene's device, either output may be null
+static int nearest_impl(pbrhip_scene* s, const void* d_points, size_t n, uint32_t* d_ident, float* d_closest) {
+  const Knobs k = read_knobs();
+  if (int rc = prepare_traversal(s)) return rc;
+  NearestArgs a{};
+  a.points = static_cast<const float4*>(d_points), a.n = (uint32_t)n;
+  a.ident = reinterpret_cast<uint4*>(d_ident), a.closest = reinterpret_cast<float4*>(d_closest);
+  a.overflow = s->counts.p + kCntOverflow, a.spill = s->spill.p;
+  launch_nearest(s->stream, s->dscene, a, k);
+  return finish_traversal(s);
+}
+
+extern "C" int pbrhip_nearest_point_device(pbrhip_scene* s, const void* d_points, size_t n, void* stream, uint32_t* d_ident, float* d_closest) {
+  return guarded([&]() -> int {
+    if (int rc = check_query("nearest_point_device", s, d_points, n, d_ident, d_closest)) return rc;
+    if (int rc = check_aligned("nearest_point_device", d_points, d_ident, d_closest)) return rc;
+    if (int rc = check_state(s, n)) return rc < 0 ? rc : PBRHIP_OK;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = wait_for_caller_stream(s, stream)) return rc;
+    return nearest_impl(s, d_points, n, d_ident, d_closest);
+  });
+}
+
+extern "C" int pbrhip_nearest_point(pbrhip_scene* s, const pbrhip_point* points, size_t n, uint32_t* ident, float* closest) {
+  return guarded([&]() -> int {
+    if (int rc = check_query("nearest_point", s, points, n, ident, closest)) return rc;
+    if (int rc = check_state(s, n)) return rc < 0 ? rc : PBRHIP_OK;
+    HIPCHK(hipSetDevice(s->device));
+    DevBuf<float4> d_pts, d_cl;
+    DevBuf<uint32_t> d_id;
+    HIPCHK(d_pts.reserve(n));
+    if (ident) HIPCHK(d_id.reserve(4 * n));
+    if (closest) HIPCHK(d_cl.reserve(n));
+    HIPCHK(hipMemcpyAsync(d_pts.p, points, n * sizeof(pbrhip_point), hipMemcpyHostToDevice, s->stream));
+    if (int rc = nearest_impl(s, d_pts.p, n, d_id.p, reinterpret_cast<float*>(d_cl.p))) return rc;
+    if (ident) HIPCHK(hipMemcpyAsync(ident, d_id.p, 4 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    if (closest) HIPCHK(hipMemcpyAsync(closest, d_cl.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBRHIP_OK;
+  });
+}
