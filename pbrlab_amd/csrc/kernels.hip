@@ -22,6 +22,7 @@
 #include "dcamera.h"
 #include "dshade.h"
 #include "kernels.h"
+#include "variants.h"
 #include "dtrace_pv.h"
 #include "dtrace_quad.h"
 
@@ -1912,18 +1913,7 @@ __global__ void k_advance(uint32_t* counts, uint32_t* heads, uint32_t* ring, uin
 }
 
 // ------------------------------------------------------------------ launchers
-// the Q tree serves the scenes whose tree was built on the host (PBRHIP_WIDE=0: never)
-static inline bool use_wide(const DScene& sc, const Knobs& k) { return sc.wide != nullptr && k.wide; }
-// A runtime property of the scene becomes a template argument here and nowhere else: with_flags(f, a, b, ...) calls the generic lambda f
-// with one std::bool_constant per flag, which the lambda's launch names as a template argument (k_trace<st, c, w, first>).  Every
-// combination of the flags is an instance in the code object: a kernel that exists for fewer has a selector of its own below.
-template <class F>
-static inline void with_flags(F&& f) { f(); }
-template <class F, class... Bools>
-static inline void with_flags(F&& f, bool flag, Bools... rest) {
-  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
+// use_wide, with_flags and with_hook_tree are variants.h's
 // the shading mode of a scene (shade_principled_path): kShadePlain | kShadeMedia | kShadeFull by its materials, kShadeEnv on top
 template <class F>
 static inline void with_shade_mode(F&& f, bool media, bool textured, bool env) {
@@ -1939,12 +1929,6 @@ template <class F>
 static inline void with_tail_mode(F&& f, bool stats, bool media, bool textured, bool env) {
   if (stats) with_flags([&](auto e) { f(std::integral_constant<int, kShadeFull | (e ? kShadeEnv : 0)>{}, std::true_type{}); }, env);
   else with_shade_mode([&](auto mode) { f(mode, std::false_type{}); }, media, textured, env);
-}
-// the hooks' <CURVES, WIDE>: the tree the render of this scene walks, but the binary tree's hooks always carry the curve code
-template <class F>
-static inline void with_hook_tree(F&& f, const DScene& sc, const Knobs& k) {
-  if (use_wide(sc, k)) with_flags([&](auto c) { f(c, std::true_type{}); }, sc.num_curves != 0);
-  else f(std::true_type{}, std::false_type{});
 }
 bool trace_uses_wide(const DScene& sc, const Knobs& k) { return use_wide(sc, k); }
 #ifndef PB_TRACE_SMALL1_RAYS

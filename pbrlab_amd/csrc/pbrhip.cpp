@@ -1,5 +1,6 @@
 // pbrhip.cpp -- C ABI (include/pbrhip.h): host scene store, model edits, getters, environment, camera and the wavefront render loop
-// that drives kernels.hip.  Commit and refit live in commit.cpp, the test hooks in hooks.cpp.  Host C++ only.
+// that drives kernels.hip.  Commit and refit live in commit.cpp, the test hooks in hooks.cpp, the image-space entry points (features,
+// filters, motion, emission) in image.cpp, the queries in query.cpp.  Host C++ only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -15,11 +16,7 @@
 #include <vector>
 
 #include "env_tables.h"
-#include "feature_kernels.h"
 #include "scene_impl.h"
-#include "svgf_kernels.h"
-#include "emission_kernels.h"
-#include "temporal_kernels.h"
 
 using namespace pb;
 
@@ -925,7 +922,7 @@ static std::vector<uint32_t> plan_groups(const Knobs& k, uint32_t np, uint32_t n
   return g;
 }
 
-static int check_render_desc(const pbrhip_scene* s, const pbrhip_render_desc* d) {
+int pb::check_render_desc(const pbrhip_scene* s, const pbrhip_render_desc* d) {
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
   PB_NOT_STALE(s);
   if (d->width == 0 || d->height == 0) return fail(PBRHIP_EINVAL, "empty image");
@@ -1425,135 +1422,15 @@ extern "C" int pbrhip_render(pbrhip_scene* s, const pbrhip_render_desc* d, const
   });
 }
 
-// ------------------------------------------------------------------ feature buffers and denoiser
-// What a first hit on a material adds to the albedo sum: rgb | the base-colour map's id (kNone: the rgb stands).  Principled: base_color.
-// Hair: base_color when it is coloured by RGB; for melanin the colour whose sigma_a under hair_param_to_bsdf's RGB mapping
-// (sigma_a = (log c / poly(beta_n))^2) is the material's: c = exp(-sqrt(sigma_a) poly(beta_n)), in double, rounded once.
-static float4 feature_albedo(const HostMaterial& hm) {
-  if (hm.kind == kMatPrincipled) return make_float4(hm.pr.base_color[0], hm.pr.base_color[1], hm.pr.base_color[2], __builtin_bit_cast(float, hm.pr.base_color_tex_id));
-  const float none = __builtin_bit_cast(float, kNone);
-  if (hm.hr.coloring_hair == 0) return make_float4(hm.hr.base_color[0], hm.hr.base_color[1], hm.hr.base_color[2], none);
-  const V3 sa = hair_param_to_bsdf(hm.hr).sigma_a;
-  const double bn = hm.hr.azimuthal_roughness;
-  const double poly = 5.969 - 0.215 * bn + 2.532 * bn * bn - 10.73 * bn * bn * bn + 5.574 * bn * bn * bn * bn + 0.245 * bn * bn * bn * bn * bn;
-  return make_float4((float)exp(-sqrt((double)sa.x) * poly), (float)exp(-sqrt((double)sa.y) * poly), (float)exp(-sqrt((double)sa.z) * poly), none);
-}
-
-// the body of pbrhip_render_features_device: device pointers on the scene's device, each may be null
-// rays: null, or the caller's rays in place of the scene's camera (k_features_rays)
-// with_emission: the pass of pbrhip_render_features_emission (k_features_emission; not with rays); d_emission may be null
-static int features_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count,
-                         const RaySource* rays = nullptr, bool with_emission = false, float* d_emission = nullptr) {
-  if (int rc = check_render_desc(s, d)) return rc;
-  if (d->num_sample == 0) return fail(PBRHIP_EINVAL, "render_features: no samples");
-  if ((uint64_t)d->first_pass + d->num_sample > (1ull << 32)) return fail(PBRHIP_EINVAL, "render_features: the passes do not fit 32 bits");
-  const Knobs k = read_knobs();
-  HIPCHK(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  const size_t npx_img = (size_t)d->width * d->height;
-  if (!(d->flags & PBRHIP_RENDER_NO_CLEAR)) {
-    if (d_albedo_hits) HIPCHK(hipMemsetAsync(d_albedo_hits, 0, npx_img * 4 * sizeof(float), st));
-    if (d_normal_depth) HIPCHK(hipMemsetAsync(d_normal_depth, 0, npx_img * 4 * sizeof(float), st));
-    if (d_count) HIPCHK(hipMemsetAsync(d_count, 0, npx_img * sizeof(uint32_t), st));
-    if (d_emission) HIPCHK(hipMemsetAsync(d_emission, 0, npx_img * 4 * sizeof(float), st));
-  }
-  if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
-  const uint32_t npix = s->pk_npix;
-  if (npix == 0 || (!d_albedo_hits && !d_normal_depth && !d_count && !d_emission)) {
-    HIPCHK(hipStreamSynchronize(st));
-    return PBRHIP_OK;
-  }
-  std::vector<float4> albedo(std::max<size_t>(s->materials.size(), 1), make_float4(0.f, 0.f, 0.f, 0.f));
-  for (size_t i = 0; i < s->materials.size(); i++) albedo[i] = feature_albedo(s->materials[i]);  // (from the host model: material updates are seen)
-  HIPCHK(s->feat_albedo.upload(albedo, st));
-  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
-  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, st));
-  HIPCHK(s->spill.reserve(kSpillWords));
-  FeatureArgs a;
-  a.user = s->cam_set ? 1u : 0u;
-  a.ucam = s->cam_set ? make_user_camera(s, d->width, d->height) : UserCamera{};
-  a.cam = s->cam_set ? Camera{} : make_camera(s, d->width, d->height);
-  a.width = d->width, a.height = d->height, a.seed_seq = d->seed_seq;
-  a.pix = s->path_pix.p, a.npix = npix;
-  a.mat_albedo = s->feat_albedo.p;
-  a.albedo_hits = reinterpret_cast<float4*>(d_albedo_hits), a.normal_depth = reinterpret_cast<float4*>(d_normal_depth), a.count = d_count;
-  a.overflow = s->counts.p + kCntOverflow, a.spill = s->spill.p;
-  // max_paths_in_flight bounds the samples of one launch as it bounds the paths of a render's chunk; a pixel's sums continue from
-  // chunk to chunk in pass order, so the split is invisible in the result
-  uint32_t chunk = d->num_sample;
-  if (d->max_paths_in_flight) chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(d->num_sample, d->max_paths_in_flight / npix));
-  FeatureRayArgs ra{};
-  if (rays) {
-    ra.src = *rays, ra.src.base_pass = d->first_pass, ra.src.height = d->height;
-    ra.width = d->width, ra.pix = a.pix, ra.npix = npix, ra.mat_albedo = a.mat_albedo;
-    ra.albedo_hits = a.albedo_hits, ra.normal_depth = a.normal_depth, ra.count = a.count, ra.overflow = a.overflow, ra.spill = a.spill;
-  }
-  for (uint32_t done = 0; done < d->num_sample; done += chunk) {
-    a.first_pass = ra.first_pass = d->first_pass + done, a.npass = ra.npass = std::min(chunk, d->num_sample - done);
-    if (rays) launch_features_rays(st, s->dscene, ra, k);
-    else if (with_emission) launch_features_emission(st, s->dscene, a, reinterpret_cast<float4*>(d_emission), k);
-    else launch_features(st, s->dscene, a, k);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_render_features_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth,
-                                             uint32_t* d_count) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
-    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count);
-  });
-}
-
-extern "C" int pbrhip_render_features(pbrhip_scene* s, const pbrhip_render_desc* d, float* albedo_hits, float* normal_depth, uint32_t* count) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
-    if (int rc = check_render_desc(s, d)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t npx = (size_t)d->width * d->height;
-    DevBuf<float> d_a, d_n;
-    DevBuf<uint32_t> d_c;
-    if (albedo_hits) HIPCHK(d_a.reserve(npx * 4));
-    if (normal_depth) HIPCHK(d_n.reserve(npx * 4));
-    if (count) HIPCHK(d_c.reserve(npx));
-    if (d->flags & PBRHIP_RENDER_NO_CLEAR) {
-      if (albedo_hits) HIPCHK(hipMemcpyAsync(d_a.p, albedo_hits, npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-      if (normal_depth) HIPCHK(hipMemcpyAsync(d_n.p, normal_depth, npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-      if (count) HIPCHK(hipMemcpyAsync(d_c.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    }
-    if (int rc = features_impl(s, d, d_a.p, d_n.p, d_c.p)) return rc;
-    if (albedo_hits) HIPCHK(hipMemcpyAsync(albedo_hits, d_a.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (normal_depth) HIPCHK(hipMemcpyAsync(normal_depth, d_n.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (count) HIPCHK(hipMemcpyAsync(count, d_c.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
 // ------------------------------------------------------------------ rendering along caller-supplied rays
 // what the ray-list entry points check before anything touches a device: pointers, then the shape of the ray buffer, then the scene
-static int check_ray_args(const char* who, const pbrhip_scene* s, const pbrhip_render_desc* d, const void* rays, uint32_t ray_passes,
-                          uint32_t camera_draws) {
+int pb::check_ray_args(const char* who, const pbrhip_scene* s, const pbrhip_render_desc* d, const void* rays, uint32_t ray_passes,
+                       uint32_t camera_draws) {
   if (!d || !rays) return fail(PBRHIP_EINVAL, "%s: NULL descriptor or rays", who);
   if (ray_passes != 1u && ray_passes != d->num_sample)
     return fail(PBRHIP_EINVAL, "%s: ray_passes %u is neither 1 nor num_sample %u", who, ray_passes, d->num_sample);
   if (camera_draws > kMaxCameraDraws) return fail(PBRHIP_EINVAL, "%s: camera_draws %u (at most %u)", who, camera_draws, kMaxCameraDraws);
   if (!s) return fail(PBRHIP_EINVAL, "%s: NULL scene", who);
-  return PBRHIP_OK;
-}
-// the caller's rays are read only after what its stream already holds (pbrhip_scene_update_triangle_mesh_device's rule): an event there,
-// and the scene's stream -- behind which every path group starts -- waits for it
-static int wait_for_caller_stream(pbrhip_scene* s, void* stream) {
-  hipEvent_t ev;
-  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
-  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
-  (void)hipEventDestroy(ev);
-  HIPCHK(e);
   return PBRHIP_OK;
 }
 
@@ -1597,703 +1474,6 @@ extern "C" int pbrhip_render_rays(pbrhip_scene* s, const pbrhip_render_desc* d, 
     HIPCHK(hipMemcpyAsync(count, s->own_count.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (stats) stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return PBRHIP_OK;
-  });
-}
-
-extern "C" int pbrhip_render_features_rays_device(pbrhip_scene* s, const pbrhip_render_desc* d, const void* d_rays, uint32_t ray_passes,
-                                                  void* stream, float* d_albedo_hits, float* d_normal_depth, uint32_t* d_count) {
-  return guarded([&]() -> int {
-    if (int rc = check_ray_args("render_features_rays", s, d, d_rays, ray_passes, 0)) return rc;
-    if (int rc = check_render_desc(s, d)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    if (int rc = wait_for_caller_stream(s, stream)) return rc;
-    RaySource src{};
-    src.rays = static_cast<const float4*>(d_rays), src.ray_passes = ray_passes;
-    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count, &src);
-  });
-}
-
-extern "C" int pbrhip_projection_rays_device(pbrhip_scene* s, uint32_t projection, float param, uint32_t width, uint32_t height,
-                                             uint32_t first_pass, uint32_t num_pass, uint64_t seed_seq, void* d_rays, void* stream) {
-  return guarded([&]() -> int {
-    if (!s || !d_rays) return fail(PBRHIP_EINVAL, "projection_rays: NULL scene or rays");
-    if (projection > PBRHIP_PROJECTION_ORTHO) return fail(PBRHIP_EINVAL, "projection_rays: unknown projection %u", projection);
-    if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "projection_rays: zero image size");
-    if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "projection_rays: image too large");
-    if ((uint64_t)first_pass + num_pass > (1ull << 32)) return fail(PBRHIP_EINVAL, "projection_rays: the passes do not fit 32 bits");
-    if (!isfinite(param) || param < 0.0f) return fail(PBRHIP_EINVAL, "projection_rays: param %g is not a finite number >= 0", (double)param);
-    if (projection == PBRHIP_PROJECTION_FISHEYE && param > 360.0f) return fail(PBRHIP_EINVAL, "projection_rays: a fisheye of %g degrees (at most 360)", (double)param);
-    if (projection == PBRHIP_PROJECTION_ORTHO && !(param > 0.0f)) return fail(PBRHIP_EINVAL, "projection_rays: an orthographic view needs its half height > 0");
-    if (!s->cam_set) return fail(PBRHIP_ESTATE, "projection_rays: the scene has no camera (pbrhip_scene_set_camera gives the frame)");
-    if (num_pass == 0) return PBRHIP_OK;
-    HIPCHK(hipSetDevice(s->device));
-    ProjectArgs a{};
-    a.cam = make_user_camera(s, width, height);
-    a.projection = projection;
-    // fisheye: the field of view in degrees, 0 = the camera's vertical one; the kernel takes half of it in radians, rounded once
-    if (projection == PBRHIP_PROJECTION_FISHEYE) a.param = (float)((double)(param > 0.0f ? param : s->cam_vfov) * M_PI / 360.0);
-    else a.param = param;
-    a.width = width, a.height = height, a.first_pass = first_pass, a.npass = num_pass, a.seed_seq = seed_seq;
-    a.rays = static_cast<float4*>(d_rays);
-    launch_project_rays(static_cast<hipStream_t>(stream), a);
-    HIPCHK(hipGetLastError());
-    return PBRHIP_OK;
-  });
-}
-
-// the checks both denoise entry points share; resolves the iteration default
-static int check_denoise(int device, uint32_t width, uint32_t height, const void* rgba, const void* count, const void* albedo_hits,
-                         const void* normal_depth, const void* feature_count, uint32_t* iterations, float sigma_color, float sigma_depth,
-                         uint32_t normal_squarings, uint32_t flags, const void* out_rgba) {
-  if (!rgba || !count || !out_rgba) return fail(PBRHIP_EINVAL, "denoise: NULL rgba, count or out_rgba");
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "denoise: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "denoise: image too large");
-  const int nfeat = (albedo_hits ? 1 : 0) + (normal_depth ? 1 : 0) + (feature_count ? 1 : 0);
-  if (nfeat != 0 && nfeat != 3) return fail(PBRHIP_EINVAL, "denoise: albedo_hits, normal_depth and feature_count come together or not at all");
-  if (sigma_color != sigma_color || sigma_depth != sigma_depth) return fail(PBRHIP_EINVAL, "denoise: a sigma is NaN");
-  if (*iterations > 8) return fail(PBRHIP_EINVAL, "denoise: %u iterations (at most 8)", *iterations);
-  if (normal_squarings > 16) return fail(PBRHIP_EINVAL, "denoise: %u normal squarings (at most 16)", normal_squarings);
-  if (flags & ~PBRHIP_DENOISE_NO_ALBEDO) return fail(PBRHIP_EINVAL, "denoise: unknown flags 0x%x", flags);
-  if (*iterations == 0) *iterations = PBRHIP_DENOISE_ITERATIONS;
-  int n = 0;
-  if (int rc = pbrhip_device_count(&n)) return rc;
-  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "denoise: device %d out of range (%d devices)", device, n);
-  return PBRHIP_OK;
-}
-
-// prepare + one launch per iteration on the device's null stream; the three temporaries (two colour images, one guide image) live
-// for the call
-static int denoise_impl(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
-                        const float* normal_depth, const uint32_t* feature_count, uint32_t iterations, float sigma_color, float sigma_depth,
-                        uint32_t normal_squarings, uint32_t flags, float* out_rgba) {
-  HIPCHK(hipSetDevice(device));
-  const size_t npx = (size_t)width * height;
-  DevBuf<float4> e0, e1, guide;
-  HIPCHK(e0.reserve(npx));
-  HIPCHK(e1.reserve(npx));
-  HIPCHK(guide.reserve(npx));
-  DenoiseArgs a;
-  a.width = width, a.height = height;
-  a.rgba = reinterpret_cast<const float4*>(rgba), a.count = count;
-  a.albedo_hits = reinterpret_cast<const float4*>(albedo_hits), a.normal_depth = reinterpret_cast<const float4*>(normal_depth), a.feature_count = feature_count;
-  a.no_albedo = (flags & PBRHIP_DENOISE_NO_ALBEDO) ? 1u : 0u;
-  a.sigma_color = sigma_color, a.sigma_depth = sigma_depth, a.normal_squarings = normal_squarings;
-  launch_denoise_prepare(nullptr, a, e0.p, guide.p);
-  HIPCHK(hipGetLastError());
-  for (uint32_t i = 0; i < iterations; i++) {
-    const bool last = i + 1 == iterations;
-    float4* const src = (i & 1u) ? e1.p : e0.p;
-    float4* const dst = last ? reinterpret_cast<float4*>(out_rgba) : ((i & 1u) ? e0.p : e1.p);
-    launch_denoise_iteration(nullptr, a, i, last, src, guide.p, dst);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_denoise_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
-                                     const float* d_albedo_hits, const float* d_normal_depth, const uint32_t* d_feature_count, uint32_t iterations,
-                                     float sigma_color, float sigma_depth, uint32_t normal_squarings, uint32_t flags, float* d_out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_denoise(device, width, height, d_rgba, d_count, d_albedo_hits, d_normal_depth, d_feature_count, &iterations, sigma_color,
-                               sigma_depth, normal_squarings, flags, d_out_rgba))
-      return rc;
-    return denoise_impl(device, width, height, d_rgba, d_count, d_albedo_hits, d_normal_depth, d_feature_count, iterations, sigma_color, sigma_depth,
-                        normal_squarings, flags, d_out_rgba);
-  });
-}
-
-extern "C" int pbrhip_denoise(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
-                              const float* normal_depth, const uint32_t* feature_count, uint32_t iterations, float sigma_color, float sigma_depth,
-                              uint32_t normal_squarings, uint32_t flags, float* out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_denoise(device, width, height, rgba, count, albedo_hits, normal_depth, feature_count, &iterations, sigma_color, sigma_depth,
-                               normal_squarings, flags, out_rgba))
-      return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_rgba, d_a, d_n, d_out;
-    DevBuf<uint32_t> d_count, d_fc;
-    HIPCHK(d_rgba.reserve(npx * 4));
-    HIPCHK(d_count.reserve(npx));
-    HIPCHK(d_out.reserve(npx * 4));
-    HIPCHK(hipMemcpy(d_rgba.p, rgba, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (albedo_hits) {
-      HIPCHK(d_a.reserve(npx * 4));
-      HIPCHK(d_n.reserve(npx * 4));
-      HIPCHK(d_fc.reserve(npx));
-      HIPCHK(hipMemcpy(d_a.p, albedo_hits, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_n.p, normal_depth, npx * 4 * sizeof(float), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_fc.p, feature_count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (int rc = denoise_impl(device, width, height, d_rgba.p, d_count.p, d_a.p, d_n.p, d_fc.p, iterations, sigma_color, sigma_depth,
-                              normal_squarings, flags, d_out.p))
-      return rc;
-    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-// ------------------------------------------------------------------ motion vectors and temporal accumulation
-extern "C" int pbrhip_scene_snapshot_pose(pbrhip_scene* s) {
-  return guarded([&]() -> int {
-    if (!s) return fail(PBRHIP_EINVAL, "scene_snapshot_pose: scene is NULL");
-    if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-    PB_NOT_STALE(s);
-    HIPCHK(hipSetDevice(s->device));
-    const size_t words = (size_t)s->tree.num_slots * 4;
-    s->pose_set = false;
-    HIPCHK(s->pose_slots.reserve(words));
-    // on the scene's stream: behind the render that still reads the slots, in front of the refit that rewrites them
-    if (words) HIPCHK(hipMemcpyAsync(s->pose_slots.p, s->dscene.slots, words * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    s->pose_cam = pose_camera(s);
-    s->pose_set = true;
-    return PBRHIP_OK;
-  });
-}
-
-// the body of pbrhip_render_motion_device: device pointers on the scene's device, each may be null
-static int motion_impl(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_motion, float* d_guide, uint32_t* d_ident) {
-  if (int rc = check_render_desc(s, d)) return rc;
-  if (!s->pose_set) return fail(PBRHIP_ESTATE, "render_motion: the scene has no pose snapshot (pbrhip_scene_snapshot_pose)");
-  const Knobs k = read_knobs();
-  HIPCHK(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  const size_t npx_img = (size_t)d->width * d->height;
-  if (d_motion) HIPCHK(hipMemsetAsync(d_motion, 0, npx_img * 4 * sizeof(float), st));
-  if (d_guide) HIPCHK(hipMemsetAsync(d_guide, 0, npx_img * 4 * sizeof(float), st));
-  if (d_ident) HIPCHK(hipMemsetAsync(d_ident, 0, npx_img * 4 * sizeof(uint32_t), st));
-  if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
-  const uint32_t npix = s->pk_npix;
-  if (npix == 0 || (!d_motion && !d_guide && !d_ident)) {
-    HIPCHK(hipStreamSynchronize(st));
-    return PBRHIP_OK;
-  }
-  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
-  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, st));
-  HIPCHK(s->spill.reserve(kSpillWords));
-  MotionArgs a{};
-  a.user = s->cam_set ? 1u : 0u, a.user_prev = s->pose_cam.set ? 1u : 0u;
-  if (a.user) a.ucam = make_user_camera(s, d->width, d->height);
-  else a.cam = make_camera(s, d->width, d->height);
-  if (a.user_prev) a.ucam_prev = make_user_camera(s->pose_cam, d->width, d->height);
-  else a.cam_prev = make_camera(s->pose_cam, d->width, d->height);
-  a.width = d->width, a.height = d->height;
-  a.pix = s->path_pix.p, a.npix = npix;
-  a.prev_slots = s->pose_slots.p;
-  a.motion = reinterpret_cast<float4*>(d_motion), a.guide = reinterpret_cast<float4*>(d_guide), a.ident = reinterpret_cast<uint4*>(d_ident);
-  a.overflow = s->counts.p + kCntOverflow, a.spill = s->spill.p;
-  launch_motion(st, s->dscene, a, k);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_render_motion_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_motion, float* d_guide, uint32_t* d_ident) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_motion: NULL argument");
-    return motion_impl(s, d, d_motion, d_guide, d_ident);
-  });
-}
-
-extern "C" int pbrhip_render_motion(pbrhip_scene* s, const pbrhip_render_desc* d, float* motion, float* guide, uint32_t* ident) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_motion: NULL argument");
-    if (int rc = check_render_desc(s, d)) return rc;
-    if (!s->pose_set) return fail(PBRHIP_ESTATE, "render_motion: the scene has no pose snapshot (pbrhip_scene_snapshot_pose)");
-    HIPCHK(hipSetDevice(s->device));
-    const size_t npx = (size_t)d->width * d->height;
-    DevBuf<float> d_m, d_g;
-    DevBuf<uint32_t> d_i;
-    if (motion) HIPCHK(d_m.reserve(npx * 4));
-    if (guide) HIPCHK(d_g.reserve(npx * 4));
-    if (ident) HIPCHK(d_i.reserve(npx * 4));
-    if (int rc = motion_impl(s, d, d_m.p, d_g.p, d_i.p)) return rc;
-    if (motion) HIPCHK(hipMemcpyAsync(motion, d_m.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (guide) HIPCHK(hipMemcpyAsync(guide, d_g.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (ident) HIPCHK(hipMemcpyAsync(ident, d_i.p, npx * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
-// the checks both accumulation entry points share, before any device work
-static int check_temporal(int device, uint32_t width, uint32_t height, const void* rgba, const void* count, const void* motion, const void* guide,
-                          const void* hist_rgba, const void* hist_guide, float alpha_min, float sigma_depth, float normal_cos_min,
-                          uint32_t max_history, const void* out_rgba) {
-  if (!rgba || !count || !motion || !guide || !out_rgba) return fail(PBRHIP_EINVAL, "temporal_accumulate: NULL rgba, count, motion, guide or out_rgba");
-  if ((hist_rgba != nullptr) != (hist_guide != nullptr)) return fail(PBRHIP_EINVAL, "temporal_accumulate: hist_rgba and hist_guide come together or not at all");
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "temporal_accumulate: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "temporal_accumulate: image too large");
-  if (alpha_min != alpha_min || sigma_depth != sigma_depth || normal_cos_min != normal_cos_min) return fail(PBRHIP_EINVAL, "temporal_accumulate: a parameter is NaN");
-  if (max_history == 0 || max_history > (1u << 24)) return fail(PBRHIP_EINVAL, "temporal_accumulate: max_history %u is not in [1, 2^24]", max_history);
-  if (out_rgba == hist_rgba) return fail(PBRHIP_EINVAL, "temporal_accumulate: out_rgba is hist_rgba (the taps of one pixel read what another wrote)");
-  int n = 0;
-  if (int rc = pbrhip_device_count(&n)) return rc;
-  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "temporal_accumulate: device %d out of range (%d devices)", device, n);
-  return PBRHIP_OK;
-}
-
-// one launch on the device's null stream
-static int temporal_impl(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* motion, const float* guide,
-                         const float* hist_rgba, const float* hist_guide, float alpha_min, float sigma_depth, float normal_cos_min,
-                         uint32_t max_history, float* out_rgba) {
-  HIPCHK(hipSetDevice(device));
-  TemporalArgs a{};
-  a.width = width, a.height = height;
-  a.rgba = reinterpret_cast<const float4*>(rgba), a.count = count;
-  a.motion = reinterpret_cast<const float4*>(motion), a.guide = reinterpret_cast<const float4*>(guide);
-  a.hist_rgba = reinterpret_cast<const float4*>(hist_rgba), a.hist_guide = reinterpret_cast<const float4*>(hist_guide);
-  a.alpha_min = alpha_min, a.sigma_depth = sigma_depth, a.normal_cos_min = normal_cos_min, a.max_history = (float)max_history;
-  a.out = reinterpret_cast<float4*>(out_rgba);
-  launch_temporal(nullptr, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_temporal_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
-                                                 const float* d_motion, const float* d_guide, const float* d_hist_rgba, const float* d_hist_guide,
-                                                 float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* d_out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_temporal(device, width, height, d_rgba, d_count, d_motion, d_guide, d_hist_rgba, d_hist_guide, alpha_min, sigma_depth,
-                                normal_cos_min, max_history, d_out_rgba))
-      return rc;
-    return temporal_impl(device, width, height, d_rgba, d_count, d_motion, d_guide, d_hist_rgba, d_hist_guide, alpha_min, sigma_depth,
-                         normal_cos_min, max_history, d_out_rgba);
-  });
-}
-
-extern "C" int pbrhip_temporal_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* motion,
-                                          const float* guide, const float* hist_rgba, const float* hist_guide, float alpha_min, float sigma_depth,
-                                          float normal_cos_min, uint32_t max_history, float* out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_temporal(device, width, height, rgba, count, motion, guide, hist_rgba, hist_guide, alpha_min, sigma_depth, normal_cos_min,
-                                max_history, out_rgba))
-      return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_img[5], d_out;  // rgba, motion, guide, hist_rgba, hist_guide
-    DevBuf<uint32_t> d_count;
-    const float* src[5] = {rgba, motion, guide, hist_rgba, hist_guide};
-    for (int i = 0; i < 5; i++) {
-      if (!src[i]) continue;
-      HIPCHK(d_img[i].reserve(npx * 4));
-      HIPCHK(hipMemcpy(d_img[i].p, src[i], npx * 4 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIPCHK(d_count.reserve(npx));
-    HIPCHK(d_out.reserve(npx * 4));
-    HIPCHK(hipMemcpy(d_count.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = temporal_impl(device, width, height, d_img[0].p, d_count.p, d_img[1].p, d_img[2].p, d_img[3].p, d_img[4].p, alpha_min, sigma_depth,
-                               normal_cos_min, max_history, d_out.p))
-      return rc;
-    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-// ------------------------------------------------------------------ variance-guided filtering
-static int check_object_ids(pbrhip_scene* s, const void* ident, size_t num_pixels, uint32_t what, const void* ids) {
-  if (!s) return fail(PBRHIP_EINVAL, "scene_object_ids: scene is NULL");
-  if (what > PBRHIP_ID_GEOM) return fail(PBRHIP_EINVAL, "scene_object_ids: unknown id %u", what);
-  if (num_pixels && (!ident || !ids)) return fail(PBRHIP_EINVAL, "scene_object_ids: NULL ident or ids");
-  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-  PB_NOT_STALE(s);
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_scene_object_ids_device(pbrhip_scene* s, const void* d_ident, size_t num_pixels, uint32_t what, void* d_ids, void* stream) {
-  return guarded([&]() -> int {
-    if (int rc = check_object_ids(s, d_ident, num_pixels, what, d_ids)) return rc;
-    if (!num_pixels) return PBRHIP_OK;
-    HIPCHK(hipSetDevice(s->device));
-    if (int rc = wait_for_caller_stream(s, stream)) return rc;
-    launch_object_ids(s->stream, s->dscene.shade, s->tree.num_slots, static_cast<const uint4*>(d_ident), num_pixels, what, static_cast<uint32_t*>(d_ids));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
-extern "C" int pbrhip_scene_object_ids(pbrhip_scene* s, const uint32_t* ident, size_t num_pixels, uint32_t what, uint32_t* ids) {
-  return guarded([&]() -> int {
-    if (int rc = check_object_ids(s, ident, num_pixels, what, ids)) return rc;
-    if (!num_pixels) return PBRHIP_OK;
-    HIPCHK(hipSetDevice(s->device));
-    DevBuf<uint32_t> d_ident, d_ids;
-    HIPCHK(d_ident.reserve(num_pixels * 4));
-    HIPCHK(d_ids.reserve(num_pixels));
-    HIPCHK(hipMemcpyAsync(d_ident.p, ident, num_pixels * 4 * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    launch_object_ids(s->stream, s->dscene.shade, s->tree.num_slots, reinterpret_cast<const uint4*>(d_ident.p), num_pixels, what, d_ids.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ids, d_ids.p, num_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
-// what every svgf entry point checks last: a device to work on
-static int check_svgf_device(const char* who, int device) {
-  int n = 0;
-  if (int rc = pbrhip_device_count(&n)) return rc;
-  if (n <= 0) return fail(PBRHIP_ENODEVICE, "no HIP device available: libpbrhip has no CPU fallback");
-  if (device < 0 || device >= n) return fail(PBRHIP_EINVAL, "%s: device %d out of range (%d devices)", who, device, n);
-  return PBRHIP_OK;
-}
-
-// the accumulation's pointers, host or device: the checks and both entry points pass them as one
-struct SvgfAccumPtrs {
-  const float* rgba;
-  const uint32_t* count;
-  const float* albedo_hits;
-  const uint32_t* feature_count;
-  const float *motion, *guide;
-  const uint32_t* ids;
-  const float *hist_illum, *hist_var, *hist_guide;
-  const uint32_t* hist_ids;
-  float *out_illum, *out_var;
-};
-
-// the checks both accumulation entry points share, before any device work
-static int check_svgf_accumulate(int device, uint32_t width, uint32_t height, const SvgfAccumPtrs& p, float alpha_min, float sigma_depth,
-                                 float normal_cos_min, uint32_t max_history) {
-  if (!p.rgba || !p.count || !p.motion || !p.guide || !p.out_illum || !p.out_var)
-    return fail(PBRHIP_EINVAL, "svgf_accumulate: NULL rgba, count, motion, guide, out_illum or out_var");
-  if ((p.albedo_hits != nullptr) != (p.feature_count != nullptr)) return fail(PBRHIP_EINVAL, "svgf_accumulate: albedo_hits and feature_count come together or not at all");
-  const int nhist = (p.hist_illum ? 1 : 0) + (p.hist_var ? 1 : 0) + (p.hist_guide ? 1 : 0);
-  if (nhist != 0 && nhist != 3) return fail(PBRHIP_EINVAL, "svgf_accumulate: hist_illum, hist_var and hist_guide come together or not at all");
-  if ((p.hist_ids != nullptr) != (p.ids != nullptr && nhist == 3))
-    return fail(PBRHIP_EINVAL, "svgf_accumulate: hist_ids is given exactly when ids is given and a history is present");
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "svgf_accumulate: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "svgf_accumulate: image too large");
-  if (alpha_min != alpha_min || sigma_depth != sigma_depth || normal_cos_min != normal_cos_min) return fail(PBRHIP_EINVAL, "svgf_accumulate: a parameter is NaN");
-  if (alpha_min < 0.0f || alpha_min > 1.0f) return fail(PBRHIP_EINVAL, "svgf_accumulate: alpha_min %g is not in [0, 1]", (double)alpha_min);
-  if (max_history == 0 || max_history > (1u << 24)) return fail(PBRHIP_EINVAL, "svgf_accumulate: max_history %u is not in [1, 2^24]", max_history);
-  const void* outs[2] = {p.out_illum, p.out_var};
-  const void* hists[4] = {p.hist_illum, p.hist_var, p.hist_guide, p.hist_ids};
-  for (const void* o : outs)
-    for (const void* h : hists)
-      if (h && o == h) return fail(PBRHIP_EINVAL, "svgf_accumulate: an output is a history buffer (the taps of one pixel read what another wrote)");
-  if ((const void*)p.out_illum == (const void*)p.out_var) return fail(PBRHIP_EINVAL, "svgf_accumulate: out_illum is out_var");
-  return check_svgf_device("svgf_accumulate", device);
-}
-
-// one launch on the device's null stream; device pointers
-static int svgf_accumulate_impl(int device, uint32_t width, uint32_t height, const SvgfAccumPtrs& p, float alpha_min, float sigma_depth,
-                                float normal_cos_min, uint32_t max_history) {
-  HIPCHK(hipSetDevice(device));
-  SvgfAccumArgs a{};
-  a.width = width, a.height = height;
-  a.rgba = reinterpret_cast<const float4*>(p.rgba), a.count = p.count;
-  a.albedo_hits = reinterpret_cast<const float4*>(p.albedo_hits), a.feature_count = p.feature_count;
-  a.motion = reinterpret_cast<const float4*>(p.motion), a.guide = reinterpret_cast<const float4*>(p.guide), a.ids = p.ids;
-  a.hist_illum = reinterpret_cast<const float4*>(p.hist_illum), a.hist_var = p.hist_var;
-  a.hist_guide = reinterpret_cast<const float4*>(p.hist_guide), a.hist_ids = p.hist_ids;
-  a.alpha_min = alpha_min, a.sigma_depth = sigma_depth, a.normal_cos_min = normal_cos_min, a.max_history = (float)max_history;
-  a.out_illum = reinterpret_cast<float4*>(p.out_illum), a.out_var = p.out_var;
-  launch_svgf_accumulate(nullptr, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_svgf_accumulate_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
-                                             const float* d_albedo_hits, const uint32_t* d_feature_count, const float* d_motion,
-                                             const float* d_guide, const uint32_t* d_ids, const float* d_hist_illum, const float* d_hist_var,
-                                             const float* d_hist_guide, const uint32_t* d_hist_ids, float alpha_min, float sigma_depth,
-                                             float normal_cos_min, uint32_t max_history, float* d_out_illum, float* d_out_var) {
-  return guarded([&]() -> int {
-    const SvgfAccumPtrs p{d_rgba, d_count, d_albedo_hits, d_feature_count, d_motion, d_guide, d_ids, d_hist_illum, d_hist_var, d_hist_guide,
-                          d_hist_ids, d_out_illum, d_out_var};
-    if (int rc = check_svgf_accumulate(device, width, height, p, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
-    return svgf_accumulate_impl(device, width, height, p, alpha_min, sigma_depth, normal_cos_min, max_history);
-  });
-}
-
-// a host image's copy on the device (null stays null): `words` 4-byte words per pixel
-template <typename T>
-static int svgf_upload(DevBuf<T>& d, const T* src, size_t npx, size_t words) {
-  if (!src) return PBRHIP_OK;
-  HIPCHK(d.reserve(npx * words));
-  HIPCHK(hipMemcpy(d.p, src, npx * words * sizeof(T), hipMemcpyHostToDevice));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_svgf_accumulate(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* albedo_hits,
-                                      const uint32_t* feature_count, const float* motion, const float* guide, const uint32_t* ids,
-                                      const float* hist_illum, const float* hist_var, const float* hist_guide, const uint32_t* hist_ids,
-                                      float alpha_min, float sigma_depth, float normal_cos_min, uint32_t max_history, float* out_illum,
-                                      float* out_var) {
-  return guarded([&]() -> int {
-    const SvgfAccumPtrs h{rgba, count, albedo_hits, feature_count, motion, guide, ids, hist_illum, hist_var, hist_guide, hist_ids, out_illum, out_var};
-    if (int rc = check_svgf_accumulate(device, width, height, h, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_f[7], d_oi, d_ov;  // rgba, albedo_hits, motion, guide, hist_illum, hist_var, hist_guide
-    DevBuf<uint32_t> d_u[4];           // count, feature_count, ids, hist_ids
-    const float* fs[7] = {rgba, albedo_hits, motion, guide, hist_illum, hist_var, hist_guide};
-    const uint32_t* us[4] = {count, feature_count, ids, hist_ids};
-    for (int i = 0; i < 7; i++)
-      if (int rc = svgf_upload(d_f[i], fs[i], npx, i == 5 ? 1 : 4)) return rc;
-    for (int i = 0; i < 4; i++)
-      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
-    HIPCHK(d_oi.reserve(npx * 4));
-    HIPCHK(d_ov.reserve(npx));
-    const SvgfAccumPtrs d{d_f[0].p, d_u[0].p, d_f[1].p, d_u[1].p, d_f[2].p, d_f[3].p, d_u[2].p, d_f[4].p, d_f[5].p, d_f[6].p, d_u[3].p, d_oi.p, d_ov.p};
-    if (int rc = svgf_accumulate_impl(device, width, height, d, alpha_min, sigma_depth, normal_cos_min, max_history)) return rc;
-    HIPCHK(hipMemcpy(out_illum, d_oi.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_var, d_ov.p, npx * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-// the checks both filter entry points share; resolves the iteration default
-static int check_svgf_filter(int device, uint32_t width, uint32_t height, const void* illum, const void* var, const void* guide,
-                             const void* albedo_hits, const void* feature_count, uint32_t* iterations, float sigma_lum, float sigma_depth,
-                             uint32_t normal_squarings, const void* out_rgba, const void* out_feedback) {
-  if (!illum || !var || !guide || !out_rgba) return fail(PBRHIP_EINVAL, "svgf_filter: NULL illum, var, guide or out_rgba");
-  if ((albedo_hits != nullptr) != (feature_count != nullptr)) return fail(PBRHIP_EINVAL, "svgf_filter: albedo_hits and feature_count come together or not at all");
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "svgf_filter: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "svgf_filter: image too large");
-  if (sigma_lum != sigma_lum || sigma_depth != sigma_depth) return fail(PBRHIP_EINVAL, "svgf_filter: a sigma is NaN");
-  if (*iterations > 8) return fail(PBRHIP_EINVAL, "svgf_filter: %u iterations (at most 8)", *iterations);
-  if (normal_squarings > 16) return fail(PBRHIP_EINVAL, "svgf_filter: %u normal squarings (at most 16)", normal_squarings);
-  if (out_rgba == illum || out_rgba == guide || out_feedback == illum || out_feedback == guide || out_feedback == out_rgba)
-    return fail(PBRHIP_EINVAL, "svgf_filter: an output is an input or the other output (the taps of one pixel read what another wrote)");
-  if (*iterations == 0) *iterations = PBRHIP_SVGF_ITERATIONS;
-  return check_svgf_device("svgf_filter", device);
-}
-
-// prepare + one launch per iteration on the device's null stream; the two temporaries (e | v, twice) live for the call
-static int svgf_filter_impl(int device, uint32_t width, uint32_t height, const float* illum, const float* var, const float* guide, const uint32_t* ids,
-                            const float* albedo_hits, const uint32_t* feature_count, uint32_t iterations, float sigma_lum, float sigma_depth,
-                            uint32_t normal_squarings, float* out_rgba, float* out_feedback) {
-  HIPCHK(hipSetDevice(device));
-  const size_t npx = (size_t)width * height;
-  DevBuf<float4> e0, e1;
-  HIPCHK(e0.reserve(npx));
-  if (iterations > 1) HIPCHK(e1.reserve(npx));
-  SvgfFilterArgs a{};
-  a.width = width, a.height = height;
-  a.illum = reinterpret_cast<const float4*>(illum), a.var = var, a.guide = reinterpret_cast<const float4*>(guide), a.ids = ids;
-  a.albedo_hits = reinterpret_cast<const float4*>(albedo_hits), a.feature_count = feature_count;
-  a.sigma_lum = sigma_lum, a.sigma_depth = sigma_depth, a.normal_squarings = normal_squarings;
-  launch_svgf_prepare(nullptr, a, e0.p);
-  HIPCHK(hipGetLastError());
-  for (uint32_t i = 0; i < iterations; i++) {
-    const bool last = i + 1 == iterations;
-    float4* const src = (i & 1u) ? e1.p : e0.p;
-    float4* const dst = last ? reinterpret_cast<float4*>(out_rgba) : ((i & 1u) ? e0.p : e1.p);
-    launch_svgf_iteration(nullptr, a, i, last, src, dst, i == 0 ? reinterpret_cast<float4*>(out_feedback) : nullptr);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_svgf_filter_device(int device, uint32_t width, uint32_t height, const float* d_illum, const float* d_var, const float* d_guide,
-                                         const uint32_t* d_ids, const float* d_albedo_hits, const uint32_t* d_feature_count, uint32_t iterations,
-                                         float sigma_lum, float sigma_depth, uint32_t normal_squarings, float* d_out_rgba, float* d_out_feedback) {
-  return guarded([&]() -> int {
-    if (int rc = check_svgf_filter(device, width, height, d_illum, d_var, d_guide, d_albedo_hits, d_feature_count, &iterations, sigma_lum, sigma_depth,
-                                   normal_squarings, d_out_rgba, d_out_feedback))
-      return rc;
-    return svgf_filter_impl(device, width, height, d_illum, d_var, d_guide, d_ids, d_albedo_hits, d_feature_count, iterations, sigma_lum, sigma_depth,
-                            normal_squarings, d_out_rgba, d_out_feedback);
-  });
-}
-
-extern "C" int pbrhip_svgf_filter(int device, uint32_t width, uint32_t height, const float* illum, const float* var, const float* guide,
-                                  const uint32_t* ids, const float* albedo_hits, const uint32_t* feature_count, uint32_t iterations, float sigma_lum,
-                                  float sigma_depth, uint32_t normal_squarings, float* out_rgba, float* out_feedback) {
-  return guarded([&]() -> int {
-    if (int rc = check_svgf_filter(device, width, height, illum, var, guide, albedo_hits, feature_count, &iterations, sigma_lum, sigma_depth,
-                                   normal_squarings, out_rgba, out_feedback))
-      return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_f[4], d_out, d_fb;  // illum, var, guide, albedo_hits
-    DevBuf<uint32_t> d_u[2];            // ids, feature_count
-    const float* fs[4] = {illum, var, guide, albedo_hits};
-    const uint32_t* us[2] = {ids, feature_count};
-    for (int i = 0; i < 4; i++)
-      if (int rc = svgf_upload(d_f[i], fs[i], npx, i == 1 ? 1 : 4)) return rc;
-    for (int i = 0; i < 2; i++)
-      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
-    HIPCHK(d_out.reserve(npx * 4));
-    if (out_feedback) HIPCHK(d_fb.reserve(npx * 4));
-    if (int rc = svgf_filter_impl(device, width, height, d_f[0].p, d_f[1].p, d_f[2].p, d_u[0].p, d_f[3].p, d_u[1].p, iterations, sigma_lum, sigma_depth,
-                                  normal_squarings, d_out.p, d_fb.p))
-      return rc;
-    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_feedback) HIPCHK(hipMemcpy(out_feedback, d_fb.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-// ------------------------------------------------------------------ the first-hit emission layer
-extern "C" int pbrhip_render_features_emission_device(pbrhip_scene* s, const pbrhip_render_desc* d, float* d_albedo_hits, float* d_normal_depth,
-                                                      uint32_t* d_count, float* d_emission) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
-    return features_impl(s, d, d_albedo_hits, d_normal_depth, d_count, nullptr, true, d_emission);
-  });
-}
-
-extern "C" int pbrhip_render_features_emission(pbrhip_scene* s, const pbrhip_render_desc* d, float* albedo_hits, float* normal_depth,
-                                               uint32_t* count, float* emission) {
-  return guarded([&]() -> int {
-    if (!s || !d) return fail(PBRHIP_EINVAL, "render_features: NULL argument");
-    if (int rc = check_render_desc(s, d)) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t npx = (size_t)d->width * d->height;
-    DevBuf<float> d_f[3];  // albedo_hits, normal_depth, emission
-    DevBuf<uint32_t> d_c;
-    float* const host[3] = {albedo_hits, normal_depth, emission};
-    for (int i = 0; i < 3; i++)
-      if (host[i]) HIPCHK(d_f[i].reserve(npx * 4));
-    if (count) HIPCHK(d_c.reserve(npx));
-    if (d->flags & PBRHIP_RENDER_NO_CLEAR) {
-      for (int i = 0; i < 3; i++)
-        if (host[i]) HIPCHK(hipMemcpyAsync(d_f[i].p, host[i], npx * 4 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-      if (count) HIPCHK(hipMemcpyAsync(d_c.p, count, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    }
-    if (int rc = features_impl(s, d, d_f[0].p, d_f[1].p, d_c.p, nullptr, true, d_f[2].p)) return rc;
-    for (int i = 0; i < 3; i++)
-      if (host[i]) HIPCHK(hipMemcpyAsync(host[i], d_f[i].p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    if (count) HIPCHK(hipMemcpyAsync(count, d_c.p, npx * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return PBRHIP_OK;
-  });
-}
-
-// the pointers of pbrhip_emission_split, host or device
-struct EmissionSplitPtrs {
-  const float* rgba;
-  const uint32_t* count;
-  const float *emission, *albedo_hits;
-  const uint32_t* feature_count;
-  float *out_rgba, *out_albedo_hits;
-};
-
-// the checks both split entry points share, before any device work
-static int check_emission_split(int device, uint32_t width, uint32_t height, const EmissionSplitPtrs& p) {
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "emission_split: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "emission_split: image too large");
-  if (!p.rgba || !p.count || !p.emission || !p.out_rgba) return fail(PBRHIP_EINVAL, "emission_split: NULL rgba, count, emission or out_rgba");
-  const int nal = (p.albedo_hits ? 1 : 0) + (p.feature_count ? 1 : 0) + (p.out_albedo_hits ? 1 : 0);
-  if (nal != 0 && nal != 3) return fail(PBRHIP_EINVAL, "emission_split: albedo_hits, feature_count and out_albedo_hits come together or not at all");
-  const void* ins[4] = {p.rgba, p.count, p.emission, p.feature_count};
-  for (const void* in : ins)
-    if (p.out_albedo_hits && (const void*)p.out_albedo_hits == in)
-      return fail(PBRHIP_EINVAL, "emission_split: out_albedo_hits is an input other than albedo_hits");
-  if (p.out_albedo_hits && (const void*)p.out_albedo_hits == (const void*)p.out_rgba) return fail(PBRHIP_EINVAL, "emission_split: out_albedo_hits is out_rgba");
-  const void* others[4] = {p.count, p.emission, p.albedo_hits, p.feature_count};
-  for (const void* in : others)
-    if (in && (const void*)p.out_rgba == in) return fail(PBRHIP_EINVAL, "emission_split: out_rgba is an input other than rgba");
-  return check_svgf_device("emission_split", device);
-}
-
-// one launch on the device's null stream; device pointers
-static int emission_split_impl(int device, uint32_t width, uint32_t height, const EmissionSplitPtrs& p) {
-  HIPCHK(hipSetDevice(device));
-  EmissionSplitArgs a{};
-  a.npx = (size_t)width * height;
-  a.rgba = reinterpret_cast<const float4*>(p.rgba), a.count = p.count, a.emission = reinterpret_cast<const float4*>(p.emission);
-  a.albedo_hits = reinterpret_cast<const float4*>(p.albedo_hits), a.feature_count = p.feature_count;
-  a.out_rgba = reinterpret_cast<float4*>(p.out_rgba), a.out_albedo_hits = reinterpret_cast<float4*>(p.out_albedo_hits);
-  launch_emission_split(nullptr, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_emission_split_device(int device, uint32_t width, uint32_t height, const float* d_rgba, const uint32_t* d_count,
-                                            const float* d_emission, const float* d_albedo_hits, const uint32_t* d_feature_count,
-                                            float* d_out_rgba, float* d_out_albedo_hits) {
-  return guarded([&]() -> int {
-    const EmissionSplitPtrs p{d_rgba, d_count, d_emission, d_albedo_hits, d_feature_count, d_out_rgba, d_out_albedo_hits};
-    if (int rc = check_emission_split(device, width, height, p)) return rc;
-    return emission_split_impl(device, width, height, p);
-  });
-}
-
-extern "C" int pbrhip_emission_split(int device, uint32_t width, uint32_t height, const float* rgba, const uint32_t* count, const float* emission,
-                                     const float* albedo_hits, const uint32_t* feature_count, float* out_rgba, float* out_albedo_hits) {
-  return guarded([&]() -> int {
-    const EmissionSplitPtrs h{rgba, count, emission, albedo_hits, feature_count, out_rgba, out_albedo_hits};
-    if (int rc = check_emission_split(device, width, height, h)) return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_f[3], d_or, d_oa;  // rgba, emission, albedo_hits
-    DevBuf<uint32_t> d_u[2];           // count, feature_count
-    const float* fs[3] = {rgba, emission, albedo_hits};
-    const uint32_t* us[2] = {count, feature_count};
-    for (int i = 0; i < 3; i++)
-      if (int rc = svgf_upload(d_f[i], fs[i], npx, 4)) return rc;
-    for (int i = 0; i < 2; i++)
-      if (int rc = svgf_upload(d_u[i], us[i], npx, 1)) return rc;
-    HIPCHK(d_or.reserve(npx * 4));
-    if (out_albedo_hits) HIPCHK(d_oa.reserve(npx * 4));
-    const EmissionSplitPtrs d{d_f[0].p, d_u[0].p, d_f[1].p, d_f[2].p, d_u[1].p, d_or.p, d_oa.p};
-    if (int rc = emission_split_impl(device, width, height, d)) return rc;
-    HIPCHK(hipMemcpy(out_rgba, d_or.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_albedo_hits) HIPCHK(hipMemcpy(out_albedo_hits, d_oa.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return PBRHIP_OK;
-  });
-}
-
-static int check_emission_merge(int device, uint32_t width, uint32_t height, const void* filtered, const void* emission, const void* count,
-                                const void* out_rgba) {
-  if (width == 0 || height == 0) return fail(PBRHIP_EINVAL, "emission_merge: empty image");
-  if ((uint64_t)width * height >= (1ull << 32)) return fail(PBRHIP_EINVAL, "emission_merge: image too large");
-  if (!filtered || !emission || !count || !out_rgba) return fail(PBRHIP_EINVAL, "emission_merge: NULL filtered_rgba, emission, count or out_rgba");
-  if (out_rgba == emission || out_rgba == count) return fail(PBRHIP_EINVAL, "emission_merge: out_rgba is an input other than filtered_rgba");
-  return check_svgf_device("emission_merge", device);
-}
-
-static int emission_merge_impl(int device, uint32_t width, uint32_t height, const float* filtered, const float* emission, const uint32_t* count,
-                               float* out_rgba) {
-  HIPCHK(hipSetDevice(device));
-  EmissionMergeArgs a{};
-  a.npx = (size_t)width * height;
-  a.filtered = reinterpret_cast<const float4*>(filtered), a.emission = reinterpret_cast<const float4*>(emission), a.count = count;
-  a.out = reinterpret_cast<float4*>(out_rgba);
-  launch_emission_merge(nullptr, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return PBRHIP_OK;
-}
-
-extern "C" int pbrhip_emission_merge_device(int device, uint32_t width, uint32_t height, const float* d_filtered_rgba, const float* d_emission,
-                                            const uint32_t* d_count, float* d_out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_emission_merge(device, width, height, d_filtered_rgba, d_emission, d_count, d_out_rgba)) return rc;
-    return emission_merge_impl(device, width, height, d_filtered_rgba, d_emission, d_count, d_out_rgba);
-  });
-}
-
-extern "C" int pbrhip_emission_merge(int device, uint32_t width, uint32_t height, const float* filtered_rgba, const float* emission,
-                                     const uint32_t* count, float* out_rgba) {
-  return guarded([&]() -> int {
-    if (int rc = check_emission_merge(device, width, height, filtered_rgba, emission, count, out_rgba)) return rc;
-    HIPCHK(hipSetDevice(device));
-    const size_t npx = (size_t)width * height;
-    DevBuf<float> d_f[2], d_out;  // filtered_rgba, emission
-    DevBuf<uint32_t> d_c;
-    const float* fs[2] = {filtered_rgba, emission};
-    for (int i = 0; i < 2; i++)
-      if (int rc = svgf_upload(d_f[i], fs[i], npx, 4)) return rc;
-    if (int rc = svgf_upload(d_c, count, npx, 1)) return rc;
-    HIPCHK(d_out.reserve(npx * 4));
-    if (int rc = emission_merge_impl(device, width, height, d_f[0].p, d_f[1].p, d_c.p, d_out.p)) return rc;
-    HIPCHK(hipMemcpy(out_rgba, d_out.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PBRHIP_OK;
   });
 }

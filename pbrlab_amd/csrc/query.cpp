@@ -29,32 +29,7 @@ static int check_state(const pbrhip_scene* s, size_t n) {
   PB_NOT_STALE(s);
   return n ? PBRHIP_OK : 1;
 }
-// the caller's array is read only after what its stream already holds (pbrhip_scene_object_ids_device's rule): an event there, and the
-// scene's stream waits for it
-static int wait_for_caller_stream(pbrhip_scene* s, void* stream) {
-  hipEvent_t ev;
-  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
-  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
-  (void)hipEventDestroy(ev);
-  HIPCHK(e);
-  return PBRHIP_OK;
-}
-// zeroed counters (queue head, overflow flag) and the spill area, on the scene's stream
-static int prepare_traversal(pbrhip_scene* s) {
-  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
-  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
-  HIPCHK(s->spill.reserve(kSpillWords));
-  return PBRHIP_OK;
-}
-// the end of every query: the counters come back, the stream drains, an overflow is reported
-static int finish_traversal(pbrhip_scene* s) {
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
-  return PBRHIP_OK;
-}
+// (wait_for_caller_stream in front of a caller's device array, prepare_traversal and finish_traversal around the launch: scene_impl.h)
 
 // ------------------------------------------------------------------ ray queries on device memory
 static int ray_query_device(const char* who, pbrhip_scene* s, const void* d_rays, size_t n, void* stream, uint32_t* d_ident, pbrhip_hit* d_hits,

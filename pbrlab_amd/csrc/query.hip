@@ -18,6 +18,7 @@
 #include "dtrace_pv.h"
 #include "feature_kernels.h"
 #include "query_kernels.h"
+#include "variants.h"
 
 namespace pb {
 
@@ -297,24 +298,15 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_query_nearest(D
 }
 
 // ------------------------------------------------------------------ launches
-// the <CURVES, WIDE> of the tree the render of this scene walks (kernels.hip::launch_trace): PBRHIP_WIDE=0 selects the binary tree
-template <class F>
-static inline void with_render_tree(F&& f, const DScene& sc, const Knobs& k) {
-  const bool wide = sc.wide != nullptr && k.wide, curves = sc.num_curves != 0;
-  if (wide && curves) f(std::true_type{}, std::true_type{});
-  else if (wide) f(std::false_type{}, std::true_type{});
-  else if (curves) f(std::true_type{}, std::false_type{});
-  else f(std::false_type{}, std::false_type{});
-}
+// the <CURVES, WIDE> of the tree the render of this scene walks (kernels.hip::launch_trace): PBRHIP_WIDE=0 selects the binary tree, and
+// unlike the hooks' a binary tree without curves has an instance without the curve code: all four combinations (variants.h::with_flags)
 
 void launch_ray_query(hipStream_t s, const DScene& sc, const RayQueryArgs& a, const Knobs& k) {
   if (!a.n) return;
   uint32_t g = (a.n + kBlock - 1) / kBlock;
   g = g < kTraceGridCap ? g : kTraceGridCap;  // (k_hook_pv's grid: the spill area is sized by it)
-  with_render_tree([&](auto c, auto w) {
-    if (a.occ) hipLaunchKernelGGL((k_query_pv<true, c, w>), dim3(g), dim3(kBlock), 0, s, sc, a);
-    else hipLaunchKernelGGL((k_query_pv<false, c, w>), dim3(g), dim3(kBlock), 0, s, sc, a);
-  }, sc, k);
+  with_flags([&](auto any, auto c, auto w) { hipLaunchKernelGGL((k_query_pv<any, c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, a.occ != nullptr,
+             sc.num_curves != 0, use_wide(sc, k));
 }
 
 static_assert((size_t)(kStackDepth - kSimpleLdsStack) * kFeatureGridCap * kBlock <= kSpillWords, "k_query_nearest's spill area (one stack per thread of its grid)");
@@ -322,7 +314,7 @@ void launch_nearest(hipStream_t s, const DScene& sc, const NearestArgs& a, const
   if (!a.n) return;
   uint32_t g = (a.n + kBlock - 1) / kBlock;
   g = g < kFeatureGridCap ? g : kFeatureGridCap;
-  with_render_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_query_nearest<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc, k);
+  with_flags([&](auto c, auto w) { hipLaunchKernelGGL((k_query_nearest<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc.num_curves != 0, use_wide(sc, k));
 }
 
 }  // namespace pb

@@ -6,12 +6,10 @@
 // equidistant fisheye, orthographic), k_features_rays is the feature kernel (features.hip) over the same rays.
 // Streaming kernels: two 16-byte words per ray, grid-stride, no LDS but the feature kernel's stack, no scratch.
 // A translation unit of its own: the render kernels' code objects do not depend on it.
-#include <type_traits>
-
 #include "denv.h"
-#include "dshade.h"
-#include "feature_kernels.h"
+#include "dfirsthit.h"
 #include "rays_kernels.h"
+#include "variants.h"
 
 namespace pb {
 
@@ -107,49 +105,26 @@ __global__ __launch_bounds__(kBlock) void k_project_rays(ProjectArgs a) {
 }
 
 // ------------------------------------------------------------------ k_features_rays
-// k_features (features.hip) with the ray of (pixel, pass) loaded: the same one-ray-per-lane traversal and LDS stack, the same
-// pass-ordered sums; the traversal starts from the caller's tmin and tmax, an inactive ray counts as a miss.
+// k_features' walker (dfirsthit.h::first_hit_walk) with the ray of (pixel, pass) loaded: the same one-ray-per-lane traversal and LDS
+// stack, the same pass-ordered sums; the traversal starts from the caller's tmin and tmax, an inactive ray counts as a sample and a miss.
+struct ListRays {
+  const FeatureRayArgs& a;
+  struct Pixel {
+    const FeatureRayArgs& a;
+    uint32_t gpix;
+    __device__ __forceinline__ bool operator()(uint32_t pass, V3& o, V3& d, float& tmin, float& tmax) const {
+      const size_t w = ray_word(a.src, a.width, gpix, pass);
+      const float4 ro = a.src.rays[w], rd = a.src.rays[w + 1];
+      o = V3(ro.x, ro.y, ro.z), d = V3(rd.x, rd.y, rd.z), tmin = ro.w, tmax = rd.w;
+      return ray_active(ro, rd);
+    }
+  };
+  __device__ __forceinline__ Pixel operator()(uint32_t gpix) const { return {a, gpix}; }
+};
 template <bool CURVES, bool WIDE>
 __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_features_rays(DScene sc, FeatureRayArgs a) {
   __shared__ uint32_t stk[kSimpleLdsStack * kBlock];
-  TravStats st = {};
-  uint32_t overflow = 0u;
-  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.npix; j += gridDim.x * kBlock) {
-    const uint32_t gpix = a.pix[j];
-    float4 A = make_float4(0.f, 0.f, 0.f, 0.f), N = A;
-    uint32_t cnt = 0u;
-    if (a.albedo_hits) A = a.albedo_hits[gpix];
-    if (a.normal_depth) N = a.normal_depth[gpix];
-    if (a.count) cnt = a.count[gpix];
-    for (uint32_t pass = a.first_pass; pass != a.first_pass + a.npass; pass++) {
-      const size_t w = ray_word(a.src, a.width, gpix, pass);
-      const float4 ro = a.src.rays[w], rd = a.src.rays[w + 1];
-      cnt++;
-      if (!ray_active(ro, rd)) continue;
-      const V3 o(ro.x, ro.y, ro.z), d(rd.x, rd.y, rd.z);
-      Hit h;
-      traverse<false, false, CURVES, WIDE>(sc, o, d, ro.w, rd.w, h, stk + threadIdx.x, kBlock, st, &overflow,
-                                           a.spill + blockIdx.x * kBlock + threadIdx.x, gridDim.x * kBlock);
-      if (h.slot == kNone) continue;
-      const Surface s = make_surface(sc, o, d, h);
-      V3 n = s.n_s;
-      if (!(s.flags & kSlotIsCurve) && dot(d, n) > 0.0f) n = -n;  // towards the viewer; a curve's tangent stays as it is
-      N.x += n.x, N.y += n.y, N.z += n.z, N.w += h.t;
-      if (a.albedo_hits) {
-        V3 c(0.0f);
-        if (s.material != kNone) {
-          const float4 m = a.mat_albedo[s.material];
-          const uint32_t tex = __float_as_uint(m.w);
-          c = tex != kNone ? texture_fetch3(sc, tex, s.tu, s.tv) : V3(m.x, m.y, m.z);
-        }
-        A.x += c.x, A.y += c.y, A.z += c.z, A.w += 1.0f;
-      }
-    }
-    if (a.albedo_hits) a.albedo_hits[gpix] = A;
-    if (a.normal_depth) a.normal_depth[gpix] = N;
-    if (a.count) a.count[gpix] = cnt;
-  }
-  if (overflow) *a.overflow = 1u;
+  first_hit_walk<CURVES, WIDE, false>(sc, a, nullptr, stk, ListRays{a});
 }
 
 // ------------------------------------------------------------------ launches
@@ -172,10 +147,7 @@ void launch_project_rays(hipStream_t s, const ProjectArgs& a) {
 void launch_features_rays(hipStream_t s, const DScene& sc, const FeatureRayArgs& a, const Knobs& k) {
   if (!a.npix || !a.npass) return;
   const uint32_t g = grid_for(a.npix, kFeatureGridCap);
-  const bool wide = sc.wide != nullptr && k.wide;
-  if (!wide) hipLaunchKernelGGL((k_features_rays<true, false>), dim3(g), dim3(kBlock), 0, s, sc, a);
-  else if (sc.num_curves != 0) hipLaunchKernelGGL((k_features_rays<true, true>), dim3(g), dim3(kBlock), 0, s, sc, a);
-  else hipLaunchKernelGGL((k_features_rays<false, true>), dim3(g), dim3(kBlock), 0, s, sc, a);
+  with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_features_rays<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc, k);
 }
 
 }  // namespace pb

@@ -321,4 +321,36 @@ Camera make_camera(const pbrhip_scene* s, uint32_t width, uint32_t height);
 PoseCamera pose_camera(const pbrhip_scene* s);
 UserCamera make_user_camera(const PoseCamera& c, uint32_t width, uint32_t height);
 Camera make_camera(const PoseCamera& c, uint32_t width, uint32_t height);
+// what every call on a render descriptor checks first: the scene's state, the image's size, the shard (pbrhip.cpp)
+int check_render_desc(const pbrhip_scene* s, const pbrhip_render_desc* d);
+// what the ray-list entry points check before anything touches a device: pointers, then the shape of the ray buffer, then the scene
+int check_ray_args(const char* who, const pbrhip_scene* s, const pbrhip_render_desc* d, const void* rays, uint32_t ray_passes, uint32_t camera_draws);
+
+// A caller's device array is read only after what its stream already holds (pbrhip_scene_update_triangle_mesh_device's rule): an event
+// there, and the scene's stream -- behind which every path group starts -- waits for it
+inline int wait_for_caller_stream(pbrhip_scene* s, void* stream) {
+  hipEvent_t ev;
+  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
+  (void)hipEventDestroy(ev);
+  HIPCHK(e);
+  return PBRHIP_OK;
+}
+// In front of a one-ray-per-lane traversal outside the render loop (feature passes, motion, queries): zeroed counters (queue head,
+// overflow flag) and the spill area, on the scene's stream
+inline int prepare_traversal(pbrhip_scene* s) {
+  HIPCHK(s->counts.reserve(kCntNum * kMaxGroups));
+  HIPCHK(hipMemsetAsync(s->counts.p, 0, sizeof(uint32_t) * kCntNum, s->stream));
+  HIPCHK(s->spill.reserve(kSpillWords));
+  return PBRHIP_OK;
+}
+// ... and behind it: the counters come back, the stream drains, an overflow is reported
+inline int finish_traversal(pbrhip_scene* s) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s->h_counts, s->counts.p, sizeof(uint32_t) * kCntNum, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (s->h_counts[kCntOverflow]) return fail(PBRHIP_EOVERFLOW, "BVH traversal stack overflow");
+  return PBRHIP_OK;
+}
 }  // namespace pb

@@ -12,6 +12,7 @@
 #include "dshade.h"
 #include "feature_kernels.h"
 #include "temporal_kernels.h"
+#include "variants.h"
 
 namespace pb {
 
@@ -69,10 +70,7 @@ void launch_motion(hipStream_t s, const DScene& sc, const MotionArgs& a, const K
   if (!a.npix) return;
   uint32_t g = (a.npix + kBlock - 1) / kBlock;
   g = g < kFeatureGridCap ? g : kFeatureGridCap;
-  const bool wide = sc.wide != nullptr && k.wide;
-  if (!wide) hipLaunchKernelGGL((k_motion<true, false>), dim3(g), dim3(kBlock), 0, s, sc, a);
-  else if (sc.num_curves != 0) hipLaunchKernelGGL((k_motion<true, true>), dim3(g), dim3(kBlock), 0, s, sc, a);
-  else hipLaunchKernelGGL((k_motion<false, true>), dim3(g), dim3(kBlock), 0, s, sc, a);
+  with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_motion<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc, k);
 }
 
 // ------------------------------------------------------------------ k_temporal
