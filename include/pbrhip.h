@@ -682,13 +682,60 @@ int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* s
  *     squared distance exceeds the best D2 cannot skip the answer, and the result is a property of (point, primitive set) alone: it does
  *     not depend on builder, tree, refit or visiting order.
  * The device variant orders the read of d_points behind `stream` as above.  Errors as the ray queries'.
- * Not provided: signed distance, the ribbon's radius, k-nearest and all-hits queries, a multi-GPU twin, asynchronous return. */
+ * Not provided: the ribbon's radius, k-nearest and all-hits queries, a multi-GPU twin, asynchronous return.  (Signed distance: below.) */
 typedef struct {
   float p[3];
   float max_dist;
 } pbrhip_point; /* 16 bytes */
 int pbrhip_nearest_point(pbrhip_scene*, const pbrhip_point* points, size_t n, uint32_t* ident, float* closest);
 int pbrhip_nearest_point_device(pbrhip_scene*, const void* d_points, size_t n, void* stream, uint32_t* d_ident, float* d_closest);
+
+/* ---- signed distance ----
+ * "How far is the nearest surface, and on which side of it am I": the nearest-point query above with a sign.  ident and closest are
+ * pbrhip_nearest_point_device's, byte for byte, on the same points; the sign comes from the angle-weighted pseudonormal (Baerentzen &
+ * Aanaes 2005) of the FEATURE of the nearest triangle the closest point lies on:
+ *   the winning segment ab, bc or ca with 0 < t < 1: that edge; with its clamped t at 0 or 1 (a segment without length has t = 0): the
+ *   vertex at that end; the plane term: the face.
+ *   sd       4 floats per query: the feature's pseudonormal N, then the signed distance: sqrtf(D2) when dot(p - q, N) >= 0, -sqrtf(D2)
+ *            when it is < 0.  Outside is positive.  A curve piece has no normal: N = 0, a positive distance.  A miss or an inactive
+ *            query: zeros (ident and closest as above).
+ * Pseudonormals.  A face's unit normal is n / sqrtf(dot(n, n)), n = cross(b - a, c - a) of the world-space corners in the order the
+ * mesh indexes them; a face whose dot(n, n) is not > 0 contributes nothing.  An edge's: the sum of the unit normals of the faces of the
+ * same object that have it; a vertex's: the sum of (corner angle x unit normal) over the faces of the same object at it, the angle
+ * atan2(|e1 x e2|, e1 . e2) between the face's two edges there; both sums in ascending canonical primitive id, normalised, or zero if
+ * their length is not > 0.  float32, every operation rounded once: the table depends on the model alone, not on builder or tree.
+ * Vertex identity: two corners are the same vertex when they belong to the same object -- the same instance and geometry -- and carry
+ * the same entry of the mesh's vertex_ids.  Equal positions under different indices are NOT welded: a mesh that duplicates its vertices
+ * along a seam has boundary edges there.  Since normals are taken from world-space corners, an instance whose transform mirrors
+ * (negative determinant) is inside-out: its signs are flipped.
+ * The sign is a guarantee only where the nearest object is a closed, consistently oriented manifold; pbrhip_sd_info reports what the
+ * scene has.  An open mesh still works: a boundary edge carries its one face's normal.
+ * The table is built on the device at the first of these calls after a commit or a refit; a scene that never calls them allocates and
+ * launches nothing for it.  A replica (pbrhip_scene_replicate) holds no geometry: PBRHIP_ESTATE.
+ * Stream ordering, the 16-byte alignment of d_points, d_ident, d_closest and d_sd, refusals and error codes: pbrhip_nearest_point_device's.
+ * Any of the three outputs may be NULL, not all.
+ * Grid: the same query at p = origin + (float)(i, j, k) * spacing (multiply, then add, each rounded once) for i < dims[0], j < dims[1],
+ * k < dims[2], all with max_dist; d_sd: dims[2] x dims[1] x dims[0] floats (x fastest; 4-byte aligned), the signed distance alone, 0
+ * where nothing lies within max_dist.  A dims of 0: PBRHIP_OK and nothing written; 2^31 points or more: PBRHIP_EINVAL.
+ * Not provided: the generalized winding number as a sign method, welding by position, the ribbon's radius, k-nearest, a multi-GPU twin. */
+typedef struct {
+  uint32_t triangles;           /* triangle slots of the scene */
+  uint32_t vertices;            /* distinct (object, index) vertices they use */
+  uint32_t edges_manifold;      /* exactly two faces, running along the edge in opposite directions */
+  uint32_t edges_boundary;      /* one face */
+  uint32_t edges_nonmanifold;   /* three or more faces */
+  uint32_t edges_inconsistent;  /* two faces running along the edge in the same direction */
+  uint64_t table_bytes;         /* device memory of the table and its lists */
+  double topology_ms, table_ms; /* host time of the lists (once per commit); device time of the last table build */
+} pbrhip_sd_info;
+int pbrhip_scene_signed_distance_info(pbrhip_scene*, pbrhip_sd_info* out);
+int pbrhip_signed_distance(pbrhip_scene*, const pbrhip_point* points, size_t n, uint32_t* ident, float* closest, float* sd);
+int pbrhip_signed_distance_device(pbrhip_scene*, const void* d_points, size_t n, void* stream, uint32_t* d_ident, float* d_closest, float* d_sd);
+int pbrhip_signed_distance_grid_device(pbrhip_scene*, const float origin[3], const float spacing[3], const uint32_t dims[3], float max_dist,
+                                       void* stream, float* d_sd);
+/* test hook: the table as the device holds it.  Per slot seven rows of four floats -- ab, bc, ca, a, b, c, face; xyz and 0 --, zeros for
+ * a curve slot; out: *num_slots x 28 floats (NULL: only the count).  Builds the table if needed. */
+int pbrhip_scene_read_pseudonormals(pbrhip_scene*, float* out, uint32_t* num_slots);
 
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks

@@ -410,6 +410,29 @@ public:
   void NearestPointDevice(const void* d_points, size_t n, uint32_t* d_ident, float* d_closest, void* stream = nullptr) const {
     Check(pbrhip_nearest_point_device(h_, d_points, n, stream, d_ident, d_closest));
   }
+  // Signed distance (include/pbrhip.h, "signed distance"): the nearest-point queries with a sign.  sd: 4 floats per query, the winning
+  // feature's pseudonormal and the signed distance (outside positive); any of the three outputs may be null.  The grid variant asks at
+  // origin + (i, j, k) * spacing and writes dims[2] x dims[1] x dims[0] floats, the signed distance alone.  SignedDistanceInfo builds
+  // the pseudonormal table if it has to and reports the scene's topology.
+  void SignedDistance(const std::vector<pbrhip_point>& points, std::vector<uint32_t>* ident, std::vector<float>* closest, std::vector<float>* sd) const {
+    if (ident) ident->assign(4 * points.size(), 0u);
+    if (closest) closest->assign(4 * points.size(), 0.0f);
+    if (sd) sd->assign(4 * points.size(), 0.0f);
+    Check(pbrhip_signed_distance(h_, points.data(), points.size(), ident ? ident->data() : nullptr, closest ? closest->data() : nullptr,
+                                 sd ? sd->data() : nullptr));
+  }
+  void SignedDistanceDevice(const void* d_points, size_t n, uint32_t* d_ident, float* d_closest, float* d_sd, void* stream = nullptr) const {
+    Check(pbrhip_signed_distance_device(h_, d_points, n, stream, d_ident, d_closest, d_sd));
+  }
+  void SignedDistanceGridDevice(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_dist, float* d_sd,
+                                void* stream = nullptr) const {
+    Check(pbrhip_signed_distance_grid_device(h_, origin, spacing, dims, max_dist, stream, d_sd));
+  }
+  pbrhip_sd_info SignedDistanceInfo() const {
+    pbrhip_sd_info info;
+    Check(pbrhip_scene_signed_distance_info(h_, &info));
+    return info;
+  }
   // which builder CommitScene uses (pbrhip_scene_set_bvh_builder; the reference has Embree's only); before CommitScene
   enum BvhBuilder { kBvhHostSah = PBRHIP_BVH_HOST_SAH, kBvhGpuLbvh = PBRHIP_BVH_GPU_LBVH, kBvhGpuLbvhWide = PBRHIP_BVH_GPU_LBVH_WIDE };
   void SetBvhBuilder(BvhBuilder b) { Check(pbrhip_scene_set_bvh_builder(h_, static_cast<int>(b))); }

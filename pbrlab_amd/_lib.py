@@ -36,6 +36,8 @@ EXPORTS = [
     "pbrhip_render_features_emission", "pbrhip_render_features_emission_device", "pbrhip_emission_split", "pbrhip_emission_split_device",
     "pbrhip_emission_merge", "pbrhip_emission_merge_device",
     "pbrhip_trace_closest_device", "pbrhip_trace_any_device", "pbrhip_nearest_point", "pbrhip_nearest_point_device",
+    "pbrhip_scene_signed_distance_info", "pbrhip_signed_distance", "pbrhip_signed_distance_device", "pbrhip_signed_distance_grid_device",
+    "pbrhip_scene_read_pseudonormals",
 ]
 
 
@@ -94,6 +96,11 @@ def lib():
         _lib.pbrhip_emission_merge.argtypes = _lib.pbrhip_emission_merge_device.argtypes = [C.c_int, u32, u32] + [vp] * 4
         _lib.pbrhip_trace_closest_device.argtypes = _lib.pbrhip_nearest_point_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         _lib.pbrhip_trace_any_device.argtypes = _lib.pbrhip_nearest_point.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        _lib.pbrhip_scene_signed_distance_info.argtypes = [vp, vp]
+        _lib.pbrhip_signed_distance.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        _lib.pbrhip_signed_distance_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp]
+        _lib.pbrhip_signed_distance_grid_device.argtypes = [vp, vp, vp, vp, f32, vp, vp]
+        _lib.pbrhip_scene_read_pseudonormals.argtypes = [vp, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

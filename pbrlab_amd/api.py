@@ -64,6 +64,11 @@ class RenderStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SdInfo(C.Structure):  # pbrhip_sd_info
+    _fields_ = ([(n, C.c_uint32) for n in ("triangles", "vertices", "edges_manifold", "edges_boundary", "edges_nonmanifold", "edges_inconsistent")] +
+                [("table_bytes", C.c_uint64), ("topology_ms", C.c_double), ("table_ms", C.c_double)])
+
+
 RAY_DT = np.dtype([("org", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])
 HIT_DT = np.dtype([("normal_g", "<f4", 3), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
                    ("instance_id", "<u4"), ("geom_id", "<u4"), ("prim_id", "<u4")])
@@ -642,6 +647,81 @@ class Scene:
         pi, pc = _query_out(ident, self, (n, 4), "int32", "ident"), _query_out(closest, self, (n, 4), "float32", "closest")
         _chk(self.L.pbrhip_nearest_point_device(self.h, ptr, n, _device_stream(stream, points), pi, pc))
         return ident, closest
+
+    # signed distance
+    def SignedDistance(self, points):
+        """pbrhip_signed_distance: NearestPoint with a sign -> (ident, closest, sd).  points, ident and closest as NearestPoint's (and
+        equal to them); sd: (n, 4) float32 = the pseudonormal N of the feature of the nearest triangle the closest point lies on, then the
+        signed distance: sqrt(D2) outside (dot(p - q, N) >= 0), -sqrt(D2) inside; a curve piece: N = 0 and a positive distance; a miss:
+        zeros.  Anything else than records or (n, 4) rows: ValueError, before any C call."""
+        points = np.asarray(points)
+        if points.dtype.names:
+            pts = np.ascontiguousarray(points, POINT_DT).reshape(-1)
+        elif points.ndim == 2 and points.shape[1] == 4:
+            pts = np.ascontiguousarray(points, np.float32)
+        else:
+            raise ValueError(f"points must be POINT_DT records or have the shape (n, 4), not {points.shape}")
+        n = len(pts)
+        ident, closest, sd = np.zeros((n, 4), np.uint32), np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+        _chk(self.L.pbrhip_signed_distance(self.h, C.c_void_p(pts.ctypes.data), n, C.c_void_p(ident.ctypes.data), C.c_void_p(closest.ctypes.data),
+                                           C.c_void_p(sd.ctypes.data)))
+        return ident, closest, sd
+
+    def SignedDistanceDevice(self, points, ident=None, closest=None, sd=None, stream=None):
+        """pbrhip_signed_distance_device: SignedDistance for n points in memory of the scene's GPU -> (ident, closest, sd).  points: a
+        float32, contiguous (n, 4) tensor or a (pointer, n) pair; ident: (n, 4) int32, closest and sd: (n, 4) float32, tensors or device
+        pointers written in place; with tensor points and none given all three are allocated; one that is not given otherwise is not
+        computed (None).  stream as NearestPointDevice's.  Device pointers must be 16-byte aligned (the library refuses others)."""
+        ptr, n = _query_array(points, self, 4, "points")
+        if ident is None and closest is None and sd is None and hasattr(points, "data_ptr"):
+            import torch
+            ident = torch.empty((n, 4), dtype=torch.int32, device=points.device)
+            closest, sd = (torch.empty((n, 4), dtype=torch.float32, device=points.device) for _ in range(2))
+        pi, pc = _query_out(ident, self, (n, 4), "int32", "ident"), _query_out(closest, self, (n, 4), "float32", "closest")
+        ps = _query_out(sd, self, (n, 4), "float32", "sd")
+        _chk(self.L.pbrhip_signed_distance_device(self.h, ptr, n, _device_stream(stream, points), pi, pc, ps))
+        return ident, closest, sd
+
+    def SignedDistanceGridDevice(self, origin, spacing, dims, max_dist=float("inf"), out=None, stream=None):
+        """pbrhip_signed_distance_grid_device: the signed distance at origin + (i, j, k) * spacing for i < dims[0], j < dims[1],
+        k < dims[2] -> out, a float32 (dims[2], dims[1], dims[0]) tensor on the scene's GPU (x fastest: what
+        torch.nn.functional.grid_sample takes as a volume) or a device pointer, written in place; allocated with torch when none is given.
+        0 where nothing lies within max_dist.  origin, spacing: three floats; dims: three integers >= 0, fewer than 2^31 points in all --
+        checked here, before any C call."""
+        o, sp = np.ascontiguousarray(origin, np.float32).reshape(-1), np.ascontiguousarray(spacing, np.float32).reshape(-1)
+        if o.shape != (3,) or sp.shape != (3,) or len(dims) != 3:
+            raise ValueError("origin, spacing and dims have three components each")
+        if any(int(d) != d or d < 0 for d in dims):
+            raise ValueError(f"dims must be three integers >= 0, not {tuple(dims)}")
+        dm = np.array([int(d) for d in dims], np.uint64)
+        if int(dm[0]) * int(dm[1]) * int(dm[2]) >= 1 << 31:
+            raise ValueError("a grid has fewer than 2^31 points")
+        dm = dm.astype(np.uint32)
+        shape = (int(dm[2]), int(dm[1]), int(dm[0]))
+        if out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.device}")
+        po = _query_out(out, self, shape, "float32", "out")
+        _chk(self.L.pbrhip_signed_distance_grid_device(self.h, C.c_void_p(o.ctypes.data), C.c_void_p(sp.ctypes.data), C.c_void_p(dm.ctypes.data),
+                                                       float(max_dist), _device_stream(stream, out), po))
+        return out
+
+    def SignedDistanceInfo(self):
+        """pbrhip_scene_signed_distance_info: builds the pseudonormal table if it has to -> dict(triangles, vertices, edges_manifold,
+        edges_boundary, edges_nonmanifold, edges_inconsistent, table_bytes, topology_ms, table_ms).  The sign is a guarantee only where the
+        nearest object has no boundary, non-manifold or inconsistently oriented edge."""
+        info = SdInfo()
+        _chk(self.L.pbrhip_scene_signed_distance_info(self.h, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def read_pseudonormals(self):
+        """pbrhip_scene_read_pseudonormals, a test hook: the pseudonormal table as the device holds it, (n, 7, 4) float32 in slot order:
+        rows ab, bc, ca, a, b, c, face (xyz, 0); zeros for a curve slot"""
+        n = C.c_uint32()
+        _chk(self.L.pbrhip_scene_read_pseudonormals(self.h, None, C.byref(n)))
+        out = np.zeros((n.value, 7, 4), np.float32)
+        _chk(self.L.pbrhip_scene_read_pseudonormals(self.h, out.ctypes.data, C.byref(n)))
+        return out
 
 
 def Render(scene, width, height, num_sample, cancel_render_flag=None, layer=None, finish_pass=None, *,

@@ -558,6 +558,7 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   // what pbrhip_scene_refit needs of this commit; the device scene is the model's again
   s->slot_gid = std::move(cs.bvh.slot_gid);
   s->rf_plan.release();
+  s->sdf.drop();  // (slot order and topology may have changed)
   s->dirty_inst.assign(s->instances.size(), 0), s->stale = false;
   s->committed = true;
   return PBRHIP_OK;
@@ -816,6 +817,7 @@ extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
   if (s->replica) return fail(PBRHIP_ESTATE, "scene_refit: a replica holds no geometry (refit the source scene and replicate it again)");
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
   if (!s->stale) return PBRHIP_OK;
+  s->sdf.table_valid = false;  // the slots are about to change: the pseudonormal table is made again when it is next asked for
   const Knobs k = read_knobs();
   HIPCHK(hipSetDevice(s->device));
   hipStream_t st = s->stream;

@@ -1,5 +1,6 @@
 // query.cpp -- the query entry points of the C ABI: ray queries on device memory and nearest-point queries, host and
 // device variants.  Host C++ only; the kernels are query.hip's.
+#include "query_checks.h"
 #include "query_kernels.h"
 #include "scene_impl.h"
 
@@ -9,27 +10,8 @@ static_assert(sizeof(pbrhip_hit) == sizeof(HookHit), "hit layout");
 static_assert(sizeof(pbrhip_ray) == 32, "ray layout");
 static_assert(sizeof(pbrhip_point) == 16, "point layout");
 
-// what every query checks before anything touches a device or the scene: pointers, then the count
-static int check_query(const char* who, const pbrhip_scene* s, const void* in, size_t n, const void* out_a, const void* out_b) {
-  if (!s) return fail(PBRHIP_EINVAL, "%s: NULL scene", who);
-  if (n && !in) return fail(PBRHIP_EINVAL, "%s: NULL input array", who);
-  if (n && !out_a && !out_b) return fail(PBRHIP_EINVAL, "%s: NULL output", who);
-  if (n >= (1ull << 31)) return fail(PBRHIP_EINVAL, "%s: too many queries (%zu; fewer than 2^31)", who, n);
-  return PBRHIP_OK;
-}
-// the kernels move 16 bytes at a time: a device pointer that is not 16-byte aligned is refused (null: not wanted)
-static int check_aligned(const char* who, const void* a, const void* b, const void* c) {
-  for (const void* p : {a, b, c})
-    if (reinterpret_cast<uintptr_t>(p) & 15u) return fail(PBRHIP_EINVAL, "%s: a device pointer is not 16-byte aligned", who);
-  return PBRHIP_OK;
-}
-// ... then the scene's state.  Returns 1 for "nothing to do" (n == 0 on a scene that could answer).
-static int check_state(const pbrhip_scene* s, size_t n) {
-  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
-  PB_NOT_STALE(s);
-  return n ? PBRHIP_OK : 1;
-}
-// (wait_for_caller_stream in front of a caller's device array, prepare_traversal and finish_traversal around the launch: scene_impl.h)
+// (what every query checks before anything touches a device or the scene -- check_query, check_aligned, check_state --: query_checks.h;
+// wait_for_caller_stream in front of a caller's device array, prepare_traversal and finish_traversal around the launch: scene_impl.h)
 
 // ------------------------------------------------------------------ ray queries on device memory
 static int ray_query_device(const char* who, pbrhip_scene* s, const void* d_rays, size_t n, void* stream, uint32_t* d_ident, pbrhip_hit* d_hits,

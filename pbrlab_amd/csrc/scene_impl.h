@@ -175,6 +175,19 @@ struct PoseCamera {
   float vfov = 30.0f, lens = 0.0f, focus = 0.0f;
   float bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
 };
+// What the signed-distance queries keep (sdf.cpp): sdf_topology.h's lists on the device -- built at the first signed
+// call after a commit, because topology is fixed across refits -- and the pseudonormal table, built lazily from the slots as they are
+// and invalidated by a refit.  A commit drops all of it.  A scene that never asks for signed distance holds empty buffers here.
+struct SdfState {
+  bool topology = false, table_valid = false;
+  DevBuf<uint32_t> slot_feat, feat_off, feat_items;
+  DevBuf<float4> faces, table;  // 2 and kSdfRows words per slot
+  pbrhip_sd_info info = {};
+  void drop() {
+    topology = table_valid = false, info = pbrhip_sd_info{};
+    slot_feat.release(), feat_off.release(), feat_items.release(), faces.release(), table.release();
+  }
+};
 inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
   return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
 }
@@ -215,6 +228,7 @@ struct pbrhip_scene {
   pb::RefitPlan rf_plan;            // built at the first refit of a committed tree, dropped by the next commit
   pb::DevBuf<float4> rf_packed;     // the dirty slots' upload: index | 64 B | 128 B (refit_gpu.hip::k_rf_scatter)
   pb::DevGeom dg;                   // device geometry mode (off, and empty, unless a *_mesh_device update switched it on)
+  pb::SdfState sdf;                 // the signed-distance queries' lists and table (empty unless one was asked)
   // device scene
   pb::TreeBufs tree;
   pb::DevBuf<pb::ShadeRec> d_shade;
