@@ -682,7 +682,8 @@ int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* s
  *     squared distance exceeds the best D2 cannot skip the answer, and the result is a property of (point, primitive set) alone: it does
  *     not depend on builder, tree, refit or visiting order.
  * The device variant orders the read of d_points behind `stream` as above.  Errors as the ray queries'.
- * Not provided: the ribbon's radius, k-nearest and all-hits queries, a multi-GPU twin, asynchronous return.  (Signed distance: below.) */
+ * Not provided: the ribbon's radius, k-nearest queries, a multi-GPU twin, asynchronous return.  (Signed distance and all-hits ray queries:
+ * below.) */
 typedef struct {
   float p[3];
   float max_dist;
@@ -736,6 +737,43 @@ int pbrhip_signed_distance_grid_device(pbrhip_scene*, const float origin[3], con
 /* test hook: the table as the device holds it.  Per slot seven rows of four floats -- ab, bc, ca, a, b, c, face; xyz and 0 --, zeros for
  * a curve slot; out: *num_slots x 28 floats (NULL: only the count).  Builds the table if needed. */
 int pbrhip_scene_read_pseudonormals(pbrhip_scene*, float* out, uint32_t* num_slots);
+
+/* ---- all-hits ray queries ----
+ * "Everything this ray hits, in order": several returns per lidar beam, the thickness of material along a ray, an inside / outside test
+ * by crossing parity where the pseudonormal sign above is no guarantee, depth peeling in one launch.  Peeling with
+ * pbrhip_trace_closest_device -- K calls, tmin advanced to the last t -- costs K traversals and loses every hit but one wherever two
+ * primitives are hit at the same t (exact duplicates, coplanar overlaps); this query does not.
+ * A UNIT is what a leaf of the tree tests once: a triangle, or one of the four linear pieces of a curve's cubic.  A unit's hit is
+ * ACCEPTED exactly when the closest-hit traversal could accept it: the primitive test passes, tmin < t <= tmax, and t lies in the interval
+ * in which the ray crosses the unit's own box (the validation of the intersection contract) -- the same functions, the same
+ * operations, the same bits of t, u, v.  For a ray let H be the accepted hits of all units of the scene, ordered by the key
+ *   (t ascending; then the canonical primitive id -- (instance, geometry, primitive) order, what PBRHIP_ID_PRIMITIVE reports -- ascending;
+ *    then u ascending).
+ * Two pieces of one cubic share an id and can tie in t: they differ in u, the curve parameter.  Two hits equal in all three are the same
+ * record.  Outputs for ray i with max_hits = K:
+ *   count[i]          |H|: every accepted hit, NOT capped by K
+ *   ident[i * K + j]  4 words each, j < K: for j < min(|H|, K) the j-th hit of that order in pbrhip_trace_closest_device's identity format
+ *                     (slot, then the bits of u, v, t; a curve hit is named by its slot as there; pbrhip_scene_object_ids_device takes
+ *                     the n * K entries as they are); every remaining entry (PBRHIP_NONE, 0, 0, 0).
+ * So ident[i * K + 0] equals pbrhip_trace_closest_device's d_ident[i] byte for byte, for every ray and every K >= 1, and the result is a
+ * property of (ray, primitive set) alone: it does not depend on builder, tree (PBRHIP_WIDE=0 / 1), refit or visiting order.  An inactive
+ * ray (the ray queries' rule above: a NaN among its eight numbers, an infinite origin or direction component, a zero direction, tmin < 0
+ * or !(tmax >= tmin)) has count 0 and a row of misses, with no fault.
+ * max_hits is in [0, PBRHIP_ALL_HITS_MAX].  Either output may be NULL, not both: max_hits == 0 requires count and ignores ident;
+ * max_hits > 0 with ident == NULL is a pure count as well.  With count the traversal enters every box the ray crosses in [tmin, tmax];
+ * without it the interval shrinks to the K-th hit once the list is full (K = 1: the closest-hit traversal), so ask for the count only
+ * when it is wanted.  The list is kept in the ray's row of ident while the kernel runs.
+ * Stream ordering, the 16-byte alignment of d_rays and d_ident (d_count: 4 bytes), refusals and error codes are
+ * pbrhip_trace_closest_device's: PBRHIP_EINVAL before any device work for a NULL scene, with n > 0 NULL rays or no usable output
+ * ("NULL" in pbrhip_last_error), max_hits > PBRHIP_ALL_HITS_MAX, n >= 2^31 or n * max_hits >= 2^31 ("too many"); PBRHIP_ESTATE: an
+ * uncommitted or stale scene; PBRHIP_EOVERFLOW: a traversal stack overflow; n == 0: PBRHIP_OK.  The host variant stages rays and outputs
+ * through device memory as pbrhip_nearest_point does.
+ * Not provided: more than PBRHIP_ALL_HITS_MAX listed hits per ray (count says how many there are; peel on from the last t), any-hit
+ * filters or callbacks, k-nearest points, a multi-GPU twin, asynchronous return. */
+#define PBRHIP_ALL_HITS_MAX 32u
+int pbrhip_trace_all(pbrhip_scene*, const pbrhip_ray* rays, size_t n, uint32_t max_hits, uint32_t* count, uint32_t* ident);
+int pbrhip_trace_all_device(pbrhip_scene*, const void* d_rays, size_t n, uint32_t max_hits, void* stream, uint32_t* d_count,
+                            uint32_t* d_ident);
 
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks

@@ -410,6 +410,19 @@ public:
   void NearestPointDevice(const void* d_points, size_t n, uint32_t* d_ident, float* d_closest, void* stream = nullptr) const {
     Check(pbrhip_nearest_point_device(h_, d_points, n, stream, d_ident, d_closest));
   }
+  // All-hits ray queries (include/pbrhip.h, "all-hits ray queries"): per ray the number of accepted hits in (tmin, tmax] -- count, not
+  // capped -- and the max_hits <= PBRHIP_ALL_HITS_MAX nearest of them, ordered by (t, canonical primitive id, u), in TraceClosestDevice's
+  // identity format -- ident, max_hits entries of 4 words per ray, (PBRHIP_NONE, 0, 0, 0) past the count.  Either output may be null, not
+  // both; max_hits == 0 asks for the count alone.  TraceAll takes host arrays (count resized to n, ident to 4 n max_hits), TraceAllDevice
+  // DEVICE pointers on the scene's GPU, read after the work already enqueued on `stream`.
+  void TraceAll(const std::vector<pbrhip_ray>& rays, uint32_t max_hits, std::vector<uint32_t>* count, std::vector<uint32_t>* ident) const {
+    if (count) count->assign(rays.size(), 0u);
+    if (ident) ident->assign(4 * rays.size() * max_hits, 0u);
+    Check(pbrhip_trace_all(h_, rays.data(), rays.size(), max_hits, count ? count->data() : nullptr, ident ? ident->data() : nullptr));
+  }
+  void TraceAllDevice(const void* d_rays, size_t n, uint32_t max_hits, uint32_t* d_count, uint32_t* d_ident, void* stream = nullptr) const {
+    Check(pbrhip_trace_all_device(h_, d_rays, n, max_hits, stream, d_count, d_ident));
+  }
   // Signed distance (include/pbrhip.h, "signed distance"): the nearest-point queries with a sign.  sd: 4 floats per query, the winning
   // feature's pseudonormal and the signed distance (outside positive); any of the three outputs may be null.  The grid variant asks at
   // origin + (i, j, k) * spacing and writes dims[2] x dims[1] x dims[0] floats, the signed distance alone.  SignedDistanceInfo builds

@@ -38,6 +38,7 @@ EXPORTS = [
     "pbrhip_trace_closest_device", "pbrhip_trace_any_device", "pbrhip_nearest_point", "pbrhip_nearest_point_device",
     "pbrhip_scene_signed_distance_info", "pbrhip_signed_distance", "pbrhip_signed_distance_device", "pbrhip_signed_distance_grid_device",
     "pbrhip_scene_read_pseudonormals",
+    "pbrhip_trace_all", "pbrhip_trace_all_device",
 ]
 
 
@@ -101,6 +102,8 @@ def lib():
         _lib.pbrhip_signed_distance_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp]
         _lib.pbrhip_signed_distance_grid_device.argtypes = [vp, vp, vp, vp, f32, vp, vp]
         _lib.pbrhip_scene_read_pseudonormals.argtypes = [vp, vp, vp]
+        _lib.pbrhip_trace_all.argtypes = [vp, vp, C.c_size_t, u32, vp, vp]
+        _lib.pbrhip_trace_all_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

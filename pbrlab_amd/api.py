@@ -142,6 +142,16 @@ def _query_out(a, scene, shape, dtype, what):
     return C.c_void_p(_image_arg(a, shape, dtype, what, getattr(scene, "device", None))[0])
 
 
+ALL_HITS_MAX = 32  # PBRHIP_ALL_HITS_MAX
+
+
+def _all_hits_k(max_hits):
+    """max_hits of an all-hits query as an int in [0, ALL_HITS_MAX]; ValueError here, before any C call"""
+    if isinstance(max_hits, bool) or int(max_hits) != max_hits or not 0 <= int(max_hits) <= ALL_HITS_MAX:
+        raise ValueError(f"max_hits must be an integer in [0, {ALL_HITS_MAX}], not {max_hits!r}")
+    return int(max_hits)
+
+
 def _device_stream(stream, *arrays):
     """The hipStream_t of a *Device update call: as given (an integer, or an object with cuda_stream); None: torch's current stream when
     an argument is a tensor (torch is then the caller's: this module does not import it otherwise), else the null stream."""
@@ -647,6 +657,52 @@ class Scene:
         pi, pc = _query_out(ident, self, (n, 4), "int32", "ident"), _query_out(closest, self, (n, 4), "float32", "closest")
         _chk(self.L.pbrhip_nearest_point_device(self.h, ptr, n, _device_stream(stream, points), pi, pc))
         return ident, closest
+
+    # all-hits ray queries
+    def TraceAll(self, rays, max_hits):
+        """pbrhip_trace_all: per ray the number of accepted hits in (tmin, tmax] and the max_hits nearest of them -> (count, ident).
+        rays: RAY_DT records or (n, 8) float32 rows org, tmin, dir, tmax (host memory).  count: (n,) uint32, every accepted hit, not
+        capped by max_hits; ident: (n, max_hits, 4) uint32, per ray the hits ordered by (t, canonical primitive id, u) as slot, bits of
+        u, v, t -- TraceClosestDevice's identity format, and ident[:, 0] equals its ident --, the entries past count (NONE, 0, 0, 0).
+        max_hits in [0, ALL_HITS_MAX].  Anything else than records or (n, 8) rows, or a max_hits outside that: ValueError, before any C
+        call."""
+        max_hits = _all_hits_k(max_hits)
+        rays = np.asarray(rays)
+        if rays.dtype.names:
+            r = np.ascontiguousarray(rays, RAY_DT).reshape(-1)
+        elif rays.ndim == 2 and rays.shape[1] == 8:
+            r = np.ascontiguousarray(rays, np.float32)
+        else:
+            raise ValueError(f"rays must be RAY_DT records or have the shape (n, 8), not {rays.shape}")
+        n = len(r)
+        count, ident = np.zeros(n, np.uint32), np.zeros((n, max_hits, 4), np.uint32)
+        _chk(self.L.pbrhip_trace_all(self.h, C.c_void_p(r.ctypes.data), n, max_hits, C.c_void_p(count.ctypes.data), C.c_void_p(ident.ctypes.data)))
+        return count, ident
+
+    def TraceAllDevice(self, rays, max_hits, count=True, ident=True, stream=None):
+        """pbrhip_trace_all_device: TraceAll for n rays in memory of the scene's GPU -> (count, ident).  rays and stream as
+        TraceClosestDevice's.  count: (n,) int32, ident: (n, max_hits, 4) int32 -- ObjectIds takes its (1, n * max_hits, 4) view --, each
+        True (allocated with torch; rays must be a tensor), a tensor or a device pointer (an int) written in place, or False / None: not
+        computed (returned as None).  With max_hits == 0 there is no ident.  Not both may be left out.  Without count the traversal stops
+        at the max_hits-th hit; with it every box the ray crosses is entered.  Device pointers of rays and ident must be 16-byte aligned."""
+        max_hits = _all_hits_k(max_hits)
+        ptr, n = _query_array(rays, self, 8, "rays")
+        count, ident = (None if a is False else a for a in (count, ident))
+        if max_hits == 0:
+            ident = None
+        if count is None and ident is None:
+            raise ValueError("TraceAllDevice: neither count nor ident is wanted" + (" (max_hits == 0 leaves the count)" if max_hits == 0 else ""))
+        if count is True or ident is True:
+            if not hasattr(rays, "data_ptr"):
+                raise TypeError("TraceAllDevice: outputs are allocated only beside tensor rays: pass tensors or device pointers")
+            import torch
+            if count is True:
+                count = torch.empty((n,), dtype=torch.int32, device=rays.device)
+            if ident is True:
+                ident = torch.empty((n, max_hits, 4), dtype=torch.int32, device=rays.device)
+        pc, pi = _query_out(count, self, (n,), "int32", "count"), _query_out(ident, self, (n, max_hits, 4), "int32", "ident")
+        _chk(self.L.pbrhip_trace_all_device(self.h, ptr, n, max_hits, _device_stream(stream, rays), pc, pi))
+        return count, ident
 
     # signed distance (DESIGN.md §20)
     def SignedDistance(self, points):
