@@ -673,7 +673,7 @@ int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* s
  * D2 is defined exactly, in float32 with every operation rounded once (DESIGN.md §19 has it operation by operation):
  *   segment (x, y): e = y - x, t = clamp(dot(p - x, e) / dot(e, e), 0, 1) (0 when dot(e, e) is not > 0), q = x + t e, |p - q|^2
  *   triangle (a, b, c): d2_raw = the minimum of the segments ab, bc, ca in that order (a strict < replaces) and, last and again by strict <,
- *     of the plane term (h h) / nn, n = cross(b - a, c - a), nn = dot(n, n), h = dot(p - a, n), which applies when nn > 0 and
+ *     of the plane term (h / nn) h, n = cross(b - a, c - a), nn = dot(n, n), h = dot(p - a, n), which applies when nn > 0 and
  *     dot(cross(y - x, p - x), n) >= 0 for the three edges; q = the closest point of the winning feature (the plane's: p - (h / nn) n);
  *     (u, v) = its barycentrics of b and c (ab: (t, 0); bc: (1 - t, t); ca: (0, 1 - t); plane: the ca and ab sign terms over nn)
  *   curve piece: the segment between its end points -- the centre line; the radius is ignored --, u = (sub + t) / 4, v = 0
@@ -681,6 +681,11 @@ int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* s
  *     with, widened the same way): every stored box of either tree contains that box, so a traversal that skips a box only when its own
  *     squared distance exceeds the best D2 cannot skip the answer, and the result is a property of (point, primitive set) alone: it does
  *     not depend on builder, tree, refit or visiting order.
+ * Domain: nn is fourth order in a triangle's edge length, so float32 bounds the scale of a scene.  The distance is within 9.08 units of
+ * 2^-24 (largest |coordinate| + distance) of its float64 value for edge length x query distance from about 1e-17 to 1e18 -- scenes whose
+ * triangles have edges of 0.3 s and whose queries lie up to 3 s away, s = 1e-8 .. 1e9 -- and at offsets up to 1e7, under anisotropic
+ * scales of 1e7 between axes and on flat scenes (measured: at most 5.10 units; DESIGN.md §19 "Domain").  A decade outside it nn
+ * underflows or overflows: the answer is still the contract's, bit for bit, but no longer the distance.
  * The device variant orders the read of d_points behind `stream` as above.  Errors as the ray queries'.
  * Not provided: the ribbon's radius, k-nearest queries, a multi-GPU twin, asynchronous return.  (Signed distance and all-hits ray queries:
  * below.) */
@@ -711,6 +716,9 @@ int pbrhip_nearest_point_device(pbrhip_scene*, const void* d_points, size_t n, v
  * (negative determinant) is inside-out: its signs are flipped.
  * The sign is a guarantee only where the nearest object is a closed, consistently oriented manifold; pbrhip_sd_info reports what the
  * scene has.  An open mesh still works: a boundary edge carries its one face's normal.
+ * Domain: pbrhip_nearest_point's (edge length x query distance from about 1e-17 to 1e18), which the table's own dot(n, n) shares: on closed
+ * shapes at the uniform scales 1e-8 .. 1e9 and at an offset of 1e4 the table stays within its rounding bound and the sign is the
+ * float64 winding number's at every point farther from the surface than the rounding of q (DESIGN.md §20 "Domain").
  * The table is built on the device at the first of these calls after a commit or a refit; a scene that never calls them allocates and
  * launches nothing for it.  A replica (pbrhip_scene_replicate) holds no geometry: PBRHIP_ESTATE.
  * Stream ordering, the 16-byte alignment of d_points, d_ident, d_closest and d_sd, refusals and error codes: pbrhip_nearest_point_device's.

@@ -101,12 +101,15 @@ struct Builder {
       return id;
     }
     uint32_t mid = first;
+    // a range whose box has no area -- segments of one axis-parallel line, or points of it -- prices every split at 0: the SAH says
+    // nothing there and its first candidate would peel one primitive (or bin) off per level; such a range is halved by the median
+    const bool flat = !(box.area() > 0.f);
     if (!uni && count <= (uint32_t)kMaxLeaf) {
       // mixed small range: split by kind
       mid = (uint32_t)(std::partition(order.begin() + first, order.begin() + first + count,
                                       [&](uint32_t g) { return kinds[g] == 0; }) -
                        order.begin());
-    } else if (count <= (uint32_t)PB_SAH_SWEEP) {
+    } else if (!flat && count <= (uint32_t)PB_SAH_SWEEP) {
       // small ranges: the exact SAH -- every split position of every axis (the bins are too coarse down here), the two sides
       // priced by the LEAVES they will make (kMaxLeaf primitives each: an odd split of four triangles costs a third leaf)
       auto leaves = [max_leaf](uint32_t n) { return (float)((n + max_leaf - 1u) / max_leaf); };
@@ -138,7 +141,7 @@ struct Builder {
     } else {
       int best_axis = -1, best_bin = 0;
       float best_cost = std::numeric_limits<float>::infinity();
-      for (int a = 0; a < 3; a++) {
+      for (int a = 0; a < 3 && !flat; a++) {
         float ext = cbox.hi[a] - cbox.lo[a];
         if (!(ext > 0.f)) continue;
         Box bb[kBins];
@@ -183,7 +186,7 @@ struct Builder {
                          order.begin());
       }
       if (mid == first || mid == first + count) {
-        // all centroids coincide (or SAH found no split): median split on the widest axis
+        // all centroids coincide, the range is flat or the SAH found no split: median split on the widest axis
         int a = 0;
         for (int c = 1; c < 3; c++)
           if (cbox.hi[c] - cbox.lo[c] > cbox.hi[a] - cbox.lo[a]) a = c;

@@ -61,9 +61,9 @@ __device__ __forceinline__ NearCand tri_nearest(V3 p, V3 a, V3 b, V3 c) {
   const float nn = dot(n, n);
   const float s_ab = dot(cross(b - a, p - a), n), s_bc = dot(cross(c - b, p - b), n), s_ca = dot(cross(a - c, p - c), n);
   if (nn > 0.0f && s_ab >= 0.0f && s_bc >= 0.0f && s_ca >= 0.0f) {
-    const float h = dot(p - a, n);
-    d2 = (h * h) / nn;
-    if (d2 < r.d2) r.d2 = d2, r.q = p - (h / nn) * n, r.u = s_ca / nn, r.v = s_ab / nn, r.feat = kFeatFace;
+    const float h = dot(p - a, n), w = h / nn;  // (h / nn) * h, not (h * h) / nn: fourth order in length, not sixth over fourth
+    d2 = w * h;
+    if (d2 < r.d2) r.d2 = d2, r.q = p - w * n, r.u = s_ca / nn, r.v = s_ab / nn, r.feat = kFeatFace;
   }
   const V3 lo(__builtin_fminf(__builtin_fminf(a.x, b.x), c.x), __builtin_fminf(__builtin_fminf(a.y, b.y), c.y), __builtin_fminf(__builtin_fminf(a.z, b.z), c.z));
   const V3 hi(__builtin_fmaxf(__builtin_fmaxf(a.x, b.x), c.x), __builtin_fmaxf(__builtin_fmaxf(a.y, b.y), c.y), __builtin_fmaxf(__builtin_fmaxf(a.z, b.z), c.z));

@@ -28,6 +28,11 @@ int main() {
       if (mode == 3 && i % 2) { c[0] = lo[3 * (i - 1)], c[1] = lo[3 * (i - 1) + 1], c[2] = lo[3 * (i - 1) + 2]; }   // duplicates
       float e = mode == 4 ? 0.f : 0.05f * (U(rng) + 1.f);
       for (int a = 0; a < 3; a++) lo[3 * i + a] = c[a] - (mode == 3 ? 0.f : e), hi[3 * i + a] = c[a] + e;
+      if (it >= 392) {  // the last cases: segments of one axis-parallel line (a scene collapsed to a line: no box has an area, every split costs 0)
+        const int ax = it % 3;
+        for (int a = 0; a < 3; a++)
+          if (a != ax) lo[3 * i + a] = hi[3 * i + a] = 0.5f;
+      }
       kinds[i] = (uint8_t)(it % 3 != 0 && rng() % 4 == 0);  // (every third case: triangles only)
     }
     FlatBvh b;

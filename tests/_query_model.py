@@ -67,8 +67,9 @@ def tri_nearest(p, a, b, c):
     inside = (nn > 0) & (s_ab >= 0) & (s_bc >= 0) & (s_ca >= 0)
     h = dot(p - a, n)
     with np.errstate(all="ignore"):
-        dp = (h * h) / nn
-        qp = p - (h / nn)[..., None] * n
+        w = h / nn
+        dp = w * h
+        qp = p - w[..., None] * n
         up, vp = s_ca / nn, s_ab / nn
     rep = inside & (dp < d2)
     d2, u, v, q = np.where(rep, dp, d2), np.where(rep, up, u), np.where(rep, vp, v), np.where(rep[..., None], qp, q)
@@ -132,9 +133,10 @@ def candidates(points, slots, shade, chunk=256):
     return out
 
 
-def brute_force(points, slots, shade):
+def brute_force(points, slots, shade, cand=None):
     """The contract's answer per query over all slots: the smallest D2 <= max_dist^2, equal D2 to the smaller gid.  Inactive queries (a
-    non-finite coordinate, max_dist NaN or < 0) miss.  -> dict(found, slot, gid, d2, dist, u, v, q, ties (gids sharing the minimum),
+    non-finite coordinate, max_dist NaN or < 0) miss.  cand: candidates(points, slots, shade) where the caller has them already (every
+    query active).  -> dict(found, slot, gid, d2, dist, u, v, q, ties (gids sharing the minimum),
     clamped (candidates the bound changed))"""
     pts = np.ascontiguousarray(points, F).reshape(-1, 4)
     shade = np.asarray(shade, np.uint32)
@@ -147,7 +149,7 @@ def brute_force(points, slots, shade):
     if ns == 0 or nq == 0:
         return res
     safe = np.where(active[:, None], pts, F(0)).astype(F)
-    D2, U, V, Q, clamped = candidates(safe, slots, shade)
+    D2, U, V, Q, clamped = candidates(safe, slots, shade) if cand is None else cand
     gid = shade[:, 24].astype(np.int64)
     valid = (D2 <= md2[:, None]) & active[:, None]
     dm = np.where(valid, D2, np.inf)

@@ -227,8 +227,9 @@ def tri_feature(p, a, b, c):
     inside = (nn > 0) & (s_ab >= 0) & (s_bc >= 0) & (s_ca >= 0)
     h = QM.dot(p - a, n)
     with np.errstate(all="ignore"):
-        dp = (h * h) / nn
-        qp = p - (h / nn)[..., None] * n
+        w = h / nn
+        dp = w * h
+        qp = p - w[..., None] * n
         up, vp = s_ca / nn, s_ab / nn
     rep = inside & (dp < d2)
     d2, u, v, q = np.where(rep, dp, d2), np.where(rep, up, u), np.where(rep, vp, v), np.where(rep[..., None], qp, q)

@@ -26,6 +26,13 @@ Tolerances (named below):
   SLIVER  1e-4  triangles with area / longest-edge^2 below this are numerically degenerate (tests/_soups.py): float32
                 barycentrics of them mean little, so they are never required; a reported hit on one must lie in the
                 triangle's box (the contract's validation rule) instead of matching float64 u, v.
+
+Absolute lengths -- the pads of the slivers' boxes, tmin of the rays -- are in units of the scene's size (Geometry.unit: the largest
+half extent of its box, rounded down to a power of two: exactly 1 for SCENES, whose half extents are 1 to 1.6, so they keep their figures).
+PLACED runs the soup at the uniform scales 1e-6, 1e-3, 1e3, 3e7 and at the offset (4096, -4096, 4096) (tests/_soups.py), where pads of
+1.0 and a tmin of 1e-3 would leave no required hit (0 of 426 at 1e-6) or no meaning.  Placements where float32 coordinates are too coarse
+for MARGIN and T_SEP to leave 400 clear hits -- the offset (1e5, 3e4, -7e4) has 53 -- are left to the bit-for-bit tests
+(tests/test_placements_cpu.py, tests/test_placements_gpu.py).
 """
 import numpy as np
 import pytest
@@ -82,6 +89,8 @@ def transformed_scene():
 def scene(name):
     if name == "soup":
         return _soups.triangle_soup(1, extra_slivers=60)[0]
+    if name.startswith("soup@"):
+        return _soups.placed_desc(_soups.triangle_soup(1, extra_slivers=60)[0], name[len("soup@"):])
     if name == "ribbons":
         return ribbon_scene()
     if name == "transformed":
@@ -90,6 +99,7 @@ def scene(name):
 
 
 SCENES = ["lambert", "hair", "soup", "ribbons", "transformed"]
+PLACED = ["soup@scale_1e-6", "soup@scale_1e-3", "soup@scale_1e3", "soup@scale_3e7", "soup@offset_4096"]
 
 
 # ---------------------------------------------------------------------------------------------------------- float64 geometry
@@ -108,6 +118,8 @@ class Geometry:
             tri_w.append(wld), tri_l.append(loc)
             tri_id.append(np.stack([np.full(len(loc), inst), np.arange(len(loc))], 1))
         self.tri = np.concatenate(tri_w)
+        half = 0.5 * (self.tri.reshape(-1, 3).max(0) - self.tri.reshape(-1, 3).min(0)).max()
+        self.unit = 2.0 ** np.floor(np.log2(half))                        # the scene's size: 1.0 for half extents in [1, 2)
         loc = np.concatenate(tri_l)
         self.tri_id = np.concatenate(tri_id)
         self.tri_ng = np.cross(loc[:, 1] - loc[:, 0], loc[:, 2] - loc[:, 0])          # local space, unnormalised
@@ -193,7 +205,7 @@ class Geometry:
         sv = np.nonzero(self.sliver)[0]
         if len(sv):
             lo, hi = self.tri[sv].min(1), self.tri[sv].max(1)
-            pad = POS_TOL * (np.abs(self.tri[sv]).max((1, 2)) + 1.0)[:, None]
+            pad = POS_TOL * (np.abs(self.tri[sv]).max((1, 2)) + self.unit)[:, None]
             with np.errstate(divide="ignore", invalid="ignore"):
                 inv = 1.0 / d
                 ta = ((lo - pad)[None] - o[:, None]) * inv[:, None]
@@ -219,6 +231,7 @@ def rays_for(geo, lo, hi, seed):
     ribbon points within 1.5 radii of the centre line) from random origins"""
     rng = np.random.RandomState(seed)
     rays = scenes.random_rays((lo, hi), N_RANDOM, seed=seed)
+    rays["tmin"] = 1e-3 * geo.unit                                         # unit directions: t is a length
     lo64, hi64 = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     org = lo64 + (hi64 - lo64) * rng.rand(N_AIMED, 3)
     tgt = np.zeros((N_AIMED, 3))
@@ -291,7 +304,7 @@ def check(desc, hits, rays, geo):
                 if not is_curve and geo.sliver[sel[0]]:
                     p = o[rid] + float(h[r]["t"]) * d[rid]
                     tri = geo.tri[sel[0]]
-                    pad = 1e-5 * (np.abs(tri).max() + 1.0)
+                    pad = 1e-5 * (np.abs(tri).max() + geo.unit)
                     assert np.all(p >= tri.min(0) - pad) and np.all(p <= tri.max(0) + pad), (rid, p, tri)
                     continue
                 dt = np.abs(t[r, sel] - h[r]["t"])
@@ -326,6 +339,6 @@ def _gpu_tracer(desc, so, rays):
 
 
 @pytest.mark.parametrize("backend", ["oracle", pytest.param("gpu", marks=pytest.mark.gpu)])
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + PLACED)
 def test_trace_closest_matches_f64_contract(name, backend):
     _run(name, _oracle_tracer if backend == "oracle" else _gpu_tracer)

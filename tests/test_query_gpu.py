@@ -75,36 +75,12 @@ def soup():
 
 @functools.lru_cache(maxsize=None)
 def curve_soup():
-    """tests/test_gpu_parity.py::test_curve_soup's recipe (seed 0): 300 cubic ribbons incl. duplicates, degenerate, zero-radius, straight
-    and grid-aligned ones, two triangles behind them; random rays and axis-aligned rays at control points"""
-    import _oracle as O
-    from pbrlab_amd import scenes
-    seed = 0
-    rng = np.random.RandomState(900 + seed)
-    nc = 300
-    cp = (rng.rand(nc, 4, 4).astype(F) * 2 - 1)
-    cp[:, 1:, :3] = cp[:, :1, :3] + np.cumsum((rng.rand(nc, 3, 3).astype(F) - 0.5) * F(0.3), axis=1)
-    cp[..., 3] = F(0.004) + rng.rand(nc, 4).astype(F) * F(0.03)
-    cp[:20] = cp[20:40]
-    cp[40:50, 1:] = cp[40:50, :1]
-    cp[50:60, :, 3] = 0.0
-    cp[60:70, 1:, :3] = cp[60:70, :1, :3] + np.arange(1, 4, dtype=F)[None, :, None] * F(0.1)
-    cp[70:90, :, :3] = np.round(cp[70:90, :, :3] * 8) / 8
-    curve = scenes.CurveShape("c", cp.reshape(-1, 4), (np.arange(nc, dtype=np.uint32) * 4))
-    tv = np.array([[-1, -1, -0.9, 1], [1, -1, -0.9, 1], [1, 1, -0.9, 1], [-1, 1, -0.9, 1]], F)
-    mat = dict(scenes.PRINCIPLED_DEFAULTS, kind="principled", name="m")
-    desc = scenes.SceneDesc(tv, np.zeros((0, 4), F), [mat],
-                            [scenes.Shape("back", np.array([[0, 1, 2], [0, 2, 3]], np.uint32), None, np.zeros(2, np.uint32))], [curve])
-    lo, hi = O.oracle_scene_from_desc(desc).FetchSceneAABB()
-    rays = scenes.random_rays((lo, hi), 5000, seed=seed)
-    extra = np.zeros(1500, O.RAY_DT)
-    tgt = cp.reshape(-1, 4)[rng.randint(nc * 4, size=1500), :3]
-    axis = rng.randint(3, size=1500)
-    dirs = np.zeros((1500, 3), F)
-    dirs[np.arange(1500), axis] = rng.choice([-1.0, 1.0], size=1500)
-    extra["org"], extra["dir"] = tgt - dirs * F(2.5), dirs
-    extra["tmin"], extra["tmax"] = 0.0, 1e30
-    return desc, np.concatenate([rays, extra])
+    """tests/_soups.py::curve_soup, seed 0 (tests/test_gpu_parity.py::test_curve_soup's scenes): 300 cubic ribbons incl. duplicates,
+    degenerate, zero-radius, straight and grid-aligned ones, two triangles behind them; random rays and axis-aligned rays at control
+    points"""
+    import _soups
+    desc, so, rays = _soups.curve_soup(0)
+    return desc, rays
 
 
 def _desc(name):
