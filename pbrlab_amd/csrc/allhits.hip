@@ -17,14 +17,6 @@ namespace pb {
 
 constexpr int kBlock = 256;
 
-// query.hip::ray_active, restated: eight numbers, none NaN, origin and direction finite, a direction other than zero, 0 <= tmin <= tmax
-// (tmax may be +inf)
-__device__ __forceinline__ bool all_ray_active(const float4& o, const float4& d) {
-  const bool finite = isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z);
-  const bool nonzero = d.x != 0.0f || d.y != 0.0f || d.z != 0.0f;
-  return finite && nonzero && o.w >= 0.0f && d.w >= o.w;  // (a NaN tmin or tmax fails both comparisons)
-}
-
 // COUNT: a.count is given (the interval never shrinks); otherwise a.ident is and a.k >= 1
 template <bool COUNT, bool CURVES, bool WIDE>
 __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_all_hits(DScene sc, AllHitsArgs a) {
@@ -35,7 +27,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_all_hits(DScene
     const float4 o4 = a.rays[2 * (size_t)i], d4 = a.rays[2 * (size_t)i + 1];
     AllList L;
     L.row = K ? a.ident + (size_t)i * K : nullptr, L.K = K, L.len = 0u, L.cnt = 0u, L.kth = d4.w;
-    if (all_ray_active(o4, d4))
+    if (ray_active(o4, d4))
       all_traverse<COUNT, CURVES, WIDE>(sc, ld3(o4), ld3(d4), o4.w, d4.w, L, stk + threadIdx.x, kBlock, &overflow,
                                         a.spill + blockIdx.x * kBlock + threadIdx.x, gridDim.x * kBlock);
     for (uint32_t j = L.len; j < K; j++) L.row[j] = make_uint4(kNone, 0u, 0u, 0u);
@@ -44,11 +36,9 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_all_hits(DScene
   if (overflow) *a.overflow = 1u;
 }
 
-static_assert((size_t)(kStackDepth - kSimpleLdsStack) * kFeatureGridCap * kBlock <= kSpillWords, "k_all_hits's spill area (one stack per thread of its grid)");
 void launch_all_hits(hipStream_t s, const DScene& sc, const AllHitsArgs& a, const Knobs& k) {
   if (!a.n) return;
-  uint32_t g = (a.n + kBlock - 1) / kBlock;
-  g = g < kFeatureGridCap ? g : kFeatureGridCap;
+  const uint32_t g = feature_grid<kBlock>(a.n);
   with_flags([&](auto cnt, auto c, auto w) { hipLaunchKernelGGL((k_all_hits<cnt, c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, a.count != nullptr,
              sc.num_curves != 0, use_wide(sc, k));
 }

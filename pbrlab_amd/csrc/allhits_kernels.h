@@ -16,7 +16,7 @@ constexpr uint32_t kAllHitsMax = 32u;  // PBRHIP_ALL_HITS_MAX
 // n rays (two 16-byte words each: org | tmin, dir | tmax) against every unit of the scene, on the <CURVES, WIDE> tree the render of this
 // scene walks.  count (null: not wanted): per ray the number of accepted hits in (tmin, tmax], not capped.  ident (null: a pure count; k
 // entries of 4 words per ray, k <= kAllHitsMax, n * k < 2^31): the first min(count, k) hits in the order (t, gid, u) as slot, bits of u,
-// v, t; the remaining entries (kNone, 0, 0, 0).  One of the two is given.  An inactive ray (query.hip::ray_active) has count 0 and a row
+// v, t; the remaining entries (kNone, 0, 0, 0).  One of the two is given.  An inactive ray (dtrace.h::ray_active) has count 0 and a row
 // of misses.  overflow: one zeroed word; spill: kSpillWords.
 struct AllHitsArgs {
   const float4* rays;

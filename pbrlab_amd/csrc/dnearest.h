@@ -1,5 +1,6 @@
 // dnearest.h -- the nearest-point contract, operation for operation, and its traversal by distance: what query.hip's
-// k_query_nearest and sdf.hip's signed kernels share.  Device code only; all arithmetic is float32 without contraction.
+// k_query_nearest and sdf.hip's signed kernels share.  The leaf decode is dtrace.h's (leaf_units); the node loop and the
+// stack are written out in nearest_traverse, which says why.  Device code only; all arithmetic is float32 without contraction.
 //
 // Beside the contract's answer a candidate carries the FEATURE of its triangle that won (kFeat*): the signed kernels keep it in the
 // best-so-far record and fetch that feature's pseudonormal once, in their epilogue.  k_query_nearest never reads it, so none of it is
@@ -99,44 +100,47 @@ __device__ __forceinline__ void nearest_offer(const DScene& sc, const NearCand& 
   if (acc) best.d2 = c.d2, best.u = c.u, best.v = c.v, best.q = c.q, best.slot = slot, best.feat = c.feat;
 }
 
-// one leaf of either tree: the leaf formats are dtrace.h::leaf_test's
-template <bool CURVES, bool WIDE>
-__device__ __forceinline__ void nearest_leaf(const DScene& sc, uint32_t leaf, V3 p, Nearest& best) {
-  uint32_t first = (leaf & 0x3FFFFFFFu) >> 3, count = (leaf & 7u) + 1u;
-  const bool is_curve = (leaf & kCurveBit) != 0;
-  if (WIDE && !CURVES) {  // one TriPair (dscene.h): triangles a and b interleaved coordinate by coordinate
-    const float4* g = sc.wide + sc.q_tri0 + (size_t)first * kTriPairWords;
-    const float4 w0 = g[0], w1 = g[1], w2 = g[2], w3 = g[3], w4 = g[4];
-    const uint32_t code_a = __float_as_uint(w4.z), code_b = __float_as_uint(w4.w);
-    nearest_offer(sc, tri_nearest(p, V3(w0.x, w0.z, w1.x), V3(w1.z, w2.x, w2.z), V3(w3.x, w3.z, w4.x)), code_a & kHitSlotMask, best);
-    if (code_b != kNone) nearest_offer(sc, tri_nearest(p, V3(w0.y, w0.w, w1.y), V3(w1.w, w2.y, w2.w), V3(w3.y, w3.w, w4.y)), code_b & kHitSlotMask, best);
-    return;
-  }
-  const bool rec = WIDE && CURVES && is_curve;  // a curve record of the Q tree: one or two pieces at points P, P + 2
-  const uint32_t sub_a = first & 3u, sub_b = leaf & 3u;
-  if (rec) first &= ~3u, count = (leaf & kCurvePairBit) ? 2u : 1u;
-  for (uint32_t k = 0; k < count; k++) {
-    const uint32_t s = first + (rec ? 2u * k : k);
-    if (WIDE) {
-      if (!is_curve) {
-        const float4* g = sc.wide + sc.q_tri0 + (size_t)s * 3;
-        const float4 a = g[0], b = g[1], c = g[2];
-        nearest_offer(sc, tri_nearest(p, ld3(a), ld3(b), ld3(c)), __float_as_uint(c.w) & kHitSlotMask, best);
-      } else {
-        const float4* g = sc.wide + sc.q_pt0 + s;
-        const float4 a = g[0], b = g[1];
-        nearest_offer(sc, piece_nearest(p, a, b, k ? sub_b : sub_a), sc.q_hitcode[s] & kHitSlotMask, best);
-      }
-    } else {
-      const float4* g = sc.slots + (size_t)s * 4;
-      const float4 a = g[0], b = g[1], c = g[2];
-      if (!CURVES || !is_curve) nearest_offer(sc, tri_nearest(p, ld3(a), ld3(b), ld3(c)), s, best);
-      else nearest_offer(sc, piece_nearest(p, a, b, __float_as_uint(c.x)), s, best);
-    }
-  }
+// before the first candidate: nothing found within max_dist (pt.w)
+__device__ __forceinline__ Nearest nearest_none(const float4& pt) {
+  Nearest best;
+  best.d2 = pt.w * pt.w, best.u = 0.0f, best.v = 0.0f, best.q = V3(0.0f), best.slot = kNone, best.feat = kFeatCurve;
+  return best;
+}
+// the answer of query i as the callers read it: ident = (slot, bits of u, v, distance), closest = (point | D2); either may be null
+__device__ __forceinline__ void nearest_store(const Nearest& best, uint32_t i, uint4* ident, float4* closest) {
+  const bool found = best.slot != kNone;
+  if (ident) ident[i] = found ? make_uint4(best.slot, __float_as_uint(best.u), __float_as_uint(best.v), __float_as_uint(sqrtf(best.d2))) : make_uint4(kNone, 0u, 0u, 0u);
+  if (closest) closest[i] = found ? make_float4(best.q.x, best.q.y, best.q.z, best.d2) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// dtrace.h::traverse_mode's stack discipline and loop, ordered and pruned by the box distance instead of the slab test
+// one leaf of either tree (dtrace.h::leaf_units): every unit's candidate offered once
+template <bool CURVES, bool WIDE>
+__device__ __forceinline__ void nearest_leaf(const DScene& sc, uint32_t leaf, V3 p, Nearest& best) {
+  leaf_units<CURVES, WIDE>(
+      sc, leaf,
+      [&](const float4& w0, const float4& w1, const float4& w2, const float4& w3, const float4& w4) {  // triangles a and b interleaved coordinate by coordinate
+        const uint32_t code_a = __float_as_uint(w4.z), code_b = __float_as_uint(w4.w);
+        nearest_offer(sc, tri_nearest(p, V3(w0.x, w0.z, w1.x), V3(w1.z, w2.x, w2.z), V3(w3.x, w3.z, w4.x)), code_a & kHitSlotMask, best);
+        if (code_b != kNone) nearest_offer(sc, tri_nearest(p, V3(w0.y, w0.w, w1.y), V3(w1.w, w2.y, w2.w), V3(w3.y, w3.w, w4.y)), code_b & kHitSlotMask, best);
+        return false;
+      },
+      [&](const float4& a, const float4& b, const float4& c, uint32_t s) {
+        nearest_offer(sc, tri_nearest(p, ld3(a), ld3(b), ld3(c)), WIDE ? __float_as_uint(c.w) & kHitSlotMask : s, best);
+        return false;
+      },
+      [&](const float4& a, const float4& b, uint32_t sub, uint32_t s, uint32_t) {
+        nearest_offer(sc, piece_nearest(p, a, b, sub), WIDE ? sc.q_hitcode[s] & kHitSlotMask : s, best);
+        return false;
+      });
+}
+
+// A traversal by distance: children in ascending order of the squared distance L from the point to their stored box, a box skipped only
+// when L exceeds the best D2 so far.  The loop is dtrace.h::walk_tree's and the stack rule dtrace.h::TravStack's, both WRITTEN OUT here and
+// kept in step by hand: as a call of the walker, and again with the shared stack alone, k_query_nearest came out 2 % slower on the Q tree
+// (the backend turns the pop's select between LDS and spill into a branch; profiles/README.md, "One stack, one walker").  With this text
+// the nearest and signed kernels compile to the instructions they had before the walker existed.  Whoever edits walk_tree or TravStack
+// edits this too; a drift shows as a bit-exact failure in tests/test_query_gpu.py (test_nearest_point_equals_the_brute_force on the
+// tie-heavy soups, test_comb_reaches_the_spill_part_of_the_stack for the spill half of the stack) and tests/test_sdf_gpu.py.
 template <bool CURVES, bool WIDE>
 __device__ __forceinline__ void nearest_traverse(const DScene& sc, V3 p, Nearest& best, uint32_t* stack, uint32_t stride, uint32_t* overflow,
                                                  uint32_t* spill, uint32_t spill_stride) {
@@ -169,11 +173,7 @@ __device__ __forceinline__ void nearest_traverse(const DScene& sc, V3 p, Nearest
         const float L = box_dist2(lo, hi, p);
         k[i] = (r[i] != kEmptyChild && L <= best.d2) ? (__float_as_uint(L) & ~3u) | (uint32_t)i : kWideMiss;  // (L >= 0: its bits order like its value)
       }
-      auto cex = [](uint32_t& a, uint32_t& b) {
-        const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-        a = lo, b = hi;
-      };
-      cex(k[0], k[1]), cex(k[2], k[3]), cex(k[0], k[2]), cex(k[1], k[3]), cex(k[1], k[2]);
+      wide_sort_keys(k);
 #pragma unroll
       for (int j = 3; j >= 1; j--) {
         if (k[j] == kWideMiss) continue;

@@ -272,6 +272,13 @@ struct DScene {
   float env_m[9];               // world_to_env, row-major (a rotation)
 };
 
+// what a trace hook or a ray query returns per ray (dshade.h::hook_result)
+struct HookHit {  // == pbrhip_hit == TraceResult (raytracer.h:9-17)
+  float ng[3];
+  float t, u, v;
+  uint32_t instance_id, geom_id, prim_id;
+};
+
 // camera of RenderingTile (render.cc:132-158), derived on the host from the scene AABB
 struct Camera {
   float org[3];

@@ -57,6 +57,21 @@ __device__ __forceinline__ Surface make_surface(const DScene& sc, V3 org, V3 dir
   return s;
 }
 
+// What a caller of the trace hooks and the ray queries gets for one ray: TraceResult of a hit (raytracer.h:9-17), its defaults for a miss
+__device__ __forceinline__ HookHit hook_result(const DScene& sc, V3 o, V3 d, const Hit& h) {
+  HookHit r;
+  r.ng[0] = 1.f, r.ng[1] = 0.f, r.ng[2] = 0.f, r.t = 1.f, r.u = 0.f, r.v = 0.f;
+  r.instance_id = r.geom_id = r.prim_id = kNone;
+  if (h.slot != kNone) {
+    Surface s = make_surface(sc, o, d, h);
+    const ShadeRec& sr = sc.shade[h.slot & kHitSlotMask];
+    r.ng[0] = s.n_g.x, r.ng[1] = s.n_g.y, r.ng[2] = s.n_g.z;
+    r.t = h.t, r.u = h.u, r.v = h.v;
+    r.instance_id = sr.instance_id, r.geom_id = sr.geom_id, r.prim_id = sr.prim_id;
+  }
+  return r;
+}
+
 // Texture::FetchFloat3 (texture.cc:43-68) -> BilinearFilter with clamp addressing (image-utils.cc:99-167):
 // px = width * u (no half-texel offset); channels the image lacks read as 0
 __device__ __forceinline__ V3 texture_fetch3(const DScene& sc, uint32_t tex_id, float u, float v) {

@@ -1,4 +1,8 @@
-// dtrace.h -- ray/primitive tests and BVH2 traversal (device).
+// dtrace.h -- ray/primitive tests and the one-query-per-lane traversal of both trees (device).
+//
+// Shared by such traversals, once: the stack (TravStack), the node loop (walk_tree), the leaf decode (leaf_units).  A query brings its box
+// tests and what it does with a unit: closest / any hit (below) and all hits (dallhits.h).  The nearest point (dnearest.h) shares the leaf
+// decode only, for a measured reason given there; the phase-voting dtrace_pv.h::trace_pv shares the stack only.
 //
 // Stands in for Embree's rtcIntersect1 / rtcOccluded1 behind pbrlab's Raytracer facade
 // (src/raytracer/raytracer_impl.cc:268-287).  Intersection contract:
@@ -317,6 +321,13 @@ __device__ __forceinline__ void box_test4q(const float4& w0, const float4& w1, c
 // One step at a wide node: the children the ray's interval [tmin, tmax] hits, nearest first.  k[0..3] ascending; a key is the
 // child's entry distance (>= 0 as an integer; its two low bits hold the child index, wide_ref), 0xFFFFFFFF = not hit.
 constexpr uint32_t kWideMiss = 0xFFFFFFFFu;
+__device__ __forceinline__ void wide_sort_keys(uint32_t k[4]) {
+  auto cex = [](uint32_t& a, uint32_t& b) {
+    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo, b = hi;
+  };
+  cex(k[0], k[1]), cex(k[2], k[3]), cex(k[0], k[2]), cex(k[1], k[3]), cex(k[1], k[2]);
+}
 __device__ __forceinline__ void wide_node_keys(const float4& w0, const float4& w1, const float4& w2, const float4& refs, V3 o,
                                                const float4& inv, float tmin, float tmax, uint32_t k[4]) {
   float ta[4], tb[4];
@@ -328,11 +339,7 @@ __device__ __forceinline__ void wide_node_keys(const float4& w0, const float4& w
     const int bits = (int)__float_as_uint(ta[i]);
     k[i] = h ? ((uint32_t)(bits < 0 ? 0 : bits) & ~3u) | (uint32_t)i : kWideMiss;
   }
-  auto cex = [](uint32_t& a, uint32_t& b) {
-    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-    a = lo, b = hi;
-  };
-  cex(k[0], k[1]), cex(k[2], k[3]), cex(k[0], k[2]), cex(k[1], k[3]), cex(k[1], k[2]);
+  wide_sort_keys(k);
 }
 __device__ __forceinline__ uint32_t wide_ref(const float4& refs, uint32_t key) {
   const uint32_t a = __float_as_uint((key & 1u) ? refs.y : refs.x), b = __float_as_uint((key & 1u) ? refs.w : refs.z);
@@ -350,158 +357,222 @@ __device__ __forceinline__ uint32_t q_final_code(const DScene& sc, uint32_t code
   return (code != kNone && (code & kQPointHit)) ? sc.q_hitcode[code & ~kQPointHit] : code;
 }
 
-// Leaf processing.  any: returns true on the first accepted hit.
-// MODE: 0 = closest hit, 1 = any hit, 2 = per lane (`any_rt`), as in trace_pv.
-template <int MODE, bool STATS, bool CURVES, bool WIDE = false>
-__device__ __forceinline__ bool leaf_test(const DScene& sc, uint32_t leaf, V3 o, V3 d, V3 inv, float tmin, float& best_t,
-                                          Hit& hit, TravStats& st, bool any_rt) {
-  const bool ANY = MODE == 2 ? any_rt : (MODE == 1);
+// Traversal stack of one lane, and THE rule of where an entry lives: the first LDS entries in LDS (lds[i * stride]), deeper ones
+// in a per-thread global area (spill[(i - LDS) * spill_stride]), none at or past kStackDepth (the overflow flag is raised: the
+// launch's result is discarded).  Keeping the LDS part small is what lets 6 blocks (24 waves) share a CU.  Every traversal uses it: the
+// walker below (LDS = kSimpleLdsStack), dtrace_pv.h::trace_pv (pv_lds_stack) and dtrace_quad.h (the quad's column).
+template <int LDS>
+struct TravStack {
+  uint32_t* lds;
+  uint32_t stride;
+  uint32_t* spill;
+  uint32_t spill_stride;
+  uint32_t* overflow;
+  // index of entry pos in lds / in spill
+  template <typename I>
+  __device__ __forceinline__ uint32_t lds_at(I pos) const { return (uint32_t)pos * stride; }
+  template <typename I>
+  __device__ __forceinline__ uint32_t spill_at(I pos) const { return (uint32_t)(pos - (I)LDS) * spill_stride; }
+  // CHECKED = false: the caller knows that pos < kStackDepth
+  template <bool CHECKED = true, typename I>
+  __device__ __forceinline__ void put(I pos, uint32_t ref) const {
+    if (pos < (I)LDS) lds[lds_at(pos)] = ref;
+    else if (!CHECKED || pos < (I)kStackDepth) spill[spill_at(pos)] = ref;
+    else *overflow = 1u;
+  }
+  template <typename I>
+  __device__ __forceinline__ uint32_t get(I pos) const { return pos < (I)LDS ? lds[lds_at(pos)] : spill[spill_at(pos)]; }
+  __device__ __forceinline__ void push(int& sp, uint32_t ref) const {
+    if (sp < LDS) lds[lds_at(sp)] = ref, sp++;
+    else if (sp < kStackDepth) spill[spill_at(sp)] = ref, sp++;
+    else *overflow = 1u;
+  }
+  __device__ __forceinline__ uint32_t pop(int& sp) const {
+    sp--;
+    return get(sp);
+  }
+};
+using SimpleStack = TravStack<kSimpleLdsStack>;  // the one-query-per-lane kernels': k_tail, the simple hooks, the first-hit walker, the queries
+
+// THE leaf decoder: a leaf reference of either tree, turned into the units a query tests once each.  Per unit one of three callables is
+// called; it returns true to stop (the decoder then returns true at once).  What a hit is called is the consumer's business.
+//   pair(w0 .. w4)                 WIDE && !CURVES: the five words of the leaf's TriPair (dscene.h), one or two triangles interleaved
+//   tri(a, b, c, s)                a triangle: the Q tree's 48-byte slot s (c.w = its hit code) or the binary tree's 64-byte one (c.w = routing)
+//   piece(a, b, sub, s, routing)   piece `sub` of a cubic, end points a, b (xyz + radius): point s of a Q-tree curve record (one or two pieces
+//                                  at P, P + 2; sub-indices in the low bits of `first` and of the reference) or the binary slot s
+template <bool CURVES, bool WIDE, typename Pair, typename Tri, typename Piece>
+__device__ __forceinline__ bool leaf_units(const DScene& sc, uint32_t leaf, Pair&& pair, Tri&& tri, Piece&& piece) {
   uint32_t first = (leaf & 0x3FFFFFFFu) >> 3, count = (leaf & 7u) + 1u;
-  bool is_curve = (leaf & kCurveBit) != 0;
-  if (WIDE && !CURVES) {  // Q tree of a triangle-only scene: one TriPair per leaf (dscene.h), both triangles in one packed test
+  const bool is_curve = (leaf & kCurveBit) != 0;
+  if (WIDE && !CURVES) {
     const float4* g = sc.wide + sc.q_tri0 + (size_t)first * kTriPairWords;
     const float4 w0 = g[0], w1 = g[1], w2 = g[2], w3 = g[3], w4 = g[4];
-    uint32_t nt = 0u;
-    const bool occluded = tri_pair_accept<MODE == 1, STATS>(sc, w0, w1, w2, w3, w4, o, d, inv, tmin, ANY, hit, nt);
-    if (STATS) st.tris += nt;
-    best_t = hit.t;
-    return occluded;
+    return pair(w0, w1, w2, w3, w4);
   }
-  // a curve record of the Q tree (dscene.h): one or two pieces at points P, P + 2; the low bits of `first` and of the reference are
-  // their indices in their cubics
   const bool rec = WIDE && CURVES && is_curve;
   const uint32_t sub_a = first & 3u, sub_b = leaf & 3u;
   if (rec) first &= ~3u, count = (leaf & kCurvePairBit) ? 2u : 1u;
   for (uint32_t k = 0; k < count; k++) {
     const uint32_t s = first + (rec ? 2u * k : k);
-    float t, u, v;
-    bool ok;
-    uint32_t code;
-    if (WIDE) {  // Q tree of a scene with curves: 48-byte triangle slots / curve records (dscene.h)
+    if (WIDE) {
       if (!is_curve) {
         const float4* g = sc.wide + sc.q_tri0 + (size_t)s * 3;
-        float4 a = g[0], b = g[1], c = g[2];
-        if (STATS) st.tris++;
-        ok = tri_test(ld3(a), ld3(b), ld3(c), o, d, inv, tmin, t, u, v) && (t <= best_t);
-        code = __float_as_uint(c.w);
+        const float4 a = g[0], b = g[1], c = g[2];
+        if (tri(a, b, c, s)) return true;
       } else {
         const float4* g = sc.wide + sc.q_pt0 + s;
-        float4 a = g[0], b = g[1];
-        if (STATS) st.curves++;
-        ok = segment_test(a, b, k ? sub_b : sub_a, o, d, inv, tmin, best_t, t, u, v);
-        code = kQPointHit | s;
+        const float4 a = g[0], b = g[1];
+        if (piece(a, b, k ? sub_b : sub_a, s, 0u)) return true;
       }
     } else {
       const float4* g = sc.slots + (size_t)s * 4;
-      float4 a = g[0], b = g[1], c = g[2];
+      const float4 a = g[0], b = g[1], c = g[2];
       if (!CURVES || !is_curve) {
-        if (STATS) st.tris++;
-        ok = tri_test(ld3(a), ld3(b), ld3(c), o, d, inv, tmin, t, u, v) && (t <= best_t);
+        if (tri(a, b, c, s)) return true;
       } else {
-        if (STATS) st.curves++;
-        ok = segment_test(a, b, __float_as_uint(c.x), o, d, inv, tmin, best_t, t, u, v);
+        if (piece(a, b, __float_as_uint(c.x), s, __float_as_uint(c.w))) return true;
       }
-      code = s | __float_as_uint(c.w);  // + routing bits (dscene.h)
     }
-    if (!ok) continue;
-    if (ANY) return true;
-    if (t == best_t && hit.slot != kNone) {  // tie: the smaller canonical primitive id wins
-      const bool less = WIDE ? q_gid(sc, code) < q_gid(sc, hit.slot) : sc.shade[s].gid < sc.shade[hit.slot & kHitSlotMask].gid;
-      if (!less) continue;
-    }
-    best_t = t;
-    hit.t = t, hit.u = u, hit.v = v, hit.slot = code;
   }
   return false;
 }
 
-// BVH2 traversal, near child first, far child on a per-lane stack (stack[i * stride]).
-// WIDE: the 4-wide tree (sc.wide must not be null): nearest hit child next, the others pushed farthest first.
-template <int MODE, bool STATS, bool CURVES, bool WIDE = false>
-__device__ __forceinline__ bool traverse_mode(const DScene& sc, V3 o, V3 d, float tmin, float tmax, Hit& hit,
-                                              uint32_t* stack, uint32_t stride, TravStats& st, uint32_t* overflow, bool any_rt,
-                                              uint32_t* spill, uint32_t spill_stride) {
-  // stack: entries 0 .. kSimpleLdsStack-1 (stack[i * stride], LDS); deeper ones in spill[(i - kSimpleLdsStack) * spill_stride]
-  auto push = [&](int& sp, uint32_t v) {
-    if (sp < kSimpleLdsStack) stack[(uint32_t)sp * stride] = v, sp++;
-    else if (sp < kStackDepth) spill[(uint32_t)(sp - kSimpleLdsStack) * spill_stride] = v, sp++;
-    else *overflow = 1u;
-  };
-  auto pop = [&](int& sp) {
-    sp--;
-    return sp < kSimpleLdsStack ? stack[(uint32_t)sp * stride] : spill[(uint32_t)(sp - kSimpleLdsStack) * spill_stride];
-  };
-  hit.slot = kNone;
-  hit.t = tmax, hit.u = 0.f, hit.v = 0.f;
+// THE node loop: fetch an inner node, ask the caller which children the query enters and in what order, push all but the nearest
+// (farthest first), pop until the next inner node, handing every leaf on the way to `leaf`.  True as soon as `leaf` says stop; false when
+// the stack runs empty or the scene has no nodes.
+//   wide_keys(w0, w1, w2, refs, k)           a QNode's four words -> k[0..3] ascending: keys with the child index in the low bits, or kWideMiss
+//   pair_test(n0, n1, n2, c0, c1, h0, h1)    three words of a BvhNode, its child references -> h0 / h1: child entered; returns "child 1 first"
+template <bool WIDE, typename WideKeys, typename PairTest, typename Leaf>
+__device__ __forceinline__ bool walk_tree(const DScene& sc, const SimpleStack& stk, WideKeys&& wide_keys, PairTest&& pair_test, Leaf&& leaf) {
   if (sc.num_nodes == 0) return false;
-  V3 inv(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  float best_t = tmax;
   int sp = 0;
   uint32_t cur = 0;
   for (;;) {
     // cur is an internal node
+    uint32_t next = kEmptyChild;
     if (WIDE) {
       const float4* np = sc.wide + (size_t)cur * 4u;  // (a wide node's reference is its 64-byte item index)
       const float4 w0 = np[0], w1 = np[1], w2 = np[2], refs = np[3];
-      if (STATS) st.nodes++;
       uint32_t k[4];
-      wide_node_keys(w0, w1, w2, refs, o, make_float4(inv.x, inv.y, inv.z, 0.f), tmin, best_t, k);
+      wide_keys(w0, w1, w2, refs, k);
 #pragma unroll
       for (int j = 3; j >= 1; j--) {
         if (k[j] == kWideMiss) continue;
-        push(sp, wide_ref(refs, k[j]));
+        stk.push(sp, wide_ref(refs, k[j]));
       }
-      uint32_t next = k[0] == kWideMiss ? kEmptyChild : wide_ref(refs, k[0]);
-      for (;;) {
-        if (next == kEmptyChild) {
-          if (sp == 0) {
-            hit.slot = q_final_code(sc, hit.slot);
-            return hit.slot != kNone;
-          }
-          next = pop(sp);
-        }
-        if (!(next & kLeafBit)) break;
-        if (leaf_test<MODE, STATS, CURVES, true>(sc, next, o, d, inv, tmin, best_t, hit, st, any_rt)) return true;
-        next = kEmptyChild;
+      if (k[0] != kWideMiss) next = wide_ref(refs, k[0]);
+    } else {
+      const float4* np = reinterpret_cast<const float4*>(sc.nodes + cur);
+      const float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
+      const uint32_t c0 = __float_as_uint(n3.x), c1 = __float_as_uint(n3.y);
+      bool h0, h1;
+      const bool second_first = pair_test(n0, n1, n2, c0, c1, h0, h1);
+      if (h0 && h1) {
+        uint32_t nearc = c0, farc = c1;
+        if (second_first) nearc = c1, farc = c0;
+        stk.push(sp, farc);
+        next = nearc;
+      } else if (h0) {
+        next = c0;
+      } else if (h1) {
+        next = c1;
       }
-      cur = next;
-      continue;
-    }
-    const float4* np = reinterpret_cast<const float4*>(sc.nodes + cur);
-    float4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3];
-    if (STATS) st.nodes++;
-    uint32_t c0 = __float_as_uint(n3.x), c1 = __float_as_uint(n3.y);
-    float t0, t1;
-    bool h0, h1;
-    box_test2(n0, n1, n2, o, inv, tmin, best_t, h0, h1, t0, t1);
-    uint32_t next = kEmptyChild;
-    if (h0 && h1) {
-      uint32_t nearc = c0, farc = c1;
-      if (t1 < t0) nearc = c1, farc = c0;
-      push(sp, farc);
-      next = nearc;
-    } else if (h0) {
-      next = c0;
-    } else if (h1) {
-      next = c1;
     }
     for (;;) {
       if (next == kEmptyChild) {
-        if (sp == 0) return hit.slot != kNone;
-        next = pop(sp);
+        if (sp == 0) return false;
+        next = stk.pop(sp);
       }
       if (!(next & kLeafBit)) break;
-      if (leaf_test<MODE, STATS, CURVES>(sc, next, o, d, inv, tmin, best_t, hit, st, any_rt)) return true;
+      if (leaf(next)) return true;
       next = kEmptyChild;
     }
     cur = next;
   }
+}
+
+// One leaf against a ray whose interval ends at best_t with hit `hit`.  Returns true on the first accepted hit of an any-hit ray.
+// MODE: 0 = closest hit, 1 = any hit, 2 = per lane (`any_rt`), as in trace_pv.
+template <int MODE, bool STATS, bool CURVES, bool WIDE = false>
+__device__ __forceinline__ bool leaf_test(const DScene& sc, uint32_t leaf, V3 o, V3 d, V3 inv, float tmin, float& best_t,
+                                          Hit& hit, TravStats& st, bool any_rt) {
+  const bool ANY = MODE == 2 ? any_rt : (MODE == 1);
+  // one unit's result -> the hit; true = stop
+  auto accept = [&](bool ok, float t, float u, float v, uint32_t code, uint32_t s) {
+    if (!ok) return false;
+    if (ANY) return true;
+    if (t == best_t && hit.slot != kNone) {  // tie: the smaller canonical primitive id wins
+      const bool less = WIDE ? q_gid(sc, code) < q_gid(sc, hit.slot) : sc.shade[s].gid < sc.shade[hit.slot & kHitSlotMask].gid;
+      if (!less) return false;
+    }
+    best_t = t;
+    hit.t = t, hit.u = u, hit.v = v, hit.slot = code;
+    return false;
+  };
+  return leaf_units<CURVES, WIDE>(
+      sc, leaf,
+      [&](const float4& w0, const float4& w1, const float4& w2, const float4& w3, const float4& w4) {  // both triangles in one packed test
+        uint32_t nt = 0u;
+        const bool occluded = tri_pair_accept<MODE == 1, STATS>(sc, w0, w1, w2, w3, w4, o, d, inv, tmin, ANY, hit, nt);
+        if (STATS) st.tris += nt;
+        best_t = hit.t;
+        return occluded;
+      },
+      [&](const float4& a, const float4& b, const float4& c, uint32_t s) {
+        float t, u, v;
+        if (STATS) st.tris++;
+        const bool ok = tri_test(ld3(a), ld3(b), ld3(c), o, d, inv, tmin, t, u, v) && (t <= best_t);
+        return accept(ok, t, u, v, WIDE ? __float_as_uint(c.w) : s | __float_as_uint(c.w), s);  // binary: + routing bits (dscene.h)
+      },
+      [&](const float4& a, const float4& b, uint32_t sub, uint32_t s, uint32_t routing) {
+        float t, u, v;
+        if (STATS) st.curves++;
+        const bool ok = segment_test(a, b, sub, o, d, inv, tmin, best_t, t, u, v);
+        return accept(ok, t, u, v, WIDE ? kQPointHit | s : s | routing, s);
+      });
+}
+
+// Closest / any hit of one ray: the walker with the slab tests against the ray's shrinking interval [tmin, best_t].
+// WIDE: the 4-wide tree (sc.wide must not be null).
+template <int MODE, bool STATS, bool CURVES, bool WIDE = false>
+__device__ __forceinline__ bool traverse_mode(const DScene& sc, V3 o, V3 d, float tmin, float tmax, Hit& hit,
+                                              uint32_t* stack, uint32_t stride, TravStats& st, uint32_t* overflow, bool any_rt,
+                                              uint32_t* spill, uint32_t spill_stride) {
+  hit.slot = kNone;
+  hit.t = tmax, hit.u = 0.f, hit.v = 0.f;
+  const V3 inv(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  float best_t = tmax;
+  const bool occluded = walk_tree<WIDE>(
+      sc, SimpleStack{stack, stride, spill, spill_stride, overflow},
+      [&](const float4& w0, const float4& w1, const float4& w2, const float4& refs, uint32_t k[4]) {
+        if (STATS) st.nodes++;
+        wide_node_keys(w0, w1, w2, refs, o, make_float4(inv.x, inv.y, inv.z, 0.f), tmin, best_t, k);
+      },
+      [&](const float4& n0, const float4& n1, const float4& n2, uint32_t, uint32_t, bool& h0, bool& h1) {
+        if (STATS) st.nodes++;
+        float t0, t1;
+        box_test2(n0, n1, n2, o, inv, tmin, best_t, h0, h1, t0, t1);
+        return t1 < t0;
+      },
+      [&](uint32_t leaf) { return leaf_test<MODE, STATS, CURVES, WIDE>(sc, leaf, o, d, inv, tmin, best_t, hit, st, any_rt); });
+  if (occluded) return true;
+  if (WIDE) hit.slot = q_final_code(sc, hit.slot);
+  return hit.slot != kNone;
 }
 template <bool ANY, bool STATS, bool CURVES, bool WIDE = false>
 __device__ __forceinline__ bool traverse(const DScene& sc, V3 o, V3 d, float tmin, float tmax, Hit& hit,
                                          uint32_t* stack, uint32_t stride, TravStats& st, uint32_t* overflow, uint32_t* spill,
                                          uint32_t spill_stride) {
   return traverse_mode<ANY ? 1 : 0, STATS, CURVES, WIDE>(sc, o, d, tmin, tmax, hit, stack, stride, st, overflow, ANY, spill, spill_stride);
+}
+
+// A ray a query or the renderer follows: eight numbers (origin | tmin, direction | tmax), none NaN, origin and direction finite, a
+// direction other than zero, 0 <= tmin <= tmax (tmax may be +inf).  The direction's length is the caller's business: it is not
+// renormalised (that would change bits).
+__device__ __forceinline__ bool ray_active(const float4& o, const float4& d) {
+  const bool finite = isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z);
+  const bool nonzero = d.x != 0.0f || d.y != 0.0f || d.z != 0.0f;
+  return finite && nonzero && o.w >= 0.0f && d.w >= o.w;  // (a NaN tmin or tmax fails both comparisons)
 }
 
 }  // namespace pb

@@ -105,37 +105,6 @@ enum : uint32_t { kStIdle = 0, kStNode = 1, kStTri = 2, kStCurve = 3, kStDone = 
 constexpr int kSuspCur = 4, kSuspMeta = 5, kSuspStack = kSuspHeaderWords;
 constexpr uint32_t kTagShadow = 0x80000000u, kTagNoSuspend = 0x40000000u, kTagResume = 0x20000000u, kTagHeld = 0x10000000u;
 
-// Traversal stack of one lane, and THE rule of where an entry lives: the first LDS entries in LDS (lds[i * stride]), deeper ones
-// in a per-thread global area (spill[(i - LDS) * spill_stride]), none at or past kStackDepth (the overflow flag is raised: the
-// launch's result is discarded).  Keeping the LDS part small is what lets 6 blocks (24 waves) share a CU.
-template <int LDS>
-struct PvStack {
-  uint32_t* lds;
-  uint32_t stride;
-  uint32_t* spill;
-  uint32_t spill_stride;
-  uint32_t* overflow;
-  // index of entry pos in lds / in spill
-  template <typename I>
-  __device__ __forceinline__ uint32_t lds_at(I pos) const { return (uint32_t)pos * stride; }
-  template <typename I>
-  __device__ __forceinline__ uint32_t spill_at(I pos) const { return (uint32_t)(pos - (I)LDS) * spill_stride; }
-  // CHECKED = false: the caller knows that pos < kStackDepth
-  template <bool CHECKED = true, typename I>
-  __device__ __forceinline__ void put(I pos, uint32_t ref) const {
-    if (pos < (I)LDS) lds[lds_at(pos)] = ref;
-    else if (!CHECKED || pos < (I)kStackDepth) spill[spill_at(pos)] = ref;
-    else *overflow = 1u;
-  }
-  template <typename I>
-  __device__ __forceinline__ uint32_t get(I pos) const { return pos < (I)LDS ? lds[lds_at(pos)] : spill[spill_at(pos)]; }
-  __device__ __forceinline__ void push(int& sp, uint32_t ref) const {
-    if (sp < LDS) lds[lds_at(sp)] = ref, sp++;
-    else if (sp < kStackDepth) spill[spill_at(sp)] = ref, sp++;
-    else *overflow = 1u;
-  }
-};
-
 // the ray's RayFrame from LDS (10 words per lane, frame[k * stride]; trace_pv stores it when the ray is fetched)
 __device__ __forceinline__ RayFrame frame_load(const float* frame, uint32_t stride) {
   RayFrame f;
@@ -165,7 +134,7 @@ __device__ __forceinline__ void trace_pv(const DScene& sc, uint32_t n, uint32_t*
   // top / ntop (binary tree): LDS copy of nodes 0 .. ntop-1 (the breadth-first top of the tree, 64 bytes each), or none
   // frame (CURVES): 10 words per lane in LDS (frame[k * stride]), the ray's RayFrame, written when the ray is fetched
   constexpr int kLds = pv_lds_stack<CURVES, WIDE>();  // stack entries of this lane that live in LDS
-  const PvStack<kLds> stk = {stk_base, stride, spill, spill_stride, overflow};
+  const TravStack<kLds> stk = {stk_base, stride, spill, spill_stride, overflow};
   const uint32_t lane = __lane_id();
   // number of set bits of a wave mask below this lane (v_mbcnt: no per-lane mask has to stay in registers)
   auto rank_in = [](unsigned long long m) {

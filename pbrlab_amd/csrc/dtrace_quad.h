@@ -15,8 +15,8 @@
 // for the pop that follows (+12 % on the hook kernels: the copies and the ballot cost more instructions than the load they save);
 // one loop with one item -- node or leaf -- per turn (+15 %); one leaf-test path for fetched and popped leaves (no change).  What
 // bounds a lone wave is the number of instructions it issues (~1 us per step with warm caches), not its loads.
-// The stack belongs to the quad (the leader's LDS column; entries are written by the lane that holds the child).  Box tests are
-// box_test4q's arithmetic for one child, the leaf test is tri_pair_accept: hits do not depend on the visiting order
+// The stack belongs to the quad (dtrace.h::TravStack over the leader's LDS column; entries are written by the lane that holds the
+// child).  Box tests are box_test4q's arithmetic for one child, the leaf test is tri_pair_accept: hits do not depend on the visiting order
 // (intersection contract, dtrace.h), so results are bit-identical to every other traversal's.
 #pragma once
 
@@ -67,12 +67,7 @@ __device__ __forceinline__ bool traverse_quad(const DScene& sc, V3 o, V3 d, floa
   const uint32_t lane = __lane_id(), j = lane & 3u, qbase = lane & ~3u;
   const V3 inv(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   const float4* const items = sc.wide;
-  auto put = [&](uint32_t pos, uint32_t ref) {
-    if (pos < (uint32_t)kSimpleLdsStack) stack[pos * stride] = ref;
-    else if (pos < (uint32_t)kStackDepth) spill[(pos - (uint32_t)kSimpleLdsStack) * spill_stride] = ref;
-    else *overflow = 1u;
-  };
-  auto get = [&](uint32_t pos) { return pos < (uint32_t)kSimpleLdsStack ? stack[pos * stride] : spill[(pos - (uint32_t)kSimpleLdsStack) * spill_stride]; };
+  const SimpleStack stk = {stack, stride, spill, spill_stride, overflow};
   uint32_t sp = 0u, next = 0u;      // the root is always an inner node
   uint32_t holder = 4u;             // lane of the quad that has prefetched `next`'s item (4: nobody)
   float4 P0 = make_float4(0.f, 0.f, 0.f, 0.f), P1 = P0, P2 = P0, P3 = P0, P4 = P0;  // this lane's prefetched child item
@@ -105,7 +100,7 @@ __device__ __forceinline__ bool traverse_quad(const DScene& sc, V3 o, V3 d, floa
       // the other hit children go on the quad's stack, farthest first: each by the lane that holds it
       if (h && key != kmin) {
         const uint32_t farther = (k1 != kWideMiss && k1 > key ? 1u : 0u) + (k2 != kWideMiss && k2 > key ? 1u : 0u) + (k3 != kWideMiss && k3 > key ? 1u : 0u);
-        put(sp + farther, ref);
+        stk.put(sp + farther, ref);
       }
       sp += nhit - 1u;
       if (sp > (uint32_t)kStackDepth) sp = (uint32_t)kStackDepth;
@@ -122,7 +117,7 @@ __device__ __forceinline__ bool traverse_quad(const DScene& sc, V3 o, V3 d, floa
       if (next == kEmptyChild) {
         if (sp == 0u) return occluded;
         sp--;
-        next = get(sp);  // (the four lanes read the same word)
+        next = stk.get(sp);  // (the four lanes read the same word)
         holder = 4u;
       }
       if (!(next & kLeafBit)) break;

@@ -26,8 +26,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_features_emissi
 // launch_features' grid and its rule for <CURVES, WIDE> (features.hip)
 void launch_features_emission(hipStream_t s, const DScene& sc, const FeatureArgs& a, float4* emission, const Knobs& k) {
   if (!a.npix || !a.npass) return;
-  uint32_t g = (a.npix + kBlock - 1) / kBlock;
-  g = g < kFeatureGridCap ? g : kFeatureGridCap;
+  const uint32_t g = feature_grid<kBlock>(a.npix);
   with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_features_emission<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a, emission); }, sc, k);
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "dscene.h"
+#include "kernels.h"
 #include "knobs.h"
 
 namespace pb {
@@ -30,6 +31,15 @@ struct FeatureArgs {
 };
 constexpr uint32_t kFeatureBlocksPerCU = 4;  // 40 KB of LDS stack per block: four blocks per CU = four waves per SIMD, 128 VGPRs
 constexpr uint32_t kFeatureGridCap = 4096;   // (the spill area of the one-ray-per-lane grids, kernels.h::kSpillWords)
+// grid of a one-query-per-lane kernel of this launch class (k_features, k_features_emission, k_motion, k_query_nearest, k_signed_query,
+// k_all_hits) over n queries: blocks of BLOCK lanes, at most kFeatureGridCap of them, each thread with a stack of its own in the spill
+// area (kernels.h::kSpillWords, which is why that header is included here)
+template <int BLOCK>
+inline uint32_t feature_grid(uint32_t n) {
+  static_assert((size_t)(kStackDepth - kSimpleLdsStack) * kFeatureGridCap * BLOCK <= kSpillWords, "spill area: one stack per thread of the grid");
+  const uint32_t g = (n + BLOCK - 1) / BLOCK;
+  return g < kFeatureGridCap ? g : kFeatureGridCap;
+}
 void launch_features(hipStream_t s, const DScene& sc, const FeatureArgs& a, const Knobs& k);
 
 // The filter's parameters as the kernels take them (pbrhip_denoise has resolved the defaults).

@@ -19,8 +19,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_features(DScene
 // the <CURVES, WIDE> of the tree the render of this scene walks; the binary tree's instance always carries the curve code (the hooks' rule)
 void launch_features(hipStream_t s, const DScene& sc, const FeatureArgs& a, const Knobs& k) {
   if (!a.npix || !a.npass) return;
-  uint32_t g = (a.npix + kBlock - 1) / kBlock;
-  g = g < kFeatureGridCap ? g : kFeatureGridCap;
+  const uint32_t g = feature_grid<kBlock>(a.npix);
   with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_features<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc, k);
 }
 

@@ -176,12 +176,6 @@ constexpr uint32_t kTraceHeads = PB_TRACE_HEADS;  // heads of k_trace's ray queu
 constexpr uint32_t kRingSlots = 16;  // iterations of one group the host may have enqueued and not yet heard of
 constexpr uint32_t kWaveLogWaves = 8192, kWaveLogLaunches = 64;  // PBRHIP_WAVE_LOG buffer: launches x waves x 4 words  // concurrent path groups (one HIP stream each)
 
-struct HookHit {  // == pbrhip_hit == TraceResult (raytracer.h:9-17)
-  float ng[3];
-  float t, u, v;
-  uint32_t instance_id, geom_id, prim_id;
-};
-
 void launch_generate(hipStream_t s, const PathState& P, uint32_t npaths);  // clears the radiance of the group's paths (PathState::slot0 ...)
 // a user camera: clears the radiance AND stores each path's first ray, throughput (1, 1, 1 | pdf +inf: MIS weight 1),
 // generator state (hold 0) and trace-queue entry -- the group then runs its first bounce as an ordinary one (PathState::first = 0)

@@ -1814,19 +1814,7 @@ __global__ __launch_bounds__(kBlock) void k_layer_unpack_add(const uint32_t* __r
 
 // ------------------------------------------------------------------ test hooks: Raytracer::FirstHitTrace1 / AnyHit1
 // Same persistent phase-voting traversal as the render path, fed from a caller-supplied ray array.
-__device__ __forceinline__ HookHit hook_result(const DScene& sc, V3 o, V3 d, const Hit& h) {
-  HookHit r;  // TraceResult defaults (raytracer.h:9-17)
-  r.ng[0] = 1.f, r.ng[1] = 0.f, r.ng[2] = 0.f, r.t = 1.f, r.u = 0.f, r.v = 0.f;
-  r.instance_id = r.geom_id = r.prim_id = kNone;
-  if (h.slot != kNone) {
-    Surface s = make_surface(sc, o, d, h);
-    const ShadeRec& sr = sc.shade[h.slot & kHitSlotMask];
-    r.ng[0] = s.n_g.x, r.ng[1] = s.n_g.y, r.ng[2] = s.n_g.z;
-    r.t = h.t, r.u = h.u, r.v = h.v;
-    r.instance_id = sr.instance_id, r.geom_id = sr.geom_id, r.prim_id = sr.prim_id;
-  }
-  return r;
-}
+// (a hit as the caller sees it: dshade.h::hook_result)
 struct HookSink {
   static constexpr bool kWalk = false, kSplit = false, kSuspend = false;
   const DScene& sc;

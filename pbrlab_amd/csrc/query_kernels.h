@@ -14,7 +14,7 @@ namespace pb {
 // n rays (two 16-byte words each: org | tmin, dir | tmax) through the production traversal (dtrace_pv.h::trace_pv), the <CURVES, WIDE>
 // instance the render of this scene walks.  occ != null: any-hit, n occlusion bytes, ident and hits are not used; else closest-hit:
 // ident (4 words per ray: slot, bits of u, v, t; a miss (kNone, 0, 0, 0)) and / or hits (HookHit), either may be null.  An inactive ray
-// (query.hip::ray_active) is a miss / not occluded.  counts: kCntNum zeroed words (queue head + overflow flag); spill: kSpillWords.
+// (dtrace.h::ray_active) is a miss / not occluded.  counts: kCntNum zeroed words (queue head + overflow flag); spill: kSpillWords.
 struct RayQueryArgs {
   const float4* rays;
   uint32_t n;

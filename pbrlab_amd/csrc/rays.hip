@@ -15,14 +15,6 @@ namespace pb {
 
 constexpr int kBlock = 256;
 
-// A ray the renderer follows: eight numbers, none NaN, origin and direction finite, a direction other than zero, 0 <= tmin <= tmax
-// (tmax may be +inf).  The direction's length is the caller's business: it is not renormalised (that would change bits).
-__device__ __forceinline__ bool ray_active(const float4& o, const float4& d) {
-  const bool finite = isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z);
-  const bool nonzero = d.x != 0.0f || d.y != 0.0f || d.z != 0.0f;
-  return finite && nonzero && o.w >= 0.0f && d.w >= o.w;  // (a NaN tmin or tmax fails both comparisons)
-}
-
 // word index of the ray of (pixel gpix, pass)
 __device__ __forceinline__ size_t ray_word(const RaySource& r, uint32_t width, uint32_t gpix, uint32_t pass) {
   const size_t plane = r.ray_passes == 1u ? 0u : (size_t)(pass - r.base_pass);

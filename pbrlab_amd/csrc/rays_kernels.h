@@ -23,7 +23,7 @@ struct RaySource {
 constexpr uint32_t kMaxCameraDraws = 16;
 
 // k_generate_camera's twin (kernels.h::launch_generate_camera): clears the radiance and stores each path's first ray as given (tmin and
-// tmax included), throughput (1, 1, 1 | pdf +inf), generator state (hold 0) and trace-queue entry.  An inactive ray (ray_active below)
+// tmax included), throughput (1, 1, 1 | pdf +inf), generator state (hold 0) and trace-queue entry.  An inactive ray (dtrace.h::ray_active)
 // becomes a certain miss with throughput 0: its sample adds (0, 0, 0, 1).
 void launch_generate_rays(hipStream_t s, const PathState& P, const RaySource& r, uint32_t npaths);
 

@@ -100,8 +100,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_signed_query(DS
       pt = a.points[i];
     }
     const V3 p(pt.x, pt.y, pt.z);
-    Nearest best;
-    best.d2 = pt.w * pt.w, best.u = 0.0f, best.v = 0.0f, best.q = V3(0.0f), best.slot = kNone, best.feat = kFeatCurve;
+    Nearest best = nearest_none(pt);
     if (point_active(pt)) nearest_traverse<CURVES, WIDE>(sc, p, best, stk + threadIdx.x, kBlock, &overflow, a.spill + blockIdx.x * kBlock + threadIdx.x,
                                                          gridDim.x * kBlock);
     const bool found = best.slot != kNone;
@@ -117,8 +116,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_signed_query(DS
       a.grid_sd[i] = sd.w;
       continue;
     }
-    if (a.ident) a.ident[i] = found ? make_uint4(best.slot, __float_as_uint(best.u), __float_as_uint(best.v), __float_as_uint(sqrtf(best.d2))) : make_uint4(kNone, 0u, 0u, 0u);
-    if (a.closest) a.closest[i] = found ? make_float4(best.q.x, best.q.y, best.q.z, best.d2) : make_float4(0.f, 0.f, 0.f, 0.f);
+    nearest_store(best, i, a.ident, a.closest);
     if (a.sd) a.sd[i] = sd;
   }
   if (overflow) *a.overflow = 1u;
@@ -126,11 +124,9 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_signed_query(DS
 
 // k_query_nearest's launch class (256 lanes, the LDS stack plus the spill area, at most kFeatureGridCap blocks); the instance is the
 // hooks' (variants.h::with_hook_tree): the answer does not depend on the tree
-static_assert((size_t)(kStackDepth - kSimpleLdsStack) * kFeatureGridCap * kBlock <= kSpillWords, "k_signed_query's spill area (one stack per thread of its grid)");
 void launch_signed(hipStream_t s, const DScene& sc, const SignedArgs& a, const Knobs& k) {
   if (!a.n) return;
-  uint32_t g = (a.n + kBlock - 1) / kBlock;
-  g = g < kFeatureGridCap ? g : kFeatureGridCap;
+  const uint32_t g = feature_grid<kBlock>(a.n);
   with_hook_tree([&](auto c, auto w) {
     if (a.grid) hipLaunchKernelGGL((k_signed_query<c, w, true>), dim3(g), dim3(kBlock), 0, s, sc, a);
     else hipLaunchKernelGGL((k_signed_query<c, w, false>), dim3(g), dim3(kBlock), 0, s, sc, a);

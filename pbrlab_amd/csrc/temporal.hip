@@ -68,8 +68,7 @@ __global__ __launch_bounds__(kBlock, kFeatureBlocksPerCU) void k_motion(DScene s
 // the <CURVES, WIDE> of launch_features (features.hip)
 void launch_motion(hipStream_t s, const DScene& sc, const MotionArgs& a, const Knobs& k) {
   if (!a.npix) return;
-  uint32_t g = (a.npix + kBlock - 1) / kBlock;
-  g = g < kFeatureGridCap ? g : kFeatureGridCap;
+  const uint32_t g = feature_grid<kBlock>(a.npix);
   with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_motion<c, w>), dim3(g), dim3(kBlock), 0, s, sc, a); }, sc, k);
 }
 

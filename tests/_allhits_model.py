@@ -21,7 +21,7 @@ def as_rays(rays):
 
 
 def ray_active(r):
-    """query.hip::ray_active: no NaN, origin and direction finite, a direction other than zero, 0 <= tmin <= tmax"""
+    """dtrace.h::ray_active: no NaN, origin and direction finite, a direction other than zero, 0 <= tmin <= tmax"""
     with np.errstate(all="ignore"):
         return (np.isfinite(r[:, 0:3]).all(axis=1) & np.isfinite(r[:, 4:7]).all(axis=1) & (r[:, 4:7] != 0).any(axis=1) & (r[:, 3] >= 0) & (r[:, 7] >= r[:, 3]))
 
@@ -104,7 +104,7 @@ def brute_force(rays, slots, shade, K, chunk=512):
 
 
 def binary_walk_all(nodes, ray, slots, shade):
-    """dallhits.h::all_traverse with COUNT over a binary tree, restated for one ray: nodes = BvhNode records
+    """dallhits.h::all_traverse (dtrace.h::walk_tree with its box tests) with COUNT over a binary tree, restated for one ray: nodes = BvhNode records
     (tests/_lbvh_model.py::NODE_DT, the stored boxes), children whose slab interval -- box_test2's, widened by 2^-16 -- meets [tmin, tmax],
     the nearer first, the other pushed.  -> (the largest number of live stack entries, the number of accepted hits)"""
     leaf_bit, empty = 0x80000000, 0xFFFFFFFF

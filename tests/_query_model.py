@@ -210,7 +210,7 @@ def soup_points(tris, seed, n=3000):
 
 
 def binary_walk(nodes, point, d2_row):
-    """query.hip::nearest_traverse over a binary tree, restated for one query: nodes = BvhNode records (tests/_lbvh_model.py::NODE_DT, the
+    """dnearest.h::nearest_traverse over a binary tree, restated for one query: nodes = BvhNode records (tests/_lbvh_model.py::NODE_DT, the
     stored boxes), point = (x, y, z, max_dist), d2_row = the contract's D2 of every slot in leaf order.  Children whose box distance does
     not exceed the best D2 so far, the nearer first, the other pushed.  -> (the largest number of live stack entries, the best D2)"""
     leaf_bit, empty = 0x80000000, 0xFFFFFFFF
