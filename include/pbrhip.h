@@ -687,8 +687,8 @@ int pbrhip_trace_any_device(pbrhip_scene*, const void* d_rays, size_t n, void* s
  * scales of 1e7 between axes and on flat scenes (measured: at most 5.10 units; DESIGN.md §19 "Domain").  A decade outside it nn
  * underflows or overflows: the answer is still the contract's, bit for bit, but no longer the distance.
  * The device variant orders the read of d_points behind `stream` as above.  Errors as the ray queries'.
- * Not provided: the ribbon's radius, k-nearest queries, a multi-GPU twin, asynchronous return.  (Signed distance and all-hits ray queries:
- * below.) */
+ * Not provided: the ribbon's radius, a multi-GPU twin, asynchronous return.  (Signed distance, all-hits ray queries and the K nearest
+ * primitives of a point: below.) */
 typedef struct {
   float p[3];
   float max_dist;
@@ -726,7 +726,7 @@ int pbrhip_nearest_point_device(pbrhip_scene*, const void* d_points, size_t n, v
  * Grid: the same query at p = origin + (float)(i, j, k) * spacing (multiply, then add, each rounded once) for i < dims[0], j < dims[1],
  * k < dims[2], all with max_dist; d_sd: dims[2] x dims[1] x dims[0] floats (x fastest; 4-byte aligned), the signed distance alone, 0
  * where nothing lies within max_dist.  A dims of 0: PBRHIP_OK and nothing written; 2^31 points or more: PBRHIP_EINVAL.
- * Not provided: the generalized winding number as a sign method, welding by position, the ribbon's radius, k-nearest, a multi-GPU twin. */
+ * Not provided: the generalized winding number as a sign method, welding by position, the ribbon's radius, a multi-GPU twin. */
 typedef struct {
   uint32_t triangles;           /* triangle slots of the scene */
   uint32_t vertices;            /* distinct (object, index) vertices they use */
@@ -777,11 +777,53 @@ int pbrhip_scene_read_pseudonormals(pbrhip_scene*, float* out, uint32_t* num_slo
  * uncommitted or stale scene; PBRHIP_EOVERFLOW: a traversal stack overflow; n == 0: PBRHIP_OK.  The host variant stages rays and outputs
  * through device memory as pbrhip_nearest_point does.
  * Not provided: more than PBRHIP_ALL_HITS_MAX listed hits per ray (count says how many there are; peel on from the last t), any-hit
- * filters or callbacks, k-nearest points, a multi-GPU twin, asynchronous return. */
+ * filters or callbacks, a multi-GPU twin, asynchronous return. */
 #define PBRHIP_ALL_HITS_MAX 32u
 int pbrhip_trace_all(pbrhip_scene*, const pbrhip_ray* rays, size_t n, uint32_t max_hits, uint32_t* count, uint32_t* ident);
 int pbrhip_trace_all_device(pbrhip_scene*, const void* d_rays, size_t n, uint32_t max_hits, void* stream, uint32_t* d_count,
                             uint32_t* d_ident);
+
+/* ---- k-nearest queries ----
+ * "Every primitive within my contact radius, or the few nearest": collision and contact candidates, attachment of hair roots or cloth to
+ * a moving body, smoothing over neighbours.  pbrhip_nearest_point above gives the one nearest; this gives the K nearest and how many lie
+ * within the radius, in one launch, without reading the slots back.
+ * A UNIT is what a leaf of the tree tests once: a triangle, or one of the four linear pieces of a curve's cubic.  For a query
+ * (p, max_dist) a unit's candidate is pbrhip_nearest_point's D2, u, v, q -- the same functions, the same operations, the same bits, the
+ * validation clamp D2 = max(d2_raw, L) included.  C(p) is the set of units with D2 <= max_dist * max_dist (rounded once; a NaN never
+ * qualifies; max_dist = +inf: no bound), ordered by the key
+ *   (D2 ascending; then the canonical primitive id -- what PBRHIP_ID_PRIMITIVE reports -- ascending; then sub ascending),
+ * sub being the piece's index inside its cubic, 0 for a triangle, so the order is total.  (This library numbers the canonical ids per
+ * unit, in (instance, geometry, primitive, sub) order: the id alone decides, and among the pieces of one cubic it decides as sub would.
+ * u could not be the last key as in pbrhip_trace_all: pieces k and k + 1 of a cubic meet in a joint, and a point nearest to that joint
+ * gives both the same D2 and the same u = (k + 1) / 4.)  Outputs for query i with max_k = K:
+ *   count[i]            |C(p)|: every unit within the radius, NOT capped by K
+ *   ident[i * K + j]    4 words each, j < K: for j < min(|C|, K) the j-th unit of that order in pbrhip_nearest_point's format (slot, then
+ *                       the bits of u, v, sqrtf(D2); pbrhip_scene_object_ids_device takes the n * K entries as they are); every
+ *                       remaining entry (PBRHIP_NONE, 0, 0, 0)
+ *   closest[i * K + j]  4 floats each: the listed unit's closest point q, then D2; every remaining entry zeros
+ * THE ORDER IS D2's, NOT THE DISTANCE's: sqrtf merges distinct D2, so two successive entries may show equal distances while their D2
+ * -- and hence their order -- differ (on the 430-triangle test soup 35 of 3000 queries have such a pair among their first 33 entries).
+ * A caller who needs the strict order reads closest's w.
+ * Entry 0 is pbrhip_nearest_point's answer byte for byte: that query gives a shared minimum to the smaller canonical id as well, two
+ * pieces of one cubic at their joint included.  The result is a property of (point, primitive set) alone: it does
+ * not depend on builder, tree (PBRHIP_WIDE=0 / 1), refit or visiting order.  An inactive query (a NaN or infinite coordinate, max_dist
+ * NaN or below 0) has count 0 and rows of misses, with no fault.
+ * max_k is in [0, PBRHIP_K_NEAREST_MAX].  Any output may be NULL, with two restrictions: closest requires ident (the list lives in the
+ * ident rows while the kernel runs), and max_k == 0 requires count (ident and closest are then ignored); max_k > 0 with ident == NULL is
+ * a pure count as well.  Without count the traversal's bound shrinks to the K-th entry's D2 once the list is full (K = 1: the
+ * nearest-point traversal); with count it stays max_dist^2 and every box within the radius is entered, so ask for the count only when it
+ * is wanted.  count with max_dist = +inf is allowed: it counts every unit whose D2 is not a NaN, at the price of a walk of the whole tree.
+ * Stream ordering, the 16-byte alignment of d_points, d_ident and d_closest (d_count: 4 bytes), refusals and error codes are
+ * pbrhip_trace_all_device's: PBRHIP_EINVAL before any device work for a NULL scene, with n > 0 NULL points or no usable output, closest
+ * without ident ("NULL" in pbrhip_last_error), max_k > PBRHIP_K_NEAREST_MAX ("max_k"), n >= 2^31 or n * max_k >= 2^31 ("too many"), a
+ * misaligned device pointer ("aligned"); PBRHIP_ESTATE: an uncommitted or stale scene or a replica; PBRHIP_EOVERFLOW: a traversal stack
+ * overflow; n == 0: PBRHIP_OK.  The host variant stages points and outputs through device memory as pbrhip_trace_all does.
+ * Not provided: more than PBRHIP_K_NEAREST_MAX listed units per query (count says how many there are), the ribbon's radius, a multi-GPU
+ * twin, asynchronous return, filters or callbacks. */
+#define PBRHIP_K_NEAREST_MAX 32u
+int pbrhip_k_nearest(pbrhip_scene*, const pbrhip_point* points, size_t n, uint32_t max_k, uint32_t* count, uint32_t* ident, float* closest);
+int pbrhip_k_nearest_device(pbrhip_scene*, const void* d_points, size_t n, uint32_t max_k, void* stream, uint32_t* d_count,
+                            uint32_t* d_ident, float* d_closest);
 
 /* ---- multi-GPU (new: the reference has one process and std::threads, render.cc:203-238) ----
  * Pixels are independent, so the only exchange is the RenderLayer at the end of a frame: rank r renders the pixel blocks

@@ -423,6 +423,22 @@ public:
   void TraceAllDevice(const void* d_rays, size_t n, uint32_t max_hits, uint32_t* d_count, uint32_t* d_ident, void* stream = nullptr) const {
     Check(pbrhip_trace_all_device(h_, d_rays, n, max_hits, stream, d_count, d_ident));
   }
+  // K-nearest queries (include/pbrhip.h, "k-nearest queries"): per query point the number of primitives within max_dist -- count, not
+  // capped -- and the max_k <= PBRHIP_K_NEAREST_MAX nearest of them, ordered by (D2, canonical primitive id, piece index), in
+  // NearestPoint's formats -- ident and closest, max_k entries of 4 words per query, (PBRHIP_NONE, 0, 0, 0) and zeros past the count.
+  // Any output may be null, but closest needs ident and max_k == 0 needs count.  KNearest takes host arrays (count resized to n, ident
+  // and closest to 4 n max_k), KNearestDevice DEVICE pointers on the scene's GPU, read after the work already enqueued on `stream`.
+  void KNearest(const std::vector<pbrhip_point>& points, uint32_t max_k, std::vector<uint32_t>* count, std::vector<uint32_t>* ident,
+                std::vector<float>* closest) const {
+    if (count) count->assign(points.size(), 0u);
+    if (ident) ident->assign(4 * points.size() * max_k, 0u);
+    if (closest) closest->assign(4 * points.size() * max_k, 0.0f);
+    Check(pbrhip_k_nearest(h_, points.data(), points.size(), max_k, count ? count->data() : nullptr, ident ? ident->data() : nullptr,
+                           closest ? closest->data() : nullptr));
+  }
+  void KNearestDevice(const void* d_points, size_t n, uint32_t max_k, uint32_t* d_count, uint32_t* d_ident, float* d_closest, void* stream = nullptr) const {
+    Check(pbrhip_k_nearest_device(h_, d_points, n, max_k, stream, d_count, d_ident, d_closest));
+  }
   // Signed distance (include/pbrhip.h, "signed distance"): the nearest-point queries with a sign.  sd: 4 floats per query, the winning
   // feature's pseudonormal and the signed distance (outside positive); any of the three outputs may be null.  The grid variant asks at
   // origin + (i, j, k) * spacing and writes dims[2] x dims[1] x dims[0] floats, the signed distance alone.  SignedDistanceInfo builds

@@ -39,6 +39,7 @@ EXPORTS = [
     "pbrhip_scene_signed_distance_info", "pbrhip_signed_distance", "pbrhip_signed_distance_device", "pbrhip_signed_distance_grid_device",
     "pbrhip_scene_read_pseudonormals",
     "pbrhip_trace_all", "pbrhip_trace_all_device",
+    "pbrhip_k_nearest", "pbrhip_k_nearest_device",
 ]
 
 
@@ -104,6 +105,8 @@ def lib():
         _lib.pbrhip_scene_read_pseudonormals.argtypes = [vp, vp, vp]
         _lib.pbrhip_trace_all.argtypes = [vp, vp, C.c_size_t, u32, vp, vp]
         _lib.pbrhip_trace_all_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp]
+        _lib.pbrhip_k_nearest.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp]
+        _lib.pbrhip_k_nearest_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp, vp]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

@@ -152,6 +152,16 @@ def _all_hits_k(max_hits):
     return int(max_hits)
 
 
+K_NEAREST_MAX = 32  # PBRHIP_K_NEAREST_MAX
+
+
+def _k_nearest_k(max_k):
+    """max_k of a k-nearest query as an int in [0, K_NEAREST_MAX]; ValueError here, before any C call"""
+    if isinstance(max_k, bool) or int(max_k) != max_k or not 0 <= int(max_k) <= K_NEAREST_MAX:
+        raise ValueError(f"max_k must be an integer in [0, {K_NEAREST_MAX}], not {max_k!r}")
+    return int(max_k)
+
+
 def _device_stream(stream, *arrays):
     """The hipStream_t of a *Device update call: as given (an integer, or an object with cuda_stream); None: torch's current stream when
     an argument is a tensor (torch is then the caller's: this module does not import it otherwise), else the null stream."""
@@ -703,6 +713,61 @@ class Scene:
         pc, pi = _query_out(count, self, (n,), "int32", "count"), _query_out(ident, self, (n, max_hits, 4), "int32", "ident")
         _chk(self.L.pbrhip_trace_all_device(self.h, ptr, n, max_hits, _device_stream(stream, rays), pc, pi))
         return count, ident
+
+    # k-nearest queries
+    def KNearest(self, points, max_k):
+        """pbrhip_k_nearest: per query point the number of primitives within max_dist and the max_k nearest of them -> (count, ident,
+        closest).  points: POINT_DT records or (n, 4) float32 rows x, y, z, max_dist (inf: no bound; host memory).  count: (n,) uint32,
+        every unit with D2 <= max_dist^2, not capped by max_k; ident: (n, max_k, 4) uint32, per query the units ordered by (D2, canonical
+        primitive id, piece index) as slot, bits of u, v, sqrt(D2) -- NearestPoint's format, and ident[:, 0] is its answer --, the
+        entries past count (NONE, 0, 0, 0); closest: (n, max_k, 4) float32 = the closest point | D2 of each listed entry, zeros past
+        them.  The order is D2's: sqrt merges distinct D2, closest[..., 3] has the strict order.  max_k in [0, K_NEAREST_MAX].
+        Anything else than records or (n, 4) rows, or a max_k outside that: ValueError, before any C call."""
+        max_k = _k_nearest_k(max_k)
+        points = np.asarray(points)
+        if points.dtype.names:
+            pts = np.ascontiguousarray(points, POINT_DT).reshape(-1)
+        elif points.ndim == 2 and points.shape[1] == 4:
+            pts = np.ascontiguousarray(points, np.float32)
+        else:
+            raise ValueError(f"points must be POINT_DT records or have the shape (n, 4), not {points.shape}")
+        n = len(pts)
+        count, ident, closest = np.zeros(n, np.uint32), np.zeros((n, max_k, 4), np.uint32), np.zeros((n, max_k, 4), np.float32)
+        _chk(self.L.pbrhip_k_nearest(self.h, C.c_void_p(pts.ctypes.data), n, max_k, C.c_void_p(count.ctypes.data), C.c_void_p(ident.ctypes.data),
+                                     C.c_void_p(closest.ctypes.data)))
+        return count, ident, closest
+
+    def KNearestDevice(self, points, max_k, count=True, ident=True, closest=False, stream=None):
+        """pbrhip_k_nearest_device: KNearest for n points in memory of the scene's GPU -> (count, ident, closest).  points and stream as
+        NearestPointDevice's.  count: (n,) int32, ident: (n, max_k, 4) int32 -- ObjectIds takes its (1, n * max_k, 4) view --, closest:
+        (n, max_k, 4) float32, each True (allocated with torch; points must be a tensor), a tensor or a device pointer (an int) written
+        in place, or False / None: not computed (returned as None).  With max_k == 0 there is neither ident nor closest; closest needs
+        ident (the list lives in its rows); count and ident may not both be left out.  Without count the traversal's bound shrinks to
+        the max_k-th entry once the list is full; with it every box within max_dist is entered (max_dist = inf: the whole tree).
+        Device pointers of points, ident and closest must be 16-byte aligned."""
+        max_k = _k_nearest_k(max_k)
+        ptr, n = _query_array(points, self, 4, "points")
+        count, ident, closest = (None if a is False else a for a in (count, ident, closest))
+        if max_k == 0:
+            ident = closest = None
+        if count is None and ident is None:
+            raise ValueError("KNearestDevice: neither count nor ident is wanted" + (" (max_k == 0 leaves the count)" if max_k == 0 else ""))
+        if closest is not None and ident is None:
+            raise ValueError("KNearestDevice: closest needs ident: the list lives in the ident rows")
+        if count is True or ident is True or closest is True:
+            if not hasattr(points, "data_ptr"):
+                raise TypeError("KNearestDevice: outputs are allocated only beside tensor points: pass tensors or device pointers")
+            import torch
+            if count is True:
+                count = torch.empty((n,), dtype=torch.int32, device=points.device)
+            if ident is True:
+                ident = torch.empty((n, max_k, 4), dtype=torch.int32, device=points.device)
+            if closest is True:
+                closest = torch.empty((n, max_k, 4), dtype=torch.float32, device=points.device)
+        pc, pi = _query_out(count, self, (n,), "int32", "count"), _query_out(ident, self, (n, max_k, 4), "int32", "ident")
+        pq = _query_out(closest, self, (n, max_k, 4), "float32", "closest")
+        _chk(self.L.pbrhip_k_nearest_device(self.h, ptr, n, max_k, _device_stream(stream, points), pc, pi, pq))
+        return count, ident, closest
 
     # signed distance (DESIGN.md §20)
     def SignedDistance(self, points):

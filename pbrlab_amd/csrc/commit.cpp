@@ -111,7 +111,9 @@ static Material make_material(const HostMaterial& hm) {
   return m;
 }
 
-// Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.
+// Flattens the primitives in canonical (instance, geom, prim, sub) order: the index is the gid.  A gid thus names a UNIT -- a triangle,
+// or one piece of a cubic --, and the pieces of one cubic have ascending gids: dknearest.h::knearest_offer orders equal distances by
+// the gid alone and relies on both.  Whoever renumbers here gives that comparison its third key, sub, back.
 static int flatten_prims(const pbrhip_scene* s, std::vector<PrimRef>* prims) {
   for (uint32_t i = 0; i < s->instances.size(); i++)
     for (uint32_t g = 0; g < s->instances[i].material_ids.size(); g++) {
