@@ -3,7 +3,8 @@ reference's rules (SURVEY.md §8(a')) and not from the oracle's code.  Test infr
 
 Scope: untransformed triangle meshes; one receiver, a planar principled surface with any set of the non-subsurface closures
 (closure_set: Lambert, anisotropic GGX with its Fresnel tint, clearcoat; cycles-principled-shader.cc:244-412) in the shader's
-own tangent frame (branchless_onb); emitters and occluders with a black material; area lights with constant shading normals
+own tangent frame (branchless_onb), its base colour a parameter or a texture read per point (tests/_texture_model.py; Textured,
+texel_pieces); emitters and occluders with a black material; area lights with constant shading normals
 per face.  A camera ray that hits such a receiver gathers light along exactly one bounce:
 
   E(x) = sum over the light faces of  int_{V(x)}  f(w) Le (cos_p cos_l / d^2) [w_nee(y) + w_bsdf(y)] dA(y)     (Lambert)
@@ -69,6 +70,8 @@ class Mesh:
     material: dict                       # principled parameters (scenes.PRINCIPLED_DEFAULTS keys)
     emission: Optional[np.ndarray] = None  # (F,3) per-face Le, or None: not an emitter
     normals: Optional[np.ndarray] = None   # (V,3) per-vertex shading normals, or None (geometric)
+    texcoords: Optional[np.ndarray] = None     # (T,2) texture coordinates, looked up through texcoord_ids ...
+    texcoord_ids: Optional[np.ndarray] = None  # ... (F,3); an id may be 0xFFFFFFFF: that face then has none (tests/_texture_model.py)
 
 
 @dataclass
@@ -76,13 +79,22 @@ class Scene:
     meshes: List[Mesh]
     receiver: int = 0                    # index of the receiving (non-black) mesh
     occluders: List[int] = field(default_factory=list)   # convex black meshes that can shadow the lights
+    textures: List[np.ndarray] = field(default_factory=list)  # (H,W,C) images; a material's *_tex_id is an index into this list
 
 
 def build(scene, S: Scene, make_principled):
     """Replay S through the builder methods of pbrlab's Scene (both back ends: OracleScene / pbrlab_amd.Scene), one mesh +
-    local scene + identity instance per mesh, per-face light params where Le differs between faces."""
+    local scene + identity instance per mesh, per-face light params where Le differs between faces.  The textures come first and
+    the materials' texture ids are remapped to what AddTexture returned, as scenes.build_scene does."""
+    tex_ids = [scene.AddTexture(np.asarray(t, np.float32)) for t in S.textures]
     for m in S.meshes:
-        mid = scene.AddMaterialParam(make_principled(m.material))
+        mat = m.material
+        if tex_ids:
+            mat = dict(mat)
+            for k in ("base_color_tex_id", "subsurface_color_tex_id"):
+                if mat[k] != 0xFFFFFFFF:
+                    mat[k] = tex_ids[mat[k]]
+        mid = scene.AddMaterialParam(make_principled(mat))
         v4 = np.concatenate([np.asarray(m.verts, np.float32), np.ones((len(m.verts), 1), np.float32)], 1)
         f = np.asarray(m.faces, np.uint32)
         if m.normals is not None:
@@ -90,7 +102,11 @@ def build(scene, S: Scene, make_principled):
             nid = f
         else:
             n4, nid = None, None
-        mesh = scene.AddTriangleMesh(v4, n4, None, f, nid, None, np.full(len(f), mid, np.uint32))
+        if m.texcoord_ids is not None:
+            tc, tid = np.asarray(m.texcoords, np.float32), np.asarray(m.texcoord_ids, np.uint32)
+        else:
+            tc, tid = None, None
+        mesh = scene.AddTriangleMesh(v4, n4, tc, f, nid, tid, np.full(len(f), mid, np.uint32))
         ls = scene.CreateLocalScene()
         scene.AddMeshToLocalScene(ls, mesh)
         inst = scene.CreateInstance(ls, None)
@@ -206,26 +222,52 @@ def ggx_vndf_pdf(wi, wo, ax, ay):
     return np.where(ok, G1o * D * 0.25 / wo_[..., 2], 0.0)
 
 
-def specular_color(wi, wo, color, ior):
-    """cycles-principled-shader.cc:54-61: Fresnel tint with the half vector of (wi, wo)"""
-    h = wi + wo
-    h = h / np.linalg.norm(h, axis=-1, keepdims=True)
-    f0 = fresnel_dielectric_cos(1.0, ior)
-    fh = (fresnel_dielectric_cos(np.sum(h * wo, -1), ior) - f0) / (1.0 - f0)
+def specular_color(wi, wo, color, ior, shared=None, key=None):
+    """cycles-principled-shader.cc:54-61: Fresnel tint with the half vector of (wi, wo).  shared, key: a dict that keeps the Fresnel
+    term, which does not depend on the colour, under that key (see lobes)"""
+    if shared is not None and key in shared:
+        fh = shared[key]
+    else:
+        h = wi + wo
+        h = h / np.linalg.norm(h, axis=-1, keepdims=True)
+        f0 = fresnel_dielectric_cos(1.0, ior)
+        fh = (fresnel_dielectric_cos(np.sum(h * wo, -1), ior) - f0) / (1.0 - f0)
+        if shared is not None:
+            shared[key] = fh
     return color * (1 - fh[..., None]) + fh[..., None]
 
 
-def closure_set(mat):
-    """ParamToBsdf, cycles-principled-shader.cc:244-412, for a material without subsurface and without textures: the enabled
-    closures with their weights, or None per closure"""
+def closure_set(mat, base=None):
+    """ParamToBsdf, cycles-principled-shader.cc:244-412, for a material without subsurface: the enabled closures with their
+    weights, or None per closure.  base: None (the material's base_color parameter), or the base colours (N, 3) a textured material
+    reads at N points (:281-289; tests/_texture_model.py): the colour-valued weights (diffuse, the specular closure's color) then have
+    that shape.  Which closures exist must not depend on the point: the enabling tests are asserted to come out alike for all N."""
     sat = lambda v: min(max(float(v), 0.0), 1.0)  # noqa: E731
-    base = np.asarray(mat["base_color"], np.float64)
+    base = np.asarray(mat["base_color"] if base is None else base, np.float64)
     metallic, spec, transmission = float(mat["metallic"]), float(mat["specular"]), float(mat["transmission"])
     assert float(mat["subsurface"]) == 0, "the random-walk closure is modelled by tests/_sss_analytic.py, not here"
     diffuse_w = (1 - sat(metallic)) * (1 - sat(transmission))                       # :326-327
     final_transmission = sat(transmission) * (1 - sat(metallic))                    # :328-329
     specular_w = 1 - final_transmission                                             # :330
     out = dict(diffuse=None, specular=None, clearcoat=None)
+    if base.ndim == 2:
+        bright = base.mean(1) > CUT_OFF
+        assert bright.all() or not bright.any(), "the diffuse closure exists for some texels and not for others"
+        if bright.all() and diffuse_w > CUT_OFF:                                    # :338-342, per point
+            out["diffuse"] = base * diffuse_w
+        if specular_w > CUT_OFF and (spec > CUT_OFF or metallic > CUT_OFF):         # :374-394, per point
+            ior = 2.0 / (1.0 - np.sqrt(max(0.08 * spec, 0.0))) - 1.0
+            aspect = np.sqrt(max(1.0 - float(mat["anisotropic"]) * 0.9, 0.0))
+            r2 = float(mat["roughness"]) ** 2
+            y = base @ Y_WEIGHT
+            rho_tint = np.where(y[:, None] > 0, base / np.where(y > 0, y, 1.0)[:, None], 0.0)
+            tint = float(mat["specular_tint"])
+            color = (1 - metallic) * (0.08 * spec * ((1 - tint) * np.ones(3) + tint * rho_tint)) + metallic * base
+            out["specular"] = dict(weight=specular_w, ax=r2 / aspect, ay=r2 * aspect, ior=ior, color=color)
+        cc = float(mat["clearcoat"])
+        if cc > CUT_OFF:                                                            # :397-409
+            out["clearcoat"] = dict(weight=0.25 * cc, alpha=float(mat["clearcoat_roughness"]) ** 2, ior=1.5, color=np.full(3, 0.04))
+        return out
     if base.mean() > CUT_OFF and diffuse_w > CUT_OFF:                               # :338-342 (subsurface == 0 < cut-off)
         out["diffuse"] = base * diffuse_w
     if specular_w > CUT_OFF and (spec > CUT_OFF or metallic > CUT_OFF):             # :374-394
@@ -244,26 +286,30 @@ def closure_set(mat):
     return out
 
 
-def selection_weights(cl, wo):
+def selection_weights(cl, wo, shared=None):
     """FetchClosureSampleWeight, :63-112 (Q7): (w_diffuse, w_specular, w_clearcoat) per wo (...,3), each the luminance of the
-    closure's weight x SpecularColor(refl, wo) with refl = wo mirrored about the normal, normalised to sum 1"""
+    closure's weight x SpecularColor(refl, wo) with refl = wo mirrored about the normal, normalised to sum 1.  Colour-valued weights
+    per point (closure_set with base (N, 3)) must broadcast against wo's leading shape."""
     wo = np.asarray(wo, np.float64)
     refl = wo * np.array([-1.0, -1.0, 1.0])
     zero = np.zeros(wo.shape[:-1])
-    wd = zero + (float(Y_WEIGHT @ cl["diffuse"]) if cl["diffuse"] is not None else 0.0)
+    if cl["diffuse"] is not None and cl["diffuse"].ndim > 1:
+        wd = zero + cl["diffuse"] @ Y_WEIGHT
+    else:
+        wd = zero + (float(Y_WEIGHT @ cl["diffuse"]) if cl["diffuse"] is not None else 0.0)
     ws = wc = zero
     if cl["specular"] is not None:
         sp = cl["specular"]
-        ws = (sp["weight"] * specular_color(refl, wo, sp["color"], sp["ior"])) @ Y_WEIGHT
+        ws = (sp["weight"] * specular_color(refl, wo, sp["color"], sp["ior"], shared, "select specular")) @ Y_WEIGHT
     if cl["clearcoat"] is not None:
         c = cl["clearcoat"]
-        wc = (c["weight"] * specular_color(refl, wo, c["color"], c["ior"])) @ Y_WEIGHT
+        wc = (c["weight"] * specular_color(refl, wo, c["color"], c["ior"], shared, "select clearcoat")) @ Y_WEIGHT
     s = wd + ws + wc
     assert np.all(s > 0), "a receiver with no closure at all"
     return wd / s, ws / s, wc / s
 
 
-def lobes(cl, wi, wo, sel=None, parts=False):
+def lobes(cl, wi, wo, sel=None, parts=False, shared=None):
     """EvalBsdf (:114-155) and what SampleBsdf (:169-242) draws, per pair of local directions (...,3):
       f       the sum of the enabled closures, (...,3)
       q_rep   the pdf the shader reports, sum_k w_k pdf_k (GGX and clearcoat with Q15's extra 1 / cos_i)
@@ -271,9 +317,12 @@ def lobes(cl, wi, wo, sel=None, parts=False):
               density of ggx_vndf_pdf at their own alpha (the clearcoat REPORTS the GTR1 pdf but is SAMPLED from GTR2).
     wi may lie below the surface (the GGX sampler can put it there): the GGX closures are then 0, while LambertBrdfPdf
     (lambert.h:11-20) still returns f = 1 / pi and the NEGATIVE pdf cos_i / pi.
-    parts=True: the clearcoat's share of f is returned as a fourth value."""
+    parts=True: the clearcoat's share of f is returned as a fourth value.
+    shared: a dict that keeps the GGX and Fresnel terms, which do not depend on any colour, between calls for closure sets that differ in their
+    colours alone, at the same wi and wo."""
     wi, wo = np.asarray(wi, np.float64), np.asarray(wo, np.float64)
-    wd, ws, wc = sel if sel is not None else selection_weights(cl, wo)
+    shared = {} if shared is None else shared
+    wd, ws, wc = sel if sel is not None else selection_weights(cl, wo, shared)
     shape = np.broadcast(wi[..., 0], wo[..., 0]).shape
     f, q, p = np.zeros(shape + (3,)), np.zeros(shape), np.zeros(shape)
     ci = np.broadcast_to(wi[..., 2], shape)
@@ -283,17 +332,21 @@ def lobes(cl, wi, wo, sel=None, parts=False):
         p = p + wd * np.maximum(ci, 0.0) / np.pi
     if cl["specular"] is not None:
         sp = cl["specular"]
-        g, pdf = ggx_eval(wi, wo, sp["ax"], sp["ay"], 2)
-        f = f + sp["weight"] * specular_color(wi, wo, sp["color"], sp["ior"]) * g[..., None]
+        if "specular" not in shared:
+            shared["specular"] = ggx_eval(wi, wo, sp["ax"], sp["ay"], 2) + (ggx_vndf_pdf(wi, wo, sp["ax"], sp["ay"]),)
+        g, pdf, drawn = shared["specular"]
+        f = f + sp["weight"] * specular_color(wi, wo, sp["color"], sp["ior"], shared, "tint specular") * g[..., None]
         q = q + ws * pdf
-        p = p + ws * ggx_vndf_pdf(wi, wo, sp["ax"], sp["ay"])
+        p = p + ws * drawn
     if cl["clearcoat"] is not None:
         c = cl["clearcoat"]
-        g, pdf = ggx_eval(wi, wo, c["alpha"], c["alpha"], 1)
-        f_cc = c["weight"] * specular_color(wi, wo, c["color"], c["ior"]) * g[..., None]
+        if "clearcoat" not in shared:
+            shared["clearcoat"] = ggx_eval(wi, wo, c["alpha"], c["alpha"], 1) + (ggx_vndf_pdf(wi, wo, c["alpha"], c["alpha"]),)
+        g, pdf, drawn = shared["clearcoat"]
+        f_cc = c["weight"] * specular_color(wi, wo, c["color"], c["ior"], shared, "tint clearcoat") * g[..., None]
         f = f + f_cc
         q = q + wc * pdf
-        p = p + wc * ggx_vndf_pdf(wi, wo, c["alpha"], c["alpha"])
+        p = p + wc * drawn
     else:
         f_cc = np.zeros_like(f)
     return (f, q, p, f_cc) if parts else (f, q, p)
@@ -430,6 +483,60 @@ def gauss_legendre01(n):
     return 0.5 * (x + 1), 0.5 * w
 
 
+class Textured:
+    """A receiver mesh with a base-colour texture (H, W, C): the colour and the texture coordinates its points read, through
+    tests/_texture_model.py.  continuous: the faces agree on the texcoords of every vertex they share (a face without texcoord ids
+    reads its own barycentrics, which jump across its edges)."""
+
+    def __init__(self, mesh, tex):
+        import _texture_model as TM
+        self.TM, self.MUTANTS, self.mesh = TM, TM.MUTANTS, mesh
+        self.tex = np.asarray(tex, np.float64)
+        if self.tex.ndim == 2:
+            self.tex = self.tex[..., None]
+        faces = np.asarray(mesh.faces)
+        fi = np.repeat(np.arange(len(faces)), 3)
+        tu, tv = TM.texcoord(mesh, fi, np.tile([0.0, 1.0, 0.0], len(faces)), np.tile([0.0, 0.0, 1.0], len(faces)))
+        seen, self.continuous = {}, True
+        for vid, c in zip(faces.ravel(), zip(tu, tv)):
+            self.continuous &= np.allclose(seen.setdefault(int(vid), c), c, atol=1e-12)
+
+    def coords(self, x):
+        face, u, v = self.TM.barycentrics(self.mesh, x)
+        return self.TM.texcoord(self.mesh, face, u, v)
+
+    def base_color(self, x, mutant=None):
+        return self.TM.base_color(self.mesh, self.tex, x, mutant)
+
+
+def texel_pieces(tx: Textured, S: Scene, cam, xs, ys):
+    """Where a bilinear texture kinks inside pixel footprints.  The model's fetch is bilinear between the texel lines W u = 0 .. W and
+    H v = 0 .. H (the clamp begins at the outer ones), and within a face the texcoords are affine in the receiver point, which is
+    affine in the jitter for a receiver parallel to the image plane: per pixel the lines are straight in jitter space.
+    Returns ({pixel index: convex pieces of the unit jitter square cut along every line that crosses it}, affine (P,) bool: the
+    fourth corner of the footprint has the texcoords the other three predict -- False where a jump of the texcoords, or a receiver
+    that is not parallel to the image plane, breaks that; such pixels are not cut)."""
+    xs, ys = np.asarray(xs, np.float64), np.asarray(ys, np.float64)
+    cj = np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0], [1.0, 1.0]])
+    d = cam.dirs(xs[:, None], ys[:, None], cj[:, 0], cj[:, 1]).reshape(-1, 3)
+    m, _, t, _ = cast(S, cam.org, d)
+    assert np.all(m == S.receiver)
+    c = np.stack(tx.coords(cam.org + t[:, None] * d), -1).reshape(len(xs), 4, 2)
+    affine = np.abs(c[:, 1] + c[:, 2] - c[:, 0] - c[:, 3]).max(1) < 1e-9
+    pieces = {}
+    square = [(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)]
+    for k, n in enumerate((tx.tex.shape[1], tx.tex.shape[0])):
+        lo, hi = c[:, :, k].min(1), c[:, :, k].max(1)
+        for line in range(n + 1):
+            for p in np.nonzero(affine & (lo < line / n - 1e-9) & (hi > line / n + 1e-9))[0]:
+                c0, a, b = c[p, 0, k], c[p, 1, k] - c[p, 0, k], c[p, 2, k] - c[p, 0, k]
+                cut = []
+                for poly in pieces.get(p, [square]):
+                    cut += [q for q in (_clip(poly, -a, -b, line / n - c0), _clip(poly, a, b, c0 - line / n)) if q]
+                pieces[p] = cut
+    return pieces, affine
+
+
 class Expectation:
     """E(x) for points x on the receiver seen along camera directions, per RGB channel."""
 
@@ -437,11 +544,25 @@ class Expectation:
         """physical_mis: w_nee + w_bsdf replaced by 1.  lobe: see __call__'s refinement.  alts: mutations of the model that the
         tests must reject, each evaluated alongside E at the same nodes and returned as three more channels, in this order:
         "honest_pdf" (p_true := q_rep, a shader whose reported pdf were its sampling density), "clearcoat_unscaled" (the
-        clearcoat lobe without microfacet-ggx.h:236's 0.25)."""
-        assert all(a in ("honest_pdf", "clearcoat_unscaled") for a in alts)
+        clearcoat lobe without microfacet-ggx.h:236's 0.25).
+        A receiver whose material carries base_color_tex_id reads its base colour per point x through tests/_texture_model.py, and
+        the closure set, the selection weights and both pdfs follow it; alts may then also name that model's mutants
+        (_texture_model.MUTANTS): the expectation of a renderer that read the texture that way."""
+        import _texture_model as TM
+        assert all(a in ("honest_pdf", "clearcoat_unscaled") + TM.MUTANTS for a in alts)
         self.S, self.order, self.physical_mis, self.alts = S, order, physical_mis, tuple(alts)
         self.channels = 3 * (1 + len(self.alts))
-        self.closures = closure_set(S.meshes[S.receiver].material)
+        rm = S.meshes[S.receiver]
+        tex_id = rm.material["base_color_tex_id"]
+        self.textured = None if tex_id == TM.NONE else Textured(rm, S.textures[tex_id])
+        assert self.textured is not None or not any(a in TM.MUTANTS for a in alts)
+        if self.textured is not None:
+            texels = np.asarray(self.textured.tex, np.float64)
+            # every texel enables the same closures (closure_set asserts it); a bilinear mix of texels then does as well
+            self.closures = closure_set(rm.material, TM.fetch(texels, *np.meshgrid(np.arange(texels.shape[1]) / texels.shape[1],
+                                                                                   np.arange(texels.shape[0]) / texels.shape[0])).reshape(-1, 3))
+        else:
+            self.closures = closure_set(rm.material)
         self.lobe = lobe                                   # None: triangles are refined by 1 / d^2 alone
         self.width = lobe_width(self.closures) if lobe else None
         rv = np.asarray(S.meshes[S.receiver].verts, np.float64)
@@ -530,6 +651,11 @@ class Expectation:
         W_ = np.outer(gw, gw).ravel()
         S_, T_ = S_.ravel(), T_.ravel()
         out = np.zeros((N, self.channels))
+        cl_pts = None
+        if self.textured is not None:
+            # the closure set per point: the model's, then one per texture mutant among the alts
+            mat = self.S.meshes[self.S.receiver].material
+            cl_pts = {a: closure_set(mat, self.textured.base_color(x, a)) for a in (None,) + self.alts if a is None or a in self.textured.MUTANTS}
         for fi, fc in enumerate(self.faces):
             o, e1, e2 = fc["e"]
             owner, tri, front = [], [], []
@@ -574,14 +700,14 @@ class Expectation:
                 owner = np.concatenate([owner[~big], np.tile(owner[big], 4)])
                 front = np.concatenate([front[~big], np.tile(front[big], 4)])
             for c0 in range(0, len(tri), CHUNK):
-                self._integrate(fc, tri[c0:c0 + CHUNK], owner[c0:c0 + CHUNK], front[c0:c0 + CHUNK], x, n_r, wo, S_, T_, W_, out)
+                self._integrate(fc, tri[c0:c0 + CHUNK], owner[c0:c0 + CHUNK], front[c0:c0 + CHUNK], x, n_r, wo, S_, T_, W_, out, cl_pts)
         return out
 
     def _lobes(self, wi, wo):
         """(f, q_rep, p_true, the clearcoat's share of f) for local directions (M,Q,3): the receiver's closure set"""
         return lobes(self.closures, wi, wo, parts=True)
 
-    def _integrate(self, fc, tri, owner, front, x, n_r, wo, S_, T_, W_, out):
+    def _integrate(self, fc, tri, owner, front, x, n_r, wo, S_, T_, W_, out, cl_pts=None):
         o, e1, e2 = fc["e"]
         A, B, C = tri[:, 0], tri[:, 1], tri[:, 2]
         area2 = np.abs((B[:, 0] - A[:, 0]) * (C[:, 1] - A[:, 1]) - (B[:, 1] - A[:, 1]) * (C[:, 0] - A[:, 0]))
@@ -601,23 +727,48 @@ class Expectation:
         q_light = pA * d2 / ns_dot
         ex, ey = branchless_onb(nrm)                             # the shader's own tangent frame: alpha_x lies along ex
         loc = lambda v: np.stack([np.sum(v * ex, -1), np.sum(v * ey, -1), np.sum(v * nrm, -1)], -1)  # noqa: E731
-        f, q_bsdf, p_true, f_cc = self._lobes(loc(w), loc(np.broadcast_to(wom, w.shape)))
-        # the BSDF-sampled path: wi ~ p_true carries f cos / q_rep  ->  f cos (p_true / q_rep); Lambert alone: ratio 1,
-        # GGX alone (Q15): ratio cos
-        bsdf_cos = cos_p * p_true / q_bsdf
-        if self.physical_mis:
-            w_nee = np.ones_like(q_nee)
-            w_bsdf = np.zeros_like(q_nee)
+        wi_l, wo_l = loc(w), loc(np.broadcast_to(wom, w.shape))
+
+        def paths(f, q_bsdf, p_true):
+            """what both sampling strategies carry per unit f: (NEE's share, the BSDF-sampled path's share, that path's cosine)"""
+            # the BSDF-sampled path: wi ~ p_true carries f cos / q_rep  ->  f cos (p_true / q_rep); Lambert alone: ratio 1,
+            # GGX alone (Q15): ratio cos
+            bsdf_cos = cos_p * p_true / q_bsdf
+            if self.physical_mis:
+                w_nee = np.ones_like(q_nee)
+                w_bsdf = np.zeros_like(q_nee)
+            else:
+                w_nee = q_nee ** 2 / (q_nee ** 2 + q_bsdf ** 2)
+                w_bsdf = np.where(front[:, None], q_bsdf ** 2 / (q_bsdf ** 2 + q_light ** 2), 0.0)
+            return cos_p * cos_l / d2 * w_nee, cos_l / d2 * w_bsdf, bsdf_cos
+
+        def at_owner(cl):
+            """a per-point closure set (closure_set with base (N, 3)) at this chunk's triangles, shaped (M, 1, 3) for lobes()"""
+            cl = dict(cl)
+            if cl["diffuse"] is not None:
+                cl["diffuse"] = cl["diffuse"][owner][:, None]
+            if cl["specular"] is not None:
+                cl["specular"] = dict(cl["specular"], color=cl["specular"]["color"][owner][:, None])
+            return cl
+        if cl_pts is None:
+            f, q_bsdf, p_true, f_cc = self._lobes(wi_l, wo_l)
         else:
-            w_nee = q_nee ** 2 / (q_nee ** 2 + q_bsdf ** 2)
-            w_bsdf = np.where(front[:, None], q_bsdf ** 2 / (q_bsdf ** 2 + q_light ** 2), 0.0)
-        k_nee, k_bsdf = cos_p * cos_l / d2 * w_nee, cos_l / d2 * w_bsdf
+            shared = {}                                          # (wo is one direction per triangle: its selection weights are taken once)
+            pick = lambda cl: selection_weights(cl, wo_l[:, :1], shared)  # noqa: E731
+            cl = at_owner(cl_pts[None])
+            f, q_bsdf, p_true, f_cc = lobes(cl, wi_l, wo_l, sel=pick(cl), parts=True, shared=shared)
+        k_nee, k_bsdf, bsdf_cos = paths(f, q_bsdf, p_true)
         g = [(k_nee + bsdf_cos * k_bsdf)[..., None] * f]
         for a in self.alts:
             if a == "honest_pdf":
                 g.append((k_nee + cos_p * k_bsdf)[..., None] * f)
-            else:
+            elif a == "clearcoat_unscaled":
                 g.append((k_nee + bsdf_cos * k_bsdf)[..., None] * (f + 3.0 * f_cc))
+            else:                                                # a texture mutant: its own closure set per point, the same transport
+                cl = at_owner(cl_pts[a])
+                fa, qa, pa = lobes(cl, wi_l, wo_l, sel=pick(cl), shared=shared)
+                ka_nee, ka_bsdf, a_cos = paths(fa, qa, pa)
+                g.append((ka_nee + a_cos * ka_bsdf)[..., None] * fa)
         val = np.concatenate([np.sum(gi * wq[..., None], 1) * fc["le"] for gi in g], -1)
         np.add.at(out, owner, val)
 
@@ -706,11 +857,19 @@ def classify_and_expect(S: Scene, cam: Camera, expectation: Expectation, sub=2, 
     cls[on_recv] = PIX_RECEIVER
     # E over the footprints of the receiver pixels
     ys, xs = np.nonzero(on_recv)
-    e, ev, pts, wo = pixel_mean(S, cam, expectation, xs, ys, sub, nodes=True)
+    info = {}
+    e, ev, pts, wo = pixel_mean(S, cam, expectation, xs, ys, sub, nodes=True, info=info)
     value[ys, xs] = e
     # where E is steep on the scale of a pixel (right next to an emitter) the rule is not trusted: such pixels are left out
     steep = (ev[..., :3].max(1) - ev[..., :3].min(1)).max(1) > STEEP * np.abs(e[:, :3]).max(1)
     cls[ys[steep], xs[steep]] = PIX_MIXED
+    tx = getattr(expectation, "textured", None)
+    if tx is not None:
+        # a jump of the texcoords (between a face that has them and one that reads its barycentrics) inside the widened footprint
+        jump = ~info["affine"]
+        if not tx.continuous:
+            jump |= np.any(face != face[..., :1], -1)[ys, xs]
+        cls[ys[jump], xs[jump]] = PIX_MIXED
     return cls, value, (pts, wo)
 
 
@@ -724,9 +883,12 @@ def on_receiver(S: Scene, cam: Camera, probe=6):
     return np.all(cast(S, cam.org, d.reshape(-1, 3))[0].reshape(H, W, -1) == S.receiver, -1)
 
 
-def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False):
+def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False, info=None):
     """mean of E over the footprints of receiver pixels (xs, ys) by a sub x sub Gauss-Legendre rule; with nodes=True also
-    the values at the nodes (P, sub^2, 3), the nodes' receiver points and their directions towards the camera"""
+    the values at the nodes (P, sub^2, 3), the nodes' receiver points and their directions towards the camera.
+    A textured receiver (expectation.textured): E has a kink along every texel line, so a footprint that such lines cross is cut
+    along them (texel_pieces) and every piece, fanned into triangles, gets a collapsed n x n rule of its own, n = max(sub, 3) (the
+    collapse costs a rule of n points two degrees); the values at the nodes stay those of the uncut rule.  info: a dict that receives texel_pieces' `affine`."""
     g, gw = gauss_legendre01(sub)
     gx, gy = np.meshgrid(g, g, indexing="ij")
     d = cam.dirs(np.asarray(xs, np.float64)[:, None], np.asarray(ys, np.float64)[:, None], gx.ravel(), gy.ravel()).reshape(-1, 3)
@@ -735,4 +897,32 @@ def pixel_mean(S, cam, expectation, xs, ys, sub, nodes=False):
     pts = cam.org + t[:, None] * d
     v = expectation(pts, -d).reshape(len(xs), sub * sub, -1)
     e = np.einsum("pqc,q->pc", v, np.outer(gw, gw).ravel())
+    tx = getattr(expectation, "textured", None)
+    if tx is not None:
+        pieces, affine = texel_pieces(tx, S, cam, xs, ys)
+        if info is not None:
+            info["affine"] = affine
+        s, ws = gauss_legendre01(max(sub, 3))
+        s_, t_ = (a.ravel() for a in np.meshgrid(s, s, indexing="ij"))
+        w_ = np.outer(ws, ws).ravel()
+        pi, jx, jy, wq = [], [], [], []
+        for p, polys in pieces.items():
+            for poly in polys:
+                for k in range(1, len(poly) - 1):
+                    A, B, C = (np.asarray(q) for q in (poly[0], poly[k], poly[k + 1]))
+                    area2 = abs((B[0] - A[0]) * (C[1] - A[1]) - (B[1] - A[1]) * (C[0] - A[0]))
+                    # collapsed square -> triangle, as Expectation._integrate: j = A + s (B - A) + s t (C - B), dj = area2 s ds dt
+                    j = A + s_[:, None] * (B - A) + (s_ * t_)[:, None] * (C - B)
+                    pi.append(np.full(len(s_), p)); jx.append(j[:, 0]); jy.append(j[:, 1]); wq.append(area2 * s_ * w_)
+        if pi:
+            pi, jx, jy, wq = (np.concatenate(a) for a in (pi, jx, jy, wq))
+            dp = cam.dirs(np.asarray(xs, np.float64)[pi], np.asarray(ys, np.float64)[pi], jx, jy)
+            mp, _, tp, _ = cast(S, cam.org, dp)
+            assert np.all(mp == S.receiver)
+            acc, area = np.zeros_like(e), np.zeros(len(e))
+            np.add.at(acc, pi, expectation(cam.org + tp[:, None] * dp, -dp) * wq[:, None])
+            np.add.at(area, pi, wq)
+            cutp = np.array(sorted(pieces))
+            assert np.allclose(area[cutp], 1.0, atol=1e-12), "the pieces do not tile the footprint"
+            e[cutp] = acc[cutp]
     return (e, v, pts, -d) if nodes else e

@@ -189,8 +189,8 @@ def group_stats(means, groups, val, skip_nan=False):
     return z, bar
 
 
-def cell_stats(means, cls, val):
-    """z per (cell, channel) and for the whole receiver, and the Bonferroni t bar.  means: (K,H,W,3) batch means."""
+def cell_groups(cls):
+    """the judged groups of pixels: every 8x8 cell's PIX_RECEIVER pixels where there are >= MIN_CELL_PIXELS, then the whole receiver"""
     rec = cls == A.PIX_RECEIVER
     groups = []
     for cy in range(0, H, CELL):
@@ -200,7 +200,12 @@ def cell_stats(means, cls, val):
             if m.sum() >= MIN_CELL_PIXELS:
                 groups.append(m)
     groups.append(rec)
-    return group_stats(means, groups, val)
+    return groups
+
+
+def cell_stats(means, cls, val):
+    """z per (cell, channel) and for the whole receiver, and the Bonferroni t bar.  means: (K,H,W,3) batch means."""
+    return group_stats(means, cell_groups(cls), val)
 
 
 def _pa():
@@ -254,9 +259,10 @@ def test_analytic_radiance(case, backend):
         assert np.abs(za).max() >= bar, (f"{name} is not rejected", np.abs(za).max(), bar)
 
 
-def test_quadrature_converged():
-    """doubling the Gauss-Legendre order changes E by < 1e-5 relative, on every case's receiver points (a sample of 400)"""
-    for case in CASES:
+def test_quadrature_converged(cases=CASES, expected=expected):
+    """doubling the Gauss-Legendre order changes E by < 1e-5 relative, on every case's receiver points (a sample of 400)
+    (tests/test_texture_radiance.py runs it on its own cases)"""
+    for case in cases:
         e = expected(case)
         rng = np.random.RandomState(3)
         i = rng.choice(len(e["pts"]), min(400, len(e["pts"])), replace=False)
@@ -306,6 +312,22 @@ def test_closure_set_model_keeps_the_closed_forms():
         b = _ClosedForms(e["S"])(e["pts"][i], e["wo"][i])
         assert a.shape == b.shape and np.abs(a - b).max() <= 1e-12 * np.abs(b).max(), (case, np.abs(a - b).max(), np.abs(b).max())
         assert case == "light_facing_away" or np.abs(b).max() > 0
+
+
+def test_untextured_expectations_are_unchanged():
+    """Expectation resolves the receiver's base colour per point for textured receivers (tests/_texture_model.py); for the thirteen
+    untextured cases it returns, bit for bit, the float64 values it returned before it could: E and every alternative on 300 receiver
+    points per case, recorded by tests/golden/make_analytic_golden.py at the commit before"""
+    import os
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "analytic_expectations.npz"))
+    for case in CASES:
+        e = expected(case)
+        i = np.random.RandomState(5).choice(len(e["pts"]), min(300, len(e["pts"])), replace=False)
+        assert np.array_equal(e["pts"][i], gold[case + "/pts"]) and np.array_equal(e["wo"][i], gold[case + "/wo"]), case
+        got = e["ex"](gold[case + "/pts"], gold[case + "/wo"])
+        assert got.dtype == np.float64 and got.shape == gold[case + "/E"].shape and got.tobytes() == gold[case + "/E"].tobytes(), \
+            (case, np.abs(got - gold[case + "/E"]).max())
+    assert len(CASES) == 13
 
 
 def test_student_t_bar():
