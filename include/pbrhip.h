@@ -120,6 +120,23 @@ typedef struct {
                            launches (the host's round trips; 0 when the next iteration was always enqueued in time) */
 } pbrhip_render_stats;
 
+/* The per-light shaft grid (PBRHIP_SHADOW_GRID=N cells per axis, 0 = off): shadow rays that start in a CLEAR cell
+ * are answered by testing the few triangle leaves the cell lists instead of being traced.  pbrhip_render_stats keeps its layout, so what
+ * the grid did is reported here: the three ray counters are those of the scene's last PBRHIP_RENDER_STATS render, which counts the rays
+ * the grid answers and traces them all the same (shadow_rays, shadow_nodes, shadow_tris stay what they were without a grid). */
+typedef struct {
+  uint32_t resolution, num_lights, max_list; /* 0, 0, 0: the scene has no grid (more than 8 lights or none, curves, no Q tree, a transformed light, the knob) */
+  uint32_t pad;
+  uint64_t bytes;                            /* of device memory (part of pbrhip_scene_info's device_bytes) */
+  uint64_t clear_cells, unknown_cells, empty_cells, listed_leaves; /* over all lights; empty_cells: CLEAR with an empty list */
+  uint64_t culled_shadow_rays;               /* shadow rays the grid answers "unoccluded" (<= shadow_rays) */
+  uint64_t clear_cell_rays, leaf_tests;      /* shadow rays that started in a CLEAR cell; two-triangle leaf tests made for them */
+  double build_ms;                           /* the device build of the grid the scene holds */
+} pbrhip_shadow_grid_info;
+int pbrhip_scene_shadow_grid_info(pbrhip_scene*, pbrhip_shadow_grid_info* out);
+/* the cells as the kernels read them (tests): num_lights x resolution^3 records of 8 words: count or 0xFFFFFFFF (UNKNOWN), then 7 leaf indices */
+int pbrhip_scene_read_shadow_grid(pbrhip_scene*, uint32_t* cells, size_t num_words);
+
 /* Layout version of the structs of this header (pbrhip_render_desc, pbrhip_render_stats, pbrhip_*_param, pbrhip_hit): it
  * changes whenever one of them changes (3 -> 4: pbrhip_render_stats grew by curve_bytes; 5 -> 6: by suspended_rays, ms_host_idle).  The library writes whole structs
  * (n of them for pbrhip_render_multi), so a caller compiled against another version must not call it: check

@@ -40,6 +40,7 @@ EXPORTS = [
     "pbrhip_scene_read_pseudonormals",
     "pbrhip_trace_all", "pbrhip_trace_all_device",
     "pbrhip_k_nearest", "pbrhip_k_nearest_device",
+    "pbrhip_scene_shadow_grid_info", "pbrhip_scene_read_shadow_grid",
 ]
 
 
@@ -107,6 +108,9 @@ def lib():
         _lib.pbrhip_trace_all_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp]
         _lib.pbrhip_k_nearest.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp]
         _lib.pbrhip_k_nearest_device.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, vp, vp]
+        if hasattr(_lib, "pbrhip_scene_shadow_grid_info"):  # (an earlier commit's library loaded through PBRHIP_LIB for an A/B has no grid)
+            _lib.pbrhip_scene_shadow_grid_info.argtypes = [vp, vp]
+            _lib.pbrhip_scene_read_shadow_grid.argtypes = [vp, vp, C.c_size_t]
         if _lib.pbrhip_abi_version() != ABI_VERSION:
             v = _lib.pbrhip_abi_version()
             _lib = None

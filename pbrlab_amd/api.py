@@ -49,6 +49,12 @@ class RenderDesc(C.Structure):
 BVH_HOST_SAH, BVH_GPU_LBVH, BVH_GPU_LBVH_WIDE = 0, 1, 2
 
 
+class ShadowGridInfo(C.Structure):  # pbrhip_shadow_grid_info
+    _fields_ = ([(n, C.c_uint32) for n in ("resolution", "num_lights", "max_list", "pad")] +
+                [(n, C.c_uint64) for n in ("bytes", "clear_cells", "unknown_cells", "empty_cells", "listed_leaves", "culled_shadow_rays",
+                                           "clear_cell_rays", "leaf_tests")] + [("build_ms", C.c_double)])
+
+
 class RenderStats(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("samples", "iterations", "chunks", "closest_rays", "closest_nodes",
                                            "closest_tris", "closest_curves", "shadow_rays", "shadow_nodes",
@@ -582,6 +588,21 @@ class Scene:
         dp = C.c_uint32()
         _chk(self.L.pbrhip_scene_info(self.h, C.byref(nn), C.byref(ns), C.byref(dp), C.byref(nb)))
         return dict(num_nodes=nn.value, num_slots=ns.value, depth=dp.value, device_bytes=nb.value)
+
+    def shadow_grid_info(self):
+        """pbrhip_scene_shadow_grid_info: the per-light shaft grid of the committed scene (resolution 0: none) and what it did in the
+        scene's last statistics render (culled_shadow_rays: the shadow rays it answers)"""
+        gi = ShadowGridInfo()
+        _chk(self.L.pbrhip_scene_shadow_grid_info(self.h, C.byref(gi)))
+        return {n: getattr(gi, n) for n, _ in gi._fields_ if n != "pad"}
+
+    def read_shadow_grid(self):
+        """pbrhip_scene_read_shadow_grid: the cells, (lights, n, n, n, 8) uint32: count or 0xFFFFFFFF, then the listed leaf indices"""
+        gi = self.shadow_grid_info()
+        n, nl = gi["resolution"], gi["num_lights"]
+        cells = np.zeros((nl, n, n, n, 8), np.uint32)
+        _chk(self.L.pbrhip_scene_read_shadow_grid(self.h, _ptr(cells), C.c_size_t(cells.size)))
+        return cells
 
     def wide_info(self):
         """pbrhip_scene_wide_info: the 4-wide quantised tree of the committed scene (wide_nodes 0: none)"""

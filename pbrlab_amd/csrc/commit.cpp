@@ -366,6 +366,14 @@ static void stage_lights(pbrhip_scene* s, CommitStage* cs) {  // the light table
   light_records(s, &s->light_heads, &cs->lrecs, &cs->lprim_cdf);
   cs->lboxes = light_boxes(s->light_heads, cs->lrecs);
   s->num_lrecs = (uint32_t)cs->lrecs.size();
+  s->light_box.assign(6 * s->light_heads.size(), 0.0f);  // (what the shaft grid is cut around: shaft_grid.h)
+  for (size_t l = 0; l < s->light_heads.size(); l++) {
+    float* b = &s->light_box[6 * l];
+    for (int a = 0; a < 3; a++) b[a] = INFINITY, b[3 + a] = -INFINITY;
+    for (uint32_t r = s->light_heads[l].first; r < s->light_heads[l].first + s->light_heads[l].count; r++)
+      for (const float* p : {cs->lrecs[r].p0, cs->lrecs[r].p1, cs->lrecs[r].p2})
+        for (int a = 0; a < 3; a++) b[a] = std::min(b[a], p[a]), b[3 + a] = std::max(b[3 + a], p[a]);
+  }
   // light sampling works on the meshes' local positions (light-manager.h:128-136 "TODO transform"), the raytracer on the
   // transformed ones: the doomed-path pretest against the light primitives (kernels.hip::misses_all_lights) is only the
   // traversal's own test when the two coincide
@@ -500,6 +508,51 @@ static int update_walk_entries(pbrhip_scene* s, const Knobs& k, bool want, const
   return PBRHIP_OK;
 }
 
+int pb::ensure_shadow_grid(pbrhip_scene* s, const Knobs& k) {
+  ShaftState& g = s->shaft;
+  DScene& d = s->dscene;
+  const TreeBufs& t = s->tree;
+  const uint32_t nl = (uint32_t)s->lights.size();
+  // who gets one: a triangle-only scene with a Q tree (the cells list its TriPair leaves) and 1 .. kShaftMaxLights lights whose records
+  // are what the raytracer sees
+  bool want = k.shadow_grid > 0 && k.shadow_grid_list > 0 && nl >= 1 && nl <= kShaftMaxLights && !s->lights_transformed && t.wide_nodes > 0 && s->num_curves == 0 &&
+              s->light_box.size() == 6 * (size_t)nl;
+  for (size_t i = 0; want && i < s->light_box.size(); i++) want = std::isfinite(s->light_box[i]);
+  for (int a = 0; a < 3; a++) want = want && std::isfinite(s->bmin[a]) && std::isfinite(s->bmax[a]);
+  const uint32_t n = want ? k.shadow_grid : 0u;
+  if (!(g.valid && g.n == n && (n == 0 || (g.max_list == k.shadow_grid_list && g.num_lights == nl)))) {
+    g.valid = false;
+    if (n == 0) {
+      g.drop();
+    } else {
+      const size_t words = (size_t)n * n * n * nl * kShaftCellWords;
+      HIPCHK(hipSetDevice(s->device));
+      HIPCHK(g.cells.reserve(words));
+      ShaftBuild b;
+      b.tree.nodes = reinterpret_cast<const QNode*>(t.d_wide.p), b.tree.tri = t.tri(), b.tree.num_nodes = t.wide_nodes;
+      b.frame = shaft_frame(s->bmin, s->bmax, n);
+      b.margin = shaft_margin(s->bmin, s->bmax);
+      b.num_lights = nl, b.max_list = k.shadow_grid_list;
+      for (uint32_t l = 0; l < nl; l++)
+        for (int a = 0; a < 3; a++) b.light_lo[l][a] = s->light_box[6 * l + a], b.light_hi[l][a] = s->light_box[6 * l + 3 + a];
+      HIPCHK(hipStreamSynchronize(s->stream));  // (what follows is the build's own time)
+      const auto t0 = std::chrono::steady_clock::now();
+      HIPCHK(build_shaft_grid_gpu(s->stream, b, g.cells.p));
+      HIPCHK(hipStreamSynchronize(s->stream));
+      g.build_ms = ms_since(t0);
+      g.n = n, g.max_list = k.shadow_grid_list, g.num_lights = nl;
+      if (k.debug) fprintf(stderr, "pbrhip: shaft grid: %u^3 cells x %u lights, lists of at most %u leaves, %.1f MB, built in %.2f ms\n", n, nl, g.max_list, words * 4 / 1048576.0, g.build_ms);
+    }
+    g.valid = true;
+  }
+  d.shaft_cells = g.n ? reinterpret_cast<const uint4*>(g.cells.p) : nullptr, d.shaft_n = g.n;
+  if (g.n) {
+    const ShaftFrame f = shaft_frame(s->bmin, s->bmax, g.n);
+    for (int a = 0; a < 3; a++) d.shaft_org[a] = f.org[a], d.shaft_inv[a] = f.inv[a];
+  }
+  return PBRHIP_OK;
+}
+
 void pb::bind_dscene(pbrhip_scene* s) {
   DScene& d = s->dscene;
   const TreeBufs& t = s->tree;
@@ -561,6 +614,8 @@ extern "C" int pbrhip_scene_commit(pbrhip_scene* s) {
   s->slot_gid = std::move(cs.bvh.slot_gid);
   s->rf_plan.release();
   s->sdf.drop();  // (slot order and topology may have changed)
+  s->shaft.valid = false;  // (the trees, the lights or the bounds may have changed)
+  if (int rc = ensure_shadow_grid(s, k)) return rc;
   s->dirty_inst.assign(s->instances.size(), 0), s->stale = false;
   s->committed = true;
   return PBRHIP_OK;
@@ -819,6 +874,7 @@ extern "C" int pbrhip_scene_refit(pbrhip_scene* s) {
   if (s->replica) return fail(PBRHIP_ESTATE, "scene_refit: a replica holds no geometry (refit the source scene and replicate it again)");
   if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
   if (!s->stale) return PBRHIP_OK;
+  s->shaft.valid = false, s->dscene.shaft_cells = nullptr;  // ... and so is what the shaft grid was cut from: it is made again before the next render
   s->sdf.table_valid = false;  // the slots are about to change: the pseudonormal table is made again when it is next asked for
   const Knobs k = read_knobs();
   HIPCHK(hipSetDevice(s->device));

@@ -270,6 +270,10 @@ struct DScene {
   float env_p;                  // probability that a NEE event samples the environment (1 without area lights, else 1/2)
   float env_area_scale;         // 1 - env_p: applied to the area lights' pdf by the environment kernels
   float env_m[9];               // world_to_env, row-major (a rotation)
+  // the per-light shaft grid (shaft_grid.h), appended likewise
+  const uint4* shaft_cells;     // num_lights x shaft_n^3 cells of two 16-byte words (state / count | leaf indices); null: no grid
+  uint32_t shaft_n;             // cells per axis
+  float shaft_org[3], shaft_inv[3];  // cell index = floor((p - org) * inv) per axis (ShaftFrame)
 };
 
 // what a trace hook or a ray query returns per ray (dshade.h::hook_result)

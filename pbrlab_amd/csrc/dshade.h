@@ -125,6 +125,7 @@ __device__ __forceinline__ uint32_t cdf_lower_bound(Cdf cdf, uint32_t n, float u
 struct Nee {
   V3 dir, emission;
   float dist, pdf_sigma;
+  uint32_t light;  // the area light the sample lies on; kNone: none was sampled, or the environment
 };
 // The light tables as the sampling reads them: from the scene in global memory, or from a copy in LDS (k_shade_principled stages
 // them when the scene has at most kLdsLights lights and light primitives: LDS reads stay off the vector-memory path).
@@ -157,6 +158,7 @@ __device__ __forceinline__ bool nee_sample_from(const Tables& lt, uint32_t num_l
   if (num_lights == 0) return false;
   float u0 = draw(rng);
   uint32_t li = cdf_lower_bound(lt.cdf(), num_lights, u0);
+  n.light = li;
   LightHead head = lt.head(li);
   float u1 = draw(rng);
   uint32_t pi = cdf_lower_bound(lt.prim_cdf(head.first), head.count, u1);
@@ -196,6 +198,7 @@ __device__ __forceinline__ bool env_nee(const DScene& sc, Rng& rng, V3 global_no
   const uint32_t row = t / sc.env_w, col = t - row * sc.env_w;
   n.dir = env_to_world(sc.env_m, env_texel_dir(col, row, sc.env_w, sc.env_h, u, v));
   n.dist = kInf;
+  n.light = kNone;
   const float c = dot(n.dir, global_normal);
   n.emission = V3(L.x, L.y, L.z) * V3(fabsf(c));
   n.pdf_sigma = sc.env_p * L.w;

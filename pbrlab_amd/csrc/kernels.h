@@ -134,6 +134,8 @@ enum : uint32_t {
   kStatSuspendedShadow,  // shadow rays suspended (counted once more as a shadow ray of the launch that resumes each)
   kStatSuspended,  // rays suspended (each is counted once more as a closest-hit ray of the launch that resumes it: subtracted there)
   kStatCycNode, kStatCycTri, kStatCycCurve, kStatCycRefill, kStatWalkCycTrav, kStatWalkCycStep,  // shader-clock cycles of the phase-voting waves' loop turns by what the turn did (lane 0 of every wave)
+  kStatCulledShadow,  // shadow rays the shaft grid answers (shaft_grid.h): a statistics render counts them here and traces them all the same
+  kStatGridClearRays, kStatGridPairTests,  // ... shadow rays that started in a CLEAR cell; leaf tests made for them
   kStatNum
 };
 

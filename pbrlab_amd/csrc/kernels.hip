@@ -22,6 +22,7 @@
 #include "dcamera.h"
 #include "dshade.h"
 #include "kernels.h"
+#include "shaft_grid.h"
 #include "variants.h"
 #include "dtrace_pv.h"
 #include "dtrace_quad.h"
@@ -739,6 +740,36 @@ __device__ __forceinline__ void count_pruned(const PathState& P) {  // P.stats i
   if (P.stats) atomicAdd(&P.stats[kStatPrunedRays], 1ull);
 }
 
+// The shaft grid's answer for one shadow ray (shaft_grid.h): true = unoccluded, and the ray need not be traced.  The cell of
+// the ray's origin for the light its end lies on; a CLEAR cell lists every triangle leaf that can hold an occluder of a ray from that
+// cell to that light, and each is tested as the traversal would test it: tri_test_pair on the leaf's own five words, the ray's own
+// origin, direction, 1 / direction and interval -- misses_all_lights' pattern.  Anything else -- no grid, a position outside it or not a
+// number, an UNKNOWN cell, a direction or a length that is no ordinary number, an accepted test -- is false: the ray is traced as before.
+__device__ __forceinline__ bool shaft_unoccluded(const PathState& P, const DScene& sc, uint32_t light, V3 o, V3 d, float tmax) {
+  uint32_t cell;
+  if (light >= sc.num_lights || !shaft_cell_of(o.x, o.y, o.z, sc.shaft_org, sc.shaft_inv, sc.shaft_n, &cell)) return false;
+  if (!(fabsf(d.x) <= 2.0f && fabsf(d.y) <= 2.0f && fabsf(d.z) <= 2.0f && tmax < kInf)) return false;
+  const uint4* c = sc.shaft_cells + ((size_t)light * sc.shaft_n * sc.shaft_n * sc.shaft_n + cell) * 2u;
+  const uint4 c0 = c[0];
+  const uint32_t count = c0.x;
+  if (count > kShaftMaxList) return false;  // UNKNOWN
+  uint4 c1 = make_uint4(0u, 0u, 0u, 0u);
+  if (count > 3u) c1 = c[1];
+  const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+  bool hit = false;
+  for (uint32_t i = 0; i < count; i++) {
+    const uint32_t lo = i == 0u ? c0.y : (i == 1u ? c0.z : c0.w), hi = i == 3u ? c1.x : (i == 4u ? c1.y : (i == 5u ? c1.z : c1.w));
+    const float4* g = sc.wide + sc.q_tri0 + (size_t)(i < 3u ? lo : hi) * kTriPairWords;
+    const float4 w0 = g[0], w1 = g[1], w2 = g[2], w3 = g[3], w4 = g[4];
+    bool ok_a, ok_b;
+    f2 t, u, v;
+    tri_test_pair(w0, w1, w2, w3, w4, o.x, o.y, o.z, d.x, d.y, d.z, ix, iy, iz, kEps, ok_a, ok_b, t, u, v);
+    hit = hit || (ok_a && t.x <= tmax) || (ok_b && t.y <= tmax);  // (a leaf of one triangle stores it twice: the same answer twice)
+  }
+  if (P.stats) atomicAdd(&P.stats[kStatGridClearRays], 1ull), atomicAdd(&P.stats[kStatGridPairTests], (unsigned long long)count);
+  return !hit;
+}
+
 // writes one shadow-queue entry
 __device__ __forceinline__ void put_shadow(const PathState& P, V3 pos, const Nee& n, V3 c_vis, V3 c_occ, uint32_t p,
                                            uint32_t mode, bool alive) {
@@ -779,7 +810,9 @@ __device__ __forceinline__ bool stage_light_tables(const DScene& sc, float* lds)
 enum : int { kShadePlain = 0, kShadeMedia = 1, kShadeFull = 2, kShadeEnv = 4 };
 constexpr int shade_base(int mode) { return mode & 3; }
 constexpr bool shade_env(int mode) { return (mode & kShadeEnv) != 0; }
-template <int MODE_ = kShadeFull>
+// GRID: an ordinary shadow ray the shaft grid answers is not queued: its contribution goes into L here (only k_shade_principled<kShadePlain>
+// asks for it)
+template <int MODE_ = kShadeFull, bool GRID = false>
 __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, const DScene& sc, uint32_t p, uint64_t rng_inc, bool first,
                                                           const PrincipledBsdf* lds_bsdf = nullptr, const float* lds_lights = nullptr) {
   constexpr int MODE = shade_base(MODE_);
@@ -788,7 +821,7 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
   bool alive = false, shadow = false;
   V3 sh_pos(0.f), c_vis(0.f);
   Nee nee;
-  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f, nee.light = kNone;
   uint32_t sh_mode = kShNormal, qbit = 0u;
   PathHead c;
   const int head = path_head<MODE != kShadeMedia, ENV>(P, sc, p, rng_inc, c, first);
@@ -937,6 +970,18 @@ __device__ __forceinline__ uint32_t shade_principled_path(const PathState& P, co
       }
     }
   }
+  if (GRID && MODE == kShadePlain && !ENV && shadow && sc.shaft_cells &&
+      shaft_unoccluded(P, sc, nee.light, sh_pos, nee.dir, smax(kEps, nee.dist - kEps))) {
+    // Between this shading and the delivery of its shadow ray by the next k_trace nothing else adds to the path's L (a path whose
+    // shadow ray is suspended is held, not shaded): adding here is the same sequence of float additions.
+    if (P.stats) {
+      atomicAdd(&P.stats[kStatCulledShadow], 1ull);  // (a statistics render counts the ray and traces it all the same: its counters stay comparable)
+    } else {
+      const float4 L4 = P.L[p];
+      P.L[p] = make_float4(L4.x + c_vis.x, L4.y + c_vis.y, L4.z + c_vis.z, L4.w);
+      shadow = false;
+    }
+  }
   if (shadow) put_shadow(P, sh_pos, nee, c_vis, V3(0.f), p, sh_mode, alive);
   return head == kHeadHeld ? kRHold : ((shadow ? kRShadow : 0u) | (alive ? kRAlive : 0u) | qbit);
 }
@@ -1001,7 +1046,7 @@ __global__ __launch_bounds__(kBlock, shade_waves(MODE_)) void k_shade_principled
     } else if (e & kQResume) {
       go = false, r = kRResume | (e & kQDoomed) | ((e & kQFirst) ? kRResumeFirst : 0u);
     }
-    if (go) r = shade_principled_path<MODE_>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, staged ? lds_bsdf : nullptr, lights_staged ? lds_lights : nullptr);
+    if (go) r = shade_principled_path<MODE_, true>(P, sc, p, rng_inc, P.first != 0u || (e & kQFirst) != 0u, staged ? lds_bsdf : nullptr, lights_staged ? lds_lights : nullptr);
     if (r == kRHold && (e & kQDoomed) && (kAnyBounce ? !P.first : !direct)) r |= kRHoldDoomed;  // (a held path hands its queue entry's kQDoomed back)
     P.q_principled[i] = p | r;
   }
@@ -1015,7 +1060,7 @@ __device__ __forceinline__ uint32_t shade_hair_path(const PathState& P, const DS
   uint32_t qbit = 0u;
   V3 sh_pos(0.f), c_vis(0.f);
   Nee nee;
-  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f, nee.light = kNone;
   PathHead c;
   const int head = path_head<true, ENV>(P, sc, p, rng_inc, c, first);
   if (head == kHeadGoes) {
@@ -1146,7 +1191,7 @@ __device__ __forceinline__ uint32_t sss_step_path(const PathState& P, const DSce
   uint32_t qbit = 0u;
   V3 sh_pos(0.f), c_vis(0.f), c_occ(0.f);
   Nee nee;
-  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f;
+  nee.dir = V3(0.f), nee.emission = V3(0.f), nee.dist = 0.f, nee.pdf_sigma = 0.f, nee.light = kNone;
   float4 o4 = P.ray_o[p], d4 = P.ray_d[p];
   float4 st4 = P.sss_sigt[p], ss4 = P.sss_sigs[p], wt4 = P.sss_thr[p];
   Hit h;
@@ -2060,6 +2105,28 @@ void launch_hook(hipStream_t s, const DScene& sc, const float4* rays, uint32_t n
       with_hook_tree([&](auto c, auto w) { hipLaunchKernelGGL((k_hook_pv<any, c, w>), g, dim3(kBlock), 0, s, sc, rays, n, hits, occ, counts, spill); }, sc, k);
     }
   }, occ != nullptr);
+}
+
+// ------------------------------------------------------------------ the per-light shaft grid's build (shaft_grid.h)
+// One thread per (light, cell) runs shaft_build_cell, the function the CPU checker runs too.  A one-off per commit / refit: a thread walks
+// the Q tree with a private stack (kShaftStack words of scratch) and stops at the first leaf beyond what a list holds.
+__global__ __launch_bounds__(kBlock) void k_shaft_grid(ShaftBuild b, uint32_t* cells) {
+  const uint32_t n3 = b.frame.n * b.frame.n * b.frame.n;
+  const size_t total = (size_t)n3 * b.num_lights;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kBlock) {
+    uint32_t rec[kShaftCellWords];
+    shaft_build_cell(b, (uint32_t)(i / n3), (uint32_t)(i % n3), rec);
+    uint4* out = reinterpret_cast<uint4*>(cells + i * kShaftCellWords);
+    out[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
+    out[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
+  }
+}
+hipError_t build_shaft_grid_gpu(hipStream_t st, const ShaftBuild& b, uint32_t* cells) {
+  const size_t total = (size_t)b.frame.n * b.frame.n * b.frame.n * b.num_lights;
+  if (total == 0) return hipSuccess;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((total + kBlock - 1) / kBlock, 65536u);
+  hipLaunchKernelGGL(k_shaft_grid, dim3(blocks), dim3(kBlock), 0, st, b, cells);
+  return hipGetLastError();
 }
 
 }  // namespace pb

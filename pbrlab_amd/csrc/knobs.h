@@ -21,6 +21,8 @@ struct Knobs {
   bool bvh_cost = true;         // PBRHIP_BVH_COST (1): 0 = the host builder and its Q collapse price a leaf per primitive and place re-insertion passes by area growth alone, as before the traversal's turns were priced (host_scene.h::BvhBuildOptions::cost; for A/Bs)
   bool sss_entry = true;        // PBRHIP_SSS_ENTRY (1): 0 = random walks start at the root, not at the cut of the Q tree around their instance
   uint32_t sss_foreign = 3;     // PBRHIP_SSS_FOREIGN (3): foreign references allowed in a walk's entry cut (at most kSssMaxForeign)
+  uint32_t shadow_grid = 64;    // PBRHIP_SHADOW_GRID (64): cells per axis of the per-light shaft grid (shaft_grid.h; at most kShaftMaxRes); 0 = no grid, every shadow ray is traced
+  uint32_t shadow_grid_list = 7;  // PBRHIP_SHADOW_GRID_LIST (7): triangle leaves a CLEAR cell may list (at most kShaftMaxList); for sweeps
   bool debug = false;           // PBRHIP_DEBUG: set = commit and render print sizes and free memory on stderr
   // path layout (ensure_pixels; part of its cache key)
   uint32_t pixel_tile = 8;      // PBRHIP_PIXEL_TILE (8): paths laid out in patches of this many pixels squared; 0 or 1 = rows

@@ -76,6 +76,8 @@ Knobs pb::read_knobs() {
   k.bvh_cost = u32("PBRHIP_BVH_COST", 1u) != 0u;
   k.sss_entry = u32("PBRHIP_SSS_ENTRY", 1u) != 0u;
   k.sss_foreign = u32("PBRHIP_SSS_FOREIGN", 3u);
+  k.shadow_grid = std::min(u32("PBRHIP_SHADOW_GRID", 64u), kShaftMaxRes);
+  k.shadow_grid_list = std::min(u32("PBRHIP_SHADOW_GRID_LIST", kShaftMaxList), kShaftMaxList);
   k.debug = env("PBRHIP_DEBUG") != nullptr;
   k.pixel_tile = u32("PBRHIP_PIXEL_TILE", 8u);
   k.patch_shuffle = u32("PBRHIP_PATCH_SHUFFLE", 1u) != 0u;
@@ -377,6 +379,44 @@ extern "C" int pbrhip_scene_info(const pbrhip_scene* s, uint64_t* num_nodes, uin
   if (num_slots) *num_slots = s->dscene.num_slots;
   if (depth) *depth = s->bvh_depth;
   if (device_bytes) *device_bytes = s->device_bytes();
+  return PBRHIP_OK;
+  });
+}
+
+extern "C" int pbrhip_scene_shadow_grid_info(pbrhip_scene* s, pbrhip_shadow_grid_info* out) {
+  return guarded([&]() -> int {
+  if (!s || !out) return fail(PBRHIP_EINVAL, "scene_shadow_grid_info: NULL argument");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
+  if (int rc = ensure_shadow_grid(s, read_knobs())) return rc;
+  const ShaftState& g = s->shaft;
+  memset(out, 0, sizeof(*out));
+  out->resolution = g.n, out->num_lights = g.n ? g.num_lights : 0u, out->max_list = g.n ? g.max_list : 0u;
+  out->bytes = g.cells.n * sizeof(uint32_t), out->build_ms = g.build_ms;
+  out->culled_shadow_rays = g.culled, out->clear_cell_rays = g.clear_rays, out->leaf_tests = g.pair_tests;
+  if (g.n) {
+    std::vector<uint32_t> h((size_t)g.n * g.n * g.n * g.num_lights * kShaftCellWords);
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpy(h.data(), g.cells.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < h.size(); c += kShaftCellWords) {
+      if (h[c] == kShaftUnknown) out->unknown_cells++;
+      else out->clear_cells++, out->empty_cells += h[c] == 0u, out->listed_leaves += h[c];
+    }
+  }
+  return PBRHIP_OK;
+  });
+}
+extern "C" int pbrhip_scene_read_shadow_grid(pbrhip_scene* s, uint32_t* cells, size_t num_words) {
+  return guarded([&]() -> int {
+  if (!s || !cells) return fail(PBRHIP_EINVAL, "scene_read_shadow_grid: NULL argument");
+  if (!s->committed) return fail(PBRHIP_ESTATE, "scene not committed");
+  PB_NOT_STALE(s);
+  if (int rc = ensure_shadow_grid(s, read_knobs())) return rc;
+  const ShaftState& g = s->shaft;
+  const size_t words = (size_t)g.n * g.n * g.n * (g.n ? g.num_lights : 0u) * kShaftCellWords;
+  if (num_words != words) return fail(PBRHIP_EINVAL, "scene_read_shadow_grid: the grid has %zu words, the buffer %zu", words, num_words);
+  HIPCHK(hipSetDevice(s->device));
+  if (words) HIPCHK(hipMemcpy(cells, g.cells.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PBRHIP_OK;
   });
 }
@@ -1296,7 +1336,7 @@ static int write_wave_log(const DevBuf<unsigned long long>& log, const char* pat
 static double ratio(unsigned long long a, unsigned long long b) { return a / (double)std::max<unsigned long long>(1, b); }
 
 // the device's statistics counters (PBRHIP_RENDER_STATS) into S; PBRHIP_PV_STATS prints the traversal's on stderr
-static int read_render_stats(const pbrhip_scene* s, const Knobs& k, pbrhip_render_stats* S) {
+static int read_render_stats(pbrhip_scene* s, const Knobs& k, pbrhip_render_stats* S) {
   unsigned long long hs[kStatNum];
   HIPCHK(hipMemcpy(hs, s->stats.p, sizeof(hs), hipMemcpyDeviceToHost));
   S->closest_rays = hs[kStatClosestRays] - hs[kStatSuspended] - hs[kStatHeld], S->closest_nodes = hs[kStatClosestNodes];  // (a suspended ray is counted by the launch that suspends it and by the one that resumes it)
@@ -1305,6 +1345,7 @@ static int read_render_stats(const pbrhip_scene* s, const Knobs& k, pbrhip_rende
   S->shadow_rays = hs[kStatShadowRays] - hs[kStatSuspendedShadow], S->shadow_nodes = hs[kStatShadowNodes];
   S->tail_closest_rays = hs[kStatTailClosestRays], S->tail_shadow_rays = hs[kStatTailShadowRays];
   S->pruned_rays = hs[kStatPrunedRays];
+  s->shaft.culled = hs[kStatCulledShadow], s->shaft.clear_rays = hs[kStatGridClearRays], s->shaft.pair_tests = hs[kStatGridPairTests];  // (pbrhip_scene_shadow_grid_info)
   S->shadow_tris = hs[kStatShadowTris], S->shadow_curves = hs[kStatShadowCurves];
   if (!k.pv_stats) return PBRHIP_OK;
   fprintf(stderr, "pv closest: it node %llu tri %llu curve %llu refill %llu | lanes/iter node %.1f tri %.1f curve %.1f\n",
@@ -1344,6 +1385,7 @@ int pb::render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile
   pbrhip_render_stats S;
   memset(&S, 0, sizeof(S));
   if (int rc = ensure_pixels(s, k, d->width, d->height, d->tile_rank, d->tile_world ? d->tile_world : 1, d->shard_block)) return rc;
+  if (int rc = ensure_shadow_grid(s, k)) return rc;  // (kept unless a refit, a replication or a knob asks for another)
   const uint32_t* const pix = d_pixels ? d_pixels : s->path_pix.p;
   const uint32_t npix = d_pixels ? num_pixels : s->pk_npix;
   const bool want_stats = (d->flags & PBRHIP_RENDER_STATS) != 0;

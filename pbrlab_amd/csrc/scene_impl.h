@@ -18,6 +18,7 @@
 #include "host_scene.h"
 #include "kernels.h"
 #include "rays_kernels.h"
+#include "shaft_grid.h"
 
 namespace pb {
 
@@ -188,6 +189,20 @@ struct SdfState {
     slot_feat.release(), feat_off.release(), feat_items.release(), faces.release(), table.release();
   }
 };
+// The per-light shaft grid (shaft_grid.h): built on the device from the trees as they are -- at the end of a commit, and
+// before the next render by whoever finds it invalid (after a refit, on a replica, after a change of its knobs).
+struct ShaftState {
+  bool valid = false;                 // `cells` describes the device scene as it is (or the scene gets no grid: n == 0)
+  uint32_t n = 0, max_list = 0;       // what it was built with (n 0: no grid)
+  uint32_t num_lights = 0;
+  DevBuf<uint32_t> cells;
+  double build_ms = 0.0;
+  uint64_t culled = 0, clear_rays = 0, pair_tests = 0;  // of the last statistics render
+  void drop() {
+    valid = false, n = max_list = num_lights = 0, build_ms = 0.0;
+    cells.release();
+  }
+};
 inline bool all_triangles(const std::vector<uint8_t>& kinds) {  // (the Q tree's triangle leaves are TriPairs, dscene.h)
   return std::all_of(kinds.begin(), kinds.end(), [](uint8_t kd) { return kd == 0; });
 }
@@ -228,6 +243,8 @@ struct pbrhip_scene {
   pb::RefitPlan rf_plan;            // built at the first refit of a committed tree, dropped by the next commit
   pb::DevBuf<float4> rf_packed;     // the dirty slots' upload: index | 64 B | 128 B (refit_gpu.hip::k_rf_scatter)
   pb::DevGeom dg;                   // device geometry mode (off, and empty, unless a *_mesh_device update switched it on)
+  pb::ShaftState shaft;             // the per-light shaft grid (no cells unless the scene gets one)
+  std::vector<float> light_box;     // per light: lo xyz, hi xyz of its primitives (stage_lights; carried over by pbrhip_scene_replicate)
   pb::SdfState sdf;                 // the signed-distance queries' lists and table (empty unless one was asked)
   // device scene
   pb::TreeBufs tree;
@@ -295,10 +312,12 @@ struct pbrhip_scene {
     f(true, s.tree.d_nodes...), f(true, s.tree.d_wide...), f(true, s.tree.d_qhit...), f(true, s.d_shade...), f(true, s.d_materials...), f(true, s.d_lrecs...);
     f(false, s.d_light_cdf...), f(false, s.d_lprim_cdf...), f(false, s.d_tex_pixels...), f(false, s.d_tex_descs...), f(false, s.d_heads...);
     f(false, s.d_light_boxes...), f(false, s.d_sss_entries...);
+    // (the shaft grid is not here: a replica builds its own; device_bytes counts it)
   }
   size_t device_bytes() const {
     size_t bytes = 0;
     each_scene_buf([&](bool counted, const auto& b) { bytes += counted ? b.n * sizeof(*b.p) : 0; }, *this);
+    bytes += shaft.cells.n * sizeof(uint32_t);
     return bytes;
   }
 };
@@ -317,6 +336,8 @@ int set_camera(pbrhip_scene* s, const float* eye, const float* lookat, const flo
 int render_impl(pbrhip_scene* s, const pbrhip_render_desc* d, const volatile unsigned char* cancel, float* d_rgba,
                 uint32_t* d_count, size_t* finish_pass, pbrhip_render_stats* stats, const uint32_t* d_pixels = nullptr,
                 uint32_t num_pixels = 0, const RaySource* rays = nullptr);
+// the shaft grid of the device scene as it is, under these knobs: kept if valid, else built (or dropped: a scene that gets none); binds DScene::shaft_*
+int ensure_shadow_grid(pbrhip_scene* s, const Knobs& k);
 void bind_dscene(pbrhip_scene* s);  // points every DScene member that comes from a scene buffer at it, with its count (commit.cpp)
 inline const HostMesh* inst_mesh(const pbrhip_scene* s, uint32_t instance_id, uint32_t geom_id) {  // (per primitive in commit's loops: inline)
   const HostInstance& in = s->instances[instance_id];
